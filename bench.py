@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- fwd+bwd frames/s of SOAR's per-frame avatar path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1 under torch.distributed.run (WORLD_SIZE set): this process is one rank.
         N > 1 without a launcher: this process only starts N ranks of itself (one per GPU, RCCL over 127.0.0.1),
         relays rank 0's JSON line and exits non-zero if a rank fails or fewer than N GPUs are visible.
+        --dump-outputs DIR: after the timed steps, one step of the timed path from the state after its first step, over the last
+        timed step's frames, as DIR/<name>.npy (see `dump_outputs`); the same in every run with the same arguments.
+        --full: everything beyond the headline as well (see below); a plain run only sets up, warms up, times the K steps,
+        dumps its outputs when asked and prints the line.
 
 One STEP = one pass of the hot path over one batch of `--frames-per-step` (default 4) synthetic video frames per GPU:
 KNN blend weights once, then per frame  LBS warp -> main rasterize fwd -> occlusion rasterize fwd (no grad) ->
@@ -12,7 +16,9 @@ backward through the main rasterizer and the warp, gradients of the shared Gauss
 with N > 1 the step ends with ONE RCCL all-reduce of that buffer (frame data-parallel, weak scaling).
 Workload (default): BASELINE config C3 -- 100k Gaussians, 1080x1920, 400-frame sequence, batch = 4 frames.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the contract fields.  With --full the line also carries `roofline` (a per-kernel pass of K more
+steps with stage timers), `repeats_ms_per_step` (SOAR_BENCH_REPEAT more timed regions), `ranks` (several ranks: K more steps with
+timed gradient waits), `cpu_baseline` and `reference_same_box`; a plain run writes them as null / [].
 """
 from __future__ import annotations
 
@@ -531,6 +537,105 @@ def dry_run(args, world, rank):
         os.write(json_fd, (json.dumps(result) + "\n").encode())
 
 
+def training_state(seq, flat, plan, adam):
+    """Everything a step of the timed path reads that the steps before it wrote: the leaves, the gradient buffer (the eager plan
+    applies the previous step's gradients at the start of a step), Adam's moments and step counts, the plan's step count (which
+    steps run the full KNN search) and the KNN neighbour sets.  -> a snapshot for `restore_training_state`."""
+    flat.wait_all()                                              # (the gradient buckets still in flight land first)
+    tensors = list(flat.leaves.values()) + [flat.flat]
+    hosts = {}
+    if adam is not None:
+        tensors += list(adam.exp_avg.values()) + list(adam.exp_avg_sq.values()) + [adam.state]
+        hosts["adam"] = adam.steps
+    if plan is not None:
+        tensors += [plan.knn.state, plan.knn.order]
+        hosts["plan"], hosts["knn"] = plan.steps, plan.knn.calls
+    with torch.no_grad():
+        return tensors, [t.detach().clone() for t in tensors], hosts
+
+
+def restore_training_state(snapshot, flat, plan, adam, schedule=True):
+    """Stream-ordered copies back into the live tensors (no host synchronisation).  schedule=False keeps the plan's and the KNN's
+    step counts running, so that the full KNN searches stay where they are in a run of many steps."""
+    tensors, saved, hosts = snapshot
+    flat.wait_all()
+    with torch.no_grad():
+        for t, s in zip(tensors, saved):
+            t.detach().copy_(s)
+    if adam is not None:
+        adam.steps = hosts["adam"]
+    if plan is not None and schedule:
+        plan.steps, plan.knn.calls = hosts["plan"], hosts["knn"]
+
+
+# The timed steps train the model on synthetic targets.  Thousands of them in a row move it far from the workload the line names: its
+# instance count grows past the binning capacity measured in the warm-up (C3, --steps 10000 without the window: 1.83 M instances
+# needed, the capacity check fails; profiles/bench_train_window.txt).  Every TRAIN_WINDOW steps the timed path therefore takes back the
+# state it started the timed region from -- stream-ordered copies of the leaves, the gradient buffer, Adam's moments and the KNN
+# neighbour sets, some tens of MB at C3: expected to cost a few tens of us of device time per window, not measured on its own (with
+# the window, --steps 10000 times 0.765-0.766 ms per step against 0.764 for --steps 200) -- so that any number of steps times the same
+# workload.  Plain runs of up to TRAIN_WINDOW steps neither restore nor take the snapshot.
+TRAIN_WINDOW = 256
+
+
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all files together (64 MB)
+DUMP_PIXEL_SEED = 0
+
+
+def dump_outputs(out_dir, seq, flat, plan):
+    """--dump-outputs DIR: what a step of the timed path computed, as a caller of that path receives it, one float32 file per array
+    (DIR/<name>.npy), so that two builds run with the same arguments can be compared output for output.  The step is the timed
+    path's step over the frames of the last timed step, taken from the state after the path's first step (`main` restores it after
+    the timed region, step counts included): it runs every stage a timed step runs -- the optimizer's update of the previous step's
+    gradients and the certified KNN refresh among them.  It is not the last timed step itself: the timed steps train the model, and
+    after thousands of them the order of the backward's floating-point atomics has moved the parameters -- and everything computed
+    from them -- by far more than rounding from run to run.
+
+        grad_<leaf>    [P, w]  the step's gradients of the leaves, summed over its frames (and ranks): the flat gradient buffer
+        param_<leaf>   [P, w]  the leaves after the step: its Adam update applied (the eager plan applies the previous step's
+                               gradients at the start of a step, --mode plan the step's own at its end; other modes have no optimizer)
+        loss           [n]     the per-frame losses of the step                                    (step plan only)
+        image_<plane>  [n, c, S]  the frames' rendered planes (color, normal, depth, opac, occ) at S pixels (step plan only)
+
+    The pixels are a fixed sample (numpy seed DUMP_PIXEL_SEED, sorted flat indices into H x W), the same in every run of the same
+    workload; S is every pixel where that fits DUMP_LIMIT_BYTES with the rest, else as many as fit.  -> {name: shape}"""
+    arrays = {}
+    for name, t in flat.views.items():
+        arrays[f"grad_{name}"] = t.detach()
+    for name, t in flat.leaves.items():
+        arrays[f"param_{name}"] = t.detach()
+    planes = {}
+    if plan is not None:
+        arrays["loss"] = plan.losses.detach()
+        for key in ("color", "normal", "depth", "opac", "occ"):
+            planes[key] = torch.stack([v[key] for v in plan.views])                   # [n, c, H, W]
+    fixed = sum(t.numel() * 4 for t in arrays.values())
+    if planes:
+        n_frames, H, W = plan.n, plan.H, plan.W
+        per_pixel = 4 * sum(int(p.shape[0] * p.shape[1]) for p in planes.values())
+        S = min(H * W, (DUMP_LIMIT_BYTES - fixed - (1 << 20)) // per_pixel)             # (1 MB left for the files' headers)
+        if S < 1:
+            raise SystemExit(f"--dump-outputs: the step's other outputs alone need {fixed} bytes (limit {DUMP_LIMIT_BYTES})")
+        if S < H * W:
+            idx = np.sort(np.random.default_rng(DUMP_PIXEL_SEED).choice(H * W, size=S, replace=False))
+            idx = torch.from_numpy(idx).to(plan.device)
+        else:
+            idx = None
+        for key, p in planes.items():
+            flat_p = p.reshape(p.shape[0], p.shape[1], H * W)
+            arrays[f"image_{key}"] = flat_p if idx is None else flat_p.index_select(2, idx)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def visible_gpu_count():
     """GPUs this job can use, found WITHOUT any torch.cuda / HIP call in this process (the parent of the ranks must never
     initialise the GPU: its children are fresh processes, but a parent that touched HIP may not exec or fork safely on this
@@ -620,6 +725,14 @@ def main():
                          "stage on the video frame -- 0.8 masked L1 + 0.2 (1 - SSIM), mask L1, cosine normal loss through the "
                          "renderer's post-ops, loss_occ through the occlusion image's backward "
                          "(TS/system/gaussian_surfel_mvdream.py:305-338, 412-417) -- a second line, same units")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel pass and the roofline (unless --no-stage-timers), "
+                         "the repeated timed regions, the per-rank diagnostics of several ranks, the CPU baselines and the reference's "
+                         "kernels on the same box (unless --no-cpu-baseline).  Off: set-up, warm-up, the K timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run one step of the timed path from the state after its first step, over the last timed step's frames, "
+                         "and write what it computed (gradients, leaves, losses, a fixed sample of the "
+                         "rendered planes) as DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: N gloo ranks on the CPU with stand-in frames through the same launcher, rendezvous, frame sharding, flat gradient "
@@ -644,6 +757,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process only starts the ranks (it never touches the GPU itself) and relays rank 0's line
         raise SystemExit(launch_ranks(args.gpus))
@@ -715,12 +830,14 @@ def main():
         return shard_frames(global_batch(step, fps_per_rank, world, seq.num_frames, frame_stride), rank, world)
 
     # instances the occlusion pass renders (camera-facing surfels only): measured once with the unfused two-call form,
-    # outside the timed region, to price B_occ of SURVEY 8(d) with the real R
-    with torch.no_grad():
-        seq.render_frame(frames_of(0)[0], bg, with_occ=False)
-        R_main0 = max(rasterizer.last_num_rendered, 1)
-        seq.render_frame(frames_of(0)[0], bg, with_occ=True)
-    occ_ratio = rasterizer.last_num_rendered / R_main0          # camera-facing share of the instances (frame 0)
+    # outside the timed region, to price B_occ of SURVEY 8(d) with the real R (--full: only the roofline needs it)
+    occ_ratio = None
+    if args.full:
+        with torch.no_grad():
+            seq.render_frame(frames_of(0)[0], bg, with_occ=False)
+            R_main0 = max(rasterizer.last_num_rendered, 1)
+            seq.render_frame(frames_of(0)[0], bg, with_occ=True)
+        occ_ratio = rasterizer.last_num_rendered / R_main0      # camera-facing share of the instances (frame 0)
     # warm-up in the synchronous form; it also measures the instances per frame that bound the binning buffers of the
     # sync-free forms (2x the largest number seen; the device checks the bound, the host checks the flag after timing)
     for k in rasterizer.stats:
@@ -734,7 +851,7 @@ def main():
     capacity = None if args.mode == "sync" else 2 * r_seen
 
     mode, stepper = args.mode, None
-    plan = None
+    plan = adam = None
     if mode in ("plan", "plan-eager"):
         try:
             from soar_amd.step_plan import FrameStepPlan
@@ -770,7 +887,7 @@ def main():
             fallback = "graph" if (mode == "plan" and world == 1) else "async"
             print(f"[bench] step plan unavailable ({type(e).__name__}: {e}); falling back to --mode {fallback}", file=sys.stderr)
             torch.cuda.synchronize()
-            mode, plan, stepper = fallback, None, None
+            mode, plan, stepper, adam = fallback, None, None, None
     if mode == "graph":
         try:
             # the whole-step graph bakes its target pointers in: every frame uses target set 0 in this mode
@@ -782,8 +899,15 @@ def main():
             mode = "async"
     if stepper is None:
         stepper = lambda frames: run_step(seq, targets, flat, frames, bg, capacity)
+    state_first = None
     for s in range(2):                                           # untimed steps in the timed mode
         stepper(frames_of(s))
+        if s == 0 and args.dump_outputs:
+            # --dump-outputs takes its step from here: one step from the seeded model has run (KNN neighbour sets, gradients and,
+            # in --mode plan, Adam's moments are there), so a step from this state runs every stage a timed step runs -- the
+            # optimizer's update and the certified KNN refresh included -- while thousands of steps of training have not yet moved
+            # the model by more than rounding from run to run
+            state_first = training_state(seq, flat, plan, adam)
     # The interpreter's cyclic collector walks every tracked object of the process when its oldest generation comes due -- 35-70 ms
     # with torch imported, measured as ONE stall of the host around step 39 of the timed region, long enough for the device to run
     # dry (0.95 -> 1.0-1.36 ms per step, run to run).  What exists now stays: collected once, then moved out of the collector's sight
@@ -799,6 +923,19 @@ def main():
     # profiles/r05_bench_spread_20steps.txt).  The untimed steps that precede the timed region are issued HERE, right in front of it.
     for s in range(max(args.warmup, 2)):
         stepper(frames_of(s))
+    # the state the timed region starts from: the timed path returns to it every TRAIN_WINDOW steps, and --full's further regions
+    # start from it as well (the same K steps again, not K more steps of training).  A plain run of up to TRAIN_WINDOW steps never
+    # needs it and takes no snapshot
+    state_timed = training_state(seq, flat, plan, adam) if (args.full or args.steps > TRAIN_WINDOW) else None
+    step_once, steps_in_window, steps_called = stepper, [0], [0]
+
+    def stepper(frames):
+        if steps_in_window[0] == TRAIN_WINDOW:
+            restore_training_state(state_timed, flat, plan, adam, schedule=False)
+            steps_in_window[0] = 0
+        steps_in_window[0] += 1
+        steps_called[0] += 1
+        step_once(frames)
     step_marks = [] if os.environ.get("SOAR_BENCH_STEP_TIMES", "0") == "1" else None      # (diagnostic: when the host issued every step)
     # the same region on the device's clock: a HIP event pair on the stream the steps are issued on (every step of the plan ends on
     # it) -- `value` stays the host's wall clock between the synchronisations, as the contract says; both are in the line
@@ -809,6 +946,24 @@ def main():
         per = [1e3 * (b - a) for a, b in zip([0.0] + step_marks[:-1], step_marks)]
         print("[bench] host issue per step (ms): " + " ".join(f"{v:.2f}" for v in per), file=sys.stderr)
     device_ms_per_step = ev_begin.elapsed_time(ev_end) / args.steps
+    steps_timed = steps_called[0]                                # steps the timed region issued (== --steps)
+    # the KNN refreshes of the steps up to here (what --dump-outputs and --full run below does not count)
+    knn_counts = (int(plan.knn.searched.item()), plan.steps) if plan is not None else None
+    if args.dump_outputs:
+        # the last timed step's frames, one step of the timed path from the state after its first step, with the schedule of that
+        # state: a plan step > 0, so the optimizer's update and the certified KNN refresh run (every rank: the step ends in its
+        # collectives)
+        flat.wait_all()
+        torch.cuda.synchronize()
+        restore_training_state(state_first, flat, plan, adam)
+        step_once(frames_of(args.warmup + args.steps - 1))
+        flat.wait_all()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, seq, flat, plan)
+            print(f"[bench] outputs of the step from the state after the first step in {args.dump_outputs}: {dumped}", file=sys.stderr)
+    # --full only: the per-kernel pass (roofline), the repeated regions and the ranks' diagnostics below
+    stage_timers = args.full and not args.no_stage_timers
     stats_timed = stats_warm                                     # real num_rendered per launch, from the synchronous warm-up
     # (this pass comes right behind the contract's timed region, in FRONT of the repeated regions: after half a second more of full load
     # the chip's clock has given back 3-6 % -- `repeats_ms_per_step` drifts by that much -- and the durations priced against the
@@ -818,7 +973,12 @@ def main():
     #      of a step overlap on separate streams and share the GPU).  Not part of `value`.
     frames_per_launch = 1
     batched_plan = plan is not None and plan.graphs is None and plan.batched and not use_dist
-    if not args.no_stage_timers and batched_plan:
+    if args.full:
+        flat.wait_all()
+        torch.cuda.synchronize()
+        restore_training_state(state_timed, flat, plan, adam)
+        steps_in_window[0] = 0
+    if stage_timers and batched_plan:
         # the timed region's own launches: every stage of the chain is ONE launch for the frames of a step, on one stream -- a
         # launch has a duration of its own, so the same plan runs the same K steps again with the event pairs switched on
         frames_per_launch = fps_per_rank
@@ -830,7 +990,7 @@ def main():
         L.soar_prof_enable(0)
         for k, v in stats_timed.items():
             rasterizer.stats[k] = v
-    elif not args.no_stage_timers:
+    elif stage_timers:
         streams_timed = rasterizer.NUM_STREAMS
         rasterizer.NUM_STREAMS = 1
         L.soar_prof_reset()
@@ -850,8 +1010,11 @@ def main():
     # over the ranks).  `value` stays the FIRST region's; these are `repeats_ms_per_step`.  With a 17 ms region one collector pause or
     # clock ramp is several per cent: the list says whether the first region was typical.
     repeats_ms = []
-    for rep in range(int(os.environ.get("SOAR_BENCH_REPEAT", "4"))):
+    for rep in range(int(os.environ.get("SOAR_BENCH_REPEAT", "4")) if args.full else 0):
+        flat.wait_all()
         torch.cuda.synchronize()
+        restore_training_state(state_timed, flat, plan, adam)
+        steps_in_window[0] = 0
         if use_dist:
             dist.barrier()
         r0 = time.perf_counter()
@@ -878,7 +1041,11 @@ def main():
     #      max is the job's; the spread is the per-frame load imbalance SURVEY 8e expects), instances per rank, and -- from K more
     #      steps with HIP events around the stream-side waits -- what of each gradient bucket's flight the step did NOT hide.
     dist_diag = None
-    if use_dist:
+    if use_dist and args.full:
+        flat.wait_all()
+        torch.cuda.synchronize()
+        restore_training_state(state_timed, flat, plan, adam)
+        steps_in_window[0] = 0
         dist_diag = rank_diagnostics(flat, stepper, frames_of, args, world, device, local_elapsed,
                                      float(max((n for n, _ in binning_status), default=0)) if binning_status else 0.0)
     elapsed = job_elapsed(elapsed, use_dist, device)
@@ -890,7 +1057,7 @@ def main():
     # ---- roofline of the dominant kernel, from HIP events recorded on the launch stream during the timed region ----
     roof = None
     stages = {}
-    if not args.no_stage_timers:
+    if stage_timers:
         for i in range(L.soar_prof_stage_count()):
             ms, n = C.c_double(0), C.c_int64(0)
             L.soar_prof_read(i, C.byref(ms), C.byref(n))
@@ -973,7 +1140,7 @@ def main():
                    "optimizer": ("Adam (eps 1e-15), one launch over all leaves, the reference's learning rates on the activated leaves "
                                  "(xyz 1.6e-5, rotation 1e-3, scale 5e-5 = 0.5 %, colour 2.5e-3): inside the timed step"
                                  if plan is not None else "none (gradients only)"),
-                   "knn": (f"neighbour sets kept on the device: {int(plan.knn.searched.item())} of {plan.steps * P} query refreshes "
+                   "knn": (f"neighbour sets kept on the device: {knn_counts[0]} of {knn_counts[1] * P} query refreshes "
                            f"needed the seeded search, the others were certified; full search every {plan.RESORT_EVERY} steps"
                            if plan is not None else "full grid search per step"),
                    "model_order": ("generator's random order (SOAR_BENCH_RANDOM_ORDER=1)" if os.environ.get("SOAR_BENCH_RANDOM_ORDER", "0") == "1" else
@@ -986,6 +1153,8 @@ def main():
                    # how long the HOST needed to issue the K timed steps, per step: close to ms_per_step = the run was bound by the
                    # host's launch rate (a slow or shared CPU), not by the device
                    "host_issue_ms_per_step": round(1e3 * host_issue / args.steps, 3),
+                   # steps the timed region issued, counted where they are issued
+                   "steps_timed": steps_timed,
                    # the timed region by a HIP event pair on the issuing stream (ms_per_step is the host's clock between the two
                    # synchronisations; the two differ by the first launch's latency and the last synchronisation's return)
                    "device_events_ms_per_step": round(device_ms_per_step, 4),
@@ -995,13 +1164,15 @@ def main():
                    "host_gc": "gc.collect() + gc.freeze() in front of the timed region (README: what a training loop should do after its set-up); "
                               "SOAR_BENCH_NO_GC_FREEZE=1 times the steps without it",
                    "num_rendered_main": int(rasterizer.stats["num_rendered"] / max(rasterizer.stats["forward_calls"], 1)),
-                   "num_rendered_occ": int(occ_ratio * rasterizer.stats["num_rendered"] / max(rasterizer.stats["forward_calls"], 1))},
+                   "num_rendered_occ": (int(occ_ratio * rasterizer.stats["num_rendered"] / max(rasterizer.stats["forward_calls"], 1))
+                                        if occ_ratio is not None else None)},
         "roofline": roof,
     }
     if dist_diag is not None:
         result["ranks"] = dist_diag
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        cpu_legs = args.full and world == 1 and not args.no_cpu_baseline
+        if cpu_legs:
             try:
                 result["cpu_baseline"] = cpu_baseline(args.workload, parts)
             except Exception as ex:          # the baseline must never hide the GPU number
@@ -1009,7 +1180,7 @@ def main():
                                           "sample": f"failed: {ex!r}"}
         else:
             result["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_legs:
             result["reference_same_box"] = reference_same_box(args.workload, device)
     if use_dist:
         dist.destroy_process_group()

@@ -13,6 +13,6 @@ export SOAR_PLAN_BATCHED=0
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-stage-timers > $out/pmc_fetch.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-stage-timers > $out/pmc_write.log 2>&1
 unset SOAR_PLAN_BATCHED
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 tail -1 $out/bench_default.json
 find $out -name "*kernel_stats.csv" | head -3

@@ -5,7 +5,7 @@ for kv in "$@"; do export "$kv"; done
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests/test_rasterizer_gpu.py tests/test_reference_build_gpu.py -m gpu -x -q > $out/pytest.log 2>&1; echo "pytest rc $?"; tail -2 $out/pytest.log
-python bench.py --no-cpu-baseline > $out/bench.json 2> $out/bench.err
+python bench.py --full --no-cpu-baseline > $out/bench.json 2> $out/bench.err
 python3 - <<PY
 import json
 d = json.loads(open("$out/bench.json").read().strip().splitlines()[-1])

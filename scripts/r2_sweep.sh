@@ -7,7 +7,7 @@ first=1
 for v in "$@"; do
   export $var=$v
   if [ $first = 1 ]; then first=0; timeout 900 python -m pytest tests/test_rasterizer_gpu.py tests/test_reference_build_gpu.py -m gpu -x -q > $out/pytest_$v.log 2>&1; echo "$var=$v pytest rc $?: $(tail -1 $out/pytest_$v.log)"; fi
-  python bench.py --no-cpu-baseline > $out/bench_$v.json 2> $out/bench_$v.err
+  python bench.py --full --no-cpu-baseline > $out/bench_$v.json 2> $out/bench_$v.err
   python3 - <<PY
 import json
 d = json.loads(open("$out/bench_$v.json").read().strip().splitlines()[-1])

@@ -18,10 +18,10 @@ python3 scripts/make_traffic_json.py $out $out/hbm_traffic.json > $out/hbm_traff
 # 3. SQ counters of the two blend kernels (batched launches)
 bash scripts/pmc_kernel.sh "render_" > $out/sq_counters.txt 2>&1
 # 4. the bench lines: default (with the CPU baselines), the avatar-loss form, the forced RCCL path, C5
-python3 bench.py --pmc-json $out/hbm_traffic.json > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --loss avatar --no-cpu-baseline > $out/bench_avatar.json 2> $out/bench_avatar.err
+python3 bench.py --full --pmc-json $out/hbm_traffic.json > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --loss avatar --no-cpu-baseline > $out/bench_avatar.json 2> $out/bench_avatar.err
 SOAR_BENCH_FORCE_DIST=1 python3 bench.py --no-cpu-baseline --no-stage-timers > $out/bench_forced_dist.json 2> $out/bench_forced_dist.err
-python3 bench.py --workload C5 --no-cpu-baseline --steps 20 > $out/bench_C5.json 2> $out/bench_C5.err
+python3 bench.py --full --workload C5 --no-cpu-baseline --steps 20 > $out/bench_C5.json 2> $out/bench_C5.err
 cat $out/batched_launches.txt
 for f in default avatar forced_dist C5; do python3 -c "
 import json,sys

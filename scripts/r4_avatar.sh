@@ -4,7 +4,7 @@ export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 python -m pytest tests/test_plugin_gpu.py tests/test_training_gpu.py tests/test_bench_gpu.py -x -q -m gpu -k "avatar or loss or fused_view or training or plan" > $out/tests.txt 2>&1
 tail -6 $out/tests.txt
 for r in 1 2 3; do
-python bench.py --loss avatar --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_avatar_$r.json
+python bench.py --full --loss avatar --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_avatar_$r.json
 python - $out/bench_avatar_$r.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -3,7 +3,7 @@
 tag=${1:-avatar}; out=$GRAFT_REPO_ROOT/gpurun_out/r4_$tag; mkdir -p $out
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python3 bench.py --loss avatar --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_avatar_C3.json
+python3 bench.py --full --loss avatar --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_avatar_C3.json
 python3 - $out/bench_avatar_C3.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

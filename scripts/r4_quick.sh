@@ -3,7 +3,7 @@ tag=${1:-quick}; out=gpurun_out/r4_$tag; mkdir -p $out
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 python -m pytest tests/test_rasterizer_gpu.py tests/test_reference_build_gpu.py tests/test_plugin_gpu.py tests/test_training_gpu.py -x -q -m gpu ${2:+-k "$2"} > $out/tests.txt 2>&1
 tail -4 $out/tests.txt
-python bench.py --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_C3.json
+python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_C3.json
 python - $out/bench_C3.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

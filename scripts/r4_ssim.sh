@@ -4,7 +4,7 @@ export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 python3 -m pytest tests/test_plugin_gpu.py tests/test_training_gpu.py -x -q -m gpu -k "ssim or avatar or loss" > $out/tests.txt 2>&1
 tail -4 $out/tests.txt
-python3 bench.py --loss avatar --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_avatar_C3.json
+python3 bench.py --full --loss avatar --steps 100 --warmup 5 --no-cpu-baseline 2> $out/bench.err | tail -1 > $out/bench_avatar_C3.json
 python3 - $out/bench_avatar_C3.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -4,7 +4,7 @@ export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 timeout 3000 python -m pytest tests -x -q -m gpu > $out/tests.txt 2>&1
 tail -3 $out/tests.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py --gpus 1 --steps 20 --warmup 5 2> $out/bench.err | tail -1 > $out/bench_driver_form.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2> $out/bench.err | tail -1 > $out/bench_driver_form.json
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r5_final/bench_driver_form.json"))

@@ -18,15 +18,15 @@ python3 scripts/make_traffic_json.py $out $out/hbm_traffic.json > $out/hbm_traff
 # 3. SQ counters of the two blend kernels (batched launches)
 bash scripts/pmc_kernel.sh "render_" > $out/sq_counters.txt 2>&1
 # 4. the bench lines: default (with the CPU baselines), the avatar-loss form, C5, C2; the driver's exact command in five fresh processes
-python3 bench.py --pmc-json $out/hbm_traffic.json > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --loss avatar --no-cpu-baseline > $out/bench_avatar.json 2> $out/bench_avatar.err
-python3 bench.py --workload C5 --no-cpu-baseline --steps 40 > $out/bench_C5.json 2> $out/bench_C5.err
-python3 bench.py --workload C2 --no-cpu-baseline > $out/bench_C2.json 2> $out/bench_C2.err
+python3 bench.py --full --pmc-json $out/hbm_traffic.json > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --loss avatar --no-cpu-baseline > $out/bench_avatar.json 2> $out/bench_avatar.err
+python3 bench.py --full --workload C5 --no-cpu-baseline --steps 40 > $out/bench_C5.json 2> $out/bench_C5.err
+python3 bench.py --full --workload C2 --no-cpu-baseline > $out/bench_C2.json 2> $out/bench_C2.err
 for r in 1 2 3 4 5; do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --pmc-json $out/hbm_traffic.json 2> /dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --pmc-json $out/hbm_traffic.json 2> /dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
-print('python bench.py --gpus 1 --steps 20 --warmup 5: %.1f frames/s  %.4f ms/step (HIP event pair: %.4f)  host issue %.3f  frac %.4f counter_frac %s' % (d['value'], d['ms_per_step'], d['config']['device_events_ms_per_step'], d['config']['host_issue_ms_per_step'], r['frac'], r.get('counter_frac')))"
+print('python bench.py --full --gpus 1 --steps 20 --warmup 5: %.1f frames/s  %.4f ms/step (HIP event pair: %.4f)  host issue %.3f  frac %.4f counter_frac %s' % (d['value'], d['ms_per_step'], d['config']['device_events_ms_per_step'], d['config']['host_issue_ms_per_step'], r['frac'], r.get('counter_frac')))"
 done > $out/bench_spread.txt
 for r in 1 2 3; do
   python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-stage-timers 2> /dev/null | tail -1 | python3 -c "

@@ -1,7 +1,7 @@
 # round 6, GPU box: pairs of blocks (-DSOAR_BWD_REGION=2) with float64 accumulation rows: what it costs, and whether the strict C3 bar holds
 out=gpurun_out/r6_region2_f64; mkdir -p $out
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
-run() { python "$@" --steps 100 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%8.1f us  %.3f ms/step' % (d['roofline']['stage_us']['render_backward'], d['ms_per_step']))"; }
+run() { python "$@" --full --steps 100 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%8.1f us  %.3f ms/step' % (d['roofline']['stage_us']['render_backward'], d['ms_per_step']))"; }
 {
 echo -n "default                       "; run bench.py
 echo -n "default, float64 rows         "; SOAR_DETERMINISTIC_BACKWARD=1 run bench.py

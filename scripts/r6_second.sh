@@ -17,7 +17,7 @@ for i in $(seq 1 8); do
   SOAR_HIP_LIB=$PWD/soar_amd/_lib/variants/region2.so timeout 600 python -m pytest tests/test_reference_build_gpu.py -q -m gpu -s -k "C3_100k_1080p or c3_frame_with" 2>&1 | grep -E "^C3|passed|failed|dL_drotations" >> $out/region2_c3_8x.txt
 done
 tail -30 $out/region2_c3_8x.txt | cut -c1-400
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2> $out/bench.err | tail -1 > $out/bench.json
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 2> $out/bench.err | tail -1 > $out/bench.json
 python - $out/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -1,4 +1,5 @@
-"""bench.py keeps its output contract: ONE JSON line with the metric fields, the roofline object and the cpu_baseline object."""
+"""bench.py keeps its output contract: ONE JSON line with the metric fields; with --full also the roofline object and the cpu_baseline
+object; --dump-outputs writes what one more step of the timed path computed, from the state after the path's first step."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("mode", ["plan", "plan-eager"])
 def test_bench_line_schema(mode):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
-                        "--mode", mode], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--mode", mode, "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -43,11 +44,64 @@ def test_bench_line_schema(mode):
         assert rb["fwd_ms"] > 0 and rb["bwd_ms"] > 0 and rb["product_one_view_fwd_ms"] > 0 and "context only" in rb["build"], rb
 
 
+def _plain_run(steps, dump_dir=None):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", str(steps), "--warmup", "2"]
+    r = subprocess.run(cmd + (["--dump-outputs", str(dump_dir)] if dump_dir else []), capture_output=True, text=True, timeout=600,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """Without --full the line keeps its headline fields and leaves out what takes runs of its own (roofline, repeats, baselines);
+    --steps sets the number of timed steps (counted where they are issued, and the timed region grows with them); --dump-outputs
+    writes, in float32 and under 64 MB, what one more step of the timed path computed from the state after the path's first step --
+    a step that applies Adam like every timed step, so the leaves it leaves behind are not the seeded ones -- and two runs agree up
+    to the order of the backward's floating-point atomics."""
+    import numpy as np
+    from soar_amd import synthetic as syn
+    d = _plain_run(5, tmp_path / "a")
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["config"]["mode"] == "plan-eager" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4 * 1000.0 / d["ms_per_step"]) <= d["value"] * (0.00051 / d["ms_per_step"] + 1e-6)
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["repeats_ms_per_step"] == [] and "reference_same_box" not in d
+    d40 = _plain_run(40)
+    assert d["config"]["steps_timed"] == 5 and d40["config"]["steps_timed"] == 40
+    # eight times the steps: the timed region (host clock and device events alike) takes several times as long
+    assert 40 * d40["ms_per_step"] > 3 * 5 * d["ms_per_step"]
+    assert 40 * d40["config"]["device_events_ms_per_step"] > 3 * 5 * d["config"]["device_events_ms_per_step"]
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    for leaf in ("xyz", "rot", "scales", "colors"):
+        assert f"grad_{leaf}" in names and f"param_{leaf}" in names
+    for plane in ("color", "normal", "depth", "opac", "occ"):
+        assert f"image_{plane}" in names
+    assert "loss" in names
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in names) <= 64_000_000
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["loss"].shape == (4,) and a["image_color"].shape == (4, 3, 256 * 192) and np.abs(a["grad_xyz"]).max() > 0
+    # the dumped step applied the optimizer's update: its leaves are not the seeded model's (bench.build_sequence's, Morton order)
+    seeded = syn.sort_surfels_spatially(syn.make_surfels(5_000, 0))
+    for leaf, t in (("xyz", seeded.xyz), ("rot", seeded.rot), ("scales", seeded.scales), ("colors", seeded.colors)):
+        assert a[f"param_{leaf}"].shape == tuple(t.shape)
+        assert (a[f"param_{leaf}"] != t.numpy()).mean() > 0.01, leaf
+    _plain_run(5, tmp_path / "b")
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in names}
+    for n in names:
+        scale = max(float(np.abs(a[n]).max()), 1e-30)
+        close = np.abs(a[n] - b[n]) <= 1e-3 * scale
+        # (a pixel whose last contributor flips with a last-bit difference of the parameters, the gradients it feeds, and an Adam
+        # update whose gradient is zero up to that order -- its sign then goes either way -- may differ)
+        assert close.all() if n == "loss" else close.mean() >= (0.999 if n.startswith("param_") else 0.99), (n, close.mean())
+
+
 def test_bench_avatar_loss_line():
     """`bench.py --loss avatar`: the second line -- the reference's avatar-stage losses in the step plan, Adam also on the occlusion
     values -- keeps the one-line contract; its roofline kernel is one of the stages that are one launch per step."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
-                        "--loss", "avatar", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--loss", "avatar", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -64,7 +118,7 @@ def test_bench_forced_dist_path_runs_rccl():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -80,7 +134,8 @@ def test_bench_forced_dist_path_runs_rccl():
     # stream (SOAR_DP_BUCKETS=0): same line, same shape
     for buckets in ("2", "0"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "4", "--warmup", "1",
-                            "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(env, SOAR_DP_BUCKETS=buckets))
+                            "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT,
+                           env=dict(env, SOAR_DP_BUCKETS=buckets))
         assert r.returncode == 0, r.stderr[-2000:]
         d1 = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
         assert d1["ranks"]["buckets"] == int(buckets) and d1["value"] > 0
