@@ -642,7 +642,7 @@ int soar_views_backward(const SoarPoseArgs *pose, int32_t n_views, const SoarVie
  * views.  soar_step_views_forward / _backward take n_poses poses with views_per_pose[p] views each (`views`: pose after pose, at most
  * 8 in all): every pose is warped once each way; front views of one size and capacity -- of ANY pose -- share their launches, one per
  * stage; the groups (another size, a back view) are issued on streams of the library's own beside each other, forked from `stream`
- * behind the warps and joined into it before the call returns (SOAR_STEP_STREAMS=0: all on `stream`).  Every pose carries its own
+ * behind the warps and joined into it before the call returns.  Every pose carries its own
  * gradient outputs: the caller adds the poses' contributions to a shared model.  soar_views_forward / _backward are the n_poses = 1 forms. */
 int soar_step_views_forward(int32_t n_poses, const SoarPoseArgs *poses, const int32_t *views_per_pose, const SoarViewArgs *views, void *stream);
 int soar_step_views_backward(int32_t n_poses, const SoarPoseArgs *poses, const int32_t *views_per_pose, const SoarViewArgs *views, void *stream);

@@ -121,7 +121,7 @@ extern "C" int ref_rast_state(void *h_, float *means2D, float *depths, float *co
 // order) or in float64 as well (mode 2: "f64" -- the value the formulas define).  The skip decisions (:653-680) are the FLOAT ones in both
 // modes, with the device expf the reference's own kernels call: they must be the decisions the forward made when it counted n_contrib.
 // The 13 sums, rounded once to float, then go through the reference's own BACKWARD::preprocess (float, as the reference runs it).
-// TEST INFRASTRUCTURE: scripts/r6_c5_triangle.py, tests/test_reference_build_gpu.py.
+// TEST INFRASTRUCTURE: scripts/c5_triangle.py, tests/test_reference_build_gpu.py.
 // ================================================================================================================================
 #include "backward.h"
 

@@ -3,7 +3,7 @@ backward-blend formulas that no float atomic order enters -- `order-free` (the r
 float64) and `f64` (per-pixel recurrences in float64 as well: the value the formulas define) --, all over the reference's own forward state and
 followed by the reference's own per-Gaussian backward (oracle/ref_build/ref_shim.hip: ref_rast_backward_wide).
 
-    python scripts/r6_c5_triangle.py [--scene C5|C3] [--grads noise|loss] [--variants name=lib.so ...] [--runs N]
+    python scripts/c5_triangle.py [--scene C5|C3] [--grads noise|loss] [--variants name=lib.so ...] [--runs N]
 
 A product variant is a library built by scripts/variant.py; each runs in a child process (SOAR_HIP_LIB).  `fp64rows` = the default build
 with float64 accumulation rows.  Distances are (max-norm, L2) relative to the f64 tensor's largest value / norm."""

@@ -463,7 +463,7 @@ item_cost_kernel(const uint32_t *__restrict__ q_keys, int P, const GridMeta *__r
             for (int off = 32; off > 0; off >>= 1) n5 += (uint32_t)__shfl_xor((int)n5, off);
             n += (uint32_t)__builtin_amdgcn_readfirstlane((int)n5);      // both boxes are scanned
         }
-        // measured: ~0.08 us per candidate + ~0.7 us per query + 12 us per segment (scripts/knn_log.py)
+        // measured: ~0.08 us per candidate + ~0.7 us per query + 12 us per segment (the per-wave timing log)
         const uint32_t us100 = 8u * n + 70u * (uint32_t)__builtin_popcountll(mine) + 1200u;
 #pragma unroll
         for (int k = 0; k < KNN_SLOTS; k++) item[k] += (seg % KNN_SLOTS) == k ? us100 : 0u;
@@ -490,7 +490,7 @@ __global__ void __launch_bounds__(1024) item_order_kernel(const uint32_t *__rest
     if (tid == 0) order[n_items] = KNN_ORDER_STAMP ^ (uint32_t)n_items;      // "this workspace holds an order for n_items items"
 }
 
-template <bool WITH_IDX, bool LOG = false>
+template <bool WITH_IDX>
 // five wavefronts per SIMD (96 VGPRs, 16 bytes of scratch per lane) against four at 110: 139 -> 132 us
 __global__ void __launch_bounds__(KNN_WAVES *WAVE) __attribute__((amdgpu_waves_per_eu(5, 8)))
 knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__restrict__ meta,
@@ -498,8 +498,7 @@ knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__r
                 const uint32_t *__restrict__ q_keys, const uint32_t *__restrict__ q_ids,
                 const float *__restrict__ rows_padded, int J, float *__restrict__ weights_out,
                 int32_t *__restrict__ knn_idx_out, const uint32_t *__restrict__ item_order,
-                KnnStatePtrs state,
-                unsigned long long *__restrict__ wave_log = nullptr)
+                KnnStatePtrs state)
 {
     constexpr int K = KNN_K;
     __shared__ float4 cand[KNN_CAND];                      // {x, y, z, sorted position}
@@ -510,8 +509,6 @@ knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__r
     __shared__ int need_s[WAVE];
     __shared__ uint32_t list_pos[KNN_WAVES][WAVE];         // the (<= K) neighbours of the query a wavefront is blending
     __shared__ float list_w[KNN_WAVES][WAVE];
-    unsigned long long t_start = 0, n_cand = 0, n_blend = 0, n_pairs = 0;
-    if (LOG) t_start = wall_clock64();
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // heaviest items first -- when the workspace holds an order for this launch (a call that keeps a stored query order on a
@@ -544,7 +541,6 @@ knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__r
         remaining &= ~__ballot(active);
         if ((seg % KNN_SLOTS) != slot) continue;
         const int cx = (int)(c % GRID_MAX), cy = (int)((c / GRID_MAX) % GRID_MAX), cz = (int)(c / (GRID_MAX * GRID_MAX));
-        if (LOG) n_pairs++;
 
         // ---- pass 1 (lane = query): the K smallest squared distances of every query; each wavefront scans a quarter
         //      of the candidates, the four sorted lists are merged through LDS; the box grows until every query is
@@ -556,7 +552,6 @@ knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__r
             __syncthreads();
             N = info[0];
             n_rows = info[1];
-            if (LOG) n_cand += N;
             float best[K];
 #pragma unroll
             for (int k = 0; k < K; k++) best[k] = 3.0e38f;
@@ -653,7 +648,6 @@ knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__r
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 cnt = min(cnt, WAVE);
-                if (LOG) n_blend += cnt;
                 // ws = (1/d) / sum(1/d), d = clamp(sqrt(d2), 1e-4, 1)   (smpl.py:630-634); normalised at the end
                 if (lane < cnt) lw[lane] = 1.0f / fminf(fmaxf(sqrtf(lw[lane]), 0.0001f), 1.0f);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -702,10 +696,6 @@ knn_cell_kernel(const float *__restrict__ xyz, int P, int V, const GridMeta *__r
                 if (lane < J) weights_out[(size_t)pl * J + lane] /= nl;
             }
         }
-    }
-    if (LOG && lane == 0) {
-        unsigned long long *w = wave_log + ((size_t)blockIdx.x * KNN_WAVES + wave) * 8;
-        w[0] = t_start; w[1] = wall_clock64(); w[2] = n_pairs; w[3] = n_cand; w[4] = n_blend;
     }
 }
 
@@ -969,11 +959,6 @@ knn_blend_search_kernel(const float *__restrict__ xyz, int P, int search_blocks,
     for (uint32_t w = searcher / KNN_WORK_LISTS; w < n_mine; w += (uint32_t)search_blocks * KNN_WAVES / KNN_WORK_LISTS) {
         const uint32_t *item = knn_work_item(st.work, P, my_list, w);
         const size_t q = item[0];
-#ifdef SOAR_KNN_SEARCH_LOG
-        const unsigned long long lt0 = wall_clock64();
-        unsigned long long lt1 = lt0, lt2 = lt0;
-        int l_sel = 0, l_cand = 0, l_rows = 0, l_nin = 0;
-#endif
         // everything within the largest new distance to an old neighbour (there are at least K vertices that close) ...
         const float tau_ub = __uint_as_float(item[1]);
         const int p = order ? (int)order[q] : (int)q;
@@ -1004,9 +989,6 @@ knn_blend_search_kernel(const float *__restrict__ xyz, int P, int search_blocks,
             next_d2 = 3.0e38f;
             // keep the KEEP best of the n_in held candidates (ties in list = grid order), remember the best one dropped
             auto select_keep = [&]() {
-#ifdef SOAR_KNN_SEARCH_LOG
-                l_sel++;
-#endif
                 if (n_in <= WAVE) {
                     // the usual case (a ball seeded by the old set holds ~38 vertices): one candidate per lane, the others' distances by
                     // v_readlane instead of an LDS read per candidate and three slots of bookkeeping
@@ -1098,9 +1080,6 @@ knn_blend_search_kernel(const float *__restrict__ xyz, int P, int search_blocks,
                     if (lane >= d) incl += up;
                 }
                 const int n_cand = (int)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
-#ifdef SOAR_KNN_SEARCH_LOG
-                l_cand += n_cand; l_rows = n_rows;
-#endif
                 row_first[wave][lane] = rs;
                 row_end[wave][lane] = incl;                           // candidates of the rows 0 .. lane
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1160,9 +1139,6 @@ knn_blend_search_kernel(const float *__restrict__ xyz, int P, int search_blocks,
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // row_first / row_end are rewritten by the next 64 rows
                 __builtin_amdgcn_wave_barrier();
             }
-#ifdef SOAR_KNN_SEARCH_LOG
-            lt1 = wall_clock64(); l_nin = n_in;
-#endif
             if (n_in >= KEEP) { select_keep(); break; }               // n_in == KEEP now
         }
         if (!sane) {                                                  // (wave-uniform)
@@ -1174,9 +1150,6 @@ knn_blend_search_kernel(const float *__restrict__ xyz, int P, int search_blocks,
             }
             continue;
         }
-#ifdef SOAR_KNN_SEARCH_LOG
-        lt2 = wall_clock64();
-#endif
         const uint32_t pos = lane < KEEP ? cp[lane] : 0u;
         const float d2 = lane < KEEP ? cd[lane] : 3.0e38f;
         float far = lane < KEEP ? d2 : 0.f;
@@ -1194,23 +1167,11 @@ knn_blend_search_kernel(const float *__restrict__ xyz, int P, int search_blocks,
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-#ifdef SOAR_KNN_SEARCH_LOG
-        const unsigned long long lt3 = wall_clock64();
-#endif
         // (as one slot of the four-query blend: its row loads travel ten at a time -- the one-query chain of 30 (LDS read, row load,
         // multiply-add) steps came out of the compiler as 30 round trips one after the other here, 11 of a search's 26 us)
         slots_fill_pair(slots[wave], 0, lane < KNN_KEEP ? p : -1, mask, pos, d2, lane);
         if (lane == 0) { slots[wave].p[2] = -1; slots[wave].p[3] = -1; }
         slots_blend<SOAR_KNN_SEARCH_UNROLL>(slots[wave], lane, rows_padded, J, weights_out);
-#ifdef SOAR_KNN_SEARCH_LOG
-        if (lane == 0) {
-            const unsigned long long lt4 = wall_clock64();
-            float *lg = st.d2 + q * KNN_STATE_STRIDE;
-            auto put = [&](int k, float v) { lg[k] = -(1.f + v); };
-            put(0, (float)(lt4 - lt0)); put(1, (float)(lt1 - lt0)); put(2, (float)(lt2 - lt1)); put(3, (float)(lt3 - lt2)); put(4, (float)(lt4 - lt3));
-            put(5, (float)growths); put(6, (float)l_sel); put(7, (float)l_cand); put(8, (float)l_rows); put(9, (float)l_nin);
-        }
-#endif
     }
     // The last of a list's searchers to get here empties the list for the next refresh (a memset launch in front of the certificate
     // kernel was 4.7 us of a 64 us refresh) and adds its length to the statistics: every searcher has read the length by then.
@@ -1371,30 +1332,12 @@ int knn_query(const KnnGrid &g, int32_t V, const float *vert_weights, int32_t J,
         hipLaunchKernelGGL(item_order_kernel, dim3(1), dim3(1024), 0, stream, ws.item_cost, nchunks * KNN_SLOTS, ws.item_order);
     }
     const dim3 grid(((P + WAVE - 1) / WAVE) * KNN_SLOTS);
-    const uint32_t *chunk_order = getenv("SOAR_KNN_NO_ORDER") ? nullptr : ws.item_order;         // development switch
-    const char *log_path = getenv("SOAR_KNN_LOG");            // diagnostic: per-wave timeline of one launch
-    if (log_path && !knn_idx_out) {
-        unsigned long long *log_dev = nullptr;
-        const size_t nbytes = sizeof(unsigned long long) * 8 * (size_t)grid.x * KNN_WAVES;
-        SOAR_HIP_OK(hipMalloc(&log_dev, nbytes));
-        SOAR_HIP_OK(hipMemsetAsync(log_dev, 0, nbytes, stream));
-        hipLaunchKernelGGL((knn_cell_kernel<false, true>), grid, dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, V, g.meta, g.cell_range,
-                           g.sorted_verts, qk1, qv1, g.rows, J, weights_out, knn_idx_out, chunk_order, st, log_dev);
-        SOAR_HIP_OK(hipStreamSynchronize(stream));
-        unsigned long long *host = (unsigned long long *)malloc(nbytes);
-        SOAR_HIP_OK(hipMemcpy(host, log_dev, nbytes, hipMemcpyDeviceToHost));
-        FILE *f = fopen(log_path, "wb");
-        if (f) { fwrite(host, 1, nbytes, f); fclose(f); }
-        free(host);
-        (void)hipFree(log_dev);
-        return 0;
-    }
     if (knn_idx_out)
         hipLaunchKernelGGL(knn_cell_kernel<true>, grid, dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, V, g.meta, g.cell_range,
-                           g.sorted_verts, qk1, qv1, g.rows, J, weights_out, knn_idx_out, chunk_order, st);
+                           g.sorted_verts, qk1, qv1, g.rows, J, weights_out, knn_idx_out, ws.item_order, st);
     else
         hipLaunchKernelGGL(knn_cell_kernel<false>, grid, dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, V, g.meta, g.cell_range,
-                           g.sorted_verts, qk1, qv1, g.rows, J, weights_out, knn_idx_out, chunk_order, st);
+                           g.sorted_verts, qk1, qv1, g.rows, J, weights_out, knn_idx_out, ws.item_order, st);
     SOAR_LAUNCH_OK("lbs_knn_weights", stream, 0);
     return 0;
 }
@@ -1526,15 +1469,8 @@ extern "C" int soar_lbs_knn_refresh(const void *grid_buffer, int32_t V, int32_t 
     static_assert(SOAR_KNN_SEARCH_BLOCKS * KNN_WAVES % KNN_WORK_LISTS == 0, "searchers per list");
     hipLaunchKernelGGL(knn_certify_kernel, dim3(nblocks), dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, g.sorted_verts, order, st.p);
     const int search_blocks = SOAR_KNN_SEARCH_BLOCKS, blend_blocks = (P + KNN_WAVES * KNN_FSLOTS - 1) / (KNN_WAVES * KNN_FSLOTS);
-#ifdef SOAR_KNN_SPLIT_LAUNCH      // diagnostic build: the two halves of the second launch one after the other (what each takes alone)
-    hipLaunchKernelGGL(knn_blend_search_kernel, dim3(blend_blocks), dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, 0,
-                       g.meta, g.cell_range, g.sorted_verts, g.rows, J, order, st.p, weights_out, searched_counter_dev);
-    hipLaunchKernelGGL(knn_blend_search_kernel, dim3(search_blocks), dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, search_blocks,
-                       g.meta, g.cell_range, g.sorted_verts, g.rows, J, order, st.p, weights_out, searched_counter_dev);
-#else
     hipLaunchKernelGGL(knn_blend_search_kernel, dim3(search_blocks + blend_blocks), dim3(KNN_WAVES * WAVE), 0, stream, xyz, P, search_blocks,
                        g.meta, g.cell_range, g.sorted_verts, g.rows, J, order, st.p, weights_out, searched_counter_dev);
-#endif
     SOAR_LAUNCH_OK("lbs_knn_refresh", stream, 0);
     return 0;
 }

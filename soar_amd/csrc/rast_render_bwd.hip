@@ -149,9 +149,6 @@ __device__ __forceinline__ void load_pixel_at_once(const BwdArgs &a, int px, int
 // About 100 vector instructions per (pixel, 64 entries) against 160 + 28; T in front of an entry is T_in / (product) with one
 // reciprocal instead of a chain of divisions -- inside the gradient tolerance like the shared reciprocal of the other form
 // (the forward's T, n_contrib and final_T are not touched by any of this).
-#ifdef SOAR_BWD_HIST
-__device__ unsigned long long g_bwd_hist[16];
-#endif
 constexpr int DPP_WAVE_SHR1 = 0x138;
 // REGION = the 4 x 4 blocks a wavefront takes: 1, 2 (side by side: 8 x 4 pixels) or the 4 of a quad.  A pair leaves 40 % fewer
 // accumulation rows and record gathers for 20 % more pixel steps: at C3 242 -> 219 us per 4-frame launch (a quad: 300; on small
@@ -635,11 +632,7 @@ __device__ __forceinline__ void backward_block(const BwdArgs &a, const int rank,
         for (int k = 0; k < KMAX; k++) {
             if (has_q && g[k] != 0xFFFFFFFFu) {
                 if (WIDE) atomicAdd(a.acc64 + (size_t)g[k] * ACC_STRIDE + q, (double)v[k]);
-#ifdef SOAR_EXP_NO_ATOMICS
-                else if (g[k] == 0xFFFFFFFEu) a.acc[q] = v[k];
-#else
                 else atomicAdd(a.acc + (size_t)g[k] * ACC_STRIDE + q, v[k]);
-#endif
             }
         }
     };
@@ -668,11 +661,7 @@ __device__ __forceinline__ void backward_block(const BwdArgs &a, const int rank,
         for (int k = 0; k < 16; k++) {
             if (has_q && g[k] != 0xFFFFFFFFu) {
                 if (WIDE) atomicAdd(a.acc64 + (size_t)g[k] * ACC_STRIDE + q, (double)v[k]);
-#ifdef SOAR_EXP_NO_ATOMICS
-                else if (g[k] == 0xFFFFFFFEu) a.acc[q] = v[k];       // (development, results wrong by construction: what the launch costs without them)
-#else
                 else atomicAdd(a.acc + (size_t)g[k] * ACC_STRIDE + q, v[k]);
-#endif
             }
         }
     };
@@ -700,13 +689,6 @@ __device__ __forceinline__ void backward_block(const BwdArgs &a, const int rank,
         // ---- one batch: cnt_e entries x the pixels that reach it
         const uint32_t nearest = (uint32_t)__builtin_amdgcn_readlane((int)epos, cnt_e - 1);
         unsigned long long act = __ballot(vLast > nearest) & (NPIX == 64 ? ~0ull : (1ull << (NPIX & 63)) - 1ull);
-#ifdef SOAR_BWD_HIST
-        if (lane == 0) {     // development (scripts/bwd_hist.py): pixel steps / batches by the batch's entry count
-            const int bk = cnt_e <= 8 ? 0 : cnt_e <= 16 ? 1 : cnt_e <= 32 ? 2 : cnt_e < 64 ? 3 : 4;
-            atomicAdd(&g_bwd_hist[bk], (unsigned long long)__builtin_popcountll(act));
-            atomicAdd(&g_bwd_hist[8 + bk], 1ull);
-        }
-#endif
         float acc[13];
 #pragma unroll
         for (int q = 0; q < 13; q++) acc[q] = 0.f;
@@ -1004,10 +986,3 @@ extern "C" int soar_selftest_affine_scan(const float *m64_dev, const float *b64_
     SOAR_LAUNCH_OK("selftest_affine_scan", stream, 1);
     return 0;
 }
-
-#ifdef SOAR_BWD_HIST
-extern "C" int soar_debug_bwd_hist(unsigned long long *out16)
-{
-    return hipMemcpyFromSymbol(out16, HIP_SYMBOL(soar::g_bwd_hist), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif

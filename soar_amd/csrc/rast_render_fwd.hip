@@ -63,7 +63,6 @@ struct FwdArgs {
     int keep_background;             // SoarRastParams.debug bit 2
     float *final_To;                 // ImageBuf::final_To / n_contrib_o (OCC): what the backward blend needs to walk the occlusion
     uint32_t *n_contrib_o;           // chain back to front (soar_rast_backward_occ)
-    unsigned long long *wave_log;    // diagnostic build only (SOAR_WAVE_LOG): per wave {t_start, t_end, list length, iterations}
     // BinBuf::block_masks (rast_blockmask.hip describes the layout): phase A's survivor word of every 64 list positions a block's
     // wavefront tests is what the backward blend walks -- left behind here instead of being derived again by a pass of its own
     unsigned long long *masks;       // or null: nothing is emitted
@@ -155,7 +154,7 @@ __device__ __forceinline__ float4 lds_at(const float4 *arr, uint32_t j16)
 // camera-facing entries is the same subsequence of this list (preprocess differs between the two passes only by the
 // back-face cull, forward.cu:262-266), so a second transmittance chain that ignores the back-facing entries reproduces
 // that pass without a second preprocess / sort / blend.
-template <bool LOG, bool OCC>
+template <bool OCC>
 __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, const int quad)
 {
     __shared__ float4 sq0[CHUNK + 1], sq1[CHUNK + 1], sq2[CHUNK + 1], sq3[CHUNK + 1];   // +1: an all-zero record
@@ -163,14 +162,11 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
     __shared__ int wave_alive[2][4];
     __shared__ unsigned short todo_ring[4][CHUNK + 4];                                    // per wavefront: 16 x LDS slot (= byte offset) of a chunk's relevant entries
     __shared__ unsigned long long wmask[4][CHUNK / WAVE];                                 // per wavefront: phase A's survivor words of a chunk
-    unsigned long long t_start = 0, t_ready = 0, t_blended = 0, n_iter = 0, n_useful = 0;
-    if (LOG) t_start = wall_clock64();
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // tile and list range in ONE load (ImageBuf::order_rec; the ranks walked here are tiles with work)
-    if (LOG && a.tile_order[rank] == 0xFFFFFFFFu) return;        // (the logging build walks the padded order)
     const uint4 orec = a.order_rec[rank];
-    const int tile = (int)orec.x, seq = rank * 4 + quad;
+    const int tile = (int)orec.x;
     const int tx = tile % a.gx, ty = tile / a.gx;
     // 4x4 pixel block of this wave inside the 8x8 quad of this workgroup inside the 16x16 tile
     const int bx0 = tx * TILE + (quad & 1) * 8 + (wave & 1) * 4, by0 = ty * TILE + (quad >> 1) * 8 + (wave >> 1) * 4;
@@ -222,10 +218,6 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
     int emit_n = 0;                                  // survivor words waiting in wmask[wave][..] (wave-uniform)
     uint32_t emit_base = 0;                          // list position of bit 0 of the first one
     auto emit_masks = [&]() {
-#ifdef SOAR_EXP_FWD_NO_MASK_EMIT       // (development, the backward's input wrong by construction: what the forward costs without leaving the
-        emit_n = 0;                    // masks behind -- 209.5-214 us against 237 per 4-frame launch at C3, profiles/README.md round 6)
-        return;
-#endif
         if (a.masks && lane < emit_n) {
             const unsigned long long wd = wmask[wave][lane];
             if (wd != 0ull) {
@@ -249,7 +241,6 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
         }
         if (base + CHUNK + tid < range.y) id_next = a.point_list[base + CHUNK + tid];
         lds_barrier();
-        if (LOG && base == range.x) t_ready = wall_clock64();
 
         if (!wave_done) {
             // The entries only matter for the pixels that are still blending: the test rectangle of phase A is the bounding
@@ -298,7 +289,6 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
 
                 // phase B -- lanes = (pixel, slot): four surviving entries per step, in list order
                 for (int it = 0; it < n_todo; it += 4) {
-                    if (LOG) n_iter++;
                     const uint32_t j16 = todo_ring[wave][it + slot];
                     const float4 q0 = lds_at(sq0, j16), q1 = lds_at(sq1, j16), q2 = lds_at(sq2, j16), q3 = lds_at(sq3, j16);
                     // x,y,A,B | C,opacity,depth,plane_a | plane_b,r,g,b | nx,ny,nz,-
@@ -308,7 +298,6 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
                     // skip rules (:512, :545) zero the effective alpha of this lane's entry
                     float a_live = (power > 0.0f) ? 0.f : alpha;
                     a_live = (alpha < 1.0f / 255.0f) ? 0.f : a_live;
-                    if (LOG) n_useful += (unsigned long long)__builtin_popcountll(__ballot(a_live * alive > 0.f));
                     const float a_eff = a_live * alive;                                   // x 1 or x 0: exact
                     // running transmittance through the four slots, reference order (:548-553, :602).
                     // Invariant: T >= 1e-4 in every lane, so "T*(1-a) < 1e-4" can only fire on a live entry.
@@ -415,7 +404,6 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
     }
     emit_masks();                                    // (the last chunk this wavefront tested)
 
-    if (LOG) t_blended = wall_clock64();
     // fold the four slots of every pixel
     D += quad_move<DPP_QUAD_XOR1>(D); D += quad_move<DPP_QUAD_XOR2>(D);
     C0 += quad_move<DPP_QUAD_XOR1>(C0); C0 += quad_move<DPP_QUAD_XOR2>(C0);
@@ -459,13 +447,6 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
             a.out_occ[2 * hw + pix] = Co + T_o * a.bg[2];
         }
     }
-    if (LOG && lane == 0) {
-        unsigned long long *w = a.wave_log + ((size_t)seq * 4 + wave) * 4;
-        // (w[2]: list length | time to the first staged chunk << 24 | time from the end of the blending to here << 44, in 10 ns)
-        const unsigned long long t_end = wall_clock64();
-        w[0] = t_start; w[1] = t_end; w[2] = (unsigned long long)(range.y - range.x) | (min(t_ready - t_start, 0xFFFFFull) << 24) | (min(t_end - t_blended, 0xFFFFFull) << 44);
-        w[3] = n_iter | (n_useful << 24);
-    }
 }
 
 // The launch covers the first gridDim.x / 4 ranks of the longest-first tile order, four workgroups (quads) per tile; the
@@ -478,7 +459,7 @@ __device__ __forceinline__ void blend_quad(const FwdArgs &a, const int rank, con
 #ifndef SOAR_FWD_WPE
 #define SOAR_FWD_WPE 7       // (71 VGPRs, 22.8 KB of LDS per workgroup: seven workgroups per CU)
 #endif
-template <bool LOG, bool OCC>
+template <bool OCC>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SOAR_FWD_WPE, 8))) render_forward_kernel(Batch<FwdArgs> batch)
 {
     int frame, bx;
@@ -488,11 +469,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SOAR_F
     const int rank0 = (kth >> 2) * 8 + xcd, quad = kth & 3;
     const int stride = (int)(gridDim.x >> 2);                // ranks per pass of the grid (a multiple of 8)
     const int Tpad = (a.ntiles + 7) / 8 * 8;
-    const int n_work = LOG ? Tpad : (int)a.tile_order[Tpad];
+    const int n_work = (int)a.tile_order[Tpad];
     for (int rank = rank0; rank < n_work; rank += stride) {
         if (quad == 0 && threadIdx.x == 0 && a.tile_order[rank] != 0xFFFFFFFFu)
             __hip_atomic_store(a.bg_tiles + a.tile_order[rank], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        blend_quad<LOG, OCC>(a, rank, quad);
+        blend_quad<OCC>(a, rank, quad);
         lds_barrier();                                       // the next item's staging overwrites this one's LDS image
     }
     // A tile that was empty in the previous forward blend into the SAME output planes with the same background still holds its
@@ -501,15 +482,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SOAR_F
     // (the caller's promise covers the buffers; that the background VALUES are those of the previous forward is checked on the
     // device: tile_order_block compared them one launch ago)
     const bool keep = a.keep_background && a.bg_state[4] == 0u;
-    if (!LOG)
-        for (int rank = n_work + bx; rank < a.ntiles; rank += (int)gridDim.x) {
-            const int tile = (int)a.tile_order[rank];
-            const uint32_t holds_background = __hip_atomic_load(a.bg_tiles + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            lds_barrier();                                   // every wavefront has read the flag before the first one may set it below
-            if (keep && holds_background == 1u) continue;
-            fill_tile<OCC>(a, tile, (int)threadIdx.x, 256);
-            if (threadIdx.x == 0) __hip_atomic_store(a.bg_tiles + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+    for (int rank = n_work + bx; rank < a.ntiles; rank += (int)gridDim.x) {
+        const int tile = (int)a.tile_order[rank];
+        const uint32_t holds_background = __hip_atomic_load(a.bg_tiles + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lds_barrier();                                       // every wavefront has read the flag before the first one may set it below
+        if (keep && holds_background == 1u) continue;
+        fill_tile<OCC>(a, tile, (int)threadIdx.x, 256);
+        if (threadIdx.x == 0) __hip_atomic_store(a.bg_tiles + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 
@@ -713,32 +693,12 @@ int launch_render_forward(const SoarRastParams &prm, const GeomBuf &g, const Bin
     a.occ_values = occ_values; a.front = g.front; a.out_occ = out_occ;
     a.final_To = img.final_To; a.n_contrib_o = img.n_contrib_o;
     a.bg_tiles = img.bg_tiles; a.bg_state = img.bg_state; a.keep_background = (prm.debug & 4) ? 1 : 0;
-    a.wave_log = nullptr;
     a.masks = reinterpret_cast<unsigned long long *>(b.block_masks); a.mask_plane = b.mask_plane;
-    const char *log_path = getenv("SOAR_WAVE_LOG");          // diagnostic: dump per-wave timelines of ONE launch
-    const int grid_ranks = blend_grid_ranks(a.ntiles);
     const int Tpad = (a.ntiles + 7) / 8 * 8;
-    const int nblocks = 4 * (log_path ? Tpad : min(Tpad, grid_ranks));
+    const int nblocks = 4 * min(Tpad, blend_grid_ranks(a.ntiles));
     StageTimer timer(ST_RENDER_FWD, stream);
-    static int logged = 0;
-    if (log_path && !logged && prm.render_front == 0) {
-        logged = 1;
-        const size_t nbytes = sizeof(unsigned long long) * 16 * (size_t)nblocks;
-        SOAR_HIP_OK(hipMalloc(&a.wave_log, nbytes));
-        SOAR_HIP_OK(hipMemsetAsync(a.wave_log, 0, nbytes, stream));
-        if (out_occ) SOAR_LAUNCH_BATCHED((render_forward_kernel<true, true>), dim3(nblocks), dim3(256), 0, stream, a);
-        else SOAR_LAUNCH_BATCHED((render_forward_kernel<true, false>), dim3(nblocks), dim3(256), 0, stream, a);
-        SOAR_HIP_OK(hipStreamSynchronize(stream));
-        unsigned long long *host = (unsigned long long *)malloc(nbytes);
-        SOAR_HIP_OK(hipMemcpy(host, a.wave_log, nbytes, hipMemcpyDeviceToHost));
-        FILE *f = fopen(log_path, "wb");
-        if (f) { fwrite(host, 1, nbytes, f); fclose(f); }
-        free(host);
-        (void)hipFree(a.wave_log);
-        return 0;
-    }
-    if (out_occ) SOAR_LAUNCH_BATCHED((render_forward_kernel<false, true>), dim3(nblocks), dim3(256), 0, stream, a);
-    else SOAR_LAUNCH_BATCHED((render_forward_kernel<false, false>), dim3(nblocks), dim3(256), 0, stream, a);
+    if (out_occ) SOAR_LAUNCH_BATCHED((render_forward_kernel<true>), dim3(nblocks), dim3(256), 0, stream, a);
+    else SOAR_LAUNCH_BATCHED((render_forward_kernel<false>), dim3(nblocks), dim3(256), 0, stream, a);
     SOAR_LAUNCH_OK("render_forward", stream, prm.debug);
     return 0;
 }

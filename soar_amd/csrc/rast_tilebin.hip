@@ -582,7 +582,6 @@ struct BinTilesArgs {
     uint32_t *point_list;
     uint32_t *tile_count;
     uint32_t capacity;
-    unsigned long long *dbg;
     uint32_t *tile_xy;       // BinBuf::tile_xy
     int split_at;            // rectangles in a band from which idle columns help (SOAR_BIN_SPLIT_AT)
     const uint32_t *work;    // ImageBuf::bin_work: header[H_BIN_WORK] super-tiles
@@ -592,8 +591,8 @@ struct BinTilesArgs {
 // leaves the sizes of the 16 lists per wavefront, an exclusive scan of those over the wavefronts (per tile) says where every
 // wavefront's entries of every tile start -- slice after slice = depth order -- and every wavefront then appends straight to the 16
 // lists at 16 running cursors in scalar registers.
-//   * These launches are bound by vector instructions: a wavefront instruction occupies its SIMD for four cycles, and the log
-//     (SOAR_BIN_LOG) of every variant tried fits  time = vector instructions of the workgroup's wavefronts / 2400 per us  + ~9 us of
+//   * These launches are bound by vector instructions: a wavefront instruction occupies its SIMD for four cycles, and the
+//     per-workgroup timings of every variant tried fit  time = vector instructions of the workgroup's wavefronts / 2400 per us  + ~9 us of
 //     fixed latencies (first loads, three barriers, the reservation's atomic).  A slab of 64 rectangles none of which touches the
 //     super-tile costs its loads and ~12 instructions (most slabs of most workgroups: 30 super-tiles walk every band; the test itself is
 //     two packed 16-bit multiply-adds and a sign mask), one with a hit ~45 more (cover mask, compaction).
@@ -673,7 +672,6 @@ __device__ __forceinline__ bool rect_hits_packed(uint2 rc, const SuperTileTest &
 }
 __device__ __forceinline__ void bin_tiles_body(const int bx, const BinTilesArgs &a)
 {
-    const unsigned long long dbg_t0 = a.dbg ? wall_clock64() : 0ull;
     constexpr int NT = BIN_SUPER * BIN_SUPER, U = SOAR_BIN_UNROLL, CAP = SOAR_BIN_CAPTURE;
     static_assert(BIN_SUPER == 4 && BIN_WAVES * WAVE >= NT, "16 tiles: a cover mask has 16 bits");
     static_assert(CAP >= 2 * WAVE && (CAP & (CAP - 1)) == 0, "a ring holds a dense slab plus what one slab of the band can add");
@@ -711,10 +709,7 @@ __device__ __forceinline__ void bin_tiles_body(const int bx, const BinTilesArgs 
         const int h = scol < se0 ? scol : scol - width;                 // its number among the columns outside the extent
         const int j = width > 0 ? h % width : 0;
         if (split && width > 0) { parts = parts_of(j); sub = h / width + 1; }
-        if (sub == 0 || sub >= parts) {
-            if (a.dbg && tid == 0) { a.dbg[(size_t)bx * 4] = 1ull; a.dbg[(size_t)bx * 4 + 1] = dbg_t0; }
-            return;
-        }
+        if (sub == 0 || sub >= parts) return;
         st = super_tile_of(bx - scol + se0 + j, gx, gy);
     } else {
         parts = parts_of(scol - se0);
@@ -815,7 +810,6 @@ __device__ __forceinline__ void bin_tiles_body(const int bx, const BinTilesArgs 
     }
     if (lane < NT) wave_tile[wave][lane] = mine;
     lds_barrier();
-    const unsigned long long dbg_t1 = a.dbg ? wall_clock64() : 0ull;
     {   // thread (w, t): the entries of tile t in the wavefronts before w, and in all of them
         const int w = (tid >> 4) & (BIN_WAVES - 1), t = tid & (NT - 1);
         uint32_t before = 0u, all = 0u;
@@ -894,14 +888,6 @@ __device__ __forceinline__ void bin_tiles_body(const int bx, const BinTilesArgs 
             });
             if (n) place(head, n);
         }
-    }
-    if (a.dbg) lds_barrier();                          // (the log's end of the workgroup: its last wavefront's)
-    if (a.dbg && tid == 0) {
-        unsigned long long *w = a.dbg + (size_t)bx * 4;
-        uint32_t kept = 0;
-        for (int t = 0; t < NT; t++) kept += tile_cnt[t];
-        w[0] = wall_clock64() - dbg_t0; w[1] = dbg_t0; w[2] = (unsigned long long)kept;
-        w[3] = ((dbg_t1 - dbg_t0) << 32) | (unsigned long long)P;
     }
 }
 
@@ -984,37 +970,9 @@ int launch_tile_binning(const SoarRastParams &prm, GeomBuf &g, BinBuf &b, ImageB
     SOAR_LAUNCH_OK("band_lists", stream, prm.debug);
     {
         StageTimer timer(ST_EMIT_KEYS, stream);
-        unsigned long long *dbg = nullptr;
-        static int dbg_left = getenv("SOAR_BIN_LOG") ? 1 : 0;          // diagnostic: per-workgroup timings of ONE launch
-        const bool log_now = dbg_left > 0 && prm.W >= 1920 && !batch_ctx().n;
-        if (log_now) {
-            dbg_left = 0;
-            SOAR_HIP_OK(hipMalloc(&dbg, 8 * (size_t)(nsx * nsy) * 4));
-            SOAR_HIP_OK(hipMemsetAsync(dbg, 0, 8 * (size_t)(nsx * nsy) * 4, stream));
-        }
         const BinTilesArgs bt = {g.header, gx, gy, band_rows, g.band_info, ba.band_rect, ba.band_id, img.ranges, b.vals_sorted,
-                                 img.tile_count, ba.capacity, dbg, b.tile_xy, split_at, img.bin_work};
+                                 img.tile_count, ba.capacity, b.tile_xy, split_at, img.bin_work};
         SOAR_LAUNCH_BATCHED(bin_tiles_kernel, dim3(min(nsx * nsy, SOAR_BIN_GRID)), dim3(BIN_THREADS), 0, stream, bt);
-        if (log_now) {
-            const int nwg = nsx * nsy;
-            const size_t nw = (size_t)nwg * 4;
-            SOAR_HIP_OK(hipStreamSynchronize(stream));
-            unsigned long long *h = (unsigned long long *)malloc(8 * nw);
-            SOAR_HIP_OK(hipMemcpy(h, dbg, 8 * nw, hipMemcpyDeviceToHost));
-            (void)hipFree(dbg);
-            {   // when the workgroups started and ended, relative to the first one's start (100 MHz clock); the busy ones one by one
-                unsigned long long first = ~0ull, last = 0ull;
-                for (int i = 0; i < nwg; i++) if (h[i * 4]) { first = h[i * 4 + 1] < first ? h[i * 4 + 1] : first; }
-                for (int i = 0; i < nwg; i++) if (h[i * 4]) { const unsigned long long e = h[i * 4 + 1] + h[i * 4]; last = e > last ? e : last; }
-                fprintf(stderr, "[bin_tiles] %d workgroups: first start to last end %.1f us\n", nwg, (last - first) / 100.0);
-                for (int i = 0; i < nwg; i++)
-                    if (h[i * 4] > 1500)
-                        fprintf(stderr, "[bin_tiles]   WG %d: start %.1f, %.1f us (walk %.1f), %llu list entries from a band of %llu\n", i,
-                                (h[i * 4 + 1] - first) / 100.0, h[i * 4] / 100.0, (h[i * 4 + 3] >> 32) / 100.0, h[i * 4 + 2] & 0xFFFFFFFFull,
-                                h[i * 4 + 3] & 0xFFFFFFFFull);
-            }
-            free(h);
-        }
     }
     SOAR_LAUNCH_OK("bin_tiles", stream, prm.debug);
     return 0;

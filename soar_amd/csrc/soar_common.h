@@ -428,8 +428,6 @@ int launch_binning(const SoarRastParams &prm, GeomBuf &g, BinBuf &b, ImageBuf &i
 // 1024 against 2048 ranks +1 ... +5 % depending on the box, 4K 4096 against 2048 +1.6 %, 540p unchanged.
 inline int blend_grid_ranks(int ntiles)
 {
-    static const int forced = getenv("SOAR_BLEND_GRID_RANKS") ? atoi(getenv("SOAR_BLEND_GRID_RANKS")) / 8 * 8 : 0;   // development switch
-    if (forced > 0) return forced;
     const int r = (ntiles / 8 + 7) / 8 * 8;
     return r < 1024 ? 1024 : (r > 4096 ? 4096 : r);
 }

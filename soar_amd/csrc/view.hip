@@ -235,8 +235,7 @@ namespace {
 // A step of the reference's training loop renders 7 views of 2 poses in 3-4 groups that share nothing but the posed surfels; every
 // group is a chain of a dozen launches that leave most of the chip idle (a 512 x 512 view has 1024 tiles).  The groups are issued on
 // streams of the library's own (per host thread, created on first use, never destroyed) forked from the caller's stream behind the
-// warps and joined into it at the end: to the caller the call is still ONE unit of work on ITS stream.  SOAR_STEP_STREAMS=0: all on
-// the caller's stream.
+// warps and joined into it at the end: to the caller the call is still ONE unit of work on ITS stream.
 struct SideStreams {
     hipStream_t s[MAX_BATCH] = {};
     hipEvent_t fork = nullptr, join[MAX_BATCH] = {};
@@ -246,8 +245,6 @@ struct SideStreams {
 SideStreams *side_streams()
 {
     static thread_local SideStreams pool;
-    static const bool enabled = []() { const char *e = getenv("SOAR_STEP_STREAMS"); return !(e && e[0] == '0'); }();
-    if (!enabled) return nullptr;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     if (pool.ok && pool.device == dev) return &pool;

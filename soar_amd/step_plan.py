@@ -164,10 +164,8 @@ class FrameStepPlan:
         self._baked = self._leaf_signature()
         # every frame chain on a stream of its own; the caller's stream only carries the prologue, the joins and the epilogue
         # (measured with device timestamps, scripts/plan_phases.py: with a frame on the caller's stream that chain starts ~70 us
-        # behind the others and ends last; SOAR_PLAN_MAIN_FRAME=1 restores that layout)
+        # behind the others and ends last)
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(self.n)]
-        if os.environ.get("SOAR_PLAN_MAIN_FRAME", "0") == "1":
-            self.streams[0] = None
         # Eager form only.  batched: ONE stream, every stage of the chain launched once for all frames (soar_batch_*: the kernels
         # take their frame from blockIdx.y) -- no fork / join per step and a quarter of the launches, but every stage ends in a
         # barrier over all frames.  Not batched: the frames' chains on streams of their own, whose small latency-bound kernels
@@ -273,28 +271,22 @@ class FrameStepPlan:
             g_normal=ptr(v["gN"]), g_occ=ptr(v["g_occ_img"]), normal_raw=1, occ_grad_summed=1, cos_scale_out=self.av_cos_scale_all.data_ptr() + 4 * i,
             background=self.ctx.params.bg_dev)
 
-    def _av_pixel(self, i, stream, mode):
+    def _av_pixel(self, i, stream):
+        # values and gradients of the four per-pixel terms in one pass (mode 3); the colour gradient takes the SSIM term's on the way
+        # (g_render = L1 part + coef[SSIM] * g_ssim); the normal gradient leaves as the gradient of the RASTERIZER's normal image
+        # (the plugin's normal' = (n (1,-1,-1) + 1) / 2 inside the mask: exact factors -- no post-ops backward pass for it)
         key = ("av_pixel", i, self._frames_now[i] % int(self.pool.shape[0]))
         args = self._av_args.get(key)
         if args is None:
             args = self._av_args[key] = self._av_pixel_args(i)
-        check(self.L.soar_avatar_pixel_losses(C.byref(args), mode, stream), "soar_avatar_pixel_losses")
-
-    def _av_onepass(self, i, stream):
-        # values and gradients of the four per-pixel terms in one pass; the colour gradient takes the SSIM term's on the way
-        # (g_render = L1 part + coef[SSIM] * g_ssim); the normal gradient leaves as the gradient of the RASTERIZER's normal image
-        # (the plugin's normal' = (n (1,-1,-1) + 1) / 2 inside the mask: exact factors -- no post-ops backward pass for it)
-        self._av_pixel(i, stream, 3)
-
-    AV_FORWARD = ("_av_finish", "_av_ssim", "_av_onepass")
-    AV_BACKWARD = ()
+        check(self.L.soar_avatar_pixel_losses(C.byref(args), 3, stream), "soar_avatar_pixel_losses")
 
     def _f_avatar_loss(self, i: int, frame: int, stream: int) -> None:
         """post-ops -> SSIM, the per-pixel terms' values (one pass), their gradients (one pass) -> post-ops backward: everything
         between the blend and the rasterizer backward of ONE frame (the form with one stream per frame)"""
         v, up = self.views[i], self.av_coef
-        for name in self.AV_FORWARD + self.AV_BACKWARD:
-            getattr(self, name)(i, stream)
+        for stage in (self._av_finish, self._av_ssim, self._av_pixel):
+            stage(i, stream)
         # the frame's loss value (device side): terms . coef + lambda_occ mean(1 - occ[mask])
         torch.add(torch.dot(v["terms"], up), v["occ_terms"][0] * self.av_occ_up[0], out=self.losses[i])
 
@@ -467,8 +459,7 @@ class FrameStepPlan:
                 L.soar_batch_end()
         if self.loss_kind == "avatar":
             from .losses import _AvatarStageLoss as S
-            batch((self._f_geometry, self._f_render) + tuple(getattr(self, name) for name in self.AV_FORWARD + self.AV_BACKWARD) +
-                  (self._f_backward_occ,))
+            batch((self._f_geometry, self._f_render, self._av_finish, self._av_ssim, self._av_pixel, self._f_backward_occ))
             # the frames' loss values: terms . coef + lambda_occ mean(1 - occ[mask])
             if len(frames) == self.n:
                 torch.addmv(self.av_occ_terms_all[:, 0] * self.av_occ_up[0], self.av_terms_all, self.av_coef, out=self.losses)
@@ -570,29 +561,17 @@ class FrameStepPlan:
         self.ctx.params.debug |= 4
 
     def _fan_out(self, main, fn) -> None:
-        """frames with a stream of their own are forked from `main` (and joined again), the others run on `main`"""
+        """every frame chain on its own stream: forked from `main` and joined into it again"""
         ev = torch.cuda.Event()
         ev.record(main)
         done = []
-        first_main = os.environ.get("SOAR_PLAN_MAIN_FIRST", "0") == "1"
-        if first_main:
-            for i in range(self.n):
-                if self.streams[i] is None:
-                    fn(i, main)
-        for i in range(self.n):
-            s = self.streams[i]
-            if s is None:
-                continue
+        for i, s in enumerate(self.streams):
             s.wait_event(ev)
             with torch.cuda.stream(s):
                 fn(i, s)
             e = torch.cuda.Event()
             e.record(s)
             done.append(e)
-        if not first_main:
-            for i in range(self.n):
-                if self.streams[i] is None:
-                    fn(i, main)
         for e in done:
             main.wait_event(e)
 
