@@ -44,7 +44,8 @@ extern "C" {
  * soar_frames_warp_preprocess (+ SoarFrameHead; SoarRastParams.debug bit 4) and soar_frames_geometry_warp_backward (+ SoarFrameTail;
  * debug bit 3): the head of the forward pass and the tail of the backward pass of all frames of a step as one kernel each;
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
- * soar_views_grad_scratch_floats (a block per back view). */
+ * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
+ * soar_mesh_filter_bytes / _components (mesh export). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -734,6 +735,39 @@ int soar_selftest_affine_scan(const float *m64_dev, const float *b64_dev, float 
 /* ---- device self-test of the blend kernels' exp: out_dev[i] = the kernels' exp(x[i]), expf_dev[i] = the device math
  * library's expf(x[i]) (what the reference's `exp(power)` becomes when built for this GPU); equal bit for bit on [-87, 0]. */
 int soar_selftest_exp(const float *x_dev, int32_t n, float *out_dev, float *expf_dev, void *stream);
+
+/* ---- mesh export (mesh.hip, soar_amd/mesh.py; DESIGN.md "Mesh export").  Not part of the training step.
+ * soar_tsdf_integrate: fuses n_views (1..64) rendered depth / opacity planes [n_views][H][W] into the TSDF of a dense grid
+ *   [X][Y][Z] (X * Y * Z < 2^31) whose voxel (x, y, z) sits at origin + voxel * (x, y, z).  viewmatrix / projmatrix
+ *   [n_views][16]: world_view_transform / full_proj_transform (row-vector convention); prcppoint [n_views][2].  Per voxel and
+ *   view: skip when the view-space z <= znear or the nearest pixel floor(pix + 0.5) is outside the image; opac < min_opacity
+ *   records s = +1, else skip when depth - z < -trunc, else s = min(1, (depth - z) / trunc); sum += s, weight += 1.  One
+ *   thread per voxel, no atomics: deterministic.  sum / weight are read and written in place (zero them before the first
+ *   call); calls accumulate.
+ * soar_mc_workspace_bytes / soar_mc_count / soar_mc_emit: marching cubes of values [X][Y][Z] at `level` (inside: value <
+ *   level), valid [X][Y][Z] bytes or NULL.  An edge carries a vertex when both ends are valid and exactly one is inside; a
+ *   cell emits triangles only when its 8 corners are valid.  soar_mc_count reads back counts_host[2] = {vertices, triangles}
+ *   (a stream synchronisation: this is the export path); soar_mc_emit then writes verts [V][3] (index coordinates) and faces
+ *   [F][3] (int32, facing the values above level) from the same workspace, values, valid and level.  Vertex ids follow
+ *   (voxel, axis), triangles (cell, table order): the output is bit-identical from run to run.
+ * soar_mesh_filter_bytes / soar_mesh_filter_components: removes the connected components (over the faces' edges) with fewer
+ *   than min_faces faces or a bounding-box diagonal below min_diag_frac times the whole mesh's, and vertices used by no face;
+ *   writes the kept vertices and the re-indexed faces in their input order to verts_out [<= V][3] / faces_out [<= F][3] and
+ *   reads back counts_host[2] = {kept vertices, kept faces} (a stream synchronisation).  Deterministic.
+ * All pointers but counts_host are device pointers; workspaces are 256-byte aligned and caller-owned. */
+int soar_tsdf_integrate(int32_t n_views, int32_t H, int32_t W, const float *depth, const float *opac, const float *viewmatrix,
+                        const float *projmatrix, const float *prcppoint, float origin_x, float origin_y, float origin_z, float voxel,
+                        int32_t X, int32_t Y, int32_t Z, float trunc, float znear, float min_opacity, float *sum, float *weight,
+                        void *stream);
+int soar_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z, size_t *bytes);
+int soar_mc_count(int32_t X, int32_t Y, int32_t Z, const float *values, const uint8_t *valid, float level, void *workspace,
+                  size_t workspace_bytes, int64_t *counts_host, void *stream);
+int soar_mc_emit(int32_t X, int32_t Y, int32_t Z, const float *values, const uint8_t *valid, float level, const void *workspace,
+                 size_t workspace_bytes, float *verts, int32_t *faces, void *stream);
+int soar_mesh_filter_bytes(int32_t V, int32_t F, size_t *bytes);
+int soar_mesh_filter_components(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t min_faces, float min_diag_frac,
+                                void *workspace, size_t workspace_bytes, float *verts_out, int32_t *faces_out, int64_t *counts_host,
+                                void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

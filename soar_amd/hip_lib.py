@@ -190,6 +190,13 @@ SIGNATURES = {
     "soar_adam_step": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "soar_adam_step_at": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
     "soar_adam_step_rows": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, C.c_int32, _vp]),
+    "soar_tsdf_integrate": (C.c_int, [C.c_int32] * 3 + [_vp] * 5 + [C.c_float] * 4 + [C.c_int32] * 3 + [C.c_float] * 3 + [_vp] * 3),
+    "soar_mc_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
+    "soar_mc_count": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "soar_mc_emit": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, C.c_float, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "soar_mesh_filter_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_filter_components": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_float, _vp, C.c_size_t, _vp, _vp,
+                                              C.POINTER(C.c_int64), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
