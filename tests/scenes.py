@@ -186,3 +186,39 @@ def torch_settings(scene: Scene, device):
         projmatrix=cam.full_proj_transform.to(device), patch_bbox=t(scene.patch_bbox), prcppoint=cam.prcppoint.to(device),
         sh_degree=scene.sh_degree, campos=cam.camera_center.to(device), prefiltered=False,
         render_front=scene.render_front, sort_descending=scene.sort_descending, debug=False, config=t(scene.config))
+
+
+def avatar_frame_loss(seq, frame, bg, pool, lam):
+    """One frame of the avatar-stage loss (the step plan's loss="avatar") composed from the autograd pieces of the plugin path
+    (TS/renderer/diff_gaussian_rasterizer.py:292-303): lbs_warp, GaussianRasterizer twice, the post-op functions,
+    losses.avatar_stage_loss + loss_occ.  The frame's targets are set (frame mod the sequence's frames) mod the pool's sets."""
+    from collections import namedtuple
+    from soar_amd import lbs, losses
+    from soar_amd.rasterizer import GaussianRasterizer
+    from soar_amd.renderer.postops import depth2normal, normal2curv
+    c, dev = seq.camera, seq.device
+    H, W = int(c.height), int(c.width)
+    camera = namedtuple("Cam", "FoVx FoVy image_height image_width prcppoint")(2 * math.atan(c.tanfovx), 2 * math.atan(c.tanfovy),
+                                                                                H, W, seq.prcp)
+    flip = torch.tensor([1.0, -1.0, -1.0], device=dev)[:, None, None]
+    f = frame % seq.num_frames
+    xyz_p, rot_p = lbs.lbs_warp(seq.xyz, seq.rot, seq.blend_weights, seq.cano2live[f])
+    ones = torch.ones_like(seq.opacity)
+    tap = torch.zeros_like(xyz_p, requires_grad=True)
+    render, normal, depth, opac, _ = GaussianRasterizer(seq.settings(bg, False, False))(
+        means3D=xyz_p, means2D=tap, opacities=ones, colors_precomp=seq.colors, scales=seq.scales, rotations=rot_p)
+    occ_img = GaussianRasterizer(seq.settings(bg, True, False))(
+        means3D=xyz_p.detach(), means2D=tap.detach(), opacities=ones, colors_precomp=seq.occ.repeat(1, 3),
+        scales=seq.scales.detach(), rotations=rot_p.detach())[0]
+    mask = opac > 1e-5
+    n = torch.where(mask.repeat(3, 1, 1), normal, normal.detach()) * flip
+    curv = normal2curv(n, opac.detach() > 1e-5)
+    n = (n + 1) / 2
+    pred = (depth2normal(depth, opac.detach() > 1e-5, camera) * flip + 1) / 2
+    out = {"render": render, "normal": n, "depth": depth, "pred_normal": pred, "mask": opac, "occ": occ_img, "curv": curv}
+    k = f % pool.shape[0]
+    gt_rgb, gt_mask, gt_normal = pool[k, 0:3], pool[k, 3:4], pool[k, 4:7]
+    blended = gt_rgb * gt_mask + bg[:, None, None] * (1 - gt_mask)
+    loss = losses.avatar_stage_loss(out, gt_rgb, gt_mask, gt_normal, gt_mask[0] > 1e-5, gt_rgb_blended=blended,
+                                    lambda_recon=lam["recon"], lambda_mask=lam["mask"], lambda_normal=lam["normal"])
+    return loss + lam["occ"] * (1 - occ_img.permute(1, 2, 0)[gt_mask[0] > 0]).mean()

@@ -44,8 +44,9 @@ def test_bench_line_schema(mode):
         assert rb["fwd_ms"] > 0 and rb["bwd_ms"] > 0 and rb["product_one_view_fwd_ms"] > 0 and "context only" in rb["build"], rb
 
 
-def _plain_run(steps, dump_dir=None):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", str(steps), "--warmup", "2"]
+def _plain_run(steps, dump_dir=None, warmup=2, extra=()):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", str(steps), "--warmup", str(warmup),
+           *extra]
     r = subprocess.run(cmd + (["--dump-outputs", str(dump_dir)] if dump_dir else []), capture_output=True, text=True, timeout=600,
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -95,6 +96,15 @@ def test_bench_plain_run_and_dumped_outputs(tmp_path):
         # (a pixel whose last contributor flips with a last-bit difference of the parameters, the gradients it feeds, and an Adam
         # update whose gradient is zero up to that order -- its sign then goes either way -- may differ)
         assert close.all() if n == "loss" else close.mean() >= (0.999 if n.startswith("param_") else 0.99), (n, close.mean())
+
+
+def test_bench_plain_run_at_8_frames_per_step():
+    """--frames-per-step 8: the plan's largest batch (fused head and tail, batched launches over 8 frames) in the bench's own run; the
+    line counts 8 frames per step."""
+    d = _plain_run(3, warmup=1, extra=("--frames-per-step", "8"))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["config"]["mode"] == "plan-eager" and d["ms_per_step"] > 0
+    # ms_per_step is printed to 3 decimals: half a unit of the last one is the tolerance
+    assert d["value"] > 0 and abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) <= d["value"] * (0.00051 / d["ms_per_step"] + 1e-6)
 
 
 def test_bench_avatar_loss_line():

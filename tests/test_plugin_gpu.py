@@ -877,51 +877,92 @@ def test_fused_frame_loss_in_rasterize_views():
         assert _rel(g_got[k].cpu().numpy(), g_ref[k].cpu().numpy()) < 1e-4, k
 
 
-@pytest.mark.parametrize("use_graphs,pooled", [(False, True), (True, True), (True, False)],
-                         ids=["eager-per-frame-targets", "graphs-per-frame-targets", "graphs-shared-targets"])
-def test_step_plan_matches_autograd(use_graphs, pooled):
+# two steps' frames per frame count: they hold frames past the 8 of the "tiny" sequence and, from 2 frames on, a frame twice in a step
+# (n = 4: the lists of the original cases; n = 9 always repeats one)
+_PLAN_FRAMES = {1: ([13], [2]), 2: ([5, 10], [3, 3]), 3: ([5, 2, 15], [3, 3, 0]), 4: ([5, 2, 7, 1], [3, 3, 0, 6]),
+                5: ([5, 2, 7, 1, 12], [3, 3, 0, 6, 9]), 8: ([5, 2, 7, 1, 12, 0, 6, 3], [3, 3, 0, 6, 4, 9, 2, 7]),
+                9: ([5, 2, 7, 1, 12, 0, 6, 3, 4], [3, 3, 0, 6, 4, 9, 2, 7, 21])}
+_PLAN_CASES = ([(False, True, 4, "synthetic", None), (True, True, 4, "synthetic", None), (True, False, 4, "synthetic", None)]
+               + [(False, True, n, "synthetic", None) for n in (1, 2, 3, 5, 8, 9)]
+               + [(False, True, n, "avatar", None) for n in (1, 5, 8)]
+               + [(False, True, n, "synthetic", False) for n in (3, 8)])
+_PLAN_IDS = (["eager-per-frame-targets", "graphs-per-frame-targets", "graphs-shared-targets"]
+             + [f"eager-per-frame-targets-n{n}" for n in (1, 2, 3, 5, 8, 9)]
+             + [f"eager-avatar-n{n}" for n in (1, 5, 8)]
+             + [f"eager-streams-n{n}" for n in (3, 8)])
+
+
+@pytest.mark.parametrize("use_graphs,pooled,n,loss,batched", _PLAN_CASES, ids=_PLAN_IDS)
+def test_step_plan_matches_autograd(use_graphs, pooled, n, loss, batched):
     """FrameStepPlan (explicit launch plan: per-frame forward+backward chains on their own streams / HIP graphs, no
     autograd) gives the losses and leaf gradients of the autograd path (render_frames + fused loss + backward) -- with the
-    per-frame targets of a resident pool picked on the device (soar_frame_loss_pooled) and with one shared target set."""
+    per-frame targets of a resident pool picked on the device (soar_frame_loss_pooled) and with one shared target set.
+    Eager at 1 to 9 frames per step: up to 8 the fused head and tail and the batched launches (frames past a workgroup's
+    four, lone frames, a second frame group), at 9 none of them and the frame ids through device memory; also the chains on
+    streams of their own, and the avatar-stage loss against its composition from the plugin's autograd pieces
+    (scenes.avatar_frame_loss).  Every image of every slot is bit for bit the autograd path's render of the slot's frame."""
     import bench
+    from scenes import avatar_frame_loss
     from soar_amd import rasterizer
     from soar_amd.frame_dp import FlatGradBuffer
     from soar_amd.step_plan import FrameStepPlan
     from soar_amd.synthetic import pool_targets
     seq, pool, _ = bench.build_sequence("tiny", DEV)
     targets = pool if pooled else pool_targets(pool, 3)
-    flat = FlatGradBuffer(seq.leaves())
+    leaves = seq.leaves()
+    if loss == "avatar":
+        seq.occ.requires_grad_(True)
+        leaves = dict(leaves, occ=seq.occ)
+    flat = FlatGradBuffer(leaves)
     bg = torch.tensor([0.2, 0.5, 0.7], device=DEV)
     bench.run_step(seq, targets, flat, [0, 1, 2, 3], bg)
     cap = 3 * rasterizer.last_num_rendered
     try:
-        plan = FrameStepPlan(seq, 4, targets, bg, cap, flat, use_graphs=use_graphs)
+        plan = FrameStepPlan(seq, n, targets, bg, cap, flat, use_graphs=use_graphs, batched=batched, loss=loss)
     except Exception as e:                      # pragma: no cover - capture unsupported on this stack
         if use_graphs:
             pytest.skip(f"HIP graph capture unavailable: {e}")
         raise
-    for frames in ([5, 2, 7, 1], [3, 3, 0, 6]):
+    if not use_graphs:
+        # the path this frame count takes (n > 8: the entries of the fused kernels and of a batch take at most 8 frames)
+        assert plan.fused_head == plan.fused_tail == (n <= 8) and plan.batched == (n <= 8 and batched is not False)
+        assert plan._ids_by_value == (n <= 8)
+    for frames in _PLAN_FRAMES[n]:
         flat.zero()
         seq.refresh_blend_weights()
-        outs = seq.render_frames(frames, bg, loss_targets=[pool_targets(pool, f) for f in frames] if pooled else targets)
-        sum(o.loss for o in outs).backward()
-        want, want_losses = flat.flat.clone(), torch.stack([o.loss.detach() for o in outs])
+        if loss == "avatar":
+            per_frame = [avatar_frame_loss(seq, f, bg, pool, plan.lam) for f in frames]
+            sum(per_frame).backward()
+            want, want_losses = flat.flat.clone(), torch.stack([l.detach() for l in per_frame])
+            with torch.no_grad():
+                outs = seq.render_frames(frames, bg)
+        else:
+            outs = seq.render_frames(frames, bg, loss_targets=[pool_targets(pool, f) for f in frames] if pooled else targets)
+            sum(o.loss for o in outs).backward()
+            want, want_losses = flat.flat.clone(), torch.stack([o.loss.detach() for o in outs])
         if pooled:
-            assert len({round(float(l), 5) for l in want_losses}) == len(set(frames))  # different frames, different targets
+            # different frames, different targets
+            assert len({round(float(l), 5) for l in want_losses}) == len({f % seq.num_frames for f in frames})
         losses = plan.run(frames)
         torch.cuda.synchronize()
-        plan.check()
+        assert all(o == 0 for _, o in plan.check())
         assert float(want.abs().sum()) > 0
         np.testing.assert_allclose(losses.cpu().numpy(), want_losses.cpu().numpy(), rtol=1e-6)
         assert _rel(flat.flat.cpu().numpy(), want.cpu().numpy()) < 1e-4
+        for i, o in enumerate(outs):
+            v = plan.views[i]
+            for name, img in (("color", o.render), ("normal", o.normal), ("depth", o.depth), ("opac", o.mask)):
+                assert torch.equal(v[name].reshape(img.shape), img), (frames, i, name)
 
 
-@pytest.mark.parametrize("workload", ["tiny", "C3"])
-def test_step_plan_fused_head_equals_warp_then_preprocess_bit_for_bit(workload, monkeypatch):
+@pytest.mark.parametrize("workload,n", [("tiny", 4), ("C3", 4), ("tiny", 1), ("tiny", 3), ("tiny", 5), ("tiny", 8), ("C3", 8)],
+                         ids=["tiny", "C3", "tiny-n1", "tiny-n3", "tiny-n5", "tiny-n8", "C3-n8"])
+def test_step_plan_fused_head_equals_warp_then_preprocess_bit_for_bit(workload, n, monkeypatch):
     """soar_frames_warp_preprocess (round 6: the warp of every frame + the per-Gaussian forward stage of the rasterizer as ONE kernel,
     preprocess_point inlined behind forward_point) against soar_lbs_warp_forward_batch + the preprocess stage of
     soar_rast_forward_geometry: posed positions and quaternions, radii, the whole geometry state (records, rectangles, depth keys,
-    tile counts: the buffers byte for byte up to the scratch behind them) and every image of the step bit for bit."""
+    tile counts: the buffers byte for byte up to the scratch behind them) and every image of the step bit for bit.  At 1 to 8 frames
+    per step: a workgroup's wavefronts past the last frame, and a second row of the grid (blockIdx.y = 1) from 5 frames on."""
     import bench
     from soar_amd import rasterizer
     from soar_amd.frame_dp import FlatGradBuffer
@@ -931,12 +972,12 @@ def test_step_plan_fused_head_equals_warp_then_preprocess_bit_for_bit(workload, 
     bg = torch.tensor([0.2, 0.5, 0.7], device=DEV)
     bench.run_step(seq, pool, flats[0], [0, 1, 2, 3], bg)
     cap = 2 * rasterizer.last_num_rendered
-    plan = FrameStepPlan(seq, 4, pool, bg, cap, flats[0], use_graphs=False)
+    plan = FrameStepPlan(seq, n, pool, bg, cap, flats[0], use_graphs=False)
     assert plan.fused_head and plan.ctx.params.debug & 16
     monkeypatch.setenv("SOAR_PLAN_FUSED_HEAD", "0")
-    plan_two = FrameStepPlan(seq, 4, pool, bg, cap, flats[1], use_graphs=False)
+    plan_two = FrameStepPlan(seq, n, pool, bg, cap, flats[1], use_graphs=False)
     assert not plan_two.fused_head and not (plan_two.ctx.params.debug & 16)
-    for frames in ([5, 2, 7, 1], [3, 3, 0, 6], [0, 1, 2, 3], [5, 6, 7, 8]):
+    for frames in ([5, 2, 7, 1], [3, 3, 0, 6], [0, 1, 2, 3], [5, 6, 7, 8]) if n == 4 else _PLAN_FRAMES[n] + (list(range(n)),):
         la, lb = plan.run(frames), plan_two.run(frames)
         torch.cuda.synchronize()
         plan.check(); plan_two.check()
@@ -949,14 +990,20 @@ def test_step_plan_fused_head_equals_warp_then_preprocess_bit_for_bit(workload, 
         assert _rel(flats[0].flat.cpu().numpy(), flats[1].flat.cpu().numpy()) < 1e-4      # (two backward blends: float-atomic order)
 
 
-@pytest.mark.parametrize("loss,workload", [("synthetic", "tiny"), ("avatar", "tiny"), ("synthetic", "C3")])
-def test_step_plan_fused_tail_equals_the_two_kernels_bit_for_bit(loss, workload, monkeypatch):
+@pytest.mark.parametrize("loss,workload,n", [("synthetic", "tiny", 4), ("avatar", "tiny", 4), ("synthetic", "C3", 4)]
+                         + [(loss, "tiny", n) for n in (1, 3, 5, 8) for loss in ("synthetic", "avatar")],
+                         ids=["synthetic-tiny", "avatar-tiny", "synthetic-C3"]
+                         + [f"{loss}-tiny-n{n}" for n in (1, 3, 5, 8) for loss in ("synthetic", "avatar")])
+def test_step_plan_fused_tail_equals_the_two_kernels_bit_for_bit(loss, workload, n, monkeypatch):
     """soar_frames_geometry_warp_backward (round 6: the per-Gaussian stage of the rasterizer backward of every frame + the warp's
     backward + the sums over the frames as ONE kernel, geometry_backward_point inlined next to backward_point) against the kernels it
     replaces, on the SAME accumulation rows (the frames' backward calls stop behind their blends, SoarRastParams.debug bit 3; float
     atomics make two blends differ in their last bits, one blend feeds both tails): soar_rast_backward_rows per frame ->
     soar_lbs_warp_backward_sum (-> soar_sum_frames): every output bit for bit -- dL_dmeans2D per frame, and the sums dL_dxyz,
-    dL_drot, dL_dscales, dL_dcolors (, dL_docc).  Then the plan with SOAR_PLAN_FUSED_TAIL=0 gives the same step to float-atomic order."""
+    dL_drot, dL_dscales, dL_dcolors (, dL_docc).  Then the plan with SOAR_PLAN_FUSED_TAIL=0 gives the same step to float-atomic order.
+    Both tails share their grouping and order of the frames, so the sums are also checked against float64 on the host: the rows summed,
+    and the vector-Jacobian product of oracle/lbs_oracle.warp summed over the frames.  At 1 to 8 frames per step: wavefronts past the
+    last frame, and from 5 frames on a second group of frames added into the sums."""
     import ctypes as C
     import bench
     from soar_amd import hip_lib, rasterizer
@@ -972,15 +1019,15 @@ def test_step_plan_fused_tail_equals_the_two_kernels_bit_for_bit(loss, workload,
     bg = torch.tensor([0.2, 0.5, 0.7], device=DEV)
     bench.run_step(seq, pool, flats[0], [0, 1, 2, 3], bg)
     cap = 2 * rasterizer.last_num_rendered
-    plan = FrameStepPlan(seq, 4, pool, bg, cap, flats[0], use_graphs=False, loss=loss)
+    plan = FrameStepPlan(seq, n, pool, bg, cap, flats[0], use_graphs=False, loss=loss)
     assert plan.fused_tail
     monkeypatch.setenv("SOAR_PLAN_FUSED_TAIL", "0")
-    plan_two = FrameStepPlan(seq, 4, pool, bg, cap, flats[1], use_graphs=False, loss=loss)
+    plan_two = FrameStepPlan(seq, n, pool, bg, cap, flats[1], use_graphs=False, loss=loss)
     assert not plan_two.fused_tail
     L = hip_lib.lib()
-    P, n = plan.P, plan.n
+    P = plan.P
     f32 = dict(dtype=torch.float32, device=DEV)
-    for frames in ([5, 2, 7, 1], [3, 3, 0, 6]):
+    for frames in _PLAN_FRAMES[n]:
         losses = plan.run(frames)
         torch.cuda.synchronize()
         plan.check()
@@ -1019,6 +1066,29 @@ def test_step_plan_fused_tail_equals_the_two_kernels_bit_for_bit(loss, workload,
         for name in flats[0].leaves:
             assert torch.equal(flats[0].views[name], views[name]), name
             assert float(views[name].abs().sum()) > 0, name
+        # ... and against float64: the plain sums of the rows element-wise within 1e-6 of the sum of their magnitudes (a float32 sum
+        # of at most 8 terms is well inside), the warp's backward with the bars of test_lbs_gpu.py::test_warp_forward_backward_match_oracle
+        from oracle import lbs_oracle as lo
+        seen = torch.stack([v["radii"] > 0 for v in plan.views]).any(0).cpu()        # Gaussians some frame of the step sees
+        assert bool(seen.any())
+        sums = [("scales", g_scl), ("colors", g_col)] + ([("occ", g_occ[..., None])] if loss == "avatar" else [])
+        for name, rows in sums:
+            rows = rows.double().cpu()
+            ref, got = rows.sum(0), flats[0].views[name].double().cpu()
+            assert float(ref[seen].abs().sum()) > 0, name
+            assert bool(((got - ref).abs() <= 1e-6 * rows.abs().sum(0)).all()), (name, float((got - ref).abs().max()))
+        xyz64 = s.xyz.detach().double().cpu().requires_grad_(True)
+        rot64 = s.rot.detach().double().cpu().requires_grad_(True)
+        w64, mats64 = plan.blend_weights.double().cpu(), plan.mats.double().cpu()
+        gm64, gr64 = g_m3.double().cpu(), g_rot.double().cpu()
+        for i in range(n):
+            p_ref, q_ref, _ = lo.warp(xyz64, rot64, w64, mats64[i])
+            ((p_ref * gm64[i]).sum() + (q_ref * gr64[i]).sum()).backward()
+        for ref in (xyz64.grad, rot64.grad):
+            assert float(ref[seen].abs().sum()) > 0
+        np.testing.assert_allclose(flats[0].views["xyz"].double().cpu().numpy(), xyz64.grad.numpy(), rtol=1e-4, atol=1e-5)
+        scale = float(rot64.grad.abs().max())
+        assert float((flats[0].views["rot"].double().cpu() - rot64.grad).abs().max()) <= 1e-4 * scale
         # ... and the whole step of the plan that keeps the two kernels: the same to float-atomic order
         losses_two = plan_two.run(frames)
         torch.cuda.synchronize()
@@ -1026,10 +1096,12 @@ def test_step_plan_fused_tail_equals_the_two_kernels_bit_for_bit(loss, workload,
         assert _rel(flats[1].flat.cpu().numpy(), fused.cpu().numpy()) < 1e-4      # (two backward blends: float-atomic order)
 
 
-def test_step_plan_batched_launches_equal_the_per_frame_chains():
+@pytest.mark.parametrize("n", [4, 1, 3, 5, 8])
+def test_step_plan_batched_launches_equal_the_per_frame_chains(n):
     """FrameStepPlan(batched=True): one stream, every stage of the chain as one launch for all frames (soar_batch_begin / _frame /
     _end, frame = blockIdx.y) against the frames' chains on streams of their own: same images bit for bit, same losses, gradients
-    to float-atomic order -- over several steps with moving frames (the kept background of empty tiles included)."""
+    to float-atomic order -- over several steps with moving frames (the kept background of empty tiles included), at 1 to 8 frames
+    per step (a batch's argument blocks, its check that every frame reached a launch and its grid follow the frame count)."""
     import bench
     from soar_amd import rasterizer
     from soar_amd.frame_dp import FlatGradBuffer
@@ -1039,9 +1111,10 @@ def test_step_plan_batched_launches_equal_the_per_frame_chains():
     bg = torch.tensor([0.2, 0.5, 0.7], device=DEV)
     bench.run_step(seq, pool, flats[0], [0, 1, 2, 3], bg)
     cap = 2 * rasterizer.last_num_rendered
-    plans = [FrameStepPlan(seq, 4, pool, bg, cap, flats[k], use_graphs=False, batched=(k == 0)) for k in range(2)]
+    plans = [FrameStepPlan(seq, n, pool, bg, cap, flats[k], use_graphs=False, batched=(k == 0)) for k in range(2)]
     assert plans[0].batched and not plans[1].batched
-    for frames in ([0, 1, 2, 3], [9, 2, 30, 17], [3, 2, 1, 0], [3, 2, 1, 0]):
+    steps = ([0, 1, 2, 3], [9, 2, 30, 17], [3, 2, 1, 0], [3, 2, 1, 0]) if n == 4 else (list(range(n)),) + _PLAN_FRAMES[n] + (_PLAN_FRAMES[n][1],)
+    for frames in steps:
         losses = []
         for plan in plans:
             losses.append(plan.run(frames).clone())

@@ -155,44 +155,15 @@ def _avatar_plan_steps(steps):
 def _avatar_composed_steps(steps):
     """The same steps composed from the autograd pieces of the plugin path: lbs_warp, GaussianRasterizer twice, the post-op functions
     (TS/renderer/diff_gaussian_rasterizer.py:292-303), losses.avatar_stage_loss + loss_occ, torch.optim.Adam."""
-    from collections import namedtuple
-    import math
-    from soar_amd import lbs, losses
-    from soar_amd.rasterizer import GaussianRasterizer
-    from soar_amd.renderer.postops import depth2normal, normal2curv
+    from scenes import avatar_frame_loss
     seq, leaves, cam, bg, pool = _avatar_scene()
-    lr, lam, H, W = _AV["lr"], _AV["lam"], _AV["H"], _AV["W"]
+    lr = _AV["lr"]
     opt = torch.optim.Adam([{"params": [leaves[n]], "lr": lr[n]} for n in lr], lr=0.0, eps=1e-15)
-    Cam = namedtuple("Cam", "FoVx FoVy image_height image_width prcppoint")
-    camera = Cam(2 * math.atan(cam.tanfovx), 2 * math.atan(cam.tanfovy), H, W, seq.prcp)
-    flip = torch.tensor([1.0, -1.0, -1.0], device=DEV)[:, None, None]
     losses_, grads, snaps = [], None, []
     for _ in range(steps):
         opt.zero_grad(set_to_none=True)
         seq.refresh_blend_weights()
-        per_frame = []
-        for f in _AV["frames"]:
-            xyz_p, rot_p = lbs.lbs_warp(seq.xyz, seq.rot, seq.blend_weights, seq.cano2live[f])
-            ones = torch.ones_like(seq.opacity)
-            tap = torch.zeros_like(xyz_p, requires_grad=True)
-            render, normal, depth, opac, _ = GaussianRasterizer(seq.settings(bg, False, False))(
-                means3D=xyz_p, means2D=tap, opacities=ones, colors_precomp=seq.colors, scales=seq.scales, rotations=rot_p)
-            occ_img = GaussianRasterizer(seq.settings(bg, True, False))(
-                means3D=xyz_p.detach(), means2D=tap.detach(), opacities=ones, colors_precomp=seq.occ.repeat(1, 3),
-                scales=seq.scales.detach(), rotations=rot_p.detach())[0]
-            mask = opac > 1e-5
-            n = torch.where(mask.repeat(3, 1, 1), normal, normal.detach()) * flip
-            curv = normal2curv(n, opac.detach() > 1e-5)
-            n = (n + 1) / 2
-            pred = (depth2normal(depth, opac.detach() > 1e-5, camera) * flip + 1) / 2
-            out = {"render": render, "normal": n, "depth": depth, "pred_normal": pred, "mask": opac, "occ": occ_img, "curv": curv}
-            k = f % pool.shape[0]
-            gt_rgb, gt_mask, gt_normal = pool[k, 0:3], pool[k, 3:4], pool[k, 4:7]
-            blended = gt_rgb * gt_mask + bg[:, None, None] * (1 - gt_mask)
-            loss = losses.avatar_stage_loss(out, gt_rgb, gt_mask, gt_normal, gt_mask[0] > 1e-5, gt_rgb_blended=blended,
-                                            lambda_recon=lam["recon"], lambda_mask=lam["mask"], lambda_normal=lam["normal"])
-            loss = loss + lam["occ"] * (1 - occ_img.permute(1, 2, 0)[gt_mask[0] > 0]).mean()
-            per_frame.append(loss)
+        per_frame = [avatar_frame_loss(seq, f, bg, pool, _AV["lam"]) for f in _AV["frames"]]
         sum(per_frame).backward()
         if grads is None:
             grads = {n: leaves[n].grad.clone() for n in lr}
