@@ -45,7 +45,8 @@ extern "C" {
  * debug bit 3): the head of the forward pass and the tail of the backward pass of all frames of a step as one kernel each;
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
- * soar_mesh_filter_bytes / _components (mesh export). */
+ * soar_mesh_filter_bytes / _components (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
+ * SoarFieldArgs: the attribute field). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -768,6 +769,56 @@ int soar_mesh_filter_bytes(int32_t V, int32_t F, size_t *bytes);
 int soar_mesh_filter_components(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t min_faces, float min_diag_frac,
                                 void *workspace, size_t workspace_bytes, float *verts_out, int32_t *faces_out, int64_t *counts_host,
                                 void *stream);
+
+/* ---- the surfels' attribute field (field.hip, soar_amd/field.py; DESIGN.md "Attribute field"): the reference's HashMLPSDFField
+ * (TS/geometry/sdf_fields.py:41-219) with nerfstudio's torch HashEncoding / MLP semantics.  Two multiresolution hash encodings of
+ * SOAR_FIELD_LEVELS levels x 2 features (`table` for shs, scales, offsets, opacities; `qtable` for quats), five heads
+ * Linear(in, 64) -> ReLU -> Linear(64, out) with in = 32 (offsets: 34, the encoding and z) and out = 3, 1, 4, 3, 1.
+ *   p = (xyz - aabb[0]) / (aabb[1] - aabb[0]) and p = 0 unless 0 < p < 1 on every axis (normalized = 0), else p = xyz;
+ *   per level l: q = p * res[l], c = ceil(q), f = floor(q) (int32), o = q - f; corner slots
+ *   ((u32)x ^ (u32)y * 2654435761 ^ (u32)z * 805459861) & (2^log2_T - 1), rows l * 2^log2_T + slot of [16 * 2^log2_T][2] tables;
+ *   trilinear weights in o.  Outputs: shs = sigmoid, scales = sigmoid * 2e-2, quats = x / max(|x|, 1e-12), offsets (input
+ *   [encoding, z], z = 0 when NULL), opacities = sigmoid.
+ * Head index k: 0 shs, 1 scales, 2 quats, 3 offsets, 4 opacities.  Weights as nn.Linear keeps them: w1 [64][in], b1 [64],
+ *   w2 [out][64], b2 [out].  A head's gradient buffer d_head[k] holds SOAR_FIELD_HEAD_FLOATS(in, out) floats:
+ *   dw1 [64][in], db1 [64], dw2 [out][64], db2 [out], in that order.
+ * soar_field_forward writes out[k] ([N][out]) and the two encodings enc / qenc ([N][32]), which soar_field_backward reads.
+ * soar_field_backward: g_out[k] [N][out] upstream gradients, NULL = zero (the head then launches nothing).  Writes what is not
+ *   NULL of d_table / d_qtable ([16 * 2^log2_T][2], zero-filled by the call), d_head[k], d_xyz [N][3], d_z [2].  The head
+ *   gradients and d_xyz / d_z are sums in a fixed order: bitwise reproducible.  The table gradients are float atomics
+ *   (global_atomic_add_f32 per corner and feature; neighbouring lanes of a wave that hold the same row add once): their last bits
+ *   depend on arrival order.  The workspace holds
+ *   soar_field_workspace_bytes(N) bytes, 256-byte aligned.  No host synchronisation, no allocation: both calls can be captured.
+ * 0 <= N <= 2^26; N = 0 launches no kernel (the backward still zero-fills its outputs). */
+#define SOAR_FIELD_LEVELS 16
+#define SOAR_FIELD_HIDDEN 64
+#define SOAR_FIELD_HEAD_FLOATS(in, out) (SOAR_FIELD_HIDDEN * (in) + SOAR_FIELD_HIDDEN + (out) * SOAR_FIELD_HIDDEN + (out))
+typedef struct SoarFieldHead {
+    const float *w1, *b1, *w2, *b2;
+} SoarFieldHead;
+
+typedef struct SoarFieldArgs {
+    int32_t N;
+    int32_t log2_T;                  /* rows per level = 2^log2_T, 1 <= log2_T <= 24 */
+    int32_t normalized;              /* is_normalized: no aabb, no selector */
+    int32_t pad_;
+    float res[SOAR_FIELD_LEVELS];    /* level resolutions (float32, nerfstudio's `scalings`) */
+    const float *xyz;                /* [N][3] */
+    const float *aabb;               /* [2][3]; unused when normalized */
+    const float *table, *qtable;     /* [16 * 2^log2_T][2] each */
+    const float *z;                  /* [2] or NULL */
+    SoarFieldHead head[5];
+    float *enc, *qenc;               /* [N][32] each */
+    float *out[5];                   /* forward outputs [N][out_k] */
+    const float *g_out[5];           /* backward: upstream gradients or NULL */
+    float *d_table, *d_qtable;       /* backward outputs or NULL */
+    float *d_head[5];
+    float *d_xyz, *d_z;
+} SoarFieldArgs;
+
+int soar_field_workspace_bytes(int32_t N, size_t *bytes);
+int soar_field_forward(const SoarFieldArgs *args, void *stream);
+int soar_field_backward(const SoarFieldArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

@@ -89,6 +89,22 @@ class SoarAvatarLossArgs(C.Structure):
                 ("normal_raw", C.c_int32), ("occ_grad_summed", C.c_int32), ("cos_scale_out", _vp), ("background", _vp)]
 
 
+class SoarFieldHead(C.Structure):
+    """Mirror of ``struct SoarFieldHead`` (include/soar_hip.h)."""
+    _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
+
+
+FIELD_LEVELS = 16        # SOAR_FIELD_LEVELS
+
+
+class SoarFieldArgs(C.Structure):
+    """Mirror of ``struct SoarFieldArgs`` (include/soar_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("log2_T", C.c_int32), ("normalized", C.c_int32), ("pad_", C.c_int32),
+                ("res", C.c_float * FIELD_LEVELS), ("xyz", _vp), ("aabb", _vp), ("table", _vp), ("qtable", _vp), ("z", _vp),
+                ("head", SoarFieldHead * 5), ("enc", _vp), ("qenc", _vp), ("out", _vp * 5), ("g_out", _vp * 5),
+                ("d_table", _vp), ("d_qtable", _vp), ("d_head", _vp * 5), ("d_xyz", _vp), ("d_z", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -197,6 +213,9 @@ SIGNATURES = {
     "soar_mesh_filter_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_mesh_filter_components": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_float, _vp, C.c_size_t, _vp, _vp,
                                               C.POINTER(C.c_int64), _vp]),
+    "soar_field_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_field_forward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp]),
+    "soar_field_backward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
