@@ -46,7 +46,8 @@ extern "C" {
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
  * soar_mesh_filter_bytes / _components (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
- * SoarFieldArgs: the attribute field). */
+ * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
+ * background). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -819,6 +820,47 @@ typedef struct SoarFieldArgs {
 int soar_field_workspace_bytes(int32_t N, size_t *bytes);
 int soar_field_forward(const SoarFieldArgs *args, void *stream);
 int soar_field_backward(const SoarFieldArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the environment-map background (envmap.hip, soar_amd/background.py): the reference's
+ * NeuralEnvironmentMapBackground ("gaussiandreamer-background") with tiny-cuda-nn's SphericalHarmonics (degree 3) and threestudio's
+ * VanillaMLP (16 neurons, 2 hidden layers, no bias, ReLU), then sigmoid.  Per pixel of dirs [B][H][W][3]:
+ *   x = ((d + 1) / 2) * 2 - 1 per component (float32; |d| = 1 is not assumed), e = the 9 SH values of x (bands 0..2, with the
+ *   0.94617469575755997 z^2 - 0.31539156525251999 form), bg = sigmoid(w3 relu(w2 relu(w1 e))) with w1 [16][9], w2 [16][16], w3 [3][16]
+ *   as nn.Linear keeps them.  color != NULL: bg = color[row] ([1][3] for every row or [B][3] per row) and the MLP is skipped.
+ * soar_envmap_forward writes bg [B][H][W][3] and, for the first n_comp rows, comp [n_comp][3][H][W] = render + (1 - mask) * bg,
+ *   each of the three operations rounded on its own.  render [n_comp][3][H][W] and mask [n_comp][1][H][W] are contiguous per image,
+ *   render_stride / mask_stride elements apart.
+ * soar_envmap_backward: g_comp the gradient of comp at strides g_comp_stride (elements, NCHW order; NULL = zero), g_bg [B][H][W][3]
+ *   contiguous (NULL = zero).  Writes what is not NULL of g_mask [n_comp][H][W] = -sum_c g_comp_c * bg_c, and d_w1 / d_w2 / d_w3
+ *   (all three or none): (1 - mask) g_comp + g_bg back through the sigmoid and the layers, summed over the pixels in double in a
+ *   fixed order (bitwise reproducible; exact zeros with color != NULL).  The gradient of render is g_comp itself (no kernel).  The
+ *   workspace holds soar_envmap_workspace_bytes(B, H, W) bytes, 256-byte aligned.  No host synchronisation, no allocation: both
+ *   calls can be captured.  B * H * W <= 2^30; B * H * W = 0 launches no kernel (the backward still zero-fills d_w*). */
+#define SOAR_ENVMAP_ENC 9
+#define SOAR_ENVMAP_HIDDEN 16
+#define SOAR_ENVMAP_WEIGHTS (SOAR_ENVMAP_HIDDEN * SOAR_ENVMAP_ENC + SOAR_ENVMAP_HIDDEN * SOAR_ENVMAP_HIDDEN + 3 * SOAR_ENVMAP_HIDDEN)
+typedef struct SoarEnvmapArgs {
+    int32_t B, H, W;
+    int32_t n_comp;                  /* rows composited, 0 <= n_comp <= B */
+    int32_t color_rows;              /* rows of color: 1 or B (read only when color != NULL) */
+    int32_t pad_;
+    int64_t render_stride, mask_stride;  /* elements from one image of render / mask to the next */
+    int64_t g_comp_stride[4];        /* strides of g_comp in elements, NCHW order */
+    const float *dirs;               /* [B][H][W][3]; unused when color != NULL */
+    const float *w1, *w2, *w3;       /* [16][9], [16][16], [3][16]; unused when color != NULL */
+    const float *color;              /* device [color_rows][3] or NULL (the MLP) */
+    const float *render, *mask;
+    float *bg;                       /* forward output [B][H][W][3] */
+    float *comp;                     /* forward output [n_comp][3][H][W] */
+    const float *g_comp;             /* backward inputs or NULL */
+    const float *g_bg;
+    float *g_mask;                   /* backward outputs or NULL */
+    float *d_w1, *d_w2, *d_w3;
+} SoarEnvmapArgs;
+
+int soar_envmap_workspace_bytes(int32_t B, int32_t H, int32_t W, size_t *bytes);
+int soar_envmap_forward(const SoarEnvmapArgs *args, void *stream);
+int soar_envmap_backward(const SoarEnvmapArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

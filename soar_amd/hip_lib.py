@@ -105,6 +105,14 @@ class SoarFieldArgs(C.Structure):
                 ("d_table", _vp), ("d_qtable", _vp), ("d_head", _vp * 5), ("d_xyz", _vp), ("d_z", _vp)]
 
 
+class SoarEnvmapArgs(C.Structure):
+    """Mirror of ``struct SoarEnvmapArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_comp", C.c_int32), ("color_rows", C.c_int32),
+                ("pad_", C.c_int32), ("render_stride", C.c_int64), ("mask_stride", C.c_int64), ("g_comp_stride", C.c_int64 * 4),
+                ("dirs", _vp), ("w1", _vp), ("w2", _vp), ("w3", _vp), ("color", _vp), ("render", _vp), ("mask", _vp),
+                ("bg", _vp), ("comp", _vp), ("g_comp", _vp), ("g_bg", _vp), ("g_mask", _vp), ("d_w1", _vp), ("d_w2", _vp), ("d_w3", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -216,6 +224,9 @@ SIGNATURES = {
     "soar_field_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_field_forward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp]),
     "soar_field_backward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp, C.c_size_t, _vp]),
+    "soar_envmap_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_envmap_forward": (C.c_int, [C.POINTER(SoarEnvmapArgs), _vp]),
+    "soar_envmap_backward": (C.c_int, [C.POINTER(SoarEnvmapArgs), _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -4,3 +4,4 @@ from .batch import GaussianBatchRenderer  # noqa: F401
 from .cameras import Camera, get_cam_info_gaussian_cxcy, get_projection_matrix_gaussian, sample_camera  # noqa: F401
 from .diff_gaussian import DiffGaussian, axis_permutation, transform_point_cloud  # noqa: F401
 from .postops import depth2normal, fov2focal, normal2curv  # noqa: F401
+from .. import background  # noqa: F401,E402  (registers "gaussiandreamer-background")

@@ -116,7 +116,13 @@ class GaussianBatchRenderer:
         dev = self.background_tensor.device
         bs = batch["c2w"].shape[0]
         rays_d_all = torch.cat([batch["rays_d"], batch["gt_rays_d"]], dim=0) if "gt_rays_d" in batch else batch["rays_d"]
-        comp_rgb_bg_all = self.background(dirs=rays_d_all)
+        # a background with `composite` (soar_amd.background) forms the background and the SDS composite in one launch behind the
+        # renders; its draws of Python's `random` and torch's CPU generator are made here, where the reference calls it
+        composite = getattr(self.background, "composite", None)
+        if composite is None:
+            comp_rgb_bg_all = self.background(dirs=rays_d_all)
+        else:
+            bg_color = self.background.draw_color(rays_d_all.shape[0], rays_d_all.device)
         T_ocam, fovy_deg = sample_camera(random_elevation_range=[-10.0, 20.0], camera_distance_range=[0.28, 0.28],
                                          relative_radius=True, fovy_range=[30, 45], zoom_range=[1.0, 1.0])
         batch["head_c2ws"] = []
@@ -160,10 +166,13 @@ class GaussianBatchRenderer:
             self._collect(acc, pkg)
         renders = stack_views(acc["render"])
         masks = stack_views(acc["mask"])
-        rgb = renders + (1 - masks) * comp_rgb_bg_all[:bs].permute(0, 3, 1, 2)
+        if composite is None:
+            comp_rgb = (renders + (1 - masks) * comp_rgb_bg_all[:bs].permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        else:
+            comp_rgb, comp_rgb_bg_all = composite(rays_d_all, renders, masks, bs, color=bg_color)
         outputs = self._finish(acc, {"normal": "comp_normal", "pred_normal": "comp_pred_normal", "depth": "comp_depth",
                                      "mask": "comp_mask", "occ": "comp_occ", "curv": "comp_curv"})
-        outputs["comp_rgb"] = rgb.permute(0, 2, 3, 1)
+        outputs["comp_rgb"] = comp_rgb
         if with_gt:
             if gt_pkgs is not None:
                 gt_outputs = self._gt_outputs(*gt_pkgs)
