@@ -47,7 +47,8 @@ extern "C" {
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
  * soar_mesh_filter_bytes / _components (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
- * background). */
+ * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
+ * the LPIPS-VGG loss). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -861,6 +862,45 @@ typedef struct SoarEnvmapArgs {
 int soar_envmap_workspace_bytes(int32_t B, int32_t H, int32_t W, size_t *bytes);
 int soar_envmap_forward(const SoarEnvmapArgs *args, void *stream);
 int soar_envmap_backward(const SoarEnvmapArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- LPIPS-VGG (lpips.hip, soar_amd/lpips.py): lpips 0.1, net='vgg', eval mode, spatial=False.  Per image n of
+ * in0 / in1 [N][3][H][W] (float32, any element strides, NCHW order):
+ *   x' = (x - shift) / scale, VGG16 features[0:30] (13 conv3x3 pad 1 + bias + ReLU, 2x2 max pools in floor mode after relu1_2,
+ *   relu2_2, relu3_3, relu4_3), taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; per tap k and pixel: u = f / (sqrt(sum_c f_c^2)
+ *   + 1e-10), s = sum_c lin_k[c] (u0_c - u1_c)^2; out[n] = sum_k mean over the tap's pixels of s.
+ * soar_lpips_pack_weights builds the private packed form (soar_lpips_weights_bytes bytes, 256-byte aligned) from the torch layouts:
+ *   conv_w[i] [Cout][Cin][3][3], conv_b[i] [Cout], lin[k] [C_k], shift [3], scale [3], all contiguous device arrays.
+ * soar_lpips_forward writes out [N] and, for every branch whose bit is set in `grads` (1: in0, 2: in1), keeps that branch's activations
+ *   and its tap gradients in the workspace (soar_lpips_workspace_bytes(N, H, W, grads) bytes, 256-byte aligned); a branch without
+ *   its bit keeps nothing.  soar_lpips_backward, with the same workspace and `grads` as the forward before it, writes g_in0 / g_in1
+ *   (NULL = not wanted; the bit must have been set) at their own strides: the input gradient of out scaled by g_out [N].
+ *   Every sum has a fixed order (bitwise reproducible); no host synchronisation, no allocation: both calls can be captured.
+ *   H, W >= 16, N >= 0 (N = 0 launches nothing), N * H * W <= 2^30. */
+#define SOAR_LPIPS_LAYERS 13
+#define SOAR_LPIPS_TAPS 5
+typedef struct SoarLpipsWeights {
+    const float *conv_w[SOAR_LPIPS_LAYERS];
+    const float *conv_b[SOAR_LPIPS_LAYERS];
+    const float *lin[SOAR_LPIPS_TAPS];
+    const float *shift, *scale;
+} SoarLpipsWeights;
+typedef struct SoarLpipsArgs {
+    int32_t N, H, W;
+    int32_t grads;                   /* bit 0: in0's branch is kept for a backward, bit 1: in1's */
+    const float *in0, *in1;          /* [N][3][H][W] at in*_stride (elements, NCHW order) */
+    int64_t in0_stride[4], in1_stride[4];
+    const void *weights;             /* soar_lpips_pack_weights' output */
+    float *out;                      /* forward output [N] */
+    const float *g_out;              /* backward input [N] */
+    float *g_in0, *g_in1;            /* backward outputs or NULL, at g_in*_stride */
+    int64_t g_in0_stride[4], g_in1_stride[4];
+} SoarLpipsArgs;
+
+int soar_lpips_weights_bytes(size_t *bytes);
+int soar_lpips_pack_weights(const SoarLpipsWeights *w, void *packed, size_t packed_bytes, void *stream);
+int soar_lpips_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t grads, size_t *bytes);
+int soar_lpips_forward(const SoarLpipsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+int soar_lpips_backward(const SoarLpipsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

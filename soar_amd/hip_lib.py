@@ -113,6 +113,21 @@ class SoarEnvmapArgs(C.Structure):
                 ("bg", _vp), ("comp", _vp), ("g_comp", _vp), ("g_bg", _vp), ("g_mask", _vp), ("d_w1", _vp), ("d_w2", _vp), ("d_w3", _vp)]
 
 
+LPIPS_LAYERS, LPIPS_TAPS = 13, 5     # SOAR_LPIPS_LAYERS, SOAR_LPIPS_TAPS
+
+
+class SoarLpipsWeights(C.Structure):
+    """Mirror of ``struct SoarLpipsWeights`` (include/soar_hip.h)."""
+    _fields_ = [("conv_w", _vp * LPIPS_LAYERS), ("conv_b", _vp * LPIPS_LAYERS), ("lin", _vp * LPIPS_TAPS), ("shift", _vp), ("scale", _vp)]
+
+
+class SoarLpipsArgs(C.Structure):
+    """Mirror of ``struct SoarLpipsArgs`` (include/soar_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("grads", C.c_int32), ("in0", _vp), ("in1", _vp),
+                ("in0_stride", C.c_int64 * 4), ("in1_stride", C.c_int64 * 4), ("weights", _vp), ("out", _vp), ("g_out", _vp),
+                ("g_in0", _vp), ("g_in1", _vp), ("g_in0_stride", C.c_int64 * 4), ("g_in1_stride", C.c_int64 * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -227,6 +242,11 @@ SIGNATURES = {
     "soar_envmap_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_envmap_forward": (C.c_int, [C.POINTER(SoarEnvmapArgs), _vp]),
     "soar_envmap_backward": (C.c_int, [C.POINTER(SoarEnvmapArgs), _vp, C.c_size_t, _vp]),
+    "soar_lpips_weights_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),
+    "soar_lpips_pack_weights": (C.c_int, [C.POINTER(SoarLpipsWeights), _vp, C.c_size_t, _vp]),
+    "soar_lpips_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_lpips_forward": (C.c_int, [C.POINTER(SoarLpipsArgs), _vp, C.c_size_t, _vp]),
+    "soar_lpips_backward": (C.c_int, [C.POINTER(SoarLpipsArgs), _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -445,7 +445,8 @@ def avatar_stage_loss(out: Dict[str, torch.Tensor], gt_rgb: torch.Tensor, gt_mas
       + lambda_depth  * mean(out["depth"]) + lambda_curv * mean(out["curv"])
 
     -- the value ``recon_loss`` / ``masked_l1`` / ``cos_loss`` give when composed by hand, as one autograd node.  (The LPIPS terms
-    of :339-352 need the external VGG network and stay with the caller.)  ``return_terms``: also the detached term vector for
+    of :339-352 are not folded in: the caller adds them with ``soar_amd.lpips.LPIPSVGG``, e.g. ``loss_fn_lpips = LPIPSVGG(sd)`` in
+    place of ``lpips.LPIPS(net='vgg').cuda().eval()``.)  ``return_terms``: also the detached term vector for
     logging (slots ``_AvatarStageLoss.L1 / L1M / COS`` = {value, selected pixels}, ``SSIM``, ``DEPTH``, ``CURV``).
     ``background`` (opt-in): the [3] background colour ``out`` was rendered over -- the gradients of pixels nothing contributed to
     (``out["mask"] <= 1e-5``), which the rasterizer's backward never reads, are then not computed (same loss value; ~40 % of the
