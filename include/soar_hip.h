@@ -48,7 +48,8 @@ extern "C" {
  * soar_mesh_filter_bytes / _components (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
- * the LPIPS-VGG loss). */
+ * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
+ * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -901,6 +902,76 @@ int soar_lpips_pack_weights(const SoarLpipsWeights *w, void *packed, size_t pack
 int soar_lpips_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t grads, size_t *bytes);
 int soar_lpips_forward(const SoarLpipsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 int soar_lpips_backward(const SoarLpipsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the SDS guidance's VAE encoder and loss tail (vae.hip, soar_amd/sds.py) ----
+ * The Stable-Diffusion-2.1 AutoencoderKL encoder (ldm Encoder: ch 128, ch_mult (1,2,4,4), 2 ResnetBlocks per level without temb,
+ * GroupNorm 32 groups eps 1e-6 + SiLU, Downsample = zero pad right / bottom by 1 + 3x3 stride-2 conv, mid ResnetBlock / single-head
+ * AttnBlock / ResnetBlock, norm_out + SiLU + conv_out 512 -> 8) and quant_conv 8 -> 8; mean, logvar = chunk(2); logvar clamped to
+ * [-30, 20]; latents = scale_factor (mean + exp(0.5 logvar) eps).  The input x [N][3][H][W] (any element strides, NCHW order) is
+ * resized to image_size^2 (bilinear, align_corners=False, no antialias) and mapped x * 2 - 1 on load.
+ * Raw weights: one contiguous device float array of soar_vae_weights_floats floats, ldm's tensors in their torch layouts, in this
+ * order (soar_amd/sds.py: WEIGHT_ORDER): conv_in.w, .b; for level i = 0..3, block j = 0..1: norm1.w, .b, conv1.w, .b, norm2.w, .b,
+ * conv2.w, .b, (nin_shortcut.w, .b when Cin != Cout); downsample.conv.w, .b (i < 3); mid.block_1 (as a block); mid.attn_1: norm.w,
+ * .b, q.w, .b, k.w, .b, v.w, .b, proj_out.w, .b; mid.block_2; norm_out.w, .b; conv_out.w, .b; quant_conv.w, .b.
+ * soar_vae_pack_weights builds the private packed form (soar_vae_weights_bytes bytes, 256-byte aligned).
+ * soar_vae_forward writes mean / logvar [N][4][h][w] (h = w = image_size / 8; NULL = not wanted) and, when latents is not NULL,
+ *   latents from eps [N][4][h][w]; it keeps what the backward needs in the workspace (soar_vae_workspace_bytes bytes).
+ * soar_vae_backward, with the workspace of the forward before it (latents written), writes g_x at its strides: the data gradient of
+ *   latents scaled by g_latents (times *g_scale when not NULL), times grad_scale[n][y][x] (NULL = 1) per input pixel.  The weights
+ *   get no gradient.
+ * Every sum has a fixed order, independent of N (bitwise reproducible; N = 4 equals four N = 1 calls); no host synchronisation, no
+ * allocation: both calls can be captured.  N >= 0 (N = 0 launches nothing), H, W >= 1, image_size a positive multiple of 8,
+ * N * image_size^2 and N * H * W <= 2^28. */
+typedef struct SoarVaeArgs {
+    int32_t N, H, W, image_size;
+    const float *x;                  /* [N][3][H][W] at x_stride (elements, NCHW order) */
+    int64_t x_stride[4];
+    const void *weights;             /* soar_vae_pack_weights' output */
+    float scale_factor;
+    const float *eps;                /* [N][4][h][w] posterior noise (needed when latents is not NULL) */
+    float *mean, *logvar, *latents;  /* forward outputs [N][4][h][w] or NULL */
+    const float *g_latents;          /* backward input [N][4][h][w] */
+    const float *g_scale;            /* backward: a device scalar multiplied into g_latents, or NULL */
+    const float *grad_scale;         /* backward: per input pixel [N][H][W] at grad_scale_stride, or NULL */
+    int64_t grad_scale_stride[3];
+    float *g_x;                      /* backward output at g_x_stride */
+    int64_t g_x_stride[4];
+} SoarVaeArgs;
+
+int soar_vae_weights_floats(size_t *floats);
+int soar_vae_weights_bytes(size_t *bytes);
+int soar_vae_pack_weights(const float *raw, size_t raw_floats, void *packed, size_t packed_bytes, void *stream);
+int soar_vae_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t image_size, size_t *bytes);
+int soar_vae_forward(const SoarVaeArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+int soar_vae_backward(const SoarVaeArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The loss tail around the caller's UNet (ImageDream's MultiviewDiffusionGuidance.forward), t read from device memory (clamped to
+ * [0, n_timesteps)).  tables [5][n_timesteps]: sqrt(ac), sqrt(1 - ac), sqrt(1 / ac), sqrt(1 / ac - 1), ac (alphas_cumprod).
+ * soar_sds_q_sample: x_in [2B][4][h][w], both halves = sqrt(ac[t]) latents + sqrt(1 - ac[t]) noise.
+ * soar_sds_loss, eps_pred [2B][4][h][w] = (text, uncond): e = uncond + guidance_scale (text - uncond);
+ *   SOAR_SDS_RECON: recon = sqrt(1/ac) x_t - sqrt(1/ac - 1) e; with recon_std_rescale r > 0, per group of n_view images
+ *     recon = r recon f + (1 - r) recon, f = (std(recon_text) + 1e-8) / (std(recon) + 1e-8) (unbiased std over the group);
+ *     loss = 0.5 sum (latents - recon)^2 / B, g_lat = (latents - recon) / B, grad_norm = |g_lat|;
+ *   SOAR_SDS_PLAIN: g = (1 - ac[t]) (e - noise), clamped to +-grad_clip when grad_clip > 0, nan_to_num; loss = 0.5 sum g^2 / B,
+ *     g_lat = g / B, grad_norm = |g|.
+ *   loss, grad_norm: device scalars.  One workgroup, sums in double in a fixed order. */
+#define SOAR_SDS_PLAIN 0
+#define SOAR_SDS_RECON 1
+typedef struct SoarSdsArgs {
+    int32_t B, n_view, h, w;
+    int32_t mode, n_timesteps;
+    float guidance_scale, recon_std_rescale, grad_clip;
+    const int64_t *t;                /* device scalar */
+    const float *tables;             /* [5][n_timesteps] */
+    const float *latents, *noise;    /* [B][4][h][w] */
+    const float *eps_pred;           /* [2B][4][h][w] */
+    float *x_in;                     /* q_sample output [2B][4][h][w] */
+    float *loss, *grad_norm;         /* device scalars */
+    float *g_lat;                    /* [B][4][h][w] */
+} SoarSdsArgs;
+
+int soar_sds_q_sample(const SoarSdsArgs *args, void *stream);
+int soar_sds_loss(const SoarSdsArgs *args, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

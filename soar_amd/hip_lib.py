@@ -128,6 +128,24 @@ class SoarLpipsArgs(C.Structure):
                 ("g_in0", _vp), ("g_in1", _vp), ("g_in0_stride", C.c_int64 * 4), ("g_in1_stride", C.c_int64 * 4)]
 
 
+class SoarVaeArgs(C.Structure):
+    """Mirror of ``struct SoarVaeArgs`` (include/soar_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("image_size", C.c_int32), ("x", _vp), ("x_stride", C.c_int64 * 4),
+                ("weights", _vp), ("scale_factor", C.c_float), ("eps", _vp), ("mean", _vp), ("logvar", _vp), ("latents", _vp),
+                ("g_latents", _vp), ("g_scale", _vp), ("grad_scale", _vp), ("grad_scale_stride", C.c_int64 * 3), ("g_x", _vp),
+                ("g_x_stride", C.c_int64 * 4)]
+
+
+SDS_PLAIN, SDS_RECON = 0, 1          # SOAR_SDS_PLAIN, SOAR_SDS_RECON
+
+
+class SoarSdsArgs(C.Structure):
+    """Mirror of ``struct SoarSdsArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("n_view", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("mode", C.c_int32), ("n_timesteps", C.c_int32),
+                ("guidance_scale", C.c_float), ("recon_std_rescale", C.c_float), ("grad_clip", C.c_float), ("t", _vp), ("tables", _vp),
+                ("latents", _vp), ("noise", _vp), ("eps_pred", _vp), ("x_in", _vp), ("loss", _vp), ("grad_norm", _vp), ("g_lat", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -247,6 +265,14 @@ SIGNATURES = {
     "soar_lpips_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_lpips_forward": (C.c_int, [C.POINTER(SoarLpipsArgs), _vp, C.c_size_t, _vp]),
     "soar_lpips_backward": (C.c_int, [C.POINTER(SoarLpipsArgs), _vp, C.c_size_t, _vp]),
+    "soar_vae_weights_floats": (C.c_int, [C.POINTER(C.c_size_t)]),
+    "soar_vae_weights_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),
+    "soar_vae_pack_weights": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "soar_vae_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_vae_forward": (C.c_int, [C.POINTER(SoarVaeArgs), _vp, C.c_size_t, _vp]),
+    "soar_vae_backward": (C.c_int, [C.POINTER(SoarVaeArgs), _vp, C.c_size_t, _vp]),
+    "soar_sds_q_sample": (C.c_int, [C.POINTER(SoarSdsArgs), _vp]),
+    "soar_sds_loss": (C.c_int, [C.POINTER(SoarSdsArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
