@@ -725,6 +725,10 @@ int soar_adam_step_at(int32_t n_rows, const SoarAdamRow *rows, double beta1, dou
  * (soar_amd/step_plan.py: the positions behind the first bucket, in front of the KNN refresh; the rest behind the second). */
 int soar_adam_step_rows(int32_t n_rows, const SoarAdamRow *rows, double beta1, double beta2, double eps, void *state_dev, int32_t advance,
                         void *stream);
+/* soar_adam_step_rows over a table of up to 40 rows (a whole geometry model -- the leaves, the attribute field's two hash tables and
+ * the weights of its heads -- in one launch: soar_amd/geometry.py); same state, same arithmetic per element. */
+int soar_adam_step_rows_wide(int32_t n_rows, const SoarAdamRow *rows, double beta1, double beta2, double eps, void *state_dev,
+                             int32_t advance, void *stream);
 
 /* soar_prof_timestamp: one-thread kernel that appends {tag, device wall clock (100 MHz ticks)} to a ring in device memory when
  * `stream` gets there: ring[0] counts the stamps, stamp n lies at ring[1 + 2 (n mod capacity)].  Timelines of launch chains
@@ -972,6 +976,35 @@ typedef struct SoarSdsArgs {
 
 int soar_sds_q_sample(const SoarSdsArgs *args, void *stream);
 int soar_sds_loss(const SoarSdsArgs *args, void *stream);
+
+/* ---- the geometry model's per-surfel passes (soar_amd/geometry.py, csrc/geometry.hip).  One thread per surfel, one launch each.
+ * Activations (TS/geometry/surfel_base.py:441-476): rotation_out = rotation / max(|rotation|_2, 1e-12) (F.normalize) [P][4],
+ * scaling_out = exp(scaling) [P][S] (S in 1..3), opacity_out / occ_out [P] and colors_out [P][3] = sigmoid.  An input that is NULL
+ * is skipped together with its output.  Backward: the five leaf gradients d_* from the five output gradients g_* (NULL = zero; a
+ * d_* that is NULL is not written), from the SAVED outputs (and, for the normalisation, the leaf: its norm is needed once more).
+ * P = 0 succeeds without a launch. */
+int soar_surfel_activations_forward(int32_t P, int32_t S, const float *rotation, const float *scaling, const float *opacity,
+                                    const float *occ, const float *colors, float *rotation_out, float *scaling_out,
+                                    float *opacity_out, float *occ_out, float *colors_out, void *stream);
+int soar_surfel_activations_backward(int32_t P, int32_t S, const float *rotation, const float *rotation_out, const float *scaling_out,
+                                     const float *opacity_out, const float *occ_out, const float *colors_out,
+                                     const float *g_rotation, const float *g_scaling, const float *g_opacity, const float *g_occ,
+                                     const float *g_colors, float *d_rotation, float *d_scaling, float *d_opacity, float *d_occ,
+                                     float *d_colors, void *stream);
+/* The per-surfel regularizers of the training step (TS/system/gaussian_surfel_mvdream.py:257-296), values and gradients in one pass:
+ *   terms[0] = mean(|xyz|_2), [1] = mean(|xyz - original_pos|_2), [2] = sum(|scaling|_2 opacity) (no gradient to scaling),
+ *   [3] = -mean((opacity - 0.5)^2), [4] = mean(scales), [5] = sum_t coef[t] terms[t].
+ * xyz, original_pos [P][3]; scaling [P][S] and opacity [P] activated; scales [P][K] (S, K in 1..3).  coef_dev: five floats in
+ * device memory; a term whose coefficient is 0 is reported as 0 and contributes no gradient.  upstream_dev: a device scalar every
+ * gradient is multiplied by, or NULL (1).  g_xyz [P][3], g_opacity [P], g_scales [P][K] (each may be NULL) receive
+ * upstream * sum_t coef[t] d terms[t]; the norm's gradient at a zero vector is zero (torch).  Sums: per-workgroup partial sums in
+ * double in `workspace` (soar_surfel_regularizers_workspace_bytes), added in a fixed order by a second one-workgroup launch: the
+ * values are bitwise reproducible.  terms_dev: six floats.  P = 0 succeeds without a launch and writes nothing. */
+int soar_surfel_regularizers_workspace_bytes(int32_t P, size_t *bytes);
+int soar_surfel_regularizers(int32_t P, int32_t S, int32_t K, const float *xyz, const float *original_pos, const float *scaling,
+                             const float *opacity, const float *scales, const float *coef_dev, const float *upstream_dev,
+                             float *terms_dev, float *g_xyz, float *g_opacity, float *g_scales, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

@@ -5,3 +5,11 @@ Host code is Python on PyTorch-ROCm; all compute runs in hand-written HIP behind
 library declared in include/soar_hip.h (built by ``soar_amd.build``).
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the geometry model ("gaussiansurfel-base") is exported here without making `import soar_amd` load torch
+    if name == "GaussianSurfelModel":
+        from .geometry import GaussianSurfelModel
+        return GaussianSurfelModel
+    raise AttributeError(f"module 'soar_amd' has no attribute '{name}'")

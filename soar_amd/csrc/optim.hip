@@ -21,11 +21,18 @@ namespace soar {
 namespace {
 
 constexpr int ADAM_MAX_ROWS = 8;
-struct AdamTable {
-    SoarAdamRow row[ADAM_MAX_ROWS];
-    int64_t first_block[ADAM_MAX_ROWS + 1];      // blocks of 1024 elements, row after row
+// a whole model in one launch (the leaves, the attribute field's hash tables and the weights of its heads: soar_amd/geometry.py) needs
+// more rows than the per-frame path's leaves: soar_adam_step_rows_wide runs a second instance of the same kernel over a wider table;
+// the entries of up to 8 rows keep their kernel and the size of its argument block
+constexpr int ADAM_MAX_ROWS_WIDE = 40;
+template <int N>
+struct AdamTableT {
+    SoarAdamRow row[N];
+    int64_t first_block[N + 1];      // blocks of 1024 elements, row after row
     int n;
 };
+using AdamTable = AdamTableT<ADAM_MAX_ROWS>;
+using AdamTableWide = AdamTableT<ADAM_MAX_ROWS_WIDE>;
 struct AdamState {           // 16 bytes of device memory owned by the caller
     int32_t step;
     float bias_correction1, bias_correction2_sqrt;
@@ -42,7 +49,8 @@ __global__ void adam_tick_kernel(AdamState *st, double beta1, double beta2)
 
 // one_minus_b1 / one_minus_b2: 1 - beta worked out in double by the host and rounded once, as torch does with its Python floats
 // (1.f - 0.9f is 0.100000024, float(1 - 0.9) is 0.1: the lerp weight would differ in its last bits)
-__global__ void __launch_bounds__(256) adam_update_kernel(AdamTable tab, const AdamState *__restrict__ st_dev, AdamState st_host, float beta2,
+template <typename Table>
+__global__ void __launch_bounds__(256) adam_update_kernel(Table tab, const AdamState *__restrict__ st_dev, AdamState st_host, float beta2,
                                                           float one_minus_b1, float one_minus_b2, float eps)
 {
     const AdamState *st = st_dev ? st_dev : &st_host;      // the step's bias corrections: from the device counter, or worked out by the host
@@ -82,6 +90,26 @@ __global__ void __launch_bounds__(256) adam_update_kernel(AdamTable tab, const A
         row.exp_avg[i] = m;
         row.exp_avg_sq[i] = v;
     }
+}
+
+// rows -> table; false (error set) if a row is malformed
+template <typename Table>
+bool adam_fill(Table &tab, int32_t n_rows, const SoarAdamRow *rows_host, int max_rows, int64_t &blocks, const char *who)
+{
+    tab.n = n_rows;
+    blocks = 0;
+    for (int r = 0; r < n_rows; r++) {
+        const SoarAdamRow &w = rows_host[r];
+        if (w.count < 0 || (w.count && (!w.param || !w.grad || !w.exp_avg || !w.exp_avg_sq))) {
+            set_error("%s: row %d has a NULL pointer or a negative count", who, r);
+            return false;
+        }
+        tab.row[r] = w;
+        tab.first_block[r] = blocks;
+        blocks += (w.count + 1023) / 1024;
+    }
+    for (int r = n_rows; r <= max_rows; r++) tab.first_block[r] = blocks;
+    return true;
 }
 
 }  // namespace
@@ -127,7 +155,7 @@ extern "C" int soar_adam_step_at(int32_t n_rows, const SoarAdamRow *rows_host, d
     st.pad = 0;
     StageTimer timer(ST_OPTIMIZER, stream);
     if (blocks > 0)
-        hipLaunchKernelGGL(adam_update_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab, (const AdamState *)nullptr, st, (float)beta2,
+        hipLaunchKernelGGL(adam_update_kernel<AdamTable>, dim3((unsigned)blocks), dim3(256), 0, stream, tab, (const AdamState *)nullptr, st, (float)beta2,
                            (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
     SOAR_LAUNCH_OK("adam_step_at", stream, 0);
     return 0;
@@ -142,25 +170,36 @@ extern "C" int soar_adam_step_rows(int32_t n_rows, const SoarAdamRow *rows_host,
         return 1;
     }
     AdamTable tab;
-    tab.n = n_rows;
     int64_t blocks = 0;
-    for (int r = 0; r < n_rows; r++) {
-        const SoarAdamRow &w = rows_host[r];
-        if (w.count < 0 || (w.count && (!w.param || !w.grad || !w.exp_avg || !w.exp_avg_sq))) {
-            set_error("soar_adam_step: row %d has a NULL pointer or a negative count", r);
-            return 1;
-        }
-        tab.row[r] = w;
-        tab.first_block[r] = blocks;
-        blocks += (w.count + 1023) / 1024;
-    }
-    for (int r = n_rows; r <= ADAM_MAX_ROWS; r++) tab.first_block[r] = blocks;
+    if (!adam_fill(tab, n_rows, rows_host, ADAM_MAX_ROWS, blocks, "soar_adam_step")) return 1;
     AdamState *st = static_cast<AdamState *>(state_dev);
     StageTimer timer(ST_OPTIMIZER, stream);
     if (advance) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, stream, st, beta1, beta2);
     if (blocks > 0)
-        hipLaunchKernelGGL(adam_update_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab, st, AdamState{}, (float)beta2, (float)(1.0 - beta1),
-                           (float)(1.0 - beta2), (float)eps);
+        hipLaunchKernelGGL(adam_update_kernel<AdamTable>, dim3((unsigned)blocks), dim3(256), 0, stream, tab, st, AdamState{}, (float)beta2,
+                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
     SOAR_LAUNCH_OK("adam_step", stream, 0);
+    return 0;
+}
+
+// soar_adam_step_rows over a table of up to 40 rows: a whole geometry model in one launch (soar_amd/geometry.py)
+extern "C" int soar_adam_step_rows_wide(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, double beta2, double eps, void *state_dev,
+                                        int32_t advance, void *stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_rows < 0 || n_rows > ADAM_MAX_ROWS_WIDE || (n_rows && !rows_host) || !state_dev) {
+        set_error("soar_adam_step_rows_wide: 0 <= n_rows <= %d, rows and the 16-byte device state must be given", ADAM_MAX_ROWS_WIDE);
+        return 1;
+    }
+    AdamTableWide tab;
+    int64_t blocks = 0;
+    if (!adam_fill(tab, n_rows, rows_host, ADAM_MAX_ROWS_WIDE, blocks, "soar_adam_step_rows_wide")) return 1;
+    AdamState *st = static_cast<AdamState *>(state_dev);
+    StageTimer timer(ST_OPTIMIZER, stream);
+    if (advance) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, stream, st, beta1, beta2);
+    if (blocks > 0)
+        hipLaunchKernelGGL(adam_update_kernel<AdamTableWide>, dim3((unsigned)blocks), dim3(256), 0, stream, tab, st, AdamState{}, (float)beta2,
+                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+    SOAR_LAUNCH_OK("adam_step_rows_wide", stream, 0);
     return 0;
 }

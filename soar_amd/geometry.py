@@ -1,0 +1,876 @@
+"""``"gaussiansurfel-base"``: the surfel geometry model -- the object that owns the parameters.
+
+Mirror of ``GaussianSurfelModel`` (TS/geometry/surfel_base.py:78-1230) where SOAR's surfel configurations reach it: the
+``Config`` (:80-126), ``create_from_pcd`` (:491-580), the properties the renderer plugin reads (:441-489; the attribute list of
+``soar_amd/renderer/diff_gaussian.py``), ``training_setup`` / ``update_learning_rate`` (:581-695), ``update_states`` and the
+densification it drives (:847-1136, :1198-1230), ``capture`` / ``restore`` (:394-440) and ``save_ply`` / ``load_ply`` (:697-846).
+``plyfile``, ``simple_knn`` and the JIT-compiled ``cuda_utils`` extension are not needed.
+
+What runs where:
+
+* the five activated properties (``get_rotation, get_scaling, get_opacity, get_occ, get_colors``) are the outputs of ONE autograd
+  node over ``soar_surfel_activations_forward / _backward`` (csrc/geometry.hip), computed once per optimizer step and cached until
+  a leaf changes (optimizer step, densification, ``restore``, ``load_ply``, ``set_leaves``);
+* ``regularizers`` -- the per-surfel terms of ``training_step`` (TS/system/gaussian_surfel_mvdream.py:257-296) -- is one autograd
+  node over ``soar_surfel_regularizers``: values and gradients from one pass, sums in double in a fixed order;
+* the optimizer (``SurfelAdam``) is ``torch.optim.Adam(groups, lr=0, eps=1e-15)`` as ONE ``soar_adam_step_rows_wide`` launch over every
+  tensor of every group, the attribute field's hash tables and head weights included;
+* densification goes through ``soar_amd.densify.SurfelDensifier``; the attribute field is ``soar_amd.field.HashMLPField``.
+
+The host-only parts (configuration, group table, learning-rate schedule, PLY reading and writing) run without a device; everything
+that computes refuses CPU tensors: there is no CPU fallback.
+
+Where this departs from the reference, on purpose:
+
+* ``original_pos`` and ``max_radii2D`` follow the rows through densification (the reference leaves ``original_pos`` at its first
+  size, so ``get_delta_xyz`` fails after the first densification): kept rows keep their values, clones and split children start at
+  their own new position (delta exactly zero) with ``max_radii2D`` = 0; ``_occ`` follows the rows too (children copy the parent);
+* a one-column ``_scaling`` (what ``create_from_pcd`` makes): the densification kernels read three scale columns, so the column is
+  handed to them three times and the first is kept.  A split child therefore gets ``log(s / 1.6)``.  The reference's
+  ``densify_and_split`` writes ``new_scaling[:, -1] = -1e10`` when ``config[0] > 0`` (:1007-1008), which for a single column is that
+  column: its split children have a scaling logit of -1e10 (size zero), are never split or pruned by size again and drop out of the
+  ``lambda_opacity`` term.  That is taken for an oversight of the three-column code it was adapted from and not reproduced; with three
+  columns the last one gets -1e10 as in the reference.  A degree-0 ``_features_rest`` ([P,0,3]) is stood in for by one zero column;
+* ``capture()`` returns copies (a checkpoint must not move when the model trains on);
+* the optimizer keeps one step counter for all rows (torch keeps one per parameter and starts it at the parameter's first gradient).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import math
+import os
+from dataclasses import dataclass, field
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import hip_lib
+from .field import HashMLPField
+from .hip_lib import check, ptr
+from .renderer import registry
+
+C0 = 0.28209479177387814                      # TS/utils/sh_utils.py
+LAMBDAS = ("lambda_position", "lambda_delta", "lambda_opacity", "lambda_sparsity", "lambda_scales")
+# the per-surfel leaves in the order of training_setup's groups (:596-673); name of the group -> attribute of the model
+LEAVES = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("color", "_colors"), ("opacity", "_opacity"),
+          ("scaling", "_scaling"), ("rotation", "_rotation"), ("occ", "_occ"))
+_DENSIFIED = ("xyz", "f_dc", "f_rest", "color", "opacity", "scaling", "rotation")      # densify.PARAMS
+
+
+def RGB2SH(rgb):
+    return (rgb - 0.5) / C0
+
+
+def SH2RGB(sh):
+    return sh * C0 + 0.5
+
+
+def inverse_sigmoid(x):
+    return torch.log(x / (1 - x))
+
+
+def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000) -> Callable[[float], float]:
+    """``get_expon_lr_func`` (TS/utils/general_utils.py:48-82): log-linear interpolation from ``lr_init`` (step 0) to ``lr_final``
+    (``max_steps``), scaled by a sine ramp from ``lr_delay_mult`` to 1 over the first ``lr_delay_steps`` steps."""
+
+    def helper(step):
+        if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            return 0.0
+        if lr_delay_steps > 0:
+            delay_rate = lr_delay_mult + (1 - lr_delay_mult) * np.sin(0.5 * np.pi * np.clip(step / lr_delay_steps, 0, 1))
+        else:
+            delay_rate = 1.0
+        t = np.clip(step / max_steps, 0, 1)
+        return delay_rate * np.exp(np.log(lr_init) * (1 - t) + np.log(lr_final) * t)
+
+    return helper
+
+
+def quaternion2rotmat(q: torch.Tensor) -> torch.Tensor:
+    """TS/utils/general_utils.py:198-215."""
+    r, x, y, z = q.split(1, -1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y), 2 * (x * y + r * z), 1 - 2 * (x * x + z * z),
+                        2 * (y * z - r * x), 2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], -1).reshape([len(q), 3, 3])
+
+
+def _need_hip(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} is on '{t.device}': soar_amd.geometry computes on HIP devices only; there is no CPU fallback")
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+# ---- the two autograd nodes ----------------------------------------------------------------------------------------------------
+class _Activations(torch.autograd.Function):
+    """(_rotation [P,4], _scaling [P,S], _opacity [P,1], _occ [P,1], _colors [P,3]) -> their activated forms, one launch each way."""
+
+    @staticmethod
+    def forward(ctx, rotation, scaling, opacity, occ, colors):
+        ins = (rotation, scaling, opacity, occ, colors)
+        for t, name in zip(ins, ("_rotation", "_scaling", "_opacity", "_occ", "_colors")):
+            _need_hip(t, name)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError(f"{name} must be a contiguous float32 tensor")
+        P, S, dev = rotation.shape[0], scaling.shape[1], rotation.device
+        outs = tuple(torch.empty_like(t) for t in ins)
+        with torch.cuda.device(dev):
+            check(hip_lib.lib().soar_surfel_activations_forward(P, S, *[ptr(t) for t in ins], *[ptr(t) for t in outs], _stream(dev)),
+                  "soar_surfel_activations_forward")
+        ctx.save_for_backward(rotation, *outs)
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        rotation, *outs = ctx.saved_tensors
+        P, S, dev = rotation.shape[0], outs[1].shape[1], rotation.device
+        gs = [None if g is None else g.to(torch.float32).contiguous() for g in grads]
+        ds = [torch.empty_like(o) if need and g is not None else None for o, g, need in zip(outs, gs, ctx.needs_input_grad)]
+        if any(d is not None for d in ds):
+            with torch.cuda.device(dev):
+                check(hip_lib.lib().soar_surfel_activations_backward(P, S, ptr(rotation), *[ptr(o) for o in outs], *[ptr(g) for g in gs],
+                                                                     *[ptr(d) for d in ds], _stream(dev)),
+                      "soar_surfel_activations_backward")
+        return tuple(ds)
+
+
+def surfel_activations(rotation, scaling, opacity, occ, colors):
+    """The five activations as one node: -> (normalize(rotation), exp(scaling), sigmoid(opacity), sigmoid(occ), sigmoid(colors))."""
+    return _Activations.apply(rotation, scaling, opacity, occ, colors)
+
+
+class _Regularizers(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, original_pos, scaling, opacity, scales, coef, upstream):
+        P, S, K, dev = xyz.shape[0], scaling.shape[1], scales.shape[1], xyz.device
+        terms = torch.zeros(6, dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        g_xyz = torch.empty_like(xyz) if need[0] else None
+        g_op = torch.empty_like(opacity) if need[3] else None
+        g_sc = torch.empty_like(scales) if need[4] else None
+        L = hip_lib.lib()
+        nb = C.c_size_t(0)
+        check(L.soar_surfel_regularizers_workspace_bytes(P, C.byref(nb)), "soar_surfel_regularizers_workspace_bytes")
+        ws = torch.empty(max(int(nb.value), 8), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(L.soar_surfel_regularizers(P, S, K, ptr(xyz), ptr(original_pos), ptr(scaling), ptr(opacity), ptr(scales), ptr(coef),
+                                             ptr(upstream), ptr(terms), ptr(g_xyz), ptr(g_op), ptr(g_sc), ptr(ws), ws.numel(),
+                                             _stream(dev)), "soar_surfel_regularizers")
+        ctx.grads = (g_xyz, g_op, g_sc)
+        loss, values = terms[5], terms[:5]
+        ctx.mark_non_differentiable(values)
+        return loss, values
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_values):
+        g_xyz, g_op, g_sc = ctx.grads              # kept: a second backward (retain_graph) scales the same precomputed gradients again
+        if g_loss is None:
+            return (None,) * 7
+        live = [g for g in (g_xyz, g_op, g_sc) if g is not None and g.numel()]
+        scaled = iter(torch._foreach_mul(live, g_loss.to(torch.float32))) if live else iter(())      # the chain rule's factor, one launch
+        out = [next(scaled) if g is not None and g.numel() else g for g in (g_xyz, g_op, g_sc)]
+        return out[0], None, None, out[1], out[2], None, None
+
+
+_COEF_CACHE: Dict[Tuple, torch.Tensor] = {}
+
+
+def _device_floats(values: Sequence[float], dev) -> torch.Tensor:
+    """Small constant vectors are uploaded once per distinct value (no host-to-device copy per step)."""
+    key = (str(dev), tuple(float(v) for v in values))
+    t = _COEF_CACHE.get(key)
+    if t is None:
+        if len(_COEF_CACHE) > 256:
+            _COEF_CACHE.clear()
+        t = _COEF_CACHE[key] = torch.tensor(key[1], dtype=torch.float32, device=dev)
+    return t
+
+
+def surfel_regularizers(xyz, original_pos, scaling, opacity, scales, lambdas: Dict[str, float], grad_scale=None):
+    """-> (loss, terms [5]).  loss = sum_t lambdas[t] terms[t] over ``LAMBDAS`` (missing = 0); terms (detached):
+    mean|xyz|, mean|xyz - original_pos|, sum(|scaling|.detach() opacity), -mean((opacity - 0.5)^2), mean(scales).  ``scaling`` and
+    ``opacity`` are the activated tensors.  ``grad_scale``: a device scalar (or a number) every gradient is multiplied by."""
+    unknown = set(lambdas) - set(LAMBDAS)
+    if unknown:
+        raise ValueError(f"unknown regularizer weights {sorted(unknown)}; known: {LAMBDAS}")
+    for t, name in ((xyz, "xyz"), (original_pos, "original_pos"), (scaling, "scaling"), (opacity, "opacity"), (scales, "scales")):
+        _need_hip(t, name)
+    dev = xyz.device
+    P = xyz.shape[0]
+    f = lambda t: t.to(torch.float32).contiguous()
+    if scaling.shape[0] != P or opacity.numel() != P or scales.shape[0] != P or original_pos.shape != xyz.shape:
+        raise ValueError("surfel_regularizers: every tensor must have one row per surfel")
+    if P == 0:
+        z = torch.zeros((), device=dev)
+        return z, torch.zeros(5, device=dev)
+    coef = _device_floats([float(lambdas.get(k, 0.0)) for k in LAMBDAS], dev)
+    if grad_scale is not None and not isinstance(grad_scale, torch.Tensor):
+        grad_scale = _device_floats([float(grad_scale)], dev)
+    if grad_scale is not None:
+        _need_hip(grad_scale, "grad_scale")
+        grad_scale = f(grad_scale.detach().reshape(-1)[:1])
+    return _Regularizers.apply(f(xyz), f(original_pos.detach()), f(scaling.reshape(P, -1)), f(opacity.reshape(P, 1)),
+                               f(scales.reshape(P, -1)), coef, grad_scale)
+
+
+# ---- the optimizer -------------------------------------------------------------------------------------------------------------
+class SurfelAdam:
+    """``torch.optim.Adam(groups, lr=0.0, eps=1e-15)`` (:675) as one ``soar_adam_step_rows_wide`` launch over every tensor of every group.
+
+    ``param_groups`` (dicts with ``name``, ``lr``, ``params``) and ``state`` (parameter -> ``exp_avg`` / ``exp_avg_sq``) have
+    torch's shape, which is what ``SurfelDensifier`` edits.  A parameter whose ``.grad`` is None is skipped, as in torch.  The
+    step counter lives on the device; ``steps`` is its host copy."""
+
+    MAX_ROWS = 40
+
+    def __init__(self, groups: List[dict], lr: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-15, on_step: Optional[Callable] = None):
+        self.param_groups = []
+        for g in groups:
+            g = dict(g)
+            g["params"] = list(g["params"])
+            g.setdefault("lr", lr)
+            self.param_groups.append(g)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.state: Dict[torch.Tensor, Dict[str, torch.Tensor]] = {}
+        for g in self.param_groups:
+            for p in g["params"]:
+                self.state[p] = {"exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
+        self.steps = 0
+        self._dev_state: Optional[torch.Tensor] = None
+        self._on_step = on_step
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.grad is not None:
+                    if set_to_none:
+                        p.grad = None
+                    else:
+                        p.grad.zero_()
+
+    def _device_counter(self, dev) -> torch.Tensor:
+        if self._dev_state is None or self._dev_state.device != dev:
+            t = self.steps
+            b1, b2 = self.betas
+            raw = np.zeros(4, np.int32)
+            raw[0] = t
+            raw[1:3] = np.array([1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)], np.float32).view(np.int32)
+            self._dev_state = torch.from_numpy(raw).to(dev)
+        return self._dev_state
+
+    def rows(self):
+        """The row table of the next step: (ctypes array, tensors to keep alive, the parameters in it)."""
+        entries, keep, params = [], [], []
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.grad is None or p.numel() == 0:
+                    continue
+                _need_hip(p, f"a parameter of group '{g['name']}'")
+                grad = p.grad
+                if grad.dtype != torch.float32 or not grad.is_contiguous():
+                    grad = grad.to(torch.float32).contiguous()
+                    keep.append(grad)
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise TypeError(f"group '{g['name']}': parameters must be contiguous float32 tensors")
+                st = self.state[p]
+                entries.append((p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), float(g["lr"])))
+                params.append(p)
+        if len(entries) > self.MAX_ROWS:
+            raise ValueError(f"{len(entries)} tensors to step; soar_adam_step_rows_wide takes {self.MAX_ROWS}")
+        table = (hip_lib.SoarAdamRow * max(len(entries), 1))()
+        for k, (a, b, c, d, n, lr) in enumerate(entries):
+            table[k].param, table[k].grad, table[k].exp_avg, table[k].exp_avg_sq, table[k].count, table[k].lr = a, b, c, d, n, lr
+        return table, keep, params
+
+    def step(self) -> None:
+        table, keep, params = self.rows()
+        if not params:
+            return
+        dev = params[0].device
+        with torch.cuda.device(dev):
+            check(hip_lib.lib().soar_adam_step_rows_wide(len(params), table, self.betas[0], self.betas[1], self.eps,
+                                                    ptr(self._device_counter(dev)), 1, _stream(dev)), "soar_adam_step_rows_wide")
+        self.steps += 1
+        torch.autograd.graph.increment_version(params)       # written through raw pointers: caches keyed on versions must see it
+        if self._on_step is not None:
+            self._on_step()
+
+    def state_dict(self) -> dict:
+        return {"steps": self.steps, "betas": self.betas, "eps": self.eps,
+                "groups": [{"name": g["name"], "lr": g["lr"],
+                            "state": [(self.state[p]["exp_avg"].clone(), self.state[p]["exp_avg_sq"].clone()) for p in g["params"]]}
+                           for g in self.param_groups]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        names = [g["name"] for g in self.param_groups]
+        if [g["name"] for g in sd["groups"]] != names:
+            raise ValueError(f"optimizer state has groups {[g['name'] for g in sd['groups']]}, the model has {names}")
+        for g, s in zip(self.param_groups, sd["groups"]):
+            g["lr"] = s["lr"]
+            if len(s["state"]) != len(g["params"]):
+                raise ValueError(f"group '{g['name']}': {len(s['state'])} saved tensors for {len(g['params'])} parameters")
+            for p, (m, v) in zip(g["params"], s["state"]):
+                if m.shape != p.shape:
+                    raise ValueError(f"group '{g['name']}': saved moments {tuple(m.shape)} for a parameter {tuple(p.shape)}")
+                self.state[p] = {"exp_avg": m.detach().clone().to(p.device), "exp_avg_sq": v.detach().clone().to(p.device)}
+        self.steps = int(sd["steps"])
+        self.betas, self.eps = (float(sd["betas"][0]), float(sd["betas"][1])), float(sd["eps"])
+        self._dev_state = None
+
+
+# ---- PLY (binary_little_endian 1.0, one vertex element of float properties) -----------------------------------------------------
+def ply_property_names(n_dc: int, n_rest: int, n_scale: int, n_rot: int = 4) -> List[str]:
+    """``construct_list_of_attributes`` (:697-709)."""
+    return (["x", "y", "z", "nx", "ny", "nz"] + [f"f_dc_{i}" for i in range(n_dc)] + [f"f_rest_{i}" for i in range(n_rest)]
+            + ["opacity"] + [f"scale_{i}" for i in range(n_scale)] + [f"rot_{i}" for i in range(n_rot)])
+
+
+def write_ply(path: str, names: List[str], rows: np.ndarray) -> None:
+    rows = np.ascontiguousarray(rows, dtype="<f4")
+    if rows.ndim != 2 or rows.shape[1] != len(names):
+        raise ValueError(f"{rows.shape} values for {len(names)} properties")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {rows.shape[0]}"] + [f"property float {n}" for n in names] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(rows.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path: str) -> Dict[str, np.ndarray]:
+    """-> property name -> [count] array of the ``vertex`` element.  Header lines may end in ``\\r\\n``; ``comment`` and
+    ``obj_info`` lines are skipped; elements after ``vertex`` are ignored, list properties and ASCII files are refused."""
+    with open(path, "rb") as f:
+        data = f.read()
+    lines, pos = [], 0
+    while True:
+        end = data.find(b"\n", pos)
+        if end < 0:
+            raise ValueError(f"{path}: no end_header line")
+        line = data[pos:end].decode("ascii", "replace").rstrip("\r").strip()
+        pos = end + 1
+        lines.append(line)
+        if line == "end_header":
+            break
+    if not lines or lines[0] != "ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    for line in lines[1:-1]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                if elements[-1][0] == "vertex" or not any(e[0] == "vertex" for e in elements):
+                    raise ValueError(f"{path}: list property '{tok[-1]}' in or before the vertex element is not supported")
+                continue
+            if tok[1] not in _PLY_TYPES:
+                raise ValueError(f"{path}: unknown property type '{tok[1]}'")
+            elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+    if fmt not in ("binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"{path}: format '{fmt}' is not supported (binary_little_endian 1.0 is what save_ply writes)")
+    order = "<" if fmt == "binary_little_endian" else ">"
+    for name, count, props in elements:
+        dt = np.dtype([(n, order + t) for n, t in props])
+        if name == "vertex":
+            if len(data) - pos < count * dt.itemsize:
+                raise ValueError(f"{path}: {count} vertices of {dt.itemsize} bytes announced, {len(data) - pos} bytes present")
+            arr = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+            return {n: np.ascontiguousarray(arr[n]) for n, _ in props}
+        pos += count * dt.itemsize
+    raise ValueError(f"{path}: no vertex element")
+
+
+# ---- the model ----------------------------------------------------------------------------------------------------------------
+@registry.register("gaussiansurfel-base")
+class GaussianSurfelModel(registry.BaseObject):
+    @dataclass
+    class Config(registry.BaseObject.Config):
+        """TS/geometry/surfel_base.py:80-126, same names and defaults."""
+        max_num: int = 500000
+        sh_degree: int = 0
+        position_lr_init: Any = 0.001
+        position_lr_final: Any = 0.00001
+        position_lr_delay_mult: Any = 0.01
+        position_lr_max_steps: Any = 2000
+        camera_lr: Any = 0.0
+        scale_lr: Any = 0.003
+        feature_lr: Any = 0.01
+        opacity_lr: Any = 0.05
+        scaling_lr: Any = 0.005
+        rotation_lr: Any = 0.005
+        pred_normal: bool = False
+        normal_lr: Any = 0.001
+        field_lr: Any = 0.01
+        occ_lr: Any = 0.01
+        background_lr: Any = 0.01
+        latent_pose_lr: Any = 0.01
+        densification_interval: int = 50
+        prune_interval: int = 50
+        opacity_reset_interval: int = 100000
+        densify_from_iter: int = 100
+        prune_from_iter: int = 100
+        densify_until_iter: int = 2000
+        prune_until_iter: int = 2000
+        densify_grad_threshold: Any = 0.01
+        min_opac_prune: Any = 0.005
+        split_thresh: Any = 0.02
+        radii2d_thresh: Any = 1000
+        sphere: bool = True
+        prune_big_points: bool = False
+        color_clip: Any = 2.0
+        geometry_convert_from: str = ""
+        load_ply_only_vertex: bool = False
+        init_num_pts: int = 100
+        pc_init_radius: float = 0.8
+        opacity_init: float = 0.1
+        shap_e_guidance_config: dict = field(default_factory=dict)
+        smpl_guidance_config: dict = field(default_factory=dict)
+
+    cfg: Config
+
+    def __init__(self, cfg: Optional[dict] = None, *args, **kwargs):
+        cfg = dict(cfg or {})
+        known = {f.name for f in dataclasses.fields(self.Config)}
+        unknown = sorted(set(cfg) - known)
+        if unknown:
+            registry.info(f"GaussianSurfelModel: ignoring unknown config keys {unknown}")
+        super().__init__({k: v for k, v in cfg.items() if k in known}, *args, **kwargs)
+
+    def configure(self, smpl_guidance=None) -> None:
+        """:145-182.  The guidance object may also be given later, to ``create_from_pcd``."""
+        self.active_sh_degree = 0
+        self.max_sh_degree = self.cfg.sh_degree
+        e = torch.empty(0)
+        self._xyz = self._features_dc = self._features_rest = self._scaling = self._rotation = self._opacity = e
+        self._colors = self._occ = self.original_pos = self.max_radii2D = e
+        self.percent_dense = 0.01
+        self.spatial_lr_scale = 0
+        self.config = [True, True, True]
+        self.smpl_guidance = smpl_guidance
+        self.attribute_field = None
+        self.optimizer: Optional[SurfelAdam] = None
+        self.densifier = None
+        self.radius = 1e-1
+        self._act = None
+        self.generation = 0            # bumped whenever the leaves are replaced or stepped
+
+    # ---- the cache of the activated leaves -------------------------------------------------------------------------------------
+    def invalidate(self, reason: str = "") -> None:
+        """Drop the cached activations (called by the optimizer after a step and by the densifier when it replaces the leaves)."""
+        self._act = None
+        self.generation += 1
+
+    def _activated(self):
+        ins = (self._rotation, self._scaling, self._opacity, self._occ, self._colors)
+        # the leaves themselves and their version counters: an in-place write (the optimizer bumps the counters) or a replaced leaf
+        # makes the cache stale without anybody calling invalidate()
+        key = (torch.is_grad_enabled(),) + tuple((id(t), t._version) for t in ins)
+        if self._act is None or self._act[0] != key:
+            self._act = (key, surfel_activations(*ins), ins)
+        return self._act[1]
+
+    get_rotation = property(lambda s: s._activated()[0])
+    get_scaling = property(lambda s: s._activated()[1])
+    get_opacity = property(lambda s: s._activated()[2])
+    get_occ = property(lambda s: s._activated()[3])
+    get_colors = property(lambda s: s._activated()[4])
+    get_xyz = property(lambda s: s._xyz)
+    get_delta_xyz = property(lambda s: s._xyz - s.original_pos)
+    get_features = property(lambda s: torch.cat((s._features_dc, s._features_rest), dim=1))
+    get_normal = property(lambda s: quaternion2rotmat(s.get_rotation)[..., 2])
+    num_points = property(lambda s: int(s._xyz.shape[0]))
+
+    def oneupSHdegree(self) -> None:
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
+    # ---- construction ----------------------------------------------------------------------------------------------------------
+    def set_leaves(self, **leaves) -> None:
+        """Replace per-surfel tensors by name (``xyz, f_dc, f_rest, color, opacity, scaling, rotation, occ``, raw values as the
+        optimizer holds them; also ``original_pos`` and ``max_radii2D``).  The optimizer, if there is one, must be set up again."""
+        attr = dict(LEAVES)
+        for k, v in leaves.items():
+            if k in attr:
+                setattr(self, attr[k], nn.Parameter(v.detach().to(torch.float32).contiguous().clone().requires_grad_(True)))
+            elif k in ("original_pos", "max_radii2D"):
+                setattr(self, k, v.detach().to(torch.float32).contiguous().clone())
+            else:
+                raise ValueError(f"unknown leaf '{k}'")
+        self.optimizer, self.densifier = None, None
+        self.invalidate()
+
+    def create_from_pcd(self, points, colors, spatial_lr_scale: float, smpl_guidance=None) -> None:
+        """:491-580.  points [P,3], colors [P,3] in (0, 1) (arrays or tensors)."""
+        from . import lbs
+        if smpl_guidance is not None:
+            self.smpl_guidance = smpl_guidance
+        guide = self.smpl_guidance
+        self.spatial_lr_scale = spatial_lr_scale
+        dev = torch.device("cuda")
+        pts = torch.as_tensor(np.asarray(points.detach().cpu() if isinstance(points, torch.Tensor) else points)).float().to(dev).contiguous()
+        col = torch.as_tensor(np.asarray(colors.detach().cpu() if isinstance(colors, torch.Tensor) else colors)).float().to(dev)
+        P = pts.shape[0]
+        fused_color = RGB2SH(col)
+        dist2 = torch.clamp_min(lbs.dist2_knn3(pts), 0.0000001)
+        scales = torch.log(torch.sqrt(dist2))[..., None]
+        init_q = getattr(guide, "init_q", None)
+        if self.config[0] > 0 and init_q is not None:
+            rots = torch.as_tensor(init_q).float().to(dev).reshape(P, 4).clone()
+        else:
+            rots = torch.zeros((P, 4), device=dev)
+            rots[:, 0] = 1
+        features = torch.zeros((P, 3, (self.max_sh_degree + 1) ** 2), device=dev)
+        features[:, :3, 0] = fused_color
+        opacities = inverse_sigmoid(0.1 * torch.ones((P, 1), dtype=torch.float, device=dev))
+        par = lambda t: nn.Parameter(t.contiguous().requires_grad_(True))
+        self.original_pos = pts.clone().detach()
+        self._xyz = par(pts)
+        self._features_dc = par(features[:, :, 0:1].transpose(1, 2))
+        self._features_rest = par(features[:, :, 1:].transpose(1, 2))
+        self._colors = par(torch.logit(col))
+        self._scaling = par(scales)
+        self._rotation = par(rots)
+        self._opacity = par(opacities)
+        self._occ = par(torch.logit(torch.ones((P, 1), device=dev) * 1e-2))
+        if not hasattr(self, "latent_pose"):
+            n_frames = len(guide.smpl_parms["body_pose"]) if guide is not None and "body_pose" in getattr(guide, "smpl_parms", {}) else 1
+            self.latent_pose = nn.Parameter(torch.zeros((n_frames, 2), device=dev).requires_grad_(True))
+        self.max_radii2D = torch.zeros((P,), device=dev)
+        cano = getattr(guide, "query_points", None)
+        cano = pts[None] if cano is None else torch.as_tensor(cano).float().to(dev).reshape(1, -1, 3)
+        aabb = torch.stack([cano.min(dim=1)[0], cano.max(dim=1)[0]]).reshape(2, 3)
+        center = aabb.mean(dim=0)
+        self.aabb = (aabb - center) * 1.5 + center
+        self.radius = 1e-1
+        self.attribute_field = HashMLPField(self.aabb).to(dev)
+        self.optimizer, self.densifier = None, None
+        self.invalidate()
+
+    # ---- the regularizers --------------------------------------------------------------------------------------------------------
+    def regularizers(self, lambdas: Dict[str, float], scales: Optional[torch.Tensor] = None, grad_scale=None):
+        """The per-surfel terms of ``training_step`` (TS/system/gaussian_surfel_mvdream.py:257-296) -> (loss, terms [5]) in the
+        order of ``LAMBDAS``.  ``scales``: what ``lambda_scales`` averages -- the field's ``scales`` output (``use_explicit`` false)
+        or None for the activated scaling.  A term whose weight is missing or 0 is reported as 0 and contributes no gradient."""
+        scaling = self.get_scaling
+        return surfel_regularizers(self._xyz, self.original_pos, scaling, self.get_opacity, scaling if scales is None else scales,
+                                   lambdas, grad_scale)
+
+    # ---- the optimizer -----------------------------------------------------------------------------------------------------------
+    def parameter_groups(self, training_args=None) -> List[dict]:
+        """The groups of ``training_setup`` (:596-673): names, order and learning rates."""
+        a = self.cfg if training_args is None else training_args
+        f = self.attribute_field
+        fp = (lambda m: list(m.parameters())) if f is not None else None
+        groups = [
+            {"params": [self._xyz], "lr": a.position_lr_init * self.spatial_lr_scale, "name": "xyz"},
+            {"params": [self._features_dc], "lr": a.feature_lr, "name": "f_dc"},
+            {"params": [self._features_rest], "lr": a.feature_lr / 20.0, "name": "f_rest"},
+            {"params": [self._colors], "lr": a.feature_lr, "name": "color"},
+        ]
+        if f is not None:
+            groups += [
+                {"params": fp(f.encoding), "lr": a.field_lr, "name": "attribute_field_encoding"},
+                {"params": fp(f.quat_encoding), "lr": a.field_lr, "name": "attribute_field_quat_encoding"},
+                {"params": fp(f.mlp_base_shs), "lr": a.field_lr, "name": "attribute_field_shs"},
+                {"params": fp(f.mlp_base_quats), "lr": a.field_lr, "name": "attribute_field_quats"},
+                {"params": fp(f.mlp_base_scales), "lr": a.field_lr * 10, "name": "attribute_field_scales"},
+                {"params": fp(f.mlp_base_offsets), "lr": a.field_lr * 0.01, "name": "attribute_field_offests"},      # (sic, :636)
+            ]
+        groups += [
+            {"params": [self._opacity], "lr": a.opacity_lr, "name": "opacity"},
+            {"params": [self._scaling], "lr": a.scaling_lr, "name": "scaling"},
+            {"params": [self._rotation], "lr": a.rotation_lr, "name": "rotation"},
+            {"params": [self._occ], "lr": a.occ_lr, "name": "occ"},
+        ]
+        if hasattr(self, "latent_pose"):
+            groups.append({"params": [self.latent_pose], "lr": a.latent_pose_lr, "name": "latent_pose"})
+        return groups
+
+    def training_setup(self, training_args=None) -> None:
+        """:581-687: the groups, Adam(lr=0, eps=1e-15), the positions' schedule, the densifier and its statistics."""
+        a = self.cfg if training_args is None else training_args
+        if training_args is not None and hasattr(training_args, "percent_dense"):
+            self.percent_dense = training_args.percent_dense
+        config = self.config.tolist() if isinstance(self.config, torch.Tensor) else list(self.config)
+        flag = float(a.camera_lr > 0)
+        config = config + [flag] if len(config) <= 3 else config[:3] + [flag] + config[4:]
+        self.config = torch.tensor([float(c) for c in config], dtype=torch.float32, device=self._xyz.device)
+        self.optimizer = SurfelAdam(self.parameter_groups(a), lr=0.0, eps=1e-15, on_step=self.invalidate)
+        self.xyz_scheduler_args = get_expon_lr_func(lr_init=a.position_lr_init * self.spatial_lr_scale,
+                                                    lr_final=a.position_lr_final * self.spatial_lr_scale,
+                                                    lr_delay_mult=a.position_lr_delay_mult, max_steps=a.position_lr_max_steps)
+        self.densifier = None
+        if self._xyz.is_cuda:
+            self._make_densifier()
+
+    def update_learning_rate(self, iteration):
+        """:689-695: the positions' learning rate of this iteration, written into the ``xyz`` group (the next step's row)."""
+        for g in self.optimizer.param_groups:
+            if g["name"] == "xyz":
+                lr = self.xyz_scheduler_args(iteration)
+                g["lr"] = lr
+                return lr
+
+    # ---- densification -----------------------------------------------------------------------------------------------------------
+    def _group(self, name: str) -> dict:
+        for g in self.optimizer.param_groups:
+            if g["name"] == name:
+                return g
+        raise KeyError(name)
+
+    def _replace_leaf(self, name: str, new: torch.Tensor, moments: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> nn.Parameter:
+        """``replace_tensor_to_optimizer`` (:847-860): a leaf gets a new tensor; its Adam moments are given or start at zero."""
+        attr = dict(LEAVES)[name]
+        old = getattr(self, attr)
+        new = new if isinstance(new, nn.Parameter) else nn.Parameter(new.detach().contiguous().requires_grad_(True))
+        if self.optimizer is not None:
+            self.optimizer.state.pop(old, None)
+            self._group(name)["params"][0] = new
+            m, v = moments if moments is not None else (torch.zeros_like(new), torch.zeros_like(new))
+            self.optimizer.state[new] = {"exp_avg": m.contiguous(), "exp_avg_sq": v.contiguous()}
+        setattr(self, attr, new)
+        return new
+
+    @staticmethod
+    def _wide(t: torch.Tensor) -> torch.Tensor:
+        """The densification kernels read three scale columns per surfel; a narrower model (``create_from_pcd`` has one column) hands
+        them its first column in the missing ones (``max`` / ``min`` over the columns are then the reference's over its own)."""
+        return t if t.shape[1] == 3 else torch.cat([t] + [t[:, :1]] * (3 - t.shape[1]), 1).contiguous()
+
+    def _densifier_params(self) -> Dict[str, torch.Tensor]:
+        params = {k: getattr(self, dict(LEAVES)[k]) for k in _DENSIFIED}
+        if self._scaling.shape[1] != 3:
+            params["scaling"] = self._wide(self._scaling.detach())
+        if self._features_rest.numel() == 0:
+            # degree 0: [P,0,3] has no rows to move, and the kernels take no empty row; one zero column stands in and is dropped again
+            params["f_rest"] = self._xyz.new_zeros((self.num_points, 1, 3))
+        return params
+
+    def _make_densifier(self) -> None:
+        from .densify import SurfelDensifier
+        # the densifier gets no optimizer: it moves the seven tensors it knows; the model moves every other per-row tensor (moments
+        # of all eight leaves, original_pos, max_radii2D, _occ) by the same row map (_row_map)
+        self.densifier = SurfelDensifier(self._densifier_params(), None, percent_dense=self.percent_dense,
+                                         surface=bool(float(self.config[0]) > 0))
+        if self.max_radii2D.shape[0] == self.num_points:
+            self.densifier.max_radii2D = self.max_radii2D
+        self.densifier.register_dependent(self)
+
+    def add_densification_stats(self, radii, viewspace_grad, scaling_grad=None) -> None:
+        """One view of ``update_states`` (:1208-1216, ``add_densification_stats`` :1113-1136)."""
+        d = self.densifier
+        d.params = self._densifier_params()
+        sg = self._scaling.grad if scaling_grad is None else scaling_grad
+        if sg is None:
+            sg = torch.zeros_like(self._scaling)
+        if sg.shape[1] != 3:                   # the reference sums the first two columns; a narrower model has fewer
+            sg = torch.cat([sg, sg.new_zeros(sg.shape[0], 3 - sg.shape[1])], 1)
+        d.max_radii2D = self.max_radii2D
+        d.add_densification_stats(radii, viewspace_grad, sg)
+
+    @torch.no_grad()
+    def update_states(self, iteration, visibility_filter, radii, viewspace_point_tensor, generator=None, noise=None):
+        """:1198-1230.  ``viewspace_point_tensor``: per view, the tensor whose ``.grad`` holds the screen-space gradients (or the
+        gradient itself).  Statistics of every view (filter = radii > 0, which is what ``visibility_filter`` holds), then on the
+        interval prune (after ``prune_from_iter``) + densify, then the periodic opacity reset.  Returns the densifier's counts when
+        the rows changed, else None."""
+        if self.densifier is None:
+            raise RuntimeError("update_states: call training_setup() first")
+        cfg = self.cfg
+        if iteration <= cfg.densify_from_iter:
+            return None
+        for i in range(len(radii)):
+            v = viewspace_point_tensor[i]
+            self.add_densification_stats(radii[i], v.grad if getattr(v, "grad", None) is not None else v)
+        result = None
+        if iteration % cfg.densification_interval == 0:
+            result = self.prune_and_densify(0.1, cfg.densify_grad_threshold, self.radius, do_prune=iteration > cfg.prune_from_iter,
+                                            generator=generator, noise=noise)
+        if (iteration - 1) % cfg.opacity_reset_interval == 0 and cfg.opacity_lr > 0:
+            self.reset_opacity(0.12, iteration)
+        return result
+
+    @staticmethod
+    def _row_map(flags: torch.Tensor, N: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (source, kept) for every row after a plan with these decision bytes (1 pruned, 2 clone, 4 split), in the densifier's
+        final order (``densify_and_clone``, ``densify_and_split`` and its prune, :982-1064): the survivors that are not split in
+        their old order, the clones, then the N children of the split rows, copy after copy.  source: the row a new row was made
+        from (a kept row: itself); kept: false for clones and children."""
+        pruned, clone, split = (flags & 1) > 0, (flags & 2) > 0, (flags & 4) > 0
+        idx = torch.arange(flags.numel(), device=flags.device)
+        stay = idx[~pruned & ~split]
+        source = torch.cat([stay, idx[clone & ~pruned]] + [idx[split & ~pruned]] * N)
+        kept = torch.arange(source.numel(), device=flags.device) < stay.numel()
+        return source, kept
+
+    def prune_and_densify(self, min_opacity, max_grad, extent, do_prune=True, do_densify=True, generator=None, noise=None):
+        """``adaptive_prune`` + ``adaptive_densify`` (:1066-1111) in one plan.  Every per-row tensor follows the rows: the seven
+        tensors of ``densification_postfix`` (:942-981) through the densifier's kernels; their Adam moments (kept rows carried
+        over, new rows zero: ``cat_tensors_to_optimizer`` / ``_prune_optimizer``), ``_occ`` (a new row copies its source),
+        ``original_pos`` (a new row starts at its own position) and ``max_radii2D`` (new rows 0) by the same row map."""
+        d = self.densifier
+        if self.num_points == 0:
+            return dict(kept=0, cloned=0, split=0, pruned=0)
+        if d.spatial_order:
+            raise RuntimeError("prune_and_densify: the model's row map (_row_map) is the densifier's append order; spatial_order is not supported")
+        d.params = self._densifier_params()
+        S = self._scaling.shape[1]
+        source, kept = self._row_map(d.flags(do_prune, do_densify, min_opacity, extent, max_grad))
+        old = {name: getattr(self, a) for name, a in LEAVES}
+        moments = {name: self.optimizer.state.get(t) for name, t in old.items()} if self.optimizer is not None else {}
+        old_pos, old_r = self.original_pos, self.max_radii2D
+        result = d._run(do_prune, do_densify, min_opacity, extent, max_grad, generator, noise=noise)
+        if source.numel() != d.num_points:
+            raise RuntimeError(f"densification: {d.num_points} rows, {source.numel()} planned")
+
+        def carried(t):                                    # kept rows keep their value, new rows start at zero
+            rows = t[source]
+            return torch.where(kept.reshape((-1,) + (1,) * (rows.dim() - 1)), rows, torch.zeros_like(rows))
+        for name, _ in LEAVES:
+            if name == "occ":
+                new = old["occ"].detach()[source]
+            elif name == "scaling" and S != 3:
+                new = d.params["scaling"].detach()[:, :S]
+            elif name == "f_rest" and old["f_rest"].shape[1] == 0:
+                new = old["f_rest"].new_zeros((d.num_points, 0, 3))
+            else:
+                new = d.params[name]
+            st = moments.get(name)
+            new = self._replace_leaf(name, new, None if st is None else (carried(st["exp_avg"]), carried(st["exp_avg_sq"])))
+            if name in d.params and new.shape == d.params[name].shape:
+                d.params[name] = new
+        self.original_pos = torch.where(kept[:, None], old_pos[source], self._xyz.detach()).contiguous()
+        self.max_radii2D = carried(old_r).contiguous()
+        d.max_radii2D = self.max_radii2D
+        self.invalidate()
+        return result
+
+    def prune_points(self, mask: torch.Tensor) -> None:
+        """``prune_points`` (:884-903): remove the rows where ``mask`` is true from every per-row tensor and its Adam moments."""
+        keep = ~mask.to(self._xyz.device).bool()
+        for name, a in LEAVES:
+            old = getattr(self, a)
+            st = self.optimizer.state.get(old) if self.optimizer is not None else None
+            self._replace_leaf(name, old.detach()[keep], None if st is None else (st["exp_avg"][keep], st["exp_avg_sq"][keep]))
+        self.original_pos = self.original_pos[keep].contiguous()
+        self.max_radii2D = self.max_radii2D[keep].contiguous()
+        if self.densifier is not None:
+            acc = self.densifier.accum[:, keep].contiguous()
+            self._make_densifier()
+            self.densifier.accum = acc
+        self.invalidate()
+
+    def reset_opacity(self, ratio: float, iteration: int = 0) -> None:
+        """:754-764: opacity <- inverse_sigmoid(sigmoid(opacity) * ratio), its Adam moments zeroed."""
+        self._replace_leaf("opacity", inverse_sigmoid(torch.sigmoid(self._opacity.detach()) * ratio))
+        self.invalidate()
+
+    # ---- checkpoints -------------------------------------------------------------------------------------------------------------
+    def capture(self):
+        """:394-412, plus what this model owns beyond the reference's tuple (colours, occlusion, ``original_pos``, the field)."""
+        c = lambda t: t.detach().clone()
+        d = self.densifier
+        return (self.active_sh_degree, c(self._xyz), c(self._features_dc), c(self._features_rest), c(self._scaling), c(self._rotation),
+                c(self._opacity), c(self.max_radii2D), None if d is None else c(d.accum), self.optimizer.state_dict(), self.spatial_lr_scale,
+                c(self.config) if isinstance(self.config, torch.Tensor) else list(self.config),
+                {"colors": c(self._colors), "occ": c(self._occ), "original_pos": c(self.original_pos),
+                 "latent_pose": c(self.latent_pose) if hasattr(self, "latent_pose") else None, "aabb": c(self.aabb),
+                 "field": {k: c(v) for k, v in self.attribute_field.state_dict().items()}})
+
+    def restore(self, model_args, training_args=None) -> None:
+        """:414-440."""
+        (self.active_sh_degree, xyz, f_dc, f_rest, scaling, rotation, opacity, max_radii2D, accum, opt_dict, self.spatial_lr_scale,
+         config, extra) = model_args
+        par = lambda t: nn.Parameter(t.detach().clone().contiguous().requires_grad_(True))
+        self._xyz, self._features_dc, self._features_rest = par(xyz), par(f_dc), par(f_rest)
+        self._scaling, self._rotation, self._opacity = par(scaling), par(rotation), par(opacity)
+        self._colors, self._occ = par(extra["colors"]), par(extra["occ"])
+        self.original_pos = extra["original_pos"].detach().clone()
+        if extra["latent_pose"] is not None:
+            self.latent_pose = par(extra["latent_pose"])
+        self.max_radii2D = max_radii2D.detach().clone()
+        self.aabb = extra["aabb"].detach().clone()
+        self.attribute_field = HashMLPField(self.aabb.cpu()).to(self._xyz.device)
+        self.attribute_field.load_state_dict(extra["field"])
+        self.config = config.tolist() if isinstance(config, torch.Tensor) else list(config)
+        self.training_setup(training_args)
+        if accum is not None and self.densifier is not None:
+            self.densifier.accum = accum.detach().clone()
+        self.optimizer.load_state_dict(opt_dict)
+        self.invalidate()
+
+    def construct_list_of_attributes(self) -> List[str]:
+        return ply_property_names(self._features_dc.shape[1] * self._features_dc.shape[2],
+                                  self._features_rest.shape[1] * self._features_rest.shape[2], self._scaling.shape[1], self._rotation.shape[1])
+
+    def save_ply(self, path: str) -> None:
+        """:711-746: binary little-endian PLY, float properties in the order of ``construct_list_of_attributes``; normals zero."""
+        n = lambda t: t.detach().cpu().numpy()
+        xyz = n(self._xyz)
+        P = xyz.shape[0]
+        f_dc = n(self._features_dc.detach().transpose(1, 2).flatten(start_dim=1).contiguous())
+        f_rest = n(self._features_rest.detach().transpose(1, 2).flatten(start_dim=1).contiguous())
+        names = self.construct_list_of_attributes()
+        w = lambda t: t.shape[1] if t.dim() > 1 else 1
+        rows = np.concatenate((xyz.reshape(P, 3), np.zeros((P, 3), np.float32), f_dc.reshape(P, w(self._features_dc) * 3),
+                               f_rest.reshape(P, w(self._features_rest) * 3), n(self._opacity).reshape(P, 1),
+                               n(self._scaling).reshape(P, w(self._scaling)), n(self._rotation).reshape(P, 4)), axis=1)
+        write_ply(path, names, rows)
+
+    def load_ply(self, path: str, device=None) -> None:
+        """:766-846.  Sets the six leaves the file holds; ``_colors``, ``_occ``, ``original_pos`` and ``max_radii2D`` are kept when
+        they have the file's number of rows and start afresh otherwise (colours from the DC coefficients, occlusion 0.01, no
+        displacement).  A file that lacks a property is refused with the property named.  Call ``training_setup`` afterwards."""
+        props = read_ply(path)
+        n_rest = 3 * (self.max_sh_degree + 1) ** 2 - 3
+        need = ["x", "y", "z", "opacity", "f_dc_0", "f_dc_1", "f_dc_2"] + [f"f_rest_{i}" for i in range(n_rest)] + ["scale_0"] + \
+               [f"rot_{i}" for i in range(4)]
+        for name in need:
+            if name not in props:
+                raise ValueError(f"{path}: property '{name}' is missing")
+        scale_names = sorted((k for k in props if k.startswith("scale_")), key=lambda x: int(x.split("_")[-1]))
+        if not 1 <= len(scale_names) <= 3:
+            raise ValueError(f"{path}: {len(scale_names)} scale_ properties (1..3 supported)")
+        dev = torch.device(device) if device is not None else (self._xyz.device if self._xyz.numel() else torch.device("cuda" if torch.cuda.is_available() else "cpu"))
+        col = lambda names: torch.from_numpy(np.stack([props[k].astype(np.float32) for k in names], axis=1)) if names else None
+        P = props["x"].shape[0]
+        par = lambda t: nn.Parameter(t.to(dev).contiguous().requires_grad_(True))
+        self._xyz = par(col(["x", "y", "z"]))
+        self._features_dc = par(col(["f_dc_0", "f_dc_1", "f_dc_2"]).reshape(P, 3, 1).transpose(1, 2))
+        rest = col([f"f_rest_{i}" for i in range(n_rest)])
+        rest = torch.zeros(P, 3, 0) if rest is None else rest.reshape(P, 3, (self.max_sh_degree + 1) ** 2 - 1)
+        self._features_rest = par(rest.transpose(1, 2))
+        self._opacity = par(col(["opacity"]))
+        self._scaling = par(col(scale_names))
+        self._rotation = par(col([f"rot_{i}" for i in range(4)]))
+        if tuple(self._colors.shape) != (P, 3) or self._colors.device != dev:
+            rgb = SH2RGB(self._features_dc.detach()[:, 0, :]).clamp(1e-4, 1 - 1e-4)
+            self._colors = par(torch.logit(rgb))
+        if tuple(self._occ.shape) != (P, 1) or self._occ.device != dev:
+            self._occ = par(torch.logit(torch.full((P, 1), 1e-2)))
+        if tuple(self.original_pos.shape) != (P, 3) or self.original_pos.device != dev:
+            self.original_pos = self._xyz.detach().clone()
+        if tuple(self.max_radii2D.shape) != (P,) or self.max_radii2D.device != dev:
+            self.max_radii2D = torch.zeros(P, device=dev)
+        self.active_sh_degree = self.max_sh_degree
+        self.optimizer, self.densifier = None, None
+        self.invalidate()

@@ -247,6 +247,7 @@ SIGNATURES = {
     "soar_adam_step": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "soar_adam_step_at": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
     "soar_adam_step_rows": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, C.c_int32, _vp]),
+    "soar_adam_step_rows_wide": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, C.c_int32, _vp]),
     "soar_tsdf_integrate": (C.c_int, [C.c_int32] * 3 + [_vp] * 5 + [C.c_float] * 4 + [C.c_int32] * 3 + [C.c_float] * 3 + [_vp] * 3),
     "soar_mc_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
     "soar_mc_count": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
@@ -273,6 +274,10 @@ SIGNATURES = {
     "soar_vae_backward": (C.c_int, [C.POINTER(SoarVaeArgs), _vp, C.c_size_t, _vp]),
     "soar_sds_q_sample": (C.c_int, [C.POINTER(SoarSdsArgs), _vp]),
     "soar_sds_loss": (C.c_int, [C.POINTER(SoarSdsArgs), _vp]),
+    "soar_surfel_activations_forward": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 10 + [_vp]),
+    "soar_surfel_activations_backward": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 16 + [_vp]),
+    "soar_surfel_regularizers_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_surfel_regularizers": (C.c_int, [C.c_int32] * 3 + [_vp] * 11 + [_vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
