@@ -1006,6 +1006,41 @@ int soar_surfel_regularizers(int32_t P, int32_t S, int32_t K, const float *xyz, 
                              float *terms_dev, float *g_xyz, float *g_opacity, float *g_scales, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* ---- avatar initialisation (soar_amd/body.py, csrc/body.hip): body-model vertices, subdivision, vertex normals, surfel frames.
+ * soar_smplx_vertices: lbs() of the SMPL-X body model plus transl for B frames in one launch,
+ *   v_shaped = v_template + shapedirs betas[b];  v_posed = v_shaped + (R[b, 1:] - I) posedirs;
+ *   out[b, v] = (sum_j lbs_weights[v, j] joint_mats[b, j]) [v_posed, 1] + transl[b].
+ * betas [betas_batch][NB] (betas_batch 1 or B), v_template [V][3], shapedirs [V][3][NB], posedirs [(J - 1) 9][V 3],
+ * lbs_weights [V][J], full_pose [B][J 3] axis-angle, joint_mats [B][J][4][4] = soar_smplx_joint_mats of the same betas and
+ * full_pose WITHOUT transl, transl [B][3] or NULL, out [B][V][3].  2 <= J <= 64.  Every sum has a fixed order that depends on
+ * neither B nor the frame's place in the batch.  B = 0 or V = 0 with valid pointers succeeds without a launch. */
+int soar_smplx_vertices(int32_t B, int32_t V, int32_t J, int32_t NB, const float *betas, int32_t betas_batch, const float *v_template,
+                        const float *shapedirs, const float *posedirs, const float *lbs_weights, const float *full_pose,
+                        const float *joint_mats, const float *transl, float *out, void *stream);
+/* Midpoint subdivision of an index triangle mesh (open, non-manifold, unused vertices: all fine), one level per call pair.
+ * soar_mesh_workspace_bytes: the workspace of a mesh of F faces (256-byte aligned), for the three mesh entry points below.
+ * soar_mesh_subdivide_edges: sorts the 3 F edge keys (min << 32) | max, leaves the unique ones in the workspace and returns their
+ *   number E (synchronises the stream).  A face naming a vertex outside [0, V) is refused.
+ * soar_mesh_subdivide: with the workspace soar_mesh_subdivide_edges filled for the same faces, writes verts_out [V + E][3] (the
+ *   old vertices, then one midpoint (a + b) * 0.5f per unique edge IN ASCENDING KEY ORDER) and faces_out [4 F][3]: the children of
+ *   face f = (a, b, c) at rows 4 f .. 4 f + 3 are (a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca). */
+int soar_mesh_workspace_bytes(int32_t F, size_t *bytes);
+int soar_mesh_subdivide_edges(int32_t V, int32_t F, const int32_t *faces, void *workspace, size_t workspace_bytes, int64_t *edges_host,
+                              void *stream);
+int soar_mesh_subdivide(int32_t V, int32_t F, int64_t E, const float *verts, const int32_t *faces, const void *workspace,
+                        size_t workspace_bytes, float *verts_out, int32_t *faces_out, void *stream);
+/* Vertex normals [V][3]: normalize(sum over the vertex's face corners, in ascending (face, corner) order, of weight * unit face
+ * normal), weight = the corner's interior angle, the face's area, or 1; normalize is x / max(|x|, 1e-12), so a vertex no face
+ * uses gets (0, 0, 0).  No atomics: bit-reproducible.  Synchronises the stream once (the face indices are checked first). */
+#define SOAR_NORMALS_ANGLE 0
+#define SOAR_NORMALS_AREA 1
+#define SOAR_NORMALS_UNIFORM 2
+int soar_mesh_vertex_normals(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t weighting, void *workspace,
+                             size_t workspace_bytes, float *normals, void *stream);
+/* Surfel frames: uz = normals[p], ux = normalize(uz x rand_dir[p]), uy = normalize(uz x ux), quats[p] = the quaternion (real part
+ * first, non-negative, unit length) of the matrix with columns (ux, uy, uz)  (TS/utils/smpl.py:115-120). */
+int soar_mesh_vertex_frames(int32_t P, const float *normals, const float *rand_dir, float *quats, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

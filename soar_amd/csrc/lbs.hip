@@ -10,6 +10,7 @@
 #include "soar_common.h"
 #include "geom_bwd_point.h"
 #include "preprocess_point.h"
+#include "soar_quat.h"
 
 // Products and sums contract to FMAs within one expression only, as written: the same point has to come out bit-identical
 // from the single-frame kernels and from the all-frames ones, whatever each kernel's surroundings let the backend fuse.
@@ -35,28 +36,6 @@ __device__ __forceinline__ void quat_to_mat(const float q[4], float m[9])
     m[0] = 1 - two_s * (j * j + k * k); m[1] = two_s * (i * j - k * r); m[2] = two_s * (i * k + j * r);
     m[3] = two_s * (i * j + k * r); m[4] = 1 - two_s * (i * i + k * k); m[5] = two_s * (j * k - i * r);
     m[6] = two_s * (i * k - j * r); m[7] = two_s * (j * k + i * r); m[8] = 1 - two_s * (i * i + j * j);
-}
-
-// candidate table of matrix_to_quaternion: returns best index, fills cand[4] and a = q_abs[best]
-__device__ __forceinline__ int mat_to_quat_candidates(const float m[9], float cand[4], float &a_best, float &x_best)
-{
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    const float xs[4] = {1.0f + m00 + m11 + m22, 1.0f + m00 - m11 - m22, 1.0f - m00 + m11 - m22, 1.0f - m00 - m11 + m22};
-    float qa[4];
-    int best = 0;
-#pragma unroll
-    for (int t = 0; t < 4; t++) qa[t] = xs[t] > 0.f ? sqrtf(xs[t]) : 0.f;
-#pragma unroll
-    for (int t = 1; t < 4; t++)
-        if (qa[t] > qa[best]) best = t;
-    a_best = qa[best];
-    x_best = xs[best];
-    const float sq = a_best * a_best;
-    if (best == 0) { cand[0] = sq; cand[1] = m21 - m12; cand[2] = m02 - m20; cand[3] = m10 - m01; }
-    else if (best == 1) { cand[0] = m21 - m12; cand[1] = sq; cand[2] = m10 + m01; cand[3] = m02 + m20; }
-    else if (best == 2) { cand[0] = m02 - m20; cand[1] = m10 + m01; cand[2] = sq; cand[3] = m12 + m21; }
-    else { cand[0] = m10 - m01; cand[1] = m20 + m02; cand[2] = m21 + m12; cand[3] = sq; }
-    return best;
 }
 
 struct WarpArgs {

@@ -12,6 +12,7 @@
 // The chain product is associated exactly like the reference's loop, ((L_root L_a) L_b) ... L_j: every lane multiplies down
 // its own root path from the locals in LDS, so no level-by-level barriers are needed.
 #include "soar_common.h"
+#include "soar_rodrigues.h"
 
 namespace soar {
 
@@ -52,20 +53,7 @@ __global__ void __launch_bounds__(64) smplx_joint_mats_kernel(JointArgs a)
     }
     __syncthreads();
     if (live) {
-        // batch_rodrigues: angle = |v + 1e-8|, K = skew(v / angle), R = I + sin K + (1 - cos) K K
-        const float *v = a.full_pose + ((size_t)b * a.J + j) * 3;
-        const float vx = v[0], vy = v[1], vz = v[2];
-        const float ex = vx + 1e-8f, ey = vy + 1e-8f, ez = vz + 1e-8f;
-        const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-        const float rx = vx / angle, ry = vy / angle, rz = vz / angle;
-        const float sn = sinf(angle), cs = 1.f - cosf(angle);
-        const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) {
-                float kk = 0.f;
-                for (int m = 0; m < 3; m++) kk += K[r * 3 + m] * K[m * 3 + c];
-                loc[j][r * 4 + c] = (r == c ? 1.f : 0.f) + sn * K[r * 3 + c] + cs * kk;
-            }
+        rodrigues<4>(a.full_pose + ((size_t)b * a.J + j) * 3, loc[j]);
         for (int k = 0; k < 3; k++) loc[j][k * 4 + 3] = par >= 0 ? Jr[k] - jrest[par][k] : Jr[k];
     }
     __syncthreads();

@@ -278,6 +278,12 @@ SIGNATURES = {
     "soar_surfel_activations_backward": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 16 + [_vp]),
     "soar_surfel_regularizers_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_surfel_regularizers": (C.c_int, [C.c_int32] * 3 + [_vp] * 11 + [_vp, C.c_size_t, _vp]),
+    "soar_smplx_vertices": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32] + [_vp] * 8 + [_vp]),
+    "soar_mesh_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_subdivide_edges": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_subdivide": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "soar_mesh_vertex_normals": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
+    "soar_mesh_vertex_frames": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

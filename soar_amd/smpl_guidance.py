@@ -26,9 +26,22 @@ _POSE_KEYS = ("global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose"
 
 
 class SMPLGuidance:
-    def __init__(self, body, smpl_parms: Dict[str, torch.Tensor], device="cuda", leg_angle: float = 30.0):
+    def __init__(self, body, smpl_parms: Dict[str, torch.Tensor], device="cuda", leg_angle: float = 30.0, faces=None,
+                 num_subdiv: int = 2, pose_correctives: bool = False, generator: Optional[torch.Generator] = None):
         """smpl_parms: betas [1,10], expression [F,10], global_orient [F,3], body_pose [F,63], jaw/leye/reye_pose [F,3],
-        left/right_hand_pose [F,45], transl [F,3]  (the keys TS/utils/smpl.py:571-587 reads)."""
+        left/right_hand_pose [F,45], transl [F,3]  (the keys TS/utils/smpl.py:571-587 reads).
+
+        ``faces`` [F,3] (the body model's triangles): the object also initialises an avatar the way the reference's ``configure``
+        does (:407-424) -- ``cano_mesh`` (the canonical vertices with ``faces``, subdivided ``num_subdiv`` times),
+        ``query_points [1,P,3]`` (its vertices) and ``init_q [P,4]`` (surfel frames from its vertex normals and random in-plane
+        directions drawn from ``generator``), all built on the device by ``soar_amd.body``.  Without ``faces`` none of the
+        three attributes exists.
+
+        ``pose_correctives=True`` (needs ``body.posedirs``): ``cano_vertices`` are the body model's full vertex forward
+        (``body.smplx_vertices``: shape blend, pose-corrective blend shapes, skinning, ``transl``), which is what the reference's
+        ``cano_smpl.vertices`` are (:510).  The default stays False because ``cano_vertices`` without the correctives are what
+        this class has always computed and what its blend weights, tests and recorded results were made with; the two differ
+        by about 1e-3 on the synthetic body."""
         self.device = torch.device(device)
         self.smpl_parms = {k: v.to(self.device) for k, v in smpl_parms.items()}
         self._jt = JointTransformer(body.v_template, body.shapedirs, body.J_regressor, body.parents).to(self.device)
@@ -45,6 +58,16 @@ class SMPLGuidance:
         v_shaped = body.v_template.to(self.device) + torch.einsum("bl,mkl->bmk", betas0, body.shapedirs.to(self.device))[0]
         Tm = torch.einsum("vj,jxy->vxy", self.ori_lbs[0], A_cano[0])
         self.cano_vertices = (torch.einsum("vxy,vy->vx", Tm[:, :3, :3], v_shaped) + Tm[:, :3, 3]).contiguous()
+        self._body = body
+        if pose_correctives:
+            from . import body as body_ops
+            self.cano_vertices = body_ops.smplx_vertices(body, betas0, cpose, self.cano_transl, joint_transformer=self._jt)[0].contiguous()
+        if faces is not None:
+            from . import body as body_ops
+            v, f = body_ops.subdivide(self.cano_vertices, torch.as_tensor(faces).to(self.device), levels=num_subdiv)
+            self.cano_mesh = body_ops.Mesh(v, f)
+            self.query_points = v[None]
+            self.init_q = body_ops.surfel_frames(body_ops.vertex_normals(v, f), generator=generator)
         self._w_cache = None
         self._follower = None
         self._mats_cache, self._mats_cache_src = {}, None
@@ -83,6 +106,15 @@ class SMPLGuidance:
         betas = torch.cat([parms["betas"][:1], self._betas(self.smpl_parms, k)[:, 10:] if "expression" not in parms
                            else parms["expression"].reshape(1, -1)], dim=1)
         return betas, self._full_pose(parms), parms["transl"].reshape(1, 3)
+
+    def vertices(self, idx) -> torch.Tensor:
+        """Live vertices [n,V,3] of the stored frames ``idx`` (an int or a sequence of ints, taken modulo the number of frames):
+        the body model's vertex forward with the pose correctives (``soar_amd.body.smplx_vertices``; needs ``body.posedirs``)."""
+        from . import body as body_ops
+        ids = [int(idx)] if isinstance(idx, int) else [int(i) for i in idx]
+        sel = [self._select(None, i, False) for i in ids]
+        betas, pose, transl = (torch.cat([s[k] for s in sel], dim=0) for k in range(3))
+        return body_ops.smplx_vertices(self._body, betas, pose, transl, joint_transformer=self._jt)
 
     # ---- fast path ------------------------------------------------------------------------------------------------
     def joint_mats(self, smpl_parms_in=None, idx=None, zero_out=False) -> torch.Tensor:
