@@ -21,6 +21,25 @@ def test_restatement_gradient_passes_gradcheck():
     assert torch.autograd.gradcheck(lambda v: R.latents(v, w, 16, eps), (x2,), fast_mode=True)
 
 
+def test_restatement_gradient_passes_gradcheck_off_grid_with_a_peaked_attention():
+    """the oracle of the GPU suite's off-grid cases at T = 9 (11 x 9 -> 24: upsampling both ways), with the attention gain that suite
+    uses at this size; the softmax it exposes is the one the network applies"""
+    w = R.cast(R.random_weights(0, ch=32, attn_gain=1.5), torch.float64)
+    plain = R.random_weights(0, ch=32)
+    for k, v in R.random_weights(0, ch=32, attn_gain=1.5).items():
+        gain = 1.5 if k in ("encoder.mid.attn_1.q.weight", "encoder.mid.attn_1.k.weight") else 1.0
+        assert torch.equal(v, plain[k] * gain), k
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand(2, 3, 11, 9, generator=g, dtype=torch.float64, requires_grad=True)
+    eps = torch.randn(2, 4, 3, 3, generator=g, dtype=torch.float64)
+    assert torch.autograd.gradcheck(lambda v: R.latents(v, w, 24, eps), (x,), fast_mode=True)
+    with torch.no_grad():
+        P = R.attention_probs(x, w, 24)
+        Pp = R.attention_probs(x, R.cast(plain, torch.float64), 24)
+    assert P.shape == (2, 9, 9) and torch.allclose(P.sum(2), torch.ones(2, 9, dtype=torch.float64), atol=1e-12)
+    assert float(P.max(2).values.mean()) > float(Pp.max(2).values.mean())
+
+
 def test_restatement_activations_stay_order_one():
     w = R.cast(R.random_weights(0), torch.float64)
     x = R.images(1, 64, 64, 3).double()
@@ -119,6 +138,19 @@ def test_workspace_sizing_refuses_bad_sizes_and_grows(lib):
     # the forward keeps every activation of level 0 (5 x 128 channels) plus three gradient buffers
     assert sizes[1, 256] > 4 * 8 * 128 * 256 * 256
     assert lib.soar_vae_workspace_bytes(0, 64, 64, 64, C.byref(n)) == 0 and n.value >= 256
+    # image_size 72 has 81 attention tokens, padded to 128: its size lies strictly between those of 64 and 80 ...
+    by_size = {}
+    for S in (64, 72, 80, 88):
+        assert lib.soar_vae_workspace_bytes(2, 50, 90, S, C.byref(n)) == 0
+        by_size[S] = n.value
+    assert by_size[64] < by_size[72] < by_size[80] < by_size[88]
+    # ... and the padded attention buffers are counted with T_pad, not T.  Everything else grows linearly with the pixel count (72
+    # and 88 share T_pad = 128 and give the slope); what is left of 72 over 64 is the step of ten [T_pad][512] and three
+    # [T_pad][T_pad] buffers from T_pad = 64 to 128 (2.9 MB at N = 2; 0.8 MB if T were counted), up to the 256-byte roundings
+    slope = (by_size[88] - by_size[72]) / (88 ** 2 - 72 ** 2)
+    step = (by_size[72] - slope * 72 ** 2) - (by_size[64] - slope * 64 ** 2)
+    attn_bytes = lambda tp: 2 * 4 * (10 * tp * 512 + 3 * tp * tp)
+    assert abs(step - (attn_bytes(128) - attn_bytes(64))) < 64 * 1024, step
     assert lib.soar_vae_weights_floats(C.byref(n)) == 0
     assert n.value == sum(int(torch.tensor(s).prod()) for _, s in R.keys(128)) == 34163664
     assert lib.soar_vae_weights_bytes(C.byref(n)) == 0 and n.value > 4 * 34163664 and n.value % 256 == 0
@@ -133,6 +165,15 @@ def test_entries_refuse_bad_arguments_without_touching_the_gpu(lib):
     a.weights = 0x100000
     assert lib.soar_vae_forward(C.byref(a), None, 0, None) != 0 and "workspace" in hip_lib.last_error()
     assert lib.soar_vae_backward(C.byref(a), 0x100000, 8, None) != 0 and "workspace" in hip_lib.last_error()
+    # one byte short at a size with a padded attention: refused by both entries, by size, before any device call
+    n = C.c_size_t(0)
+    a.N, a.H, a.W, a.image_size = 2, 50, 90, 72
+    assert lib.soar_vae_workspace_bytes(2, 50, 90, 72, C.byref(n)) == 0
+    for entry in (lib.soar_vae_forward, lib.soar_vae_backward):
+        assert entry(C.byref(a), 0x100000, n.value - 1, None) != 0
+        assert "workspace" in hip_lib.last_error() and f"must be {n.value} bytes" in hip_lib.last_error() and f"got {n.value - 1}" in hip_lib.last_error()
+    assert lib.soar_vae_forward(C.byref(a), 0x100000, n.value, None) != 0 and "NULL x" in hip_lib.last_error()
+    a.N, a.H, a.W, a.image_size = 1, 64, 64, 64
     a.image_size = 36
     assert lib.soar_vae_forward(C.byref(a), None, 0, None) != 0 and "multiple of 8" in hip_lib.last_error()
     a.image_size, a.N = 64, -2

@@ -38,10 +38,12 @@ def keys(ch=128):
     return out
 
 
-def random_weights(seed=0, ch=128):
+def random_weights(seed=0, ch=128, attn_gain=1.0):
     """Seeded ldm-layout weights (float32, CPU), scaled so that activations stay O(1) through all 32 convolutions: fan-in scaled
     convolutions (the second of a block and proj_out at half that, so the residual stream grows slowly), GroupNorm affines near
-    (1, 0), attention scores O(1)."""
+    (1, 0), attention scores O(1).  attn_gain multiplies the attention's q and k weights (the scores by its square): at 1 the
+    softmax is close to uniform, at 2 - 3 a row has a dominant key (``attention_probs`` measures it); the other tensors do not
+    depend on it."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for k, shape in keys(ch):
@@ -53,6 +55,9 @@ def random_weights(seed=0, ch=128):
             fan_in = shape[1] * shape[2] * shape[3]
             scale = 0.5 if (".conv2." in k or "proj_out" in k) else 1.0
             sd[k] = torch.randn(shape, generator=g) * (scale / fan_in ** 0.5)
+    if attn_gain != 1.0:
+        for n in ("q", "k"):
+            sd[f"encoder.mid.attn_1.{n}.weight"] = sd[f"encoder.mid.attn_1.{n}.weight"] * attn_gain
     return sd
 
 
@@ -77,21 +82,27 @@ def _resblock(x, w, p):
     return x + h
 
 
-def _attn(x, w, p):
-    h = _gn(x, w, p + ".norm", silu=False)
+def _attn_probs(h, w, p):
+    """the normed input [B, C, H, W] -> softmax(q^T k / sqrt(C)) [B, T, T] (rows: queries) and v"""
     q, k, v = (_conv(h, w, f"{p}.{n}") for n in ("q", "k", "v"))
     B, C, H, W = q.shape
     q = q.reshape(B, C, H * W).permute(0, 2, 1)
     k = k.reshape(B, C, H * W)
     s = torch.bmm(q, k) * (int(C) ** (-0.5))
-    s = torch.softmax(s, dim=2)
+    return torch.softmax(s, dim=2), v
+
+
+def _attn(x, w, p):
+    h = _gn(x, w, p + ".norm", silu=False)
+    s, v = _attn_probs(h, w, p)
+    B, C, H, W = v.shape
     v = v.reshape(B, C, H * W)
     o = torch.bmm(v, s.permute(0, 2, 1)).reshape(B, C, H, W)
     return x + _conv(o, w, p + ".proj_out")
 
 
-def moments(x, w, image_size):
-    """x [N, 3, H, W] in [0, 1] -> (mean, logvar) [N, 4, s/8, s/8], logvar clamped"""
+def _to_mid(x, w, image_size):
+    """the resize, conv_in, the four levels and mid.block_1: the attention block's input"""
     x = F.interpolate(x, (image_size, image_size), mode="bilinear", align_corners=False) * 2 - 1
     h = _conv(x, w, "encoder.conv_in", padding=1)
     for i in range(4):
@@ -99,7 +110,18 @@ def moments(x, w, image_size):
             h = _resblock(h, w, f"encoder.down.{i}.block.{j}")
         if i < 3:
             h = _conv(F.pad(h, (0, 1, 0, 1)), w, f"encoder.down.{i}.downsample.conv", stride=2)
-    h = _resblock(h, w, "encoder.mid.block_1")
+    return _resblock(h, w, "encoder.mid.block_1")
+
+
+def attention_probs(x, w, image_size):
+    """x [N, 3, H, W] -> the attention's softmax matrix [N, T, T], T = (image_size / 8)^2, row = query"""
+    h = _gn(_to_mid(x, w, image_size), w, "encoder.mid.attn_1.norm", silu=False)
+    return _attn_probs(h, w, "encoder.mid.attn_1")[0]
+
+
+def moments(x, w, image_size):
+    """x [N, 3, H, W] in [0, 1] -> (mean, logvar) [N, 4, s/8, s/8], logvar clamped"""
+    h = _to_mid(x, w, image_size)
     h = _attn(h, w, "encoder.mid.attn_1")
     h = _resblock(h, w, "encoder.mid.block_2")
     h = _conv(_gn(h, w, "encoder.norm_out"), w, "encoder.conv_out", padding=1)
