@@ -49,7 +49,8 @@ extern "C" {
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
- * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail). */
+ * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail).  soar_data_mask_bbox / _crops /
+ * _step_batch (+ SoarDataStepArgs: the training data module). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1040,6 +1041,57 @@ int soar_mesh_vertex_normals(int32_t V, int32_t F, const float *verts, const int
 /* Surfel frames: uz = normals[p], ux = normalize(uz x rand_dir[p]), uy = normalize(uz x ux), quats[p] = the quaternion (real part
  * first, non-negative, unit length) of the matrix with columns (ux, uy, uz)  (TS/utils/smpl.py:115-120). */
 int soar_mesh_vertex_frames(int32_t P, const float *normals, const float *rand_dir, float *quats, void *stream);
+
+/* ---- the training data module (soar_amd/data.py, csrc/data.hip): the video stays on the device as bytes; boxes and crops once,
+ * a step's whole batch in one launch.  Restates TS/data/uncond_multiview.py:246-313 and :340-681 and threestudio's get_ray_directions,
+ * get_rays, get_projection_matrix and get_mvp_matrix.  Every call checks its arguments before any launch.
+ * soar_data_mask_bbox: boxes [N][4] = the inclusive (xmin, ymin, xmax, ymax) of the non-zero bytes of masks [N][H][W]; a frame without
+ *   one gets (W, H, -1, -1).  One workgroup per frame, integer min / max only: deterministic.  N = 0 succeeds without a launch.
+ * soar_data_crops: the 512 x 512 ImageDream crops of N frames from images [N][H][W][3], masks [N][H][W] (0 / 1) and the boxes ON THE
+ *   DEVICE.  c = min + (max - min) / 2 in float32; s = max(xmax - xmin, ymax - ymin) * 1.1 in double, as the reference's Python
+ *   number; box = c -+ (float)(s / 2).  Crop pixel (u, v) samples x = ((lin[u] / W * 2 - 1) + 1) * (W / 2) - 0.5 (the last
+ *   multiply-subtract fused), y likewise, lin = torch.linspace(box.x0, box.x1, 512) in torch's own arithmetic (a fused start + step i
+ *   below the middle, end - step (511 - i) from it on): the positions of F.grid_sample(align_corners=False) bit for bit.  Bilinear,
+ *   zero padding; the RGB taps are byte / 255 * mask, the mask taps the mask.  rgb_crop [N][512][512][3], mask_crop [N][512][512].
+ *   The sources are read as bytes: no scratch, whatever N.  A sentinel box gives a crop of zeros. */
+#define SOAR_DATA_CROP 512
+#define SOAR_DATA_MAX_VIEWS 8
+#define SOAR_DATA_SMALL_FLOATS 256
+int soar_data_mask_bbox(int32_t N, int32_t H, int32_t W, const uint8_t *masks, int32_t *boxes, void *stream);
+int soar_data_crops(int32_t N, int32_t H, int32_t W, const uint8_t *images, const uint8_t *masks, const int32_t *boxes, float *rgb_crop,
+                    float *mask_crop, void *stream);
+/* soar_data_step_batch: ONE launch per training step.  The small inputs travel in the struct, by value, as soar_cameras_from_c2w takes
+ * its host matrices: no copy, no synchronisation.  An output that is NULL is not written (and its inputs not read).
+ *   random views (B <= 8, H x W):  cam_d [B][H][W][3] = ((i + .5 - W / 2) / focal[b], -(j + .5 - H / 2) / focal[b], -1);
+ *     rays_d[r] = sum_k cam_d[k] c2w[b][r][k] in the order k = 0, 1, 2, then x / max(|x|, 1e-12) when rays_d_normalize.
+ *     (rays_o is the translation column: the caller expands it from `small`.)
+ *     proj [B][4][4]: [0][0] = 1 / (tan_half[b] aspect), [1][1] = -1 / tan_half[b], [2][2] = -(far + near) / (far - near),
+ *     [2][3] = -2 far near / (far - near), [3][2] = -1;  mvp_mtx [B][4][4] = proj [R^T | -R^T t].
+ *   the frame's own camera:  gt_cam_d [512][512][3] = ((i + .5 - cx) / fx, -(j + .5 - cy) / fy, -1) with fx, fy, cx, cy from
+ *     normal_Ks [n_frames][3][3] on the device at row `frame`, gt_rays_d = the rotation by gt_c2w, always normalised;
+ *     gt_mvp_mtx [4][4] with gt_near and, when gt_has_cxcy, [0][2] = -(2 cx - W) / W and [1][2] = -(2 cy - H) / H of the video image.
+ *   the frame, gathered and converted:  gt_rgb [Hv][Wv][3] = byte / 255 * mask, gt_mask [Hv][Wv] = mask,
+ *     gt_normal_F / _B [512][512][3] = byte / 255, gt_normal_mask [512][512] = byte / 255, gt_rgb_crop / gt_mask_crop = the rows of
+ *     rgb_crop / mask_crop.  Streaming: 16-byte loads and stores (through LDS, so that neighbouring lanes store neighbouring 16 bytes)
+ *     when Hv Wv is a multiple of 16, byte loads otherwise; the float outputs must be 16-byte aligned.
+ *   small_out [n_small] = small[0 .. n_small): the step's per-camera vectors, as they are, for the caller to slice. */
+typedef struct SoarDataStepArgs {
+    int32_t B, H, W;               /* the random views */
+    int32_t n_frames, Hv, Wv;      /* the stored video */
+    int32_t frame;                 /* gt_index */
+    int32_t rays_d_normalize, gt_has_cxcy, n_small;
+    double near_plane, far_plane;  /* of the random views (0.1, 1000 in the reference: Python numbers, hence doubles) */
+    double gt_near;                /* the frame's own near plane; its far plane is 1000 */
+    float c2w[SOAR_DATA_MAX_VIEWS][16], focal[SOAR_DATA_MAX_VIEWS], tan_half[SOAR_DATA_MAX_VIEWS];
+    float gt_c2w[16], gt_tan_half, gt_cx, gt_cy;
+    float small[SOAR_DATA_SMALL_FLOATS];
+    const uint8_t *images, *masks, *normal_F, *normal_B, *normal_mask;
+    const float *rgb_crop, *mask_crop, *normal_Ks;
+    float *rays_d, *cam_d, *gt_rays_d, *gt_cam_d;
+    float *gt_rgb, *gt_mask, *gt_normal_F, *gt_normal_B, *gt_normal_mask, *gt_rgb_crop, *gt_mask_crop;
+    float *mvp_mtx, *proj, *gt_mvp_mtx, *small_out;
+} SoarDataStepArgs;
+int soar_data_step_batch(const SoarDataStepArgs *args, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

@@ -146,6 +146,25 @@ class SoarSdsArgs(C.Structure):
                 ("latents", _vp), ("noise", _vp), ("eps_pred", _vp), ("x_in", _vp), ("loss", _vp), ("grad_norm", _vp), ("g_lat", _vp)]
 
 
+DATA_CROP, DATA_MAX_VIEWS, DATA_SMALL_FLOATS = 512, 8, 256     # SOAR_DATA_CROP, SOAR_DATA_MAX_VIEWS, SOAR_DATA_SMALL_FLOATS
+
+
+class SoarDataStepArgs(C.Structure):
+    """Mirror of ``struct SoarDataStepArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_frames", C.c_int32), ("Hv", C.c_int32), ("Wv", C.c_int32),
+                ("frame", C.c_int32), ("rays_d_normalize", C.c_int32), ("gt_has_cxcy", C.c_int32), ("n_small", C.c_int32),
+                ("near_plane", C.c_double), ("far_plane", C.c_double), ("gt_near", C.c_double),
+                ("c2w", (C.c_float * 16) * DATA_MAX_VIEWS), ("focal", C.c_float * DATA_MAX_VIEWS), ("tan_half", C.c_float * DATA_MAX_VIEWS),
+                ("gt_c2w", C.c_float * 16), ("gt_tan_half", C.c_float), ("gt_cx", C.c_float), ("gt_cy", C.c_float),
+                ("small", C.c_float * DATA_SMALL_FLOATS),
+                ("images", _vp), ("masks", _vp), ("normal_F", _vp), ("normal_B", _vp), ("normal_mask", _vp),
+                ("rgb_crop", _vp), ("mask_crop", _vp), ("normal_Ks", _vp),
+                ("rays_d", _vp), ("cam_d", _vp), ("gt_rays_d", _vp), ("gt_cam_d", _vp),
+                ("gt_rgb", _vp), ("gt_mask", _vp), ("gt_normal_F", _vp), ("gt_normal_B", _vp), ("gt_normal_mask", _vp),
+                ("gt_rgb_crop", _vp), ("gt_mask_crop", _vp),
+                ("mvp_mtx", _vp), ("proj", _vp), ("gt_mvp_mtx", _vp), ("small_out", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -284,6 +303,9 @@ SIGNATURES = {
     "soar_mesh_subdivide": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp]),
     "soar_mesh_vertex_normals": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
     "soar_mesh_vertex_frames": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
+    "soar_data_mask_bbox": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "soar_data_crops": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "soar_data_step_batch": (C.c_int, [C.POINTER(SoarDataStepArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
