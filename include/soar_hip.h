@@ -252,6 +252,39 @@ int soar_rast_backward_scaled(const SoarRastParams *prm,
                               float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos,
                               void *workspace, size_t workspace_bytes,
                               void *stream);
+/* soar_rast_backward / soar_rast_backward_occ for the training step plan: the same calls with the form of the backward blend named by
+ * the caller.  region = 1: a wavefront per 4 x 4 pixel block -- exactly what the entries above launch; region = 2: a wavefront per
+ * pair of blocks side by side (40 % fewer accumulation rows; faster from about a megapixel up, slower on small images, and inside
+ * the strict gradient bar for loss-derived image gradients only: rast_render_bwd.hip). */
+int soar_rast_backward_plan(const SoarRastParams *prm, int32_t region,
+                            const float *means3D, const int32_t *radii, const float *shs,
+                            const float *colors_precomp, const float *scales, const float *rotations,
+                            const float *cov3D_precomp,
+                            const void *geom_buffer, const void *binning_buffer, const void *image_buffer,
+                            int64_t num_rendered,
+                            const float *dL_dout_color, const float *dL_dout_normal,
+                            const float *dL_dout_depth, const float *dL_dout_opac,
+                            float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity, float *dL_dmeans3D,
+                            float *dL_dcov3D, float *dL_dsh, float *dL_dscales, float *dL_drotations,
+                            float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos,
+                            void *workspace, size_t workspace_bytes,
+                            void *stream);
+int soar_rast_backward_occ_plan(const SoarRastParams *prm, int32_t region,
+                                const float *means3D, const int32_t *radii, const float *shs,
+                                const float *colors_precomp, const float *scales, const float *rotations,
+                                const float *cov3D_precomp,
+                                const void *geom_buffer, const void *binning_buffer, const void *image_buffer,
+                                int64_t num_rendered,
+                                const float *dL_dout_color, const float *dL_dout_normal,
+                                const float *dL_dout_depth, const float *dL_dout_opac, const float *dL_dout_occ,
+                                const float *normal_scale_dev, int32_t occ_planes,
+                                float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity, float *dL_dmeans3D,
+                                float *dL_dcov3D, float *dL_dsh, float *dL_dscales, float *dL_drotations,
+                                float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos, float *dL_docc,
+                                void *workspace, size_t workspace_bytes,
+                                void *stream);
+/* how many frames' backward blends this process has issued in each form since the library was loaded (host-side counters) */
+int soar_rast_backward_region_counts(int64_t *single_blocks, int64_t *pairs);
 /* bytes of `workspace` needed by soar_rast_backward (per-Gaussian accumulation rows) */
 int soar_rast_backward_workspace_bytes(int32_t P, size_t *bytes);
 

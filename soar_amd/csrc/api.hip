@@ -689,7 +689,7 @@ static int backward_impl(const SoarRastParams *prm, const float *means3D, const 
                               float *dL_dmeans3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscales, float *dL_drotations,
                               float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos, void *workspace,
                               size_t workspace_bytes, const float *dL_dout_occ, float *dL_docc, const float *normal_scale_dev, int occ_planes,
-                              void *stream_)
+                              int region, void *stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (check_params(prm)) return 1;
@@ -739,7 +739,7 @@ static int backward_impl(const SoarRastParams *prm, const float *means3D, const 
     }
     if (num_rendered > 0 || wide) {
         if (launch_render_backward(*prm, g, b, img, dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac, grad_scale_dev, acc,
-                                   acc64, num_rendered > 0, dL_dout_occ, dL_docc, normal_scale_dev, occ_planes, stream))
+                                   acc64, num_rendered > 0, dL_dout_occ, dL_docc, normal_scale_dev, occ_planes, region, stream))
             return 1;
     }
     // SoarRastParams.debug bit 3: the rows stay in the workspace for soar_frames_geometry_warp_backward (lbs.hip), which runs the
@@ -769,7 +769,7 @@ int soar_rast_backward_scaled(const SoarRastParams *prm, const float *means3D, c
     return backward_impl(prm, means3D, radii, shs, colors_precomp, scales, rotations, cov3D_precomp, geom_buffer, binning_buffer, image_buffer,
                          num_rendered, dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac, grad_scale_dev, dL_dmeans2D, dL_dcolors,
                          dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos, workspace,
-                         workspace_bytes, nullptr, nullptr, nullptr, 3, stream_);
+                         workspace_bytes, nullptr, nullptr, nullptr, 3, /*region=*/0, stream_);
 }
 
 int soar_rast_backward_occ(const SoarRastParams *prm, const float *means3D, const int32_t *radii, const float *shs,
@@ -788,7 +788,54 @@ int soar_rast_backward_occ(const SoarRastParams *prm, const float *means3D, cons
     return backward_impl(prm, means3D, radii, shs, colors_precomp, scales, rotations, cov3D_precomp, geom_buffer, binning_buffer, image_buffer,
                          num_rendered, dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac, nullptr, dL_dmeans2D, dL_dcolors,
                          dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos, workspace,
-                         workspace_bytes, dL_dout_occ, dL_docc, normal_scale_dev, occ_planes, stream_);
+                         workspace_bytes, dL_dout_occ, dL_docc, normal_scale_dev, occ_planes, /*region=*/0, stream_);
+}
+
+// The training step plan's forms of soar_rast_backward / soar_rast_backward_occ: the caller names the form of the backward blend,
+// region = 1 (a wavefront per 4 x 4 block: what the entries above launch) or 2 (a wavefront per pair of blocks; rast_render_bwd.hip
+// says who should ask for it).
+int soar_rast_backward_plan(const SoarRastParams *prm, int32_t region, const float *means3D, const int32_t *radii, const float *shs,
+                            const float *colors_precomp, const float *scales, const float *rotations,
+                            const float *cov3D_precomp, const void *geom_buffer, const void *binning_buffer,
+                            const void *image_buffer, int64_t num_rendered, const float *dL_dout_color,
+                            const float *dL_dout_normal, const float *dL_dout_depth, const float *dL_dout_opac,
+                            float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity, float *dL_dmeans3D, float *dL_dcov3D,
+                            float *dL_dsh, float *dL_dscales, float *dL_drotations, float *dL_dviewmat, float *dL_dprojmat,
+                            float *dL_dcampos, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (region != 1 && region != 2) { set_error("soar_rast_backward_plan: region is 1 or 2, got %d", region); return 1; }
+    return backward_impl(prm, means3D, radii, shs, colors_precomp, scales, rotations, cov3D_precomp, geom_buffer, binning_buffer, image_buffer,
+                         num_rendered, dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac, nullptr, dL_dmeans2D, dL_dcolors,
+                         dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos, workspace,
+                         workspace_bytes, nullptr, nullptr, nullptr, 3, region, stream_);
+}
+
+int soar_rast_backward_occ_plan(const SoarRastParams *prm, int32_t region, const float *means3D, const int32_t *radii, const float *shs,
+                                const float *colors_precomp, const float *scales, const float *rotations,
+                                const float *cov3D_precomp, const void *geom_buffer, const void *binning_buffer,
+                                const void *image_buffer, int64_t num_rendered, const float *dL_dout_color,
+                                const float *dL_dout_normal, const float *dL_dout_depth, const float *dL_dout_opac,
+                                const float *dL_dout_occ, const float *normal_scale_dev, int32_t occ_planes, float *dL_dmeans2D,
+                                float *dL_dcolors, float *dL_dopacity, float *dL_dmeans3D, float *dL_dcov3D, float *dL_dsh,
+                                float *dL_dscales, float *dL_drotations, float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos,
+                                float *dL_docc, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (region != 1 && region != 2) { set_error("soar_rast_backward_occ_plan: region is 1 or 2, got %d", region); return 1; }
+    if (!dL_dout_occ || !dL_docc) { set_error("soar_rast_backward_occ_plan: dL_dout_occ / dL_docc must not be NULL"); return 1; }
+    if (occ_planes != 1 && occ_planes != 3) { set_error("soar_rast_backward_occ_plan: occ_planes is 3 or 1, got %d", occ_planes); return 1; }
+    return backward_impl(prm, means3D, radii, shs, colors_precomp, scales, rotations, cov3D_precomp, geom_buffer, binning_buffer, image_buffer,
+                         num_rendered, dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac, nullptr, dL_dmeans2D, dL_dcolors,
+                         dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos, workspace,
+                         workspace_bytes, dL_dout_occ, dL_docc, normal_scale_dev, occ_planes, region, stream_);
+}
+
+int soar_rast_backward_region_counts(int64_t *single_blocks, int64_t *pairs)
+{
+    if (!single_blocks || !pairs) { set_error("soar_rast_backward_region_counts: NULL"); return 1; }
+    long long s = 0, p = 0;
+    render_backward_region_counts(&s, &p);
+    *single_blocks = (int64_t)s; *pairs = (int64_t)p;
+    return 0;
 }
 
 int soar_rast_mark_visible(int32_t P, const float *means3D, const float *viewmatrix, const float *projmatrix,

@@ -18,6 +18,7 @@
 // (352 us); this file holds the form that replaced them (298-306 us).
 #include "soar_common.h"
 
+#include <atomic>
 #include <type_traits>
 
 #include <cstdio>
@@ -151,12 +152,19 @@ __device__ __forceinline__ void load_pixel_at_once(const BwdArgs &a, int px, int
 // (the forward's T, n_contrib and final_T are not touched by any of this).
 constexpr int DPP_WAVE_SHR1 = 0x138;
 // REGION = the 4 x 4 blocks a wavefront takes: 1, 2 (side by side: 8 x 4 pixels) or the 4 of a quad.  A pair leaves 40 % fewer
-// accumulation rows and record gathers for 20 % more pixel steps: at C3 242 -> 219 us per 4-frame launch (a quad: 300; on small
-// images -- C2, 250 tiles with work per frame -- halving the number of wavefronts costs more than it saves: 82 -> 113 us).  NOT the
-// default: with pairs the worst element of dL_drotations of the C3-size surfel scene lands at 1.07e-4 / 1.16e-4 of the reference's
-// in six runs of eight (7.0e-5 in the others; single blocks: 4.9-6.6e-5 in sixteen) -- a pixel's entries are spread over 1.4 x as
-// many batches, and although every step of that is within an ulp the strict 1e-4 bar of tests/test_reference_build_gpu.py has no
-// room for it.  -DSOAR_BWD_REGION=2 builds it.
+// accumulation rows and record gathers for more pixel steps (+9.6 % vector instructions, profiles/r07_ab_backward_pairs_plan.txt): at C3 242 -> 219 us per 4-frame launch (a quad: 300; on small
+// images -- C2, 250 tiles with work per frame -- halving the number of wavefronts costs more than it saves: 82 -> 113 us).
+// Both forms (1 and 2) are compiled into the library and launch_render_backward takes the choice per launch:
+//   * the training step plan (soar_rast_backward_plan / soar_rast_backward_occ_plan, soar_amd/step_plan.py) asks for pairs when the
+//     frame has at least 2^20 pixels and for single blocks below (SOAR_PLAN_BWD_REGION=1|2 overrides the rule).  Its upstream
+//     gradients are loss-derived, and with those the pair form sits at 5.3e-5 of the reference's kernels in 8 runs of 8 at C3
+//     (profiles/r06_region2_c3_strict_8_runs.txt) and closer to the float64 evaluation than the reference's own kernels at C5
+//     (profiles/r06_c5_triangle.txt);
+//   * every caller that does not ask -- soar_rast_backward, _scaled, _occ: the synchronous and autograd entry points, the plugin
+//     path -- gets SOAR_BWD_REGION, whose default stays 1.  With WHITE-NOISE upstream gradients (the strict test of
+//     tests/test_reference_build_gpu.py at C3 size) the worst element of dL_drotations lands at 1.07e-4 / 1.16e-4 of the reference's
+//     in six runs of eight with pairs (7.0e-5 in the others; single blocks: 4.9-6.6e-5 in sixteen) -- a pixel's entries are spread
+//     over 1.4 x as many batches, and although every step of that is within an ulp the strict 1e-4 bar has no room for it.
 #ifndef SOAR_BWD_REGION
 #define SOAR_BWD_REGION 1
 #endif
@@ -167,6 +175,11 @@ static_assert(!(SOAR_BWD_PACKED && SOAR_BWD_DIV), "the packed pixel steps only c
 #ifndef SOAR_BWD_UNIT_GROUPS
 #define SOAR_BWD_UNIT_GROUPS 4     // (mask words compacted at a time: 1.3 KB of list; with the 32 pixels' rows 7.7 KB of LDS per wavefront: 21 per CU, the registers allow 20)
 #endif
+// Both forms in one build, by the compiler's resource report (gfx950, float32 and float64 rows alike; no scratch, no spills anywhere):
+//   single blocks  92 VGPRs, 6400 B of LDS, 5 waves per SIMD      with the occlusion chain  100 VGPRs, 6912 B, 4 waves
+//   pairs          94 VGPRs, 7680 B of LDS, 5 waves per SIMD      with the occlusion chain   95 VGPRs, 8192 B, 5 waves
+// -- the figures of the two single-form builds (-DSOAR_BWD_REGION=1 / 2): every instantiation has its own LDS arrays, sized by its
+// own NPIX, and at most 20 wavefronts per CU x 8 KB = 160 KB fit the CU's LDS in either form.
 constexpr int UNIT_GROUPS = SOAR_BWD_UNIT_GROUPS;    // mask words (64 list positions each) the block walk compacts at a time
 
 // v of the lane the DPP control names; `otherwise` where that lane does not exist or the row is masked out
@@ -916,11 +929,42 @@ __global__ void narrow_rows_kernel(Batch<NarrowArgs> batch)
 }
 }  // namespace
 
+namespace {
+std::atomic<long long> g_blend_frames[2];      // frames whose backward blend was issued with single blocks / with pairs (soar_rast_backward_region_counts)
+
+// the blend of one frame (of a batch) in the form REGION: one launch site per instantiation, so a batch's frames agree in their form
+template <int REGION>
+int launch_backward_blend(const BwdArgs &a, bool wide, bool blend, bool occ, hipStream_t stream)
+{
+    const int grid_ranks = blend_grid_ranks(a.ntiles);
+    const dim3 grid_blocks((16 / REGION) * min((a.ntiles + 7) / 8 * 8, grid_ranks));
+    if (wide) {
+        if (blend && occ) SOAR_LAUNCH_BATCHED((render_backward_blocks_occ_kernel<true, REGION>), grid_blocks, dim3(64), 0, stream, a);
+        else if (blend) SOAR_LAUNCH_BATCHED((render_backward_blocks_kernel<true, REGION>), grid_blocks, dim3(64), 0, stream, a);
+    } else {
+        if (occ) SOAR_LAUNCH_BATCHED((render_backward_blocks_occ_kernel<false, REGION>), grid_blocks, dim3(64), 0, stream, a);
+        else SOAR_LAUNCH_BATCHED((render_backward_blocks_kernel<false, REGION>), grid_blocks, dim3(64), 0, stream, a);
+    }
+    if (blend || !wide) g_blend_frames[REGION - 1].fetch_add(1, std::memory_order_relaxed);
+    return 0;
+}
+}  // namespace
+
+void render_backward_region_counts(long long *single_blocks, long long *pairs)
+{
+    *single_blocks = g_blend_frames[0].load(std::memory_order_relaxed);
+    *pairs = g_blend_frames[1].load(std::memory_order_relaxed);
+}
+
+// region: 1 = a wavefront per 4 x 4 block, 2 = per pair of blocks, 0 = the caller does not ask (SOAR_BWD_REGION)
 int launch_render_backward(const SoarRastParams &prm, const GeomBuf &g, const BinBuf &b, const ImageBuf &img,
                            const float *dL_dcolor, const float *dL_dnormal, const float *dL_ddepth, const float *dL_dopac,
                            const float *grad_scale, float *acc, double *acc64, bool blend, const float *dL_dout_occ, float *dL_docc,
-                           const float *normal_scale, int occ_planes, hipStream_t stream)
+                           const float *normal_scale, int occ_planes, int region, hipStream_t stream)
 {
+    static_assert(SOAR_BWD_REGION == 1 || SOAR_BWD_REGION == 2, "the compiled forms: single blocks and pairs");
+    if (region == 0) region = SOAR_BWD_REGION;
+    if (region != 1 && region != 2) { set_error("render_backward: region is 1 (single blocks) or 2 (pairs), got %d", region); return 1; }
     BwdArgs a;
     a.normal_scale = normal_scale;
     a.occ_planes = occ_planes;
@@ -936,21 +980,15 @@ int launch_render_backward(const SoarRastParams &prm, const GeomBuf &g, const Bi
     a.dL_dcolor = dL_dcolor; a.dL_dnormal = dL_dnormal; a.dL_ddepth = dL_ddepth; a.dL_dopac = dL_dopac;
     a.acc = acc; a.acc64 = acc64;
     StageTimer timer(ST_RENDER_BWD, stream);
-    const int grid_ranks = blend_grid_ranks(a.ntiles);
     a.masks = b.block_masks; a.mask_plane = b.mask_plane;
-    constexpr int region = SOAR_BWD_REGION;
-    const dim3 grid_blocks((16 / region) * min((a.ntiles + 7) / 8 * 8, grid_ranks));
+    if (region == 2 ? launch_backward_blend<2>(a, acc64 != nullptr, blend, occ, stream) : launch_backward_blend<1>(a, acc64 != nullptr, blend, occ, stream))
+        return 1;
     if (acc64) {
-        if (blend && occ) SOAR_LAUNCH_BATCHED((render_backward_blocks_occ_kernel<true, region>), grid_blocks, dim3(64), 0, stream, a);
-        else if (blend) SOAR_LAUNCH_BATCHED((render_backward_blocks_kernel<true, region>), grid_blocks, dim3(64), 0, stream, a);
         // in a batch this launches with the last frame like the blend in front of it (it used to launch per call, i.e. for
         // the frames 0 .. n-2 BEFORE their rows had been accumulated)
         NarrowArgs na;
         na.n = (size_t)prm.P * ACC_STRIDE; na.wide = acc64; na.narrow = acc;
         SOAR_LAUNCH_BATCHED(narrow_rows_kernel, dim3((unsigned)((na.n + 255) / 256)), dim3(256), 0, stream, na);
-    } else {
-        if (occ) SOAR_LAUNCH_BATCHED((render_backward_blocks_occ_kernel<false, region>), grid_blocks, dim3(64), 0, stream, a);
-        else SOAR_LAUNCH_BATCHED((render_backward_blocks_kernel<false, region>), grid_blocks, dim3(64), 0, stream, a);
     }
     SOAR_LAUNCH_OK("render_backward", stream, prm.debug & 1);
     return 0;

@@ -188,6 +188,11 @@ SIGNATURES = {
                                   + [_vp] * 11 + [_vp, C.c_size_t, _vp]),
     "soar_rast_backward_occ": (C.c_int, [C.POINTER(SoarRastParams)] + [_vp] * 7 + [_vp, _vp, _vp, C.c_int64] + [_vp] * 6 + [C.c_int32]
                                + [_vp] * 12 + [_vp, C.c_size_t, _vp]),
+    "soar_rast_backward_plan": (C.c_int, [C.POINTER(SoarRastParams), C.c_int32] + [_vp] * 7 + [_vp, _vp, _vp, C.c_int64] + [_vp] * 4
+                                + [_vp] * 11 + [_vp, C.c_size_t, _vp]),
+    "soar_rast_backward_occ_plan": (C.c_int, [C.POINTER(SoarRastParams), C.c_int32] + [_vp] * 7 + [_vp, _vp, _vp, C.c_int64] + [_vp] * 6
+                                    + [C.c_int32] + [_vp] * 12 + [_vp, C.c_size_t, _vp]),
+    "soar_rast_backward_region_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "soar_batch_begin": (C.c_int, [C.c_int32]),
     "soar_batch_frame": (C.c_int, [C.c_int32]),
     "soar_batch_end": (C.c_int, []),

@@ -128,6 +128,12 @@ class FrameStepPlan:
                 t.prm = C.addressof(self.ctx.params)
                 t.means3D, t.rotations, t.radii = v["xyz_p"].data_ptr(), v["rot_p"].data_ptr(), v["radii"].data_ptr()
                 t.geom_buffer, t.workspace, t.dL_dmeans2D = v["geom"].data_ptr(), v["work"].data_ptr(), v["g_means2D"].data_ptr()
+        # The backward blend's form (csrc/rast_render_bwd.hip): a wavefront per pair of 4 x 4 blocks from 2^20 pixels up -- 40 % fewer
+        # accumulation rows, which is what that launch waits for at 1080p and above --, a wavefront per block below, where halving
+        # the number of wavefronts costs more than the rows save.  The plan's upstream gradients are loss-derived, for which pairs
+        # hold the strict gradient bar; every other caller of the rasterizer keeps single blocks.  SOAR_PLAN_BWD_REGION=1 / 2 forces one.
+        env = os.environ.get("SOAR_PLAN_BWD_REGION")
+        self.bwd_region = int(env) if env in ("1", "2") else (2 if W * H >= (1 << 20) else 1)
         # ... and the head of the forward pass likewise (soar_frames_warp_preprocess; SOAR_PLAN_FUSED_HEAD=0: warp, then preprocess)
         self.fused_head = os.environ.get("SOAR_PLAN_FUSED_HEAD", "1") != "0" and self.n <= 8
         if self.fused_head:
@@ -402,20 +408,21 @@ class FrameStepPlan:
     def _f_backward(self, i: int, stream: int) -> None:
         def build():
             L, s, v = self.L, self.seq, self.views[i]
-            return (L.soar_rast_backward, (C.byref(self.ctx.params), ptr(v["xyz_p"]), ptr(v["radii"]), None, ptr(s.colors.detach()),
-                                           ptr(s.scales.detach()), ptr(v["rot_p"]), None, ptr(v["geom"]), ptr(v["binning"]), ptr(v["img"]),
-                                           self.capacity, ptr(v["gC"]), ptr(v["gN"]), ptr(v["gD"]), ptr(v["gO"]), ptr(v["g_means2D"]),
-                                           ptr(self.g_colors[i]), ptr(v["g_opacity"]), ptr(v["g_means3D"]), ptr(v["g_cov3D"]), None,
-                                           ptr(self.g_scales[i]), ptr(v["g_rot_p"]), ptr(v["g_view"]), ptr(v["g_proj"]), ptr(v["g_campos"]),
-                                           ptr(v["work"]), v["work"].numel(), stream), "backward")
+            return (L.soar_rast_backward_plan, (C.byref(self.ctx.params), self.bwd_region, ptr(v["xyz_p"]), ptr(v["radii"]), None,
+                                                ptr(s.colors.detach()), ptr(s.scales.detach()), ptr(v["rot_p"]), None, ptr(v["geom"]),
+                                                ptr(v["binning"]), ptr(v["img"]), self.capacity, ptr(v["gC"]), ptr(v["gN"]), ptr(v["gD"]),
+                                                ptr(v["gO"]), ptr(v["g_means2D"]), ptr(self.g_colors[i]), ptr(v["g_opacity"]),
+                                                ptr(v["g_means3D"]), ptr(v["g_cov3D"]), None, ptr(self.g_scales[i]), ptr(v["g_rot_p"]),
+                                                ptr(v["g_view"]), ptr(v["g_proj"]), ptr(v["g_campos"]), ptr(v["work"]), v["work"].numel(),
+                                                stream), "backward")
         self._call(("backward", i, stream), build)
 
     def _f_backward_occ(self, i: int, stream: int) -> None:
-        """the rasterizer backward with the fused occlusion chain taken along (soar_rast_backward_occ): dL/docc of the frame without a
+        """the rasterizer backward with the fused occlusion chain taken along (soar_rast_backward_occ_plan): dL/docc of the frame without a
         walk of its own"""
         def build():
             L, s, v = self.L, self.seq, self.views[i]
-            return (L.soar_rast_backward_occ, (C.byref(self.ctx.params), ptr(v["xyz_p"]), ptr(v["radii"]), None, ptr(s.colors.detach()),
+            return (L.soar_rast_backward_occ_plan, (C.byref(self.ctx.params), self.bwd_region, ptr(v["xyz_p"]), ptr(v["radii"]), None, ptr(s.colors.detach()),
                                                ptr(s.scales.detach()), ptr(v["rot_p"]), None, ptr(v["geom"]), ptr(v["binning"]), ptr(v["img"]),
                                                self.capacity, ptr(v["gC"]), ptr(v["gN"]), ptr(v["gD"]), ptr(v["gO"]), ptr(v["g_occ_img"]),
                                                self.av_cos_scale_all.data_ptr() + 4 * i, 1, ptr(v["g_means2D"]), ptr(self.g_colors[i]), ptr(v["g_opacity"]), ptr(v["g_means3D"]),
