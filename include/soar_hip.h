@@ -50,7 +50,9 @@ extern "C" {
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
  * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail).  soar_data_mask_bbox / _crops /
- * _step_batch (+ SoarDataStepArgs: the training data module). */
+ * _step_batch (+ SoarDataStepArgs: the training data module).  soar_frame_loss_partials / _pooled_partials,
+ * soar_frames_geometry_warp_backward_losses (+ SoarLossFinish), soar_adam_step_at_gather: two small launches of the step plan folded
+ * into their neighbours. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -433,6 +435,20 @@ typedef struct SoarFrameTail {
 int soar_frames_geometry_warp_backward(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot, const float *weights,
                                        const float *joint_mats, int32_t P, int32_t J, const float *scales, float *dL_dxyz, float *dL_drot,
                                        float *dL_dscales, float *dL_dcolors, float *dL_docc, void *stream);
+/* ... which also finishes the frames' image losses: soar_frame_loss_partials / soar_frame_loss_pooled_partials left the per-workgroup
+ * partial sums of frame f in its scratch and what to do with them in finish[f] (HOST array, n entries); one more workgroup per frame
+ * adds them up -- in soar_frame_loss's order: the same bits in loss_out -- off the chain between the loss and the backward blend,
+ * which reads the gradient planes, never the value.  finish == NULL: soar_frames_geometry_warp_backward. */
+typedef struct SoarLossFinish {
+    const float *sums4;          /* the loss call's scratch */
+    float *loss_out;             /* [1] */
+    int32_t blocks, n;           /* partial sums (4 floats each), pixels */
+    float w_color, w_mask, w_normal, w_depth;
+} SoarLossFinish;
+int soar_frames_geometry_warp_backward_losses(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot,
+                                              const float *weights, const float *joint_mats, int32_t P, int32_t J, const float *scales,
+                                              float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors, float *dL_docc,
+                                              const SoarLossFinish *finish, void *stream);
 
 /* The warps of the n frames of one optimizer step, one launch each way (no reference counterpart: the reference warps frame by
  * frame).  The canonical model (xyz, rot) and the blend weights are shared; joint_mats [n][J][16]; xyz_out / dL_dxyz_out
@@ -478,6 +494,19 @@ int soar_frame_loss_pooled(int32_t W, int32_t H, const float *color, const float
                            float w_color, float w_mask, float w_normal, float w_depth, float *loss_out, float *scratch,
                            float *dL_dcolor, float *dL_dnormal, float *dL_ddepth, float *dL_dopac, const void *image_buffer,
                            const float *background, int32_t normalize_depth, void *stream);
+/* The two calls above without their second launch: the gradient planes and the partial sums in `scratch` are written, loss_out is
+ * NOT; *finish_out (host memory) receives what soar_frames_geometry_warp_backward_losses needs to write it later in the step. */
+int soar_frame_loss_partials(int32_t W, int32_t H, const float *color, const float *normal, const float *depth,
+                             const float *opac, const float *target_color, const float *target_mask,
+                             const float *target_normal, float w_color, float w_mask, float w_normal, float w_depth,
+                             float *loss_out, float *scratch, float *dL_dcolor, float *dL_dnormal, float *dL_ddepth,
+                             float *dL_dopac, const void *image_buffer, const float *background, int32_t normalize_depth,
+                             SoarLossFinish *finish_out, void *stream);
+int soar_frame_loss_pooled_partials(int32_t W, int32_t H, const float *color, const float *normal, const float *depth,
+                                    const float *opac, const float *target_pool, int32_t n_sets, const int32_t *set_index_dev,
+                                    float w_color, float w_mask, float w_normal, float w_depth, float *loss_out, float *scratch,
+                                    float *dL_dcolor, float *dL_dnormal, float *dL_ddepth, float *dL_dopac, const void *image_buffer,
+                                    const float *background, int32_t normalize_depth, SoarLossFinish *finish_out, void *stream);
 
 /* ---- the same terms in ONE pass over the images (round 4, ABI 6): masked L1 of the colours over `sel`, L1 of the mask image over
  * every pixel, cosine loss of the normals over `sel_normal`, and -- when `occ` is given -- masked L1 of the occlusion image against 1
@@ -754,6 +783,12 @@ int soar_adam_step(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, d
  * out on the host in double precision, there is no device counter and no launch to advance it.  Several calls with the same `step`
  * update further rows of that step.  Not inside a captured graph (a replay would repeat the step number). */
 int soar_adam_step_at(int32_t n_rows, const SoarAdamRow *rows, double beta1, double beta2, double eps, int64_t step, void *stream);
+/* soar_adam_step_at and soar_gather_step_inputs_ids (same arguments, same results) in ONE launch: the gather depends on nothing the
+ * update writes, its n_frames workgroups ride behind the update's.  The first launch of a training step's prologue. */
+int soar_adam_step_at_gather(int32_t n_rows, const SoarAdamRow *rows, double beta1, double beta2, double eps, int64_t step,
+                             int32_t n_frames, int32_t num_frames_seq, int32_t floats_per_frame, int32_t n_sets,
+                             const int32_t *frame_ids_host, const float *table_dev, float *mats_out_dev, int32_t *set_index_out_dev,
+                             void *stream);
 /* The same step in parts: `advance` != 0 moves the step counter (and the bias corrections) on before the rows are updated, 0 updates
  * further rows of the SAME step -- a caller whose gradients arrive in buckets updates the leaves of a bucket as soon as it is there
  * (soar_amd/step_plan.py: the positions behind the first bucket, in front of the KNN refresh; the rest behind the second). */

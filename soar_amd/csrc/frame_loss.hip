@@ -6,6 +6,7 @@
 // the same structure: per-pixel terms averaged over the image).  In eager torch this is ~25 full-image kernels per
 // frame; here every pixel is read once and its four gradient planes are written once.
 #include "soar_common.h"
+#include "loss_finish.h"
 
 #include <type_traits>
 
@@ -118,8 +119,7 @@ __global__ void __launch_bounds__(256) frame_loss_kernel(Batch<LossArgs> batch)
         a.sums[4 * blockIdx.x + threadIdx.x] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
 
-// loss = wc*S[0]/(3n) + wm*S[1]/n + wn*S[2]/(3n) + wd*S[3]/n,  S = the workgroups' partial sums added in a fixed order (thread t
-// takes workgroups t, t + 256, ...; then a fixed tree): no atomics, the value does not depend on who finished first
+// the sum of the partials and the value: loss_finish_sum (loss_finish.h)
 struct LossFinishArgs {
     const float *sums;
     int blocks, n;
@@ -129,31 +129,8 @@ struct LossFinishArgs {
 __global__ void __launch_bounds__(256) frame_loss_finish_kernel(Batch<LossFinishArgs> batch)
 {
     const LossFinishArgs &fa = batch.v[blockIdx.y];
-    const float *sums = fa.sums;
-    const int blocks = fa.blocks, n = fa.n;
-    const float wc = fa.wc, wm = fa.wm, wn = fa.wn, wd = fa.wd;
-    float *loss = fa.loss;
     __shared__ float4 red[256];
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int b = threadIdx.x; b < blocks; b += 256) {
-        const float4 v = reinterpret_cast<const float4 *>(sums)[b];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            const float4 o = red[threadIdx.x + off];
-            float4 m = red[threadIdx.x];
-            m.x += o.x; m.y += o.y; m.z += o.z; m.w += o.w;
-            red[threadIdx.x] = m;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float4 S = red[0];
-        *loss = (wc * S.x / (3.f * n) + wm * S.y / n) + (wn * S.z / (3.f * n) + wd * S.w / n);
-    }
+    loss_finish_sum(fa.sums, fa.blocks, fa.n, fa.wc, fa.wm, fa.wn, fa.wd, fa.loss, red);
 }
 
 }  // namespace
@@ -166,7 +143,8 @@ static int frame_loss_launch(int32_t W, int32_t H, const float *color, const flo
                              const float *target_color, const float *target_mask, const float *target_normal,
                              const int32_t *set_index_dev, int32_t n_sets, float w_color, float w_mask, float w_normal,
                              float w_depth, float *loss_out, float *sums4, float *dL_dcolor, float *dL_dnormal, float *dL_ddepth,
-                             float *dL_dopac, const void *image_buffer, const float *background, int32_t normalize_depth, hipStream_t stream);
+                             float *dL_dopac, const void *image_buffer, const float *background, int32_t normalize_depth, hipStream_t stream,
+                             SoarLossFinish *finish_out = nullptr);
 
 extern "C" int soar_frame_loss(int32_t W, int32_t H, const float *color, const float *normal, const float *depth,
                                const float *opac, const float *target_color, const float *target_mask,
@@ -193,11 +171,39 @@ extern "C" int soar_frame_loss_pooled(int32_t W, int32_t H, const float *color, 
                              image_buffer, background, normalize_depth, static_cast<hipStream_t>(stream_));
 }
 
+extern "C" int soar_frame_loss_partials(int32_t W, int32_t H, const float *color, const float *normal, const float *depth,
+                                        const float *opac, const float *target_color, const float *target_mask,
+                                        const float *target_normal, float w_color, float w_mask, float w_normal, float w_depth,
+                                        float *loss_out, float *sums4, float *dL_dcolor, float *dL_dnormal, float *dL_ddepth,
+                                        float *dL_dopac, const void *image_buffer, const float *background, int32_t normalize_depth,
+                                        SoarLossFinish *finish_out, void *stream_)
+{
+    if (!finish_out) { set_error("soar_frame_loss_partials: finish_out is NULL"); return 1; }
+    return frame_loss_launch(W, H, color, normal, depth, opac, target_color, target_mask, target_normal, nullptr, 1, w_color,
+                             w_mask, w_normal, w_depth, loss_out, sums4, dL_dcolor, dL_dnormal, dL_ddepth, dL_dopac, image_buffer,
+                             background, normalize_depth, static_cast<hipStream_t>(stream_), finish_out);
+}
+
+extern "C" int soar_frame_loss_pooled_partials(int32_t W, int32_t H, const float *color, const float *normal, const float *depth,
+                                               const float *opac, const float *target_pool, int32_t n_sets,
+                                               const int32_t *set_index_dev, float w_color, float w_mask, float w_normal, float w_depth,
+                                               float *loss_out, float *sums4, float *dL_dcolor, float *dL_dnormal, float *dL_ddepth,
+                                               float *dL_dopac, const void *image_buffer, const float *background,
+                                               int32_t normalize_depth, SoarLossFinish *finish_out, void *stream_)
+{
+    if (!finish_out) { set_error("soar_frame_loss_pooled_partials: finish_out is NULL"); return 1; }
+    if (n_sets <= 0 || !set_index_dev) { set_error("soar_frame_loss_pooled_partials: need n_sets > 0 and a device index"); return 1; }
+    return frame_loss_launch(W, H, color, normal, depth, opac, target_pool, target_pool, target_pool, set_index_dev, n_sets,
+                             w_color, w_mask, w_normal, w_depth, loss_out, sums4, dL_dcolor, dL_dnormal, dL_ddepth, dL_dopac,
+                             image_buffer, background, normalize_depth, static_cast<hipStream_t>(stream_), finish_out);
+}
+
 static int frame_loss_launch(int32_t W, int32_t H, const float *color, const float *normal, const float *depth, const float *opac,
                              const float *target_color, const float *target_mask, const float *target_normal,
                              const int32_t *set_index_dev, int32_t n_sets, float w_color, float w_mask, float w_normal,
                              float w_depth, float *loss_out, float *sums4, float *dL_dcolor, float *dL_dnormal, float *dL_ddepth,
-                             float *dL_dopac, const void *image_buffer, const float *background, int32_t normalize_depth, hipStream_t stream)
+                             float *dL_dopac, const void *image_buffer, const float *background, int32_t normalize_depth, hipStream_t stream,
+                             SoarLossFinish *finish_out)
 {
     if (W <= 0 || H <= 0) { set_error("soar_frame_loss: bad image size %dx%d", W, H); return 1; }
     if (!color || !normal || !depth || !opac || !target_color || !target_mask || !target_normal || !loss_out || !sums4 ||
@@ -228,6 +234,12 @@ static int frame_loss_launch(int32_t W, int32_t H, const float *color, const flo
     const int blocks = min(SOAR_FRAME_LOSS_SCRATCH_FLOATS / 4, max(1, (a.n / (vec4 ? 4 : 1) + 255) / 256));
     if (vec4) SOAR_LAUNCH_BATCHED(frame_loss_kernel<4>, dim3(blocks), dim3(256), 0, stream, a);
     else SOAR_LAUNCH_BATCHED(frame_loss_kernel<1>, dim3(blocks), dim3(256), 0, stream, a);
+    if (finish_out) {
+        // (the partial sums wait for soar_frames_geometry_warp_backward_losses: nothing between here and there reads the value)
+        *finish_out = SoarLossFinish{sums4, loss_out, blocks, a.n, w_color, w_mask, w_normal, w_depth};
+        SOAR_LAUNCH_OK("frame_loss", stream, 0);
+        return 0;
+    }
     const soar::LossFinishArgs fa = {sums4, blocks, a.n, w_color, w_mask, w_normal, w_depth, loss_out};
     SOAR_LAUNCH_BATCHED(frame_loss_finish_kernel, dim3(1), dim3(256), 0, stream, fa);
     SOAR_LAUNCH_OK("frame_loss", stream, 0);

@@ -8,6 +8,7 @@
 //  * warp_backward_kernel : analytic gradient w.r.t. canonical xyz and quaternion.
 //  * dist2_knn3_kernel    : simple-knn distCUDA2 semantics (mean of the 3 smallest squared distances, self excluded).
 #include "soar_common.h"
+#include "loss_finish.h"
 #include "geom_bwd_point.h"
 #include "preprocess_point.h"
 #include "soar_quat.h"
@@ -474,12 +475,25 @@ struct TailOut {
     float *dL_dmeans2D[MAX_BATCH];   // per frame [P,3]
     float *dL_dscales, *dL_dcolors, *dL_docc;      // sums over the frames: [P,3], [P,3], [P] or NULL
 };
+// The frames' image losses, finished here (soar_frames_geometry_warp_backward_losses): workgroup `first_block` + f of the launch adds
+// up frame f's partial sums exactly as frame_loss_finish_kernel would have, between the loss and the backward blend -- where nothing
+// needs the value.  The kernel boundary in front of this launch is the ordering; n = 0: no such workgroups.
+struct TailLosses {
+    int n, first_block;
+    SoarLossFinish v[MAX_BATCH];
+};
 #ifndef SOAR_TAIL_WPE
 #define SOAR_TAIL_WPE 4
 #endif
-__global__ void __launch_bounds__(WARP_THREADS) __attribute__((amdgpu_waves_per_eu(SOAR_TAIL_WPE, 8))) geom_warp_backward_frames_kernel(WarpArgs a, int n, Batch<GeomBwdArgs> fr, TailOut out)
+__global__ void __launch_bounds__(WARP_THREADS) __attribute__((amdgpu_waves_per_eu(SOAR_TAIL_WPE, 8))) geom_warp_backward_frames_kernel(WarpArgs a, int n, Batch<GeomBwdArgs> fr, TailOut out, TailLosses losses)
 {
-    extern __shared__ float wtile[];
+    extern __shared__ __attribute__((aligned(16))) float wtile[];
+    static_assert(WARP_THREADS == 256 && WARP_NF * TAIL_C * WAVE * sizeof(float) >= 256 * sizeof(float4), "loss_finish_sum: 256 threads, 4 KB of LDS");
+    if (losses.n && (int)blockIdx.x >= losses.first_block) {             // (uniform: a whole workgroup)
+        const SoarLossFinish &l = losses.v[(int)blockIdx.x - losses.first_block];
+        loss_finish_sum(l.sums4, l.blocks, l.n, l.w_color, l.w_mask, l.w_normal, l.w_depth, l.loss_out, reinterpret_cast<float4 *>(wtile));
+        return;
+    }
     float *red = wtile + WAVE * a.J;                             // [WARP_NF][TAIL_C][WAVE]
     const int tid = threadIdx.x, k = __builtin_amdgcn_readfirstlane(tid / WAVE), lane = tid % WAVE;
     const int p0 = blockIdx.x * WAVE, p = p0 + lane;
@@ -737,8 +751,17 @@ int soar_frames_geometry_warp_backward(int32_t n, const SoarFrameTail *frames, c
                                        const float *joint_mats, int32_t P, int32_t J, const float *scales, float *dL_dxyz, float *dL_drot,
                                        float *dL_dscales, float *dL_dcolors, float *dL_docc, void *stream_)
 {
+    return soar_frames_geometry_warp_backward_losses(n, frames, xyz, rot, weights, joint_mats, P, J, scales, dL_dxyz, dL_drot, dL_dscales,
+                                                     dL_dcolors, dL_docc, nullptr, stream_);
+}
+
+int soar_frames_geometry_warp_backward_losses(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot,
+                                              const float *weights, const float *joint_mats, int32_t P, int32_t J, const float *scales,
+                                              float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors, float *dL_docc,
+                                              const SoarLossFinish *finish, void *stream_)
+{
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const char *who = "soar_frames_geometry_warp_backward";
+    const char *who = finish ? "soar_frames_geometry_warp_backward_losses" : "soar_frames_geometry_warp_backward";
     if (n < 1 || n > MAX_BATCH || !frames) { set_error("%s: 1 <= n <= %d frames", who, MAX_BATCH); return 1; }
     if (!weights) { set_error("%s: needs the blend weights", who); return 1; }
     if (warp_check(xyz, rot, weights, joint_mats, P, J)) return 1;
@@ -766,9 +789,22 @@ int soar_frames_geometry_warp_backward(int32_t n, const SoarFrameTail *frames, c
         fill_geom_bwd_args(fr.v[f], *t.prm, t.means3D, t.radii, nullptr, scales, t.rotations, nullptr, g, static_cast<const float *>(t.workspace));
         out.dL_dmeans2D[f] = t.dL_dmeans2D;
     }
+    TailLosses losses{};
+    const int blocks = (P + WAVE - 1) / WAVE;
+    if (finish) {
+        losses.n = n; losses.first_block = blocks;
+        for (int f = 0; f < n; f++) {
+            const SoarLossFinish &l = finish[f];
+            if (!l.sums4 || !l.loss_out || l.blocks < 1 || l.blocks > SOAR_FRAME_LOSS_SCRATCH_FLOATS / 4 || l.n < 1) {
+                set_error("%s: frame %d: finish[] is not what soar_frame_loss_partials left", who, f);
+                return 1;
+            }
+            losses.v[f] = l;
+        }
+    }
     const size_t lds = sizeof(float) * (WAVE * (size_t)J + WARP_NF * TAIL_C * WAVE);
     StageTimer timer(ST_LBS_WARP_BWD, stream);
-    hipLaunchKernelGGL(geom_warp_backward_frames_kernel, dim3((P + WAVE - 1) / WAVE), dim3(WARP_THREADS), lds, stream, a, (int)n, fr, out);
+    hipLaunchKernelGGL(geom_warp_backward_frames_kernel, dim3(blocks + losses.n), dim3(WARP_THREADS), lds, stream, a, (int)n, fr, out, losses);
     SOAR_LAUNCH_OK("frames_geometry_warp_backward", stream, 0);
     return 0;
 }

@@ -47,12 +47,33 @@ __global__ void adam_tick_kernel(AdamState *st, double beta1, double beta2)
     st->bias_correction2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)t));
 }
 
+// The step's input gather riding along (soar_adam_step_at_gather): workgroups [first_block, first_block + n_frames) of the launch do
+// what gather_step_inputs_ids_kernel's do (frame_loss.hip) -- copy the joint transforms of the step's frames out of the sequence
+// table, write their target-set indices -- and nothing else.  They read nothing the update writes.  n_frames = 0: no such workgroups.
+struct AdamGather {
+    int n_frames, num_frames_seq, floats_per_frame, n_sets;
+    int64_t first_block;
+    int32_t id[MAX_BATCH];
+    const float *table;
+    float *mats_out;
+    int32_t *set_out;
+};
+
 // one_minus_b1 / one_minus_b2: 1 - beta worked out in double by the host and rounded once, as torch does with its Python floats
 // (1.f - 0.9f is 0.100000024, float(1 - 0.9) is 0.1: the lerp weight would differ in its last bits)
 template <typename Table>
 __global__ void __launch_bounds__(256) adam_update_kernel(Table tab, const AdamState *__restrict__ st_dev, AdamState st_host, float beta2,
-                                                          float one_minus_b1, float one_minus_b2, float eps)
+                                                          float one_minus_b1, float one_minus_b2, float eps, AdamGather ga)
 {
+    if (ga.n_frames && (int64_t)blockIdx.x >= ga.first_block) {           // (uniform: a whole workgroup)
+        const int f = (int)((int64_t)blockIdx.x - ga.first_block);
+        int id = ga.id[f] % ga.num_frames_seq;
+        if (id < 0) id += ga.num_frames_seq;
+        for (int k = threadIdx.x; k < ga.floats_per_frame; k += 256)
+            ga.mats_out[(size_t)f * ga.floats_per_frame + k] = ga.table[(size_t)id * ga.floats_per_frame + k];
+        if (threadIdx.x == 0 && ga.set_out) ga.set_out[f] = ga.n_sets > 0 ? id % ga.n_sets : 0;
+        return;
+    }
     const AdamState *st = st_dev ? st_dev : &st_host;      // the step's bias corrections: from the device counter, or worked out by the host
     // rows of a step that was never started (advance = 0 on a fresh, zeroed state): 1 - beta1^0 = 0 would make the step size infinite
     if (st->step <= 0) return;
@@ -126,10 +147,34 @@ extern "C" int soar_adam_step(int32_t n_rows, const SoarAdamRow *rows_host, doub
 
 // The same update with the step number kept by the caller (as torch.optim.Adam does: its bias corrections are Python floats): no
 // device counter, no launch to advance it.  Not for a captured graph -- a replay would repeat the same step number.
+static int adam_step_at(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, double beta2, double eps, int64_t step,
+                        const AdamGather *gather, hipStream_t stream);
+
 extern "C" int soar_adam_step_at(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, double beta2, double eps, int64_t step,
                                  void *stream_)
 {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return adam_step_at(n_rows, rows_host, beta1, beta2, eps, step, nullptr, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int soar_adam_step_at_gather(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, double beta2, double eps, int64_t step,
+                                        int32_t n_frames, int32_t num_frames_seq, int32_t floats_per_frame, int32_t n_sets,
+                                        const int32_t *frame_ids_host, const float *table_dev, float *mats_out_dev,
+                                        int32_t *set_index_out_dev, void *stream_)
+{
+    if (n_frames <= 0 || n_frames > MAX_BATCH || num_frames_seq <= 0 || floats_per_frame <= 0 || !frame_ids_host || !table_dev || !mats_out_dev) {
+        set_error("soar_adam_step_at_gather: bad gather arguments (at most %d frames per step)", MAX_BATCH);
+        return 1;
+    }
+    AdamGather ga = {};
+    ga.n_frames = n_frames; ga.num_frames_seq = num_frames_seq; ga.floats_per_frame = floats_per_frame; ga.n_sets = n_sets;
+    for (int f = 0; f < n_frames; f++) ga.id[f] = frame_ids_host[f];
+    ga.table = table_dev; ga.mats_out = mats_out_dev; ga.set_out = set_index_out_dev;
+    return adam_step_at(n_rows, rows_host, beta1, beta2, eps, step, &ga, static_cast<hipStream_t>(stream_));
+}
+
+static int adam_step_at(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, double beta2, double eps, int64_t step,
+                        const AdamGather *gather, hipStream_t stream)
+{
     if (n_rows < 0 || n_rows > ADAM_MAX_ROWS || (n_rows && !rows_host) || step < 1) {
         set_error("soar_adam_step_at: 0 <= n_rows <= %d, rows must be given, step >= 1", ADAM_MAX_ROWS);
         return 1;
@@ -153,10 +198,12 @@ extern "C" int soar_adam_step_at(int32_t n_rows, const SoarAdamRow *rows_host, d
     st.bias_correction1 = (float)(1.0 - pow(beta1, (double)step));
     st.bias_correction2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
     st.pad = 0;
+    AdamGather ga = {};
+    if (gather) { ga = *gather; ga.first_block = blocks; }
     StageTimer timer(ST_OPTIMIZER, stream);
-    if (blocks > 0)
-        hipLaunchKernelGGL(adam_update_kernel<AdamTable>, dim3((unsigned)blocks), dim3(256), 0, stream, tab, (const AdamState *)nullptr, st, (float)beta2,
-                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+    if (blocks + ga.n_frames > 0)
+        hipLaunchKernelGGL(adam_update_kernel<AdamTable>, dim3((unsigned)(blocks + ga.n_frames)), dim3(256), 0, stream, tab, (const AdamState *)nullptr, st,
+                           (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, ga);
     SOAR_LAUNCH_OK("adam_step_at", stream, 0);
     return 0;
 }
@@ -177,7 +224,7 @@ extern "C" int soar_adam_step_rows(int32_t n_rows, const SoarAdamRow *rows_host,
     if (advance) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, stream, st, beta1, beta2);
     if (blocks > 0)
         hipLaunchKernelGGL(adam_update_kernel<AdamTable>, dim3((unsigned)blocks), dim3(256), 0, stream, tab, st, AdamState{}, (float)beta2,
-                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, AdamGather{});
     SOAR_LAUNCH_OK("adam_step", stream, 0);
     return 0;
 }
@@ -199,7 +246,7 @@ extern "C" int soar_adam_step_rows_wide(int32_t n_rows, const SoarAdamRow *rows_
     if (advance) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, stream, st, beta1, beta2);
     if (blocks > 0)
         hipLaunchKernelGGL(adam_update_kernel<AdamTableWide>, dim3((unsigned)blocks), dim3(256), 0, stream, tab, st, AdamState{}, (float)beta2,
-                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+                           (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, AdamGather{});
     SOAR_LAUNCH_OK("adam_step_rows_wide", stream, 0);
     return 0;
 }

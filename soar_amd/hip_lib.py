@@ -70,6 +70,12 @@ class SoarFrameTail(C.Structure):
                 ("dL_dmeans2D", _vp)]
 
 
+class SoarLossFinish(C.Structure):
+    """Mirror of ``struct SoarLossFinish`` (include/soar_hip.h): what soar_frame_loss_partials leaves for the tail of the step."""
+    _fields_ = [("sums4", _vp), ("loss_out", _vp), ("blocks", C.c_int32), ("n", C.c_int32), ("w_color", C.c_float), ("w_mask", C.c_float),
+                ("w_normal", C.c_float), ("w_depth", C.c_float)]
+
+
 class SoarViewArgs(C.Structure):
     """Mirror of ``struct SoarViewArgs`` (include/soar_hip.h)."""
     _fields_ = [("rast", SoarRastParams), ("focal_k00", C.c_float), ("focal_k11", C.c_float), ("back", C.c_int32), ("pad_", C.c_int32),
@@ -217,6 +223,7 @@ SIGNATURES = {
     "soar_frames_warp_preprocess": (C.c_int, [C.c_int32, _vp] + [_vp] * 4 + [C.c_int32, C.c_int32] + [_vp] * 6),
     "soar_rast_backward_rows": (C.c_int, [_vp] * 22),
     "soar_frames_geometry_warp_backward": (C.c_int, [C.c_int32, _vp] + [_vp] * 4 + [C.c_int32, C.c_int32] + [_vp] * 7),
+    "soar_frames_geometry_warp_backward_losses": (C.c_int, [C.c_int32, _vp] + [_vp] * 4 + [C.c_int32, C.c_int32] + [_vp] * 8),
     "soar_dist2_knn3": (C.c_int, [_vp, C.c_int32, _vp, _vp]),
     "soar_depth2normal": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     "soar_depth2normal_backward": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp,
@@ -245,6 +252,10 @@ SIGNATURES = {
                                   C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "soar_frame_loss_pooled": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_float, C.c_float, C.c_float,
                                          C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
+    "soar_frame_loss_partials": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float,
+                                           C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    "soar_frame_loss_pooled_partials": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_float, C.c_float,
+                                                  C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "soar_selftest_exp": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "soar_selftest_affine_scan": (C.c_int, [_vp, _vp, _vp, _vp]),
     "soar_prof_enable": (C.c_int, [C.c_int]),
@@ -270,6 +281,8 @@ SIGNATURES = {
     "soar_avatar_pixel_losses": (C.c_int, [C.POINTER(SoarAvatarLossArgs), C.c_int32, _vp]),
     "soar_adam_step": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "soar_adam_step_at": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
+    "soar_adam_step_at_gather": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, C.c_int64] + [C.c_int32] * 4
+                                 + [C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
     "soar_adam_step_rows": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, C.c_int32, _vp]),
     "soar_adam_step_rows_wide": (C.c_int, [C.c_int32, C.POINTER(SoarAdamRow), C.c_double, C.c_double, C.c_double, _vp, C.c_int32, _vp]),
     "soar_tsdf_integrate": (C.c_int, [C.c_int32] * 3 + [_vp] * 5 + [C.c_float] * 4 + [C.c_int32] * 3 + [C.c_float] * 3 + [_vp] * 3),

@@ -45,10 +45,12 @@ class FusedAdam:
             rows[k].count, rows[k].lr = p.numel(), self.lr[n]
         return rows
 
-    def step(self, stream: Optional[int] = None, names=None, advance: bool = True) -> None:
+    def step(self, stream: Optional[int] = None, names=None, advance: bool = True, gather=None) -> None:
         """One Adam step of every leaf from the gradients in the flat buffer (behind whatever the stream already holds -- make it
         wait for pending reductions first: ``flat.wait_all()``).  ``names``: only these leaves; ``advance=False``: they belong to the
-        step a former call started (the positions behind the first gradient bucket, the rest behind the second)."""
+        step a former call started (the positions behind the first gradient bucket, the rest behind the second).  ``gather``: the
+        arguments of ``soar_gather_step_inputs_ids`` without the stream -- the step plan's input gather rides in this launch
+        (``soar_adam_step_at_gather``; host step counter only)."""
         self.flat.check_views()
         dev = self.flat.flat.device
         names = self.names if names is None else [n for n in self.names if n in names]
@@ -56,11 +58,17 @@ class FusedAdam:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
             if self.device_counter:
+                if gather is not None:
+                    raise ValueError("gather rides with the host step counter only (device_counter = False)")
                 check(hip_lib.lib().soar_adam_step_rows(len(names), rows, self.betas[0], self.betas[1], self.eps, ptr(self.state),
                                                         1 if advance else 0, stream), "soar_adam_step_rows")
             else:
                 # the step number lives here, like torch.optim.Adam's: no device counter, no launch to advance it
                 if advance:
                     self.steps += 1
+                if gather is not None:
+                    check(hip_lib.lib().soar_adam_step_at_gather(len(names), rows, self.betas[0], self.betas[1], self.eps, self.steps,
+                                                                 *gather, stream), "soar_adam_step_at_gather")
+                    return
                 check(hip_lib.lib().soar_adam_step_at(len(names), rows, self.betas[0], self.betas[1], self.eps, self.steps, stream),
                       "soar_adam_step_at")

@@ -183,6 +183,15 @@ class FrameStepPlan:
             env = os.environ.get("SOAR_PLAN_BATCHED")
             batched = (env != "0") if env in ("0", "1") else (self.W * self.H <= 3_000_000)
         self.batched = bool(batched) and self.n <= 8
+        # Two small launches of the batched eager chain folded into their neighbours (the kernels and entry points of the two-launch
+        # forms stay: every other path uses them; profiles/r08_ab_chain_launches.txt).  SOAR_PLAN_LOSS_IN_TAIL=0:
+        # frame_loss_finish_kernel between the loss and the backward blend again; SOAR_PLAN_GATHER_IN_ADAM=0: the input gather as
+        # the prologue's own first launch again.
+        fold = self.batched and not use_graphs
+        self.loss_in_tail = fold and self.fused_tail and loss == "synthetic" and os.environ.get("SOAR_PLAN_LOSS_IN_TAIL", "1") != "0"
+        if self.loss_in_tail:
+            self._loss_finish = (hip_lib.SoarLossFinish * self.n)()        # written by every step's loss calls, read by its tail call
+        self.gather_in_adam = fold and self.n <= 8 and os.environ.get("SOAR_PLAN_GATHER_IN_ADAM", "1") != "0"
         self._call_cache = {}
         self.optimizer = None                     # see _run_eager
         self.optimizer_in_two_parts = None        # None: when a gradient reduction is in flight; True / False force it (tests)
@@ -324,11 +333,19 @@ class FrameStepPlan:
         if self.stamps is not None and self.fine_stamps:
             self._stamp(100 + 10 * i + stage, stream)
 
-    def _prologue(self, stream: int, resort: bool = True) -> None:
+    def _gather_args(self):
+        """the arguments of soar_gather_step_inputs_ids, without the stream"""
+        s = self.seq
+        n_sets = int(self.pool.shape[0]) if self.pool is not None else 0
+        return (self.n, s.num_frames, 55 * 16, n_sets, (C.c_int32 * self.n)(*self._frames_now), ptr(s.cano2live), ptr(self.mats), ptr(self.frame_sel))
+
+    def _prologue(self, stream: int, resort: bool = True, gathered: bool = False) -> None:
         L, s = self.L, self.seq
         self._stamp(0, stream)
         n_sets = int(self.pool.shape[0]) if self.pool is not None else 0
-        if self._ids_by_value:
+        if gathered:
+            pass                                 # (the optimizer's launch in front of this took the gather along: soar_adam_step_at_gather)
+        elif self._ids_by_value:
             # (launched directly: the step's frame ids travel in the kernel's arguments -- no host -> device copy in front of a step)
             ids = (C.c_int32 * self.n)(*self._frames_now)
             check(L.soar_gather_step_inputs_ids(self.n, s.num_frames, 55 * 16, n_sets, ids, ptr(s.cano2live), ptr(self.mats),
@@ -392,6 +409,20 @@ class FrameStepPlan:
         def build():
             L, v, W, H = self.L, self.views[i], self.W, self.H
             wc, wm, wn, wd = self.weights
+            if self.loss_in_tail:
+                # (the partial sums stay in v["sums"]; the epilogue's launch writes losses[i]: soar_frames_geometry_warp_backward_losses)
+                fin = C.addressof(self._loss_finish[i])
+                if self.pool is not None:
+                    return (L.soar_frame_loss_pooled_partials, (W, H, ptr(v["color"]), ptr(v["normal"]), ptr(v["depth"]), ptr(v["opac"]), ptr(self.pool),
+                                                                int(self.pool.shape[0]), ptr(self.frame_sel[i]), wc, wm, wn, wd, ptr(self.losses[i]),
+                                                                ptr(v["sums"]), ptr(v["gC"]), ptr(v["gN"]), ptr(v["gD"]), ptr(v["gO"]), ptr(v["img"]),
+                                                                self.ctx.params.bg_dev, int(self.ctx.params.cfg_normalize_depth), fin, stream),
+                            "frame_loss_pooled_partials")
+                tc, tm, tn = self.targets
+                return (L.soar_frame_loss_partials, (W, H, ptr(v["color"]), ptr(v["normal"]), ptr(v["depth"]), ptr(v["opac"]), ptr(tc), ptr(tm), ptr(tn),
+                                                     wc, wm, wn, wd, ptr(self.losses[i]), ptr(v["sums"]), ptr(v["gC"]), ptr(v["gN"]), ptr(v["gD"]),
+                                                     ptr(v["gO"]), ptr(v["img"]), self.ctx.params.bg_dev, int(self.ctx.params.cfg_normalize_depth),
+                                                     fin, stream), "frame_loss_partials")
             if self.pool is not None:
                 return (L.soar_frame_loss_pooled, (W, H, ptr(v["color"]), ptr(v["normal"]), ptr(v["depth"]), ptr(v["opac"]), ptr(self.pool),
                                                    int(self.pool.shape[0]), ptr(self.frame_sel[i]), wc, wm, wn, wd, ptr(self.losses[i]),
@@ -493,9 +524,15 @@ class FrameStepPlan:
             # the per-Gaussian stage of every frame's rasterizer backward and the warp's backward in ONE kernel: the frames' backward
             # calls stopped behind their blends (SoarRastParams.debug bit 3), their accumulation rows wait in the workspaces
             occ = ptr(fv["occ"]) if (self.loss_kind == "avatar" and "occ" in fv) else None
-            check(L.soar_frames_geometry_warp_backward(self.n, self._tail_frames, ptr(s.xyz.detach()), ptr(s.rot.detach()), ptr(self.blend_weights),
-                                                       ptr(self.mats), self.P, J, ptr(s.scales.detach()), ptr(fv["xyz"]), ptr(fv["rot"]),
-                                                       ptr(fv["scales"]), ptr(fv["colors"]), occ, stream), "frames_geometry_warp_backward")
+            if self.loss_in_tail:
+                check(L.soar_frames_geometry_warp_backward_losses(self.n, self._tail_frames, ptr(s.xyz.detach()), ptr(s.rot.detach()),
+                                                                  ptr(self.blend_weights), ptr(self.mats), self.P, J, ptr(s.scales.detach()),
+                                                                  ptr(fv["xyz"]), ptr(fv["rot"]), ptr(fv["scales"]), ptr(fv["colors"]), occ,
+                                                                  self._loss_finish, stream), "frames_geometry_warp_backward_losses")
+            else:
+                check(L.soar_frames_geometry_warp_backward(self.n, self._tail_frames, ptr(s.xyz.detach()), ptr(s.rot.detach()), ptr(self.blend_weights),
+                                                           ptr(self.mats), self.P, J, ptr(s.scales.detach()), ptr(fv["xyz"]), ptr(fv["rot"]),
+                                                           ptr(fv["scales"]), ptr(fv["colors"]), occ, stream), "frames_geometry_warp_backward")
             self._stamp(2 * self.n + 3, stream)
             return
         check(L.soar_lbs_warp_backward_sum(ptr(s.xyz.detach()), ptr(s.rot.detach()), ptr(self.blend_weights), ptr(self.mats), self.n,
@@ -550,9 +587,11 @@ class FrameStepPlan:
             in_flight = in_flight and self.flat.n_buckets > 1      # (one bucket: everything arrives together, one optimizer launch)
             # (no reduction pending: one launch for all leaves)
             self.flat.wait_bucket(0)
+            # (the input gather rides in the optimizer's first launch; no optimizer, the first step: the prologue's own launch)
+            ride = opt is not None and self.gather_in_adam and self._ids_by_value and not opt.device_counter
             if opt is not None:
-                opt.step(main.cuda_stream, names=("xyz",) if in_flight else None, advance=True)
-            self._prologue(main.cuda_stream, self.steps % self.RESORT_EVERY == 0)
+                opt.step(main.cuda_stream, names=("xyz",) if in_flight else None, advance=True, gather=self._gather_args() if ride else None)
+            self._prologue(main.cuda_stream, self.steps % self.RESORT_EVERY == 0, gathered=ride)
             self.flat.wait_all()
             if opt is not None and in_flight:
                 opt.step(main.cuda_stream, names=tuple(n for n in opt.names if n != "xyz"), advance=False)
