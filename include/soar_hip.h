@@ -52,7 +52,7 @@ extern "C" {
  * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail).  soar_data_mask_bbox / _crops /
  * _step_batch (+ SoarDataStepArgs: the training data module).  soar_frame_loss_partials / _pooled_partials,
  * soar_frames_geometry_warp_backward_losses (+ SoarLossFinish), soar_adam_step_at_gather: two small launches of the step plan folded
- * into their neighbours. */
+ * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1160,6 +1160,34 @@ typedef struct SoarDataStepArgs {
     float *mvp_mtx, *proj, *gt_mvp_mtx, *small_out;
 } SoarDataStepArgs;
 int soar_data_step_batch(const SoarDataStepArgs *args, void *stream);
+
+/* ---- test-split evaluation (eval.hip, soar_amd/evaluate.py): the numbers of the reference's test_step
+ * (TS/system/gaussian_surfel_mvdream.py:527-589), which takes them from skimage on the host.  Per image n, in one pass:
+ *   gt_white = gt_mask > 0.5 ? gt_rgb : 1.0f;
+ *   mse = sum over the 3 H W values of (double)(d * d), d = gt_white - pred and d * d in float32, / (3 H W);
+ *   psnr = 10 log10(1 / mse) (data range 1; +inf when mse == 0);
+ *   ssim = structural_similarity(pred, gt_white, channel_axis=-1, data_range=1): per channel, over the (H - 6)(W - 6) 7x7 windows
+ *     wholly inside the image, in float64: u* = window sums of x, y, xx, yy, xy / 49, v = 49 / 48 (uxx - ux ux) (vy, vxy likewise),
+ *     S = (2 ux uy + C1)(2 vxy + C2) / ((ux ux + uy uy + C1)(vx + vy + C2)), C1 = 1e-4, C2 = 9e-4; the mean of S over the windows,
+ *     then over the channels;
+ *   metrics[n] = {psnr, ssim, mse};  pred2 = pred * 2 - 1, gt2 = gt_white * 2 - 1 (the LPIPS inputs);
+ *   grid (NULL = skip) [N][H][2 W][3] = pred | gt_white as bytes: clamp(v, 0, 1) * 255, truncated.
+ * pred, gt_rgb [N][H][W][3] and gt_mask [N][H][W] are read at their element strides; gt_white, pred2, gt2 are contiguous [N][H][W][3].
+ * No float atomics: every workgroup writes four float64 partial sums into `scratch` (soar_eval_scratch_bytes bytes, 8-byte aligned),
+ * a second kernel of the same call adds them in a fixed order: two calls give the same bits.  No host synchronisation, no allocation.
+ * Refused before any launch: H < 7 or W < 7 (no window fits; skimage raises too), N < 1, N > 65535, N H W > 2^30, a NULL pointer other
+ * than grid, a short scratch. */
+typedef struct SoarEvalArgs {
+    int32_t N, H, W, pad_;
+    const float *pred, *gt_rgb, *gt_mask;
+    int64_t pred_stride[4], gt_stride[4];   /* elements, in the order N, H, W, channel */
+    int64_t mask_stride[3];                 /* elements, N, H, W */
+    float *gt_white, *pred2, *gt2;
+    uint8_t *grid;                          /* or NULL */
+    double *metrics;                        /* [N][3] */
+} SoarEvalArgs;
+int soar_eval_scratch_bytes(int32_t N, int32_t H, int32_t W, size_t *bytes);
+int soar_eval_image_metrics(const SoarEvalArgs *args, void *scratch, size_t scratch_bytes, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

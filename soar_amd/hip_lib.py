@@ -171,6 +171,13 @@ class SoarDataStepArgs(C.Structure):
                 ("mvp_mtx", _vp), ("proj", _vp), ("gt_mvp_mtx", _vp), ("small_out", _vp)]
 
 
+class SoarEvalArgs(C.Structure):
+    """Mirror of ``struct SoarEvalArgs`` (include/soar_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pad_", C.c_int32), ("pred", _vp), ("gt_rgb", _vp), ("gt_mask", _vp),
+                ("pred_stride", C.c_int64 * 4), ("gt_stride", C.c_int64 * 4), ("mask_stride", C.c_int64 * 3),
+                ("gt_white", _vp), ("pred2", _vp), ("gt2", _vp), ("grid", _vp), ("metrics", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -324,6 +331,8 @@ SIGNATURES = {
     "soar_data_mask_bbox": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "soar_data_crops": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "soar_data_step_batch": (C.c_int, [C.POINTER(SoarDataStepArgs), _vp]),
+    "soar_eval_scratch_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_eval_image_metrics": (C.c_int, [C.POINTER(SoarEvalArgs), _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
