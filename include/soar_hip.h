@@ -45,7 +45,7 @@ extern "C" {
  * debug bit 3): the head of the forward pass and the tail of the backward pass of all frames of a step as one kernel each;
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
- * soar_mesh_filter_bytes / _components (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
+ * soar_mesh_filter_bytes / _components, soar_mesh_simplify_bytes / _count / soar_mesh_simplify (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
@@ -845,6 +845,23 @@ int soar_mesh_filter_bytes(int32_t V, int32_t F, size_t *bytes);
 int soar_mesh_filter_components(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t min_faces, float min_diag_frac,
                                 void *workspace, size_t workspace_bytes, float *verts_out, int32_t *faces_out, int64_t *counts_host,
                                 void *stream);
+/* Decimation by quadric vertex clustering (mesh_simplify.hip; DESIGN.md 9b states the computation; not pymeshlab's edge collapse).
+ * One output vertex per occupied cell of the uniform grid of size `cell` over the vertices' bounding box (n_k = floor((hi_k -
+ * lo_k) / cell) + 1 cells along axis k, at most 2^21), placed at the minimum of the summed float64 face quadrics (eigenvalues
+ * below 1e-3 of the largest count as zero; the cluster's mean vertex where that leaves the cell's neighbourhood); faces with two
+ * corners in one cell and all but the first of the faces with the same three cells are dropped, cells no face uses too.
+ * Surviving faces keep their input order and winding, output vertices follow the cell key (ix * ny + iy) * nz + iz.
+ * soar_mesh_simplify_bytes: the workspace of a mesh of 1 <= V <= 2^30 vertices and 0 <= F <= 2^30 faces.
+ * soar_mesh_simplify_count: counts_host[2] = {output vertices, output faces} for `cell`; no quadric work, no output mesh.
+ * soar_mesh_simplify: the same counts, verts_out [<= V][3] and faces_out [<= F][3].
+ * Refused before any launch: V < 1, F < 0, V or F above 2^30, a cell size that is not positive and finite, NULL pointers, a short or misaligned
+ * workspace.  Refused after the bounding-box launch, before any other: a non-finite coordinate, more than 2^21 cells along an
+ * axis.  Both read back the bounding box and the totals (two stream synchronisations).  Deterministic bit for bit. */
+int soar_mesh_simplify_bytes(int32_t V, int32_t F, size_t *bytes);
+int soar_mesh_simplify_count(int32_t V, int32_t F, const float *verts, const int32_t *faces, float cell, void *workspace,
+                             size_t workspace_bytes, int64_t *counts_host, void *stream);
+int soar_mesh_simplify(int32_t V, int32_t F, const float *verts, const int32_t *faces, float cell, void *workspace,
+                       size_t workspace_bytes, float *verts_out, int32_t *faces_out, int64_t *counts_host, void *stream);
 
 /* ---- the surfels' attribute field (field.hip, soar_amd/field.py; DESIGN.md "Attribute field"): the reference's HashMLPSDFField
  * (TS/geometry/sdf_fields.py:41-219) with nerfstudio's torch HashEncoding / MLP semantics.  Two multiresolution hash encodings of

@@ -40,6 +40,8 @@ EXTRA_FLAGS = {
     "densify.hip": ["-ffp-contract=off"],
     # vertex positions and fused distances are checked bit for bit / to 1e-5 against CPU restatements (tests/)
     "mesh.hip": ["-ffp-contract=off"],
+    # cell indices decide the clustering; the float64 quadric sums are restated operation by operation (tests/mesh_simplify_ref.py)
+    "mesh_simplify.hip": ["-ffp-contract=off"],
     # the background's composite must equal torch's three separate operations bit for bit
     "envmap.hip": ["-ffp-contract=off"],
     # exactly zero gradients where a difference is exactly zero, and values that do not depend on what the compiler fuses
@@ -56,7 +58,7 @@ EXTRA_FLAGS = {
 }
 SOURCES = ["api.hip", "rast_preprocess.hip", "rast_binning.hip", "rast_tilebin.hip", "rast_blockmask.hip", "rast_render_fwd.hip", "rast_render_bwd.hip",
            "rast_geom_bwd.hip", "lbs.hip", "lbs_knn.hip", "frame_loss.hip", "postops.hip", "ssim.hip", "image_losses.hip", "smplx_joints.hip", "densify.hip", "optim.hip", "view.hip",
-           "mesh.hip", "field.hip", "envmap.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip"]
+           "mesh.hip", "mesh_simplify.hip", "field.hip", "envmap.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(_HERE, "..", "include", "soar_hip.h")]
 
 

@@ -299,6 +299,9 @@ SIGNATURES = {
     "soar_mesh_filter_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_mesh_filter_components": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_float, _vp, C.c_size_t, _vp, _vp,
                                               C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_simplify_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_simplify_count": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_simplify": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, _vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_int64), _vp]),
     "soar_field_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_field_forward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp]),
     "soar_field_backward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp, C.c_size_t, _vp]),

@@ -1,4 +1,5 @@
-"""Mesh export of a surfel avatar: TSDF fusion of rendered depth, marching cubes, small-component removal (csrc/mesh.hip).
+"""Mesh export of a surfel avatar: TSDF fusion of rendered depth, marching cubes, small-component removal (csrc/mesh.hip),
+decimation to a face budget (csrc/mesh_simplify.hip).
 
 Replaces the exporter behind every SOAR configuration (``exporter_type: "gaussiandreamer-mesh-exporter"`` ->
 ``geometry.extract_mesh()``).  The reference samples a 3-D Gaussian density built from ``get_scaling`` on a 128^3 grid
@@ -10,6 +11,9 @@ sphere, the depth is fused into a truncated signed-distance volume and its zero 
 * ``marching_cubes``: welded, crack-free, outward-facing triangles in index coordinates (like ``mcubes.marching_cubes``).
 * ``filter_components``: drops components with fewer than 64 faces or a bounding-box diagonal below 20 % of the mesh's
   (the reference's ``clean_mesh(min_f=64, min_d=20)``, geometry/mesh_utils.py:91-150).
+* ``simplify`` / ``decimate``: quadric vertex clustering at a cell size / at the cell size a face budget asks for, in place of
+  the reference's ``decimate_mesh`` (pymeshlab's quadric edge collapse, geometry/mesh_utils.py:45-88).  A different algorithm
+  with the same purpose: no output is comparable bit for bit with pymeshlab's.
 * ``extract_mesh``: the whole path, from the rasterizer's inputs to a world-space ``Mesh``.  A POSED mesh: warp the canonical
   surfels first (``soar_amd.lbs.lbs_warp(xyz, rot, weights, joint_mats)``) and pass the warped positions and rotations.
 
@@ -152,6 +156,113 @@ def filter_components(verts: torch.Tensor, faces: torch.Tensor, min_faces: int =
     return vo[:int(counts[0])].clone(), fo[:int(counts[1])].clone()
 
 
+# ---- decimation ------------------------------------------------------------------------------------------------------
+
+DECIMATE_TARGET = 100_000    # the reference's extract_mesh(decimate_target=1e5)
+
+
+def _f32(x: float) -> float:
+    """x rounded to float32 (for a quotient of two float32 values: the float32 quotient)"""
+    return C.c_float(x).value
+
+
+def _mesh_tensors(mesh) -> Tuple[torch.Tensor, torch.Tensor]:
+    verts, faces = mesh
+    _hip(verts, "vertices")
+    _hip(faces, "faces")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError(f"vertices must be [V,3] float32 (got {tuple(verts.shape)} {verts.dtype})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or faces.device != verts.device:
+        raise ValueError(f"faces must be [F,3] int32 on the vertices' device (got {tuple(faces.shape)} {faces.dtype} on {faces.device})")
+    return verts.contiguous(), faces.contiguous()
+
+
+class _Simplifier:
+    """The workspace and the two calls of one mesh (``decimate`` probes many cell sizes with one workspace)."""
+
+    def __init__(self, verts: torch.Tensor, faces: torch.Tensor):
+        self.verts, self.faces = verts, faces
+        self.V, self.F = int(verts.shape[0]), int(faces.shape[0])
+        self.lib = hip_lib.lib()
+        nb = C.c_size_t(0)
+        check(self.lib.soar_mesh_simplify_bytes(self.V, self.F, C.byref(nb)), "soar_mesh_simplify_bytes")
+        self.nb = nb.value
+        self.ws = _workspace(self.nb, verts.device)
+        self.fptr = faces.data_ptr() if self.F > 0 else verts.data_ptr()
+
+    def count(self, cell: float) -> Tuple[int, int]:
+        counts = (C.c_int64 * 2)()
+        with torch.cuda.device(self.verts.device):
+            check(self.lib.soar_mesh_simplify_count(self.V, self.F, self.verts.data_ptr(), self.fptr, cell, self.ws.data_ptr(), self.nb,
+                                                    counts, _stream(self.verts.device)), "soar_mesh_simplify_count")
+        return int(counts[0]), int(counts[1])
+
+    def run(self, cell: float) -> Mesh:
+        dev = self.verts.device
+        vo = torch.empty(self.V, 3, device=dev)
+        fo = torch.empty(max(self.F, 1), 3, dtype=torch.int32, device=dev)
+        counts = (C.c_int64 * 2)()
+        with torch.cuda.device(dev):
+            check(self.lib.soar_mesh_simplify(self.V, self.F, self.verts.data_ptr(), self.fptr, cell, self.ws.data_ptr(), self.nb,
+                                              vo.data_ptr(), fo.data_ptr(), counts, _stream(dev)), "soar_mesh_simplify")
+        return Mesh(vo[:int(counts[0])].clone(), fo[:int(counts[1])].clone())
+
+
+def simplify(mesh: Mesh, cell: float) -> Mesh:
+    """One pass of quadric vertex clustering (Lindstrom 2000) at cell size ``cell``: the vertices inside one cell of the uniform
+    grid over the bounding box become one vertex, placed where the summed quadrics of the faces around them are least; faces
+    that lose a corner this way, and repeated faces, go.  Surviving faces keep their order and winding.  DESIGN.md 9b states
+    the computation; it is deterministic bit for bit.  Where two sheets of the surface pass through one cell the result has
+    non-manifold edges, and nothing repairs them."""
+    verts, faces = _mesh_tensors(mesh)
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f"cell must be positive and finite (got {cell})")
+    if verts.shape[0] == 0:
+        return Mesh(verts.new_zeros(0, 3), torch.zeros(0, 3, dtype=torch.int32, device=verts.device))
+    return _Simplifier(verts, faces).run(cell)
+
+
+def _decimate_cells(count, target_faces: int, max_cells: int) -> int:
+    """The search of ``decimate``: ``count(R)`` = faces left at ``R`` cells along the longest axis.  R doubles from 1 until
+    count(R) > target_faces or R == max_cells; then a bisection under count(lo) <= target_faces < count(hi) -> lo."""
+    lo, hi, R = 1, None, 1
+    while True:
+        if count(R) > target_faces:
+            hi = R
+            break
+        lo = R
+        if R >= max_cells:
+            return lo
+        R = min(2 * R, max_cells)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if count(mid) <= target_faces:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def decimate(mesh: Mesh, target_faces: int = DECIMATE_TARGET, max_cells: int = 4096) -> Mesh:
+    """``mesh`` with at most ``target_faces`` faces: ``simplify`` at cell = L / R (float32), L the longest extent of the
+    bounding box, R the integer ``_decimate_cells`` finds (about two dozen counting passes, two int64 read back from each).  A
+    mesh within the budget comes back as it is, the same tensors.  The face count is not exactly monotone in R, so R is what
+    the search finds, not a proven maximum.  (One cell, R = 1, leaves no face: every budget >= 0 can be met.)"""
+    target_faces, max_cells = int(target_faces), int(max_cells)
+    if target_faces < 0 or max_cells < 1:
+        raise ValueError(f"need target_faces >= 0 and max_cells >= 1 (got {target_faces}, {max_cells})")
+    verts, faces = _mesh_tensors(mesh)
+    if faces.shape[0] <= target_faces:
+        return mesh
+    L = float((verts.max(0).values - verts.min(0).values).max())
+    if not (L > 0.0 and math.isfinite(L)):
+        raise ValueError(f"the mesh's bounding box has the longest extent {L}")
+    s = _Simplifier(verts, faces)
+    R = _decimate_cells(lambda r: s.count(_f32(L / r))[1], target_faces, max_cells)
+    return s.run(_f32(L / R))
+
+
 # ---- the whole path --------------------------------------------------------------------------------------------------
 
 def export_grid(means3D: torch.Tensor, scales: torch.Tensor, resolution: int):
@@ -221,12 +332,15 @@ def render_depth(means3D, rotations, scales, opacities, cams, fov, image_size: i
 
 @torch.no_grad()
 def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.Tensor, opacities: torch.Tensor, resolution: int = 256,
-                 n_views: int = 48, image_size: int = 1024, group: int = 8) -> Mesh:
+                 n_views: int = 48, image_size: int = 1024, group: int = 8, decimate_target: Optional[int] = None) -> Mesh:
     """World-space mesh of the surfels (rasterizer conventions: scales [P,3] with z = -1e10, opacities [P,1]).
 
     Renders ``n_views`` depth maps of ``image_size``^2 in groups of ``group`` views (one group's planes alive at a time), fuses
     them into a TSDF of ``resolution`` voxels along the longest axis, extracts the zero level set of the observed voxels and
-    removes small components.  For a posed mesh, warp the surfels with ``soar_amd.lbs`` first."""
+    removes small components.  For a posed mesh, warp the surfels with ``soar_amd.lbs`` first.
+
+    ``decimate_target``: None (the default) returns that mesh; a number runs ``decimate`` on it, the face budget of the
+    reference's ``extract_mesh(decimate_target=1e5)`` (by vertex clustering, not pymeshlab's edge collapse)."""
     _hip(means3D, "means3D")
     dev = means3D.device
     f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()
@@ -248,6 +362,8 @@ def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.T
     verts, faces = marching_cubes(field, 0.0, valid)
     del field, valid
     verts, faces = filter_components(verts, faces)
+    if decimate_target is not None:
+        verts, faces = decimate(Mesh(verts, faces), int(decimate_target))
     org = torch.tensor(origin, dtype=torch.float32, device=dev)
     return Mesh(verts * voxel + org, faces)
 
