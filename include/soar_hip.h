@@ -45,7 +45,8 @@ extern "C" {
  * debug bit 3): the head of the forward pass and the tail of the backward pass of all frames of a step as one kernel each;
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
- * soar_mesh_filter_bytes / _components, soar_mesh_simplify_bytes / _count / soar_mesh_simplify (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
+ * soar_mesh_filter_bytes / _components, soar_mesh_simplify_bytes / _count / soar_mesh_simplify, soar_mesh_attr_transfer[_bytes],
+ * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes] (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
@@ -862,6 +863,42 @@ int soar_mesh_simplify_count(int32_t V, int32_t F, const float *verts, const int
                              size_t workspace_bytes, int64_t *counts_host, void *stream);
 int soar_mesh_simplify(int32_t V, int32_t F, const float *verts, const int32_t *faces, float cell, void *workspace,
                        size_t workspace_bytes, float *verts_out, int32_t *faces_out, int64_t *counts_host, void *stream);
+/* Colour, smoothing and pruning of the exported mesh (mesh_attr.hip; DESIGN.md 9b, "Colour, smoothing, skinning" states the
+ * computation).  Every workspace is the caller's, 256-byte aligned, sized by the call's _bytes query.  A size, pointer or
+ * workspace that is refused is refused before anything is launched; the CONTENTS of idx and faces can only be judged on the
+ * device, so transfer, adjacency and prune refuse those after their launches, with their outputs written (see each call).
+ * soar_mesh_attr_transfer: verts [V][3] mesh vertices, points [N][3] surfel centres, colors [N][3], idx [V][K] the K nearest centres
+ *   of every vertex, 1 <= K <= 8, AS soar_lbs_knn_query WRITES THEM to knn_idx_out (ascending float32 squared distance, equal
+ *   distances among the K by ascending index; that order is kept.  Which of several points at exactly the K-th distance the
+ *   search keeps is its grid walk's matter, not the lower index: it admits only a strictly nearer point).  color_out [V][3] = clamp(float32 mean of the K colours added in rank order, 0, 1);
+ *   quality_out [V] = the squared distance to rank 0, (dx dx + dy dy) + dz dz in float32; d2_out [V][K] all K of them, or NULL.
+ *   Reads back how many vertices had an index outside [0, N) (one stream synchronisation) and refuses then.
+ * soar_mesh_adjacency: faces [F][3] -> CSR rows.  row_start [V + 1], nbr [6 F], border [V].  Row i holds, for every face at i, its
+ *   two other corners; the row is ascending, so a neighbour across an edge of m faces stands m times.  border[i] = 1 when some
+ *   neighbour stands exactly once (an edge of exactly one face).  Built by a sort of the 6 F entries: deterministic.  faces and nbr
+ *   may be NULL when F = 0.  A face naming a vertex outside [0, V) or one vertex twice is counted on the device and the call
+ *   refused at its end (its one stream synchronisation); the rows written then leave that face out and are not to be used.
+ * soar_mesh_smooth: `steps` Jacobi steps of the uniform umbrella operator over those rows: S = the sum of the positions of the row in
+ *   row order -- for a border vertex only of the neighbours that stand once --, P' = (P + S) / (n + 1), n the number of terms; n = 0
+ *   keeps P.  float32, no atomics: bit-reproducible.  verts_out [V][3] must not be verts; steps = 0 copies.  nnz = 6 F; row bounds
+ *   and entries outside their ranges are skipped.
+ * soar_mesh_prune: drops the vertices with quality > thresh (a NaN quality stays) and the faces that touch one; the kept keep their
+ *   order, faces are re-indexed, keep_out [<= V] = the old index of every new vertex, counts_host[2] = {vertices, faces} kept.
+ *   verts_out [<= V][3], faces_out [<= F][3].  One stream synchronisation, for the totals.
+ * All: 1 <= V <= 2^30, 0 <= F <= 2^28. */
+int soar_mesh_attr_transfer_bytes(int32_t V, int32_t K, size_t *bytes);
+int soar_mesh_attr_transfer(int32_t V, int32_t N, int32_t K, const float *verts, const float *points, const float *colors,
+                            const int32_t *idx, void *workspace, size_t workspace_bytes, float *color_out, float *quality_out,
+                            float *d2_out, void *stream);
+int soar_mesh_adjacency_bytes(int32_t V, int32_t F, size_t *bytes);
+int soar_mesh_adjacency(int32_t V, int32_t F, const int32_t *faces, void *workspace, size_t workspace_bytes, int32_t *row_start,
+                        int32_t *nbr, uint8_t *border, void *stream);
+int soar_mesh_smooth_bytes(int32_t V, size_t *bytes);
+int soar_mesh_smooth(int32_t V, int32_t nnz, const float *verts, const int32_t *row_start, const int32_t *nbr, const uint8_t *border,
+                     int32_t steps, void *workspace, size_t workspace_bytes, float *verts_out, void *stream);
+int soar_mesh_prune_bytes(int32_t V, int32_t F, size_t *bytes);
+int soar_mesh_prune(int32_t V, int32_t F, const float *verts, const int32_t *faces, const float *quality, float thresh, void *workspace,
+                    size_t workspace_bytes, float *verts_out, int32_t *faces_out, int32_t *keep_out, int64_t *counts_host, void *stream);
 
 /* ---- the surfels' attribute field (field.hip, soar_amd/field.py; DESIGN.md "Attribute field"): the reference's HashMLPSDFField
  * (TS/geometry/sdf_fields.py:41-219) with nerfstudio's torch HashEncoding / MLP semantics.  Two multiresolution hash encodings of

@@ -302,6 +302,15 @@ SIGNATURES = {
     "soar_mesh_simplify_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_mesh_simplify_count": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
     "soar_mesh_simplify": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, _vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_attr_transfer_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_attr_transfer": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "soar_mesh_adjacency_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_adjacency": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "soar_mesh_smooth_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_smooth": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_size_t, _vp, _vp]),
+    "soar_mesh_prune_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_prune": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, C.c_size_t, _vp, _vp, _vp,
+                                  C.POINTER(C.c_int64), _vp]),
     "soar_field_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_field_forward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp]),
     "soar_field_backward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp, C.c_size_t, _vp]),

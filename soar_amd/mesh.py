@@ -16,6 +16,14 @@ sphere, the depth is fused into a truncated signed-distance volume and its zero 
   with the same purpose: no output is comparable bit for bit with pymeshlab's.
 * ``extract_mesh``: the whole path, from the rasterizer's inputs to a world-space ``Mesh``.  A POSED mesh: warp the canonical
   surfels first (``soar_amd.lbs.lbs_warp(xyz, rot, weights, joint_mats)``) and pass the warped positions and rotations.
+* ``vertex_attributes`` / ``prune_by_quality`` / ``adjacency`` / ``smooth`` (csrc/mesh_attr.hip): the colour of a vertex from its
+  k nearest surfels, the squared distance to the nearest as its quality, pruning by that quality and Laplacian smoothing -- the
+  reference's ``poisson_mesh`` refinement (utils/general_utils.py:269-302) without the hole closing ("Colour,
+  smoothing, skinning").
+* ``skin_weights`` / ``pose_mesh``: SMPL-X blend weights of the mesh vertices (the rule ``query_weights_smpl`` applies to surfels)
+  and the mesh in any number of poses with the existing warp and normal kernels: one export, many frames.
+* ``export_avatar``: all of it in the reference's order, from canonical surfels to mesh, colours, quality, normals and weights;
+  ``save_obj`` / ``save_ply`` / ``save_skinned`` write them.
 
 Every output is deterministic: the same input gives the same tensors bit for bit.  HIP only; there is no CPU path.
 """
@@ -337,7 +345,8 @@ def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.T
 
     Renders ``n_views`` depth maps of ``image_size``^2 in groups of ``group`` views (one group's planes alive at a time), fuses
     them into a TSDF of ``resolution`` voxels along the longest axis, extracts the zero level set of the observed voxels and
-    removes small components.  For a posed mesh, warp the surfels with ``soar_amd.lbs`` first.
+    removes small components.  For a posed mesh, warp the surfels with ``soar_amd.lbs`` first -- or, for many poses of one
+    avatar, export the canonical surfels once (``export_avatar``) and pose the mesh (``pose_mesh``).
 
     ``decimate_target``: None (the default) returns that mesh; a number runs ``decimate`` on it, the face budget of the
     reference's ``extract_mesh(decimate_target=1e5)`` (by vertex clustering, not pymeshlab's edge collapse)."""
@@ -368,10 +377,348 @@ def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.T
     return Mesh(verts * voxel + org, faces)
 
 
-def save_obj(path: str, mesh: Mesh) -> None:
-    """Wavefront OBJ: ``v x y z`` lines (float32 round-trip precision), then ``f a b c`` lines with 1-based indices."""
+# ---- colour, quality, smoothing (csrc/mesh_attr.hip) -------------------------------------------------------------------------
+
+ATTR_K, ATTR_MAX_K = 4, 8    # the reference's knn_points(K=4) (utils/general_utils.py:270); the kernel's upper bound
+SMOOTH_STEPS = 3             # apply_coord_laplacian_smoothing(stepsmoothnum=3) (:301)
+
+
+def _bytes(fn, name: str, *sizes) -> int:
+    nb = C.c_size_t(0)
+    check(fn(*sizes, C.byref(nb)), name)
+    return nb.value
+
+
+@torch.no_grad()
+def vertex_attributes(vertices: torch.Tensor, means3D: torch.Tensor, colors: torch.Tensor, k: int = ATTR_K
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Colour and quality of mesh vertices [V,3] from the surfels (centres ``means3D`` [N,3], ``colors`` [N,3]) ->
+    ``(color [V,3], quality [V], idx [V,k])``.
+
+    ``idx``: the k nearest centres of every vertex (1 <= k <= 8, k <= N), from the exact grid search that also skins the surfels
+    (``soar_lbs_knn_build_grid`` / ``_query``), nearest first, ties to the lower index.  ``color``: the float32 mean of their colours
+    added in that order, clamped to [0,1].  ``quality``: the SQUARED distance to the nearest one, as pytorch3d's ``knn_points``
+    returns it and the reference thresholds it (utils/general_utils.py:270-292)."""
+    _hip(vertices, "vertices")
+    _hip(means3D, "means3D")
+    _hip(colors, "colors")
+    dev = vertices.device
+    f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    v, pts, col = f32(vertices), f32(means3D), f32(colors)
+    k = int(k)
+    V, N = int(v.shape[0]), int(pts.shape[0])
+    if v.dim() != 2 or v.shape[1] != 3 or pts.dim() != 2 or pts.shape[1] != 3 or col.shape != pts.shape:
+        raise ValueError(f"need vertices [V,3], means3D [N,3] and colors [N,3] (got {tuple(v.shape)}, {tuple(pts.shape)}, {tuple(col.shape)})")
+    if not (1 <= k <= ATTR_MAX_K and k <= N):
+        raise ValueError(f"need 1 <= k <= min({ATTR_MAX_K}, N) (k={k}, N={N})")
+    color = torch.empty(V, 3, device=dev)
+    quality = torch.empty(V, device=dev)
+    idx = torch.empty(V, k, dtype=torch.int32, device=dev)
+    if V == 0:
+        return color, quality, idx
+    L = hip_lib.lib()
+    grid = _workspace(_bytes(L.soar_lbs_knn_grid_bytes, "soar_lbs_knn_grid_bytes", N), dev)
+    qws = _workspace(_bytes(L.soar_lbs_knn_query_bytes, "soar_lbs_knn_query_bytes", V), dev)
+    tws = _workspace(_bytes(L.soar_mesh_attr_transfer_bytes, "soar_mesh_attr_transfer_bytes", V, k), dev)
+    blend = torch.empty(V, 3, device=dev)      # the query's own output (the inverse-distance blend of the colours): not used
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        # the colours ride as the grid's "skinning rows" (J = 3): the query needs some, and only its indices are kept
+        check(L.soar_lbs_knn_build_grid(pts.data_ptr(), N, col.data_ptr(), 3, grid.data_ptr(), st), "soar_lbs_knn_build_grid")
+        check(L.soar_lbs_knn_query(grid.data_ptr(), N, col.data_ptr(), 3, v.data_ptr(), V, k, blend.data_ptr(), idx.data_ptr(),
+                                   qws.data_ptr(), qws.numel(), st), "soar_lbs_knn_query")
+        check(L.soar_mesh_attr_transfer(V, N, k, v.data_ptr(), pts.data_ptr(), col.data_ptr(), idx.data_ptr(), tws.data_ptr(), tws.numel(),
+                                        color.data_ptr(), quality.data_ptr(), None, st), "soar_mesh_attr_transfer")
+    return color, quality, idx
+
+
+@torch.no_grad()
+def prune_by_quality(mesh: Mesh, quality: torch.Tensor, thresh: float) -> Tuple[Mesh, torch.Tensor]:
+    """Drop the vertices with ``quality > thresh`` and every face that touches one (the reference's
+    ``compute_selection_by_condition_per_vertex("q>thrsh")`` + ``meshing_remove_selected_vertices``) -> ``(Mesh, keep)``, ``keep``
+    [V'] int32 the old index of every vertex left.  Kept vertices and faces stay in their order.  Holes are not closed."""
+    verts, faces = _mesh_tensors(mesh)
+    _hip(quality, "quality")
+    dev = verts.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    q = quality.detach().to(dev, torch.float32).contiguous()
+    if q.shape != (V,):
+        raise ValueError(f"quality must be [{V}] (got {tuple(q.shape)})")
+    thresh = float(thresh)
+    if math.isnan(thresh):
+        raise ValueError("thresh is not a number")
+    if V == 0:
+        return Mesh(verts, faces), torch.zeros(0, dtype=torch.int32, device=dev)
+    L = hip_lib.lib()
+    nb = _bytes(L.soar_mesh_prune_bytes, "soar_mesh_prune_bytes", V, F)
+    ws = _workspace(nb, dev)
+    vo = torch.empty(V, 3, device=dev)
+    fo = torch.empty(max(F, 1), 3, dtype=torch.int32, device=dev)
+    keep = torch.empty(V, dtype=torch.int32, device=dev)
+    counts = (C.c_int64 * 2)()
+    with torch.cuda.device(dev):
+        check(L.soar_mesh_prune(V, F, verts.data_ptr(), faces.data_ptr() if F else None, q.data_ptr(), thresh, ws.data_ptr(), nb,
+                                vo.data_ptr(), fo.data_ptr(), keep.data_ptr(), counts, _stream(dev)), "soar_mesh_prune")
+    nv, nf = int(counts[0]), int(counts[1])
+    return Mesh(vo[:nv].clone(), fo[:nf].clone()), keep[:nv].clone()
+
+
+@torch.no_grad()
+def adjacency(mesh: Mesh) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Vertex adjacency in CSR form -> ``(row_start [V+1] int32, nbr [6F] int32, border [V] bool)``.  Row i holds the two other
+    corners of every face at vertex i, ascending: a neighbour across an edge of m faces stands m times.  ``border``: the vertex has
+    an edge that belongs to exactly one face.  A face that names a vertex twice is refused."""
+    verts, faces = _mesh_tensors(mesh)
+    dev = verts.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    row_start = torch.zeros(V + 1, dtype=torch.int32, device=dev)
+    nbr = torch.empty(6 * F, dtype=torch.int32, device=dev)
+    border = torch.zeros(V, dtype=torch.uint8, device=dev)
+    if V > 0:
+        L = hip_lib.lib()
+        nb = _bytes(L.soar_mesh_adjacency_bytes, "soar_mesh_adjacency_bytes", V, F)
+        ws = _workspace(nb, dev)
+        with torch.cuda.device(dev):
+            check(L.soar_mesh_adjacency(V, F, faces.data_ptr() if F else None, ws.data_ptr(), nb, row_start.data_ptr(),
+                                        nbr.data_ptr() if F else None, border.data_ptr(), _stream(dev)), "soar_mesh_adjacency")
+    return row_start, nbr, border.bool()
+
+
+@torch.no_grad()
+def smooth(mesh: Mesh, steps: int = SMOOTH_STEPS) -> Mesh:
+    """``steps`` Jacobi steps of Laplacian smoothing with the uniform umbrella operator, the role of the reference's
+    ``apply_coord_laplacian_smoothing(stepsmoothnum=3, boundary=True)`` ("Colour, smoothing, skinning" states the
+    operator; it is this project's definition, not a bit copy of pymeshlab's).  A vertex moves to ``(P + S) / (n + 1)``: S sums, over every face at the vertex,
+    that face's two other corners; a border vertex sums only its neighbours across border edges, so a border slides along itself;
+    a vertex without neighbours stays.  Faces are unchanged.  Deterministic bit for bit."""
+    verts, faces = _mesh_tensors(mesh)
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"steps must be >= 0 (got {steps})")
+    V = int(verts.shape[0])
+    if V == 0 or steps == 0:
+        return Mesh(verts.clone(), faces)
+    dev = verts.device
+    row_start, nbr, border = adjacency(Mesh(verts, faces))
+    border = border.to(torch.uint8)
+    L = hip_lib.lib()
+    nb = _bytes(L.soar_mesh_smooth_bytes, "soar_mesh_smooth_bytes", V)
+    ws = _workspace(nb, dev)
+    out = torch.empty_like(verts)
+    with torch.cuda.device(dev):
+        check(L.soar_mesh_smooth(V, int(nbr.shape[0]), verts.data_ptr(), row_start.data_ptr(), nbr.data_ptr() if nbr.numel() else None,
+                                 border.data_ptr(), steps, ws.data_ptr(), nb, out.data_ptr(), _stream(dev)), "soar_mesh_smooth")
+    return Mesh(out, faces)
+
+
+# ---- the rig -------------------------------------------------------------------------------------------------------------------
+
+@torch.no_grad()
+def skin_weights(mesh: Mesh, smpl_vertices: torch.Tensor, lbs_weights: torch.Tensor, K: int = 30) -> torch.Tensor:
+    """Blend weights [V,J] of the mesh vertices: ``soar_amd.lbs.knn_blend_weights`` on them, the inverse-distance blend of the
+    skinning rows of the K nearest canonical SMPL-X vertices that ``query_weights_smpl`` gives the surfels
+    (TS/utils/smpl.py:618-637).  The mesh must be in the canonical space of ``smpl_vertices`` [Vs,3] / ``lbs_weights`` [Vs,J]."""
+    from . import lbs
+    verts, _ = _mesh_tensors(mesh)
+    _hip(smpl_vertices, "smpl_vertices")
+    return lbs.knn_blend_weights(verts, smpl_vertices, lbs_weights, K=int(K))
+
+
+@torch.no_grad()
+def pose_mesh(mesh: Mesh, weights: torch.Tensor, joint_mats: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The canonical mesh in B poses -> ``(vertices [B,V,3], normals [B,V,3])``.  ``weights`` [V,J] from ``skin_weights``,
+    ``joint_mats`` [B,J,4,4] (cano2live).  The positions are those of ``soar_lbs_warp_forward`` pose by pose (one batched launch,
+    unit quaternions for the rotations it also warps); the normals are ``soar_mesh_vertex_normals`` (angle-weighted) of every
+    posed mesh.  The faces do not change."""
+    from . import body
+    verts, faces = _mesh_tensors(mesh)
+    _hip(weights, "weights")
+    _hip(joint_mats, "joint_mats")
+    dev = verts.device
+    V = int(verts.shape[0])
+    w = weights.detach().to(dev, torch.float32).contiguous()
+    A = joint_mats.detach().to(dev, torch.float32).contiguous()
+    if A.dim() != 4 or A.shape[2:] != (4, 4) or w.shape != (V, A.shape[1]):
+        raise ValueError(f"need weights [V,J] and joint_mats [B,J,4,4] (got {tuple(w.shape)}, {tuple(A.shape)}; V={V})")
+    B, J = int(A.shape[0]), int(A.shape[1])
+    out = torch.empty(B, V, 3, device=dev)
+    normals = torch.zeros(B, V, 3, device=dev)
+    if B == 0 or V == 0:
+        return out, normals
+    rot = torch.zeros(V, 4, device=dev)
+    rot[:, 0] = 1.0
+    rot_out = torch.empty(B, V, 4, device=dev)
+    with torch.cuda.device(dev):
+        check(hip_lib.lib().soar_lbs_warp_forward_batch(verts.data_ptr(), rot.data_ptr(), w.data_ptr(), A.data_ptr(), B, V, J, out.data_ptr(),
+                                                        rot_out.data_ptr(), _stream(dev)), "soar_lbs_warp_forward_batch")
+    for b in range(B):
+        normals[b] = body.vertex_normals(out[b], faces)
+    return out, normals
+
+
+def _surfel_tensors(model_or_tensors, use_explicit: bool):
+    """-> (means3D, rotations, scales [P,3], opacities, colors) as the renderer hands them to the rasterizer.
+
+    A 5-tuple or a dict with those names is taken as it is.  Anything else is a ``GaussianSurfelModel``, read as
+    ``renderer/diff_gaussian.py`` reads it: scales [P,1] and colours [P,3] are the attribute field's ``scales`` and ``shs`` at the
+    surfel centres, or, with ``use_explicit``, the leaves ``get_scaling`` / ``get_colors``; the scale is repeated to three columns
+    and the third set to -1e10, the rasterizer's flat axis."""
+    m = model_or_tensors
+    if isinstance(m, dict):
+        return tuple(m[k] for k in ("means3D", "rotations", "scales", "opacities", "colors"))
+    if isinstance(m, (tuple, list)):
+        if len(m) != 5:
+            raise ValueError("need (means3D, rotations, scales, opacities, colors)")
+        return tuple(m)
+    xyz = m.get_xyz
+    _hip(xyz, "get_xyz")
+    if use_explicit:
+        scale, colors = m.get_scaling, m.get_colors
+    else:
+        if getattr(m, "attribute_field", None) is None:
+            raise ValueError("the model has no attribute_field: pass use_explicit=True to export its explicit scales and colours")
+        fields = m.attribute_field(xyz.detach())
+        scale, colors = fields["scales"], fields["shs"]
+    if scale.dim() != 2 or scale.shape != (xyz.shape[0], 1):
+        raise ValueError(f"the model's scale must be [{int(xyz.shape[0])},1] (got {tuple(scale.shape)})")
+    scales = scale.detach().repeat(1, 3)
+    scales[:, 2] = -1e10
+    return xyz, m.get_rotation, scales, m.get_opacity, colors
+
+
+def _check_surfels(means3D, rotations, scales, opacities, colors) -> None:
+    """The rasterizer reads these buffers by the surfel count alone: every shape is checked before anything is launched."""
+    P = int(means3D.shape[0]) if means3D.dim() == 2 else -1
+    want = (("means3D", means3D, ((P, 3),)), ("rotations", rotations, ((P, 4),)), ("scales", scales, ((P, 3),)),
+            ("opacities", opacities, ((P, 1), (P,))), ("colors", colors, ((P, 3),)))
+    for name, t, shapes in want:
+        if not isinstance(t, torch.Tensor) or P < 1 or tuple(t.shape) not in shapes:
+            raise ValueError(f"{name} must be {' or '.join(str(list(s)) for s in shapes)} with P >= 1 "
+                             f"(got {tuple(getattr(t, 'shape', ()))}; P is means3D's row count)")
+
+
+@torch.no_grad()
+def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: torch.Tensor, resolution: int = 256,
+                  decimate_target: Optional[int] = DECIMATE_TARGET, quality_thresh: Optional[float] = None,
+                  smooth_steps: int = SMOOTH_STEPS, k: int = ATTR_K, K: int = 30, n_views: int = 48, image_size: int = 1024,
+                  group: int = 8, use_explicit: bool = False) -> dict:
+    """A coloured, animatable mesh from CANONICAL-space surfels in one call -> ``dict(mesh, color, quality, normals, weights)``.
+
+    ``model_or_tensors``: the tuple ``(means3D [P,3], rotations [P,4], scales [P,3] with z = -1e10, opacities [P,1], colors [P,3]
+    in [0,1])`` (or a dict with those names), or a ``GaussianSurfelModel``.  Of a model, scales and colours are what its renderer
+    draws: the attribute field's outputs at the surfel centres, as every SOAR configuration has it (``use_explicit: false``), or
+    the explicit leaves with ``use_explicit=True`` (the renderer's switch of that name).  Any other shape is refused.
+
+    The steps in the reference's order (utils/general_utils.py:263-302): ``extract_mesh`` (with ``decimate_target``),
+    ``vertex_attributes``, ``prune_by_quality`` when ``quality_thresh`` is given, ``smooth``, then ``vertex_attributes`` again on
+    the moved vertices (the colours and qualities returned), angle-weighted vertex normals and ``skin_weights`` against
+    ``smpl_vertices`` / ``lbs_weights``.  ``pose_mesh(out["mesh"], out["weights"], joint_mats)`` then gives any pose."""
+    from . import body
+    means3D, rotations, scales, opacities, colors = _surfel_tensors(model_or_tensors, bool(use_explicit))
+    _check_surfels(means3D, rotations, scales, opacities, colors)
+    for t, name in ((means3D, "means3D"), (rotations, "rotations"), (scales, "scales"), (opacities, "opacities"), (colors, "colors")):
+        _hip(t, name)
+    dev = means3D.device
+    f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    means3D, colors = f32(means3D), f32(colors)
+    m = extract_mesh(means3D, rotations, scales, opacities, resolution=resolution, n_views=n_views, image_size=image_size, group=group,
+                     decimate_target=decimate_target)
+    if quality_thresh is not None:
+        _, quality, _ = vertex_attributes(m.vertices, means3D, colors, k)
+        m, _ = prune_by_quality(m, quality, quality_thresh)
+    m = smooth(m, smooth_steps)
+    color, quality, _ = vertex_attributes(m.vertices, means3D, colors, k)
+    normals = body.vertex_normals(m.vertices, m.faces)
+    weights = skin_weights(m, smpl_vertices.to(dev), lbs_weights.to(dev), K)
+    return dict(mesh=m, color=color, quality=quality, normals=normals, weights=weights)
+
+
+# ---- writers -------------------------------------------------------------------------------------------------------------------
+
+def _host(t: Optional[torch.Tensor], rows: int, cols: Optional[int], name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    h = t.detach().cpu().to(torch.float32)
+    if h.shape != ((rows,) if cols is None else (rows, cols)):
+        raise ValueError(f"{name} must be [{rows}{'' if cols is None else ',' + str(cols)}] (got {tuple(h.shape)})")
+    return h.contiguous()
+
+
+def save_obj(path: str, mesh: Mesh, colors: Optional[torch.Tensor] = None) -> None:
+    """Wavefront OBJ: ``v x y z`` lines (float32 round-trip precision), then ``f a b c`` lines with 1-based indices.  With
+    ``colors`` [V,3] the vertex lines are ``v x y z r g b``, the extension MeshLab reads and the reference's ``save_obj_mesh``
+    writes."""
     v = mesh.vertices.detach().cpu().to(torch.float32).tolist()
     f = mesh.faces.detach().cpu().to(torch.int64).tolist()
+    c = _host(colors, len(v), 3, "colors")
     with open(path, "w") as fh:
-        fh.writelines(f"v {a:.9g} {b:.9g} {c:.9g}\n" for a, b, c in v)
+        if c is None:
+            fh.writelines(f"v {a:.9g} {b:.9g} {c:.9g}\n" for a, b, c in v)
+        else:
+            fh.writelines(f"v {x:.9g} {y:.9g} {z:.9g} {r:.9g} {g:.9g} {b:.9g}\n" for (x, y, z), (r, g, b) in zip(v, c.tolist()))
         fh.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in f)
+
+
+def save_ply(path: str, mesh: Mesh, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+             quality: Optional[torch.Tensor] = None) -> None:
+    """PLY, ``binary_little_endian 1.0``.  Vertex: float ``x y z``, then float ``nx ny nz`` with ``normals`` [V,3], uchar ``red green
+    blue`` with ``colors`` [V,3] (floor(255 c + 0.5) of the colour clamped to [0,1]), float ``quality`` with ``quality`` [V].
+    Face: ``list uchar int vertex_indices``."""
+    import numpy as np
+    v = _host(mesh.vertices, int(mesh.vertices.shape[0]), 3, "vertices")
+    V = int(v.shape[0])
+    f = mesh.faces.detach().cpu().to(torch.int32).contiguous().numpy()
+    n, c, q = _host(normals, V, 3, "normals"), _host(colors, V, 3, "colors"), _host(quality, V, None, "quality")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if n is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if c is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if q is not None:
+        fields += [("quality", "<f4")]
+    rec = np.zeros(V, dtype=np.dtype(fields))
+    for k, name in enumerate("xyz"):
+        rec[name] = v[:, k].numpy()
+    if n is not None:
+        for k, name in enumerate(("nx", "ny", "nz")):
+            rec[name] = n[:, k].numpy()
+    if c is not None:
+        c8 = torch.floor(c.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).numpy()
+        for k, name in enumerate(("red", "green", "blue")):
+            rec[name] = c8[:, k]
+    if q is not None:
+        rec["quality"] = q.numpy()
+    frec = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    frec["n"] = 3
+    frec["v"] = f
+    kinds = {"<f4": "float", "u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {V}"]
+    header += [f"property {kinds[t]} {name}" for name, t in fields]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def save_skinned(path_npz: str, mesh: Mesh, weights: torch.Tensor, colors: torch.Tensor) -> None:
+    """The rigged asset as an uncompressed ``.npz`` that ``numpy.load`` reads: ``vertices`` [V,3] float32, ``faces`` [F,3] int32,
+    ``weights`` [V,J] float32, ``colors`` [V,3] float32.  ``pose_mesh`` (or any linear-blend skinning) poses it with [J,4,4] joint
+    transforms.  The archive's members carry a fixed date (``numpy.savez`` stamps the time of writing): the same asset gives the
+    same bytes."""
+    import io
+    import zipfile
+
+    import numpy as np
+    V = int(mesh.vertices.shape[0])
+    w = weights.detach().cpu().to(torch.float32).contiguous()
+    if w.dim() != 2 or w.shape[0] != V:
+        raise ValueError(f"weights must be [{V},J] (got {tuple(w.shape)})")
+    arrays = dict(vertices=_host(mesh.vertices, V, 3, "vertices").numpy(),
+                  faces=mesh.faces.detach().cpu().to(torch.int32).contiguous().numpy(), weights=w.numpy(),
+                  colors=_host(colors, V, 3, "colors").numpy())
+    with zipfile.ZipFile(path_npz, "w", zipfile.ZIP_STORED) as zf:
+        for name, arr in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arr), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue())
