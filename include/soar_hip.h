@@ -46,7 +46,7 @@ extern "C" {
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
  * soar_mesh_filter_bytes / _components, soar_mesh_simplify_bytes / _count / soar_mesh_simplify, soar_mesh_attr_transfer[_bytes],
- * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes] (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
+ * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes], soar_mesh_close_holes[_bytes] (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
@@ -899,6 +899,25 @@ int soar_mesh_smooth(int32_t V, int32_t nnz, const float *verts, const int32_t *
 int soar_mesh_prune_bytes(int32_t V, int32_t F, size_t *bytes);
 int soar_mesh_prune(int32_t V, int32_t F, const float *verts, const int32_t *faces, const float *quality, float thresh, void *workspace,
                     size_t workspace_bytes, float *verts_out, int32_t *faces_out, int32_t *keep_out, int64_t *counts_host, void *stream);
+/* Hole closing of the exported mesh (mesh_holes.hip; DESIGN.md 9b, "Closing holes" states the definition: a deterministic loop
+ * search with a centroid fan, NOT MeshLab's minimum-weight ear cutting).  Half-edge h = 3 f + c runs faces[f][c] ->
+ * faces[f][(c + 1) % 3]; it is a border when its undirected edge occurs once among the 3 F half-edges (soar_mesh_adjacency's rule).
+ * A vertex is simple when one border half-edge leaves it and one arrives.  A loop of 3 <= n <= max_hole_edges border half-edges
+ * whose vertices are all simple and which do not all come from one face is closed: n = 3 by one face, n >= 4 by one new vertex (the
+ * mean of the ring's vertices, added in float64 in ring order from the loop's least half-edge id, rounded once) and n faces, every
+ * new face with its border edge reversed.  Anything else is left as it is.
+ * soar_mesh_close_holes: verts_out [V + (3 F) / 4][3] and faces_out [4 F][3] hold the V vertices and F faces unchanged, then the new
+ *   ones loop by loop in ascending order of the loops' least half-edge ids; loop_edges_out [F] the n of every closed loop in that
+ *   order; counts_host[4] = {vertices, faces, loops closed, border half-edges still open}.  The outputs must not be the inputs.
+ *   1 <= V <= 2^30, 0 <= F <= 2^28, 3 <= max_hole_edges <= 65535; the workspace is the caller's, 256-byte aligned, sized by
+ *   soar_mesh_close_holes_bytes; sizes, pointers and workspaces that are refused are refused before any launch.  F = 0 copies the
+ *   vertices (faces, faces_out and loop_edges_out may then be NULL).  A face naming a vertex outside [0, V) or one vertex twice is
+ *   counted on the device and the call refused at its end (the one stream synchronisation, which also reads the totals); the outputs
+ *   written then are not to be used.  Integer atomics only: bit-reproducible. */
+int soar_mesh_close_holes_bytes(int32_t V, int32_t F, size_t *bytes);
+int soar_mesh_close_holes(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t max_hole_edges, void *workspace,
+                          size_t workspace_bytes, float *verts_out, int32_t *faces_out, int32_t *loop_edges_out, int64_t *counts_host,
+                          void *stream);
 
 /* ---- the surfels' attribute field (field.hip, soar_amd/field.py; DESIGN.md "Attribute field"): the reference's HashMLPSDFField
  * (TS/geometry/sdf_fields.py:41-219) with nerfstudio's torch HashEncoding / MLP semantics.  Two multiresolution hash encodings of

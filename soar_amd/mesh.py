@@ -18,8 +18,10 @@ sphere, the depth is fused into a truncated signed-distance volume and its zero 
   surfels first (``soar_amd.lbs.lbs_warp(xyz, rot, weights, joint_mats)``) and pass the warped positions and rotations.
 * ``vertex_attributes`` / ``prune_by_quality`` / ``adjacency`` / ``smooth`` (csrc/mesh_attr.hip): the colour of a vertex from its
   k nearest surfels, the squared distance to the nearest as its quality, pruning by that quality and Laplacian smoothing -- the
-  reference's ``poisson_mesh`` refinement (utils/general_utils.py:269-302) without the hole closing ("Colour,
-  smoothing, skinning").
+  reference's ``poisson_mesh`` refinement (utils/general_utils.py:269-302) ("Colour, smoothing, skinning").
+* ``close_holes`` / ``open_border_edges`` (csrc/mesh_holes.hip): caps every simple border loop of at most ``max_hole_edges`` edges
+  with a fan around its centroid, the place of ``meshing_close_holes(maxholesize=300)`` in that refinement -- a deterministic loop
+  search, not MeshLab's ear cutting ("Closing holes") --, and the number of border edges of a mesh.
 * ``skin_weights`` / ``pose_mesh``: SMPL-X blend weights of the mesh vertices (the rule ``query_weights_smpl`` applies to surfels)
   and the mesh in any number of poses with the existing warp and normal kernels: one export, many frames.
 * ``export_avatar``: all of it in the reference's order, from canonical surfels to mesh, colours, quality, normals and weights;
@@ -436,7 +438,8 @@ def vertex_attributes(vertices: torch.Tensor, means3D: torch.Tensor, colors: tor
 def prune_by_quality(mesh: Mesh, quality: torch.Tensor, thresh: float) -> Tuple[Mesh, torch.Tensor]:
     """Drop the vertices with ``quality > thresh`` and every face that touches one (the reference's
     ``compute_selection_by_condition_per_vertex("q>thrsh")`` + ``meshing_remove_selected_vertices``) -> ``(Mesh, keep)``, ``keep``
-    [V'] int32 the old index of every vertex left.  Kept vertices and faces stay in their order.  Holes are not closed."""
+    [V'] int32 the old index of every vertex left.  Kept vertices and faces stay in their order.  The holes this leaves are
+    ``close_holes``' to close."""
     verts, faces = _mesh_tensors(mesh)
     _hip(quality, "quality")
     dev = verts.device
@@ -509,6 +512,62 @@ def smooth(mesh: Mesh, steps: int = SMOOTH_STEPS) -> Mesh:
         check(L.soar_mesh_smooth(V, int(nbr.shape[0]), verts.data_ptr(), row_start.data_ptr(), nbr.data_ptr() if nbr.numel() else None,
                                  border.data_ptr(), steps, ws.data_ptr(), nb, out.data_ptr(), _stream(dev)), "soar_mesh_smooth")
     return Mesh(out, faces)
+
+
+# ---- hole closing (csrc/mesh_holes.hip) -----------------------------------------------------------------------------------------
+
+MAX_HOLE_EDGES = 300         # meshing_close_holes(maxholesize=300) (utils/general_utils.py:296)
+HOLE_EDGES_RANGE = (3, 65535)
+
+
+def _close_holes(verts: torch.Tensor, faces: torch.Tensor, max_hole_edges: int):
+    """-> (verts_out, faces_out, loop_edges, counts[4]) of soar_mesh_close_holes, the outputs at their full capacity"""
+    dev = verts.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    L = hip_lib.lib()
+    nb = _bytes(L.soar_mesh_close_holes_bytes, "soar_mesh_close_holes_bytes", V, F)
+    ws = _workspace(nb, dev)
+    vo = torch.empty(V + (3 * F) // 4, 3, device=dev)
+    fo = torch.empty(max(4 * F, 1), 3, dtype=torch.int32, device=dev)
+    loops = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
+    counts = (C.c_int64 * 4)()
+    with torch.cuda.device(dev):
+        check(L.soar_mesh_close_holes(V, F, verts.data_ptr(), faces.data_ptr() if F else None, int(max_hole_edges), ws.data_ptr(), nb,
+                                      vo.data_ptr(), fo.data_ptr(), loops.data_ptr(), counts, _stream(dev)), "soar_mesh_close_holes")
+    return vo, fo, loops, [int(c) for c in counts]
+
+
+@torch.no_grad()
+def close_holes(mesh: Mesh, max_hole_edges: int = MAX_HOLE_EDGES) -> Tuple[Mesh, torch.Tensor]:
+    """Cap the holes of at most ``max_hole_edges`` border edges -> ``(Mesh, closed)``, ``closed`` [L] int32 the edge count of every
+    loop that was closed, in output order.  The place of the reference's ``meshing_close_holes(maxholesize=300)``; the definition is
+    this project's ("Closing holes"), a loop search with a centroid fan and not MeshLab's minimum-weight ear cutting.
+
+    A border edge belongs to exactly one face (``adjacency``'s rule).  A border loop is closed when it has 3 .. ``max_hole_edges``
+    edges, every vertex on it has exactly one border edge arriving and one leaving (two holes that touch in a vertex stay open, as
+    MeshLab leaves non-manifold borders) and it is not the rim of a lone triangle.  A loop of three gets one face; a longer one a
+    new vertex at the mean of its ring (summed in float64 in ring order) and one face per edge, each with the border edge reversed,
+    so the patch continues the surface's orientation.  The rim of a small open component is a loop like any other.  The input's
+    vertices and faces come first, unchanged; new vertices and faces follow loop by loop.  Deterministic bit for bit."""
+    max_hole_edges = int(max_hole_edges)
+    if not HOLE_EDGES_RANGE[0] <= max_hole_edges <= HOLE_EDGES_RANGE[1]:
+        raise ValueError(f"need {HOLE_EDGES_RANGE[0]} <= max_hole_edges <= {HOLE_EDGES_RANGE[1]} (got {max_hole_edges})")
+    verts, faces = _mesh_tensors(mesh)
+    if verts.shape[0] == 0:
+        return Mesh(verts.clone(), faces.clone()), torch.zeros(0, dtype=torch.int32, device=verts.device)
+    vo, fo, loops, (nv, nf, nl, _) = _close_holes(verts, faces, max_hole_edges)
+    return Mesh(vo[:nv].clone(), fo[:nf].clone()), loops[:nl].clone()
+
+
+@torch.no_grad()
+def open_border_edges(mesh: Mesh) -> int:
+    """The number of border edges (edges of exactly one face) of ``mesh``: 0 for a watertight one.  ``soar_mesh_close_holes``' fourth
+    count at the smallest ``max_hole_edges`` with the loops it closes added back, so nothing new is computed for it."""
+    verts, faces = _mesh_tensors(mesh)
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        return 0
+    _, _, loops, (_, _, nl, still_open) = _close_holes(verts, faces, HOLE_EDGES_RANGE[0])
+    return still_open + 3 * nl
 
 
 # ---- the rig -------------------------------------------------------------------------------------------------------------------
@@ -601,7 +660,7 @@ def _check_surfels(means3D, rotations, scales, opacities, colors) -> None:
 def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: torch.Tensor, resolution: int = 256,
                   decimate_target: Optional[int] = DECIMATE_TARGET, quality_thresh: Optional[float] = None,
                   smooth_steps: int = SMOOTH_STEPS, k: int = ATTR_K, K: int = 30, n_views: int = 48, image_size: int = 1024,
-                  group: int = 8, use_explicit: bool = False) -> dict:
+                  group: int = 8, use_explicit: bool = False, max_hole_edges: Optional[int] = None) -> dict:
     """A coloured, animatable mesh from CANONICAL-space surfels in one call -> ``dict(mesh, color, quality, normals, weights)``.
 
     ``model_or_tensors``: the tuple ``(means3D [P,3], rotations [P,4], scales [P,3] with z = -1e10, opacities [P,1], colors [P,3]
@@ -610,9 +669,14 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
     the explicit leaves with ``use_explicit=True`` (the renderer's switch of that name).  Any other shape is refused.
 
     The steps in the reference's order (utils/general_utils.py:263-302): ``extract_mesh`` (with ``decimate_target``),
-    ``vertex_attributes``, ``prune_by_quality`` when ``quality_thresh`` is given, ``smooth``, then ``vertex_attributes`` again on
-    the moved vertices (the colours and qualities returned), angle-weighted vertex normals and ``skin_weights`` against
-    ``smpl_vertices`` / ``lbs_weights``.  ``pose_mesh(out["mesh"], out["weights"], joint_mats)`` then gives any pose."""
+    ``vertex_attributes``, ``prune_by_quality`` when ``quality_thresh`` is given, ``close_holes`` when ``max_hole_edges`` is given,
+    ``smooth``, then ``vertex_attributes`` again on the moved vertices (the colours and qualities returned), angle-weighted vertex
+    normals and ``skin_weights`` against ``smpl_vertices`` / ``lbs_weights``.  ``pose_mesh(out["mesh"], out["weights"], joint_mats)``
+    then gives any pose.
+
+    ``max_hole_edges``: None (the default) closes nothing and returns exactly what this function returned before it had the
+    argument.  A number closes the holes of at most that many edges that the pruning (or the extraction) left, before the smoothing,
+    and the dict gains ``closed`` (``close_holes``' second result); 300 is recommended, the reference's ``maxholesize``."""
     from . import body
     means3D, rotations, scales, opacities, colors = _surfel_tensors(model_or_tensors, bool(use_explicit))
     _check_surfels(means3D, rotations, scales, opacities, colors)
@@ -626,11 +690,17 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
     if quality_thresh is not None:
         _, quality, _ = vertex_attributes(m.vertices, means3D, colors, k)
         m, _ = prune_by_quality(m, quality, quality_thresh)
+    closed = None
+    if max_hole_edges is not None:
+        m, closed = close_holes(m, max_hole_edges)
     m = smooth(m, smooth_steps)
     color, quality, _ = vertex_attributes(m.vertices, means3D, colors, k)
     normals = body.vertex_normals(m.vertices, m.faces)
     weights = skin_weights(m, smpl_vertices.to(dev), lbs_weights.to(dev), K)
-    return dict(mesh=m, color=color, quality=quality, normals=normals, weights=weights)
+    out = dict(mesh=m, color=color, quality=quality, normals=normals, weights=weights)
+    if closed is not None:
+        out["closed"] = closed
+    return out
 
 
 # ---- writers -------------------------------------------------------------------------------------------------------------------
