@@ -1262,6 +1262,41 @@ typedef struct SoarEvalArgs {
 int soar_eval_scratch_bytes(int32_t N, int32_t H, int32_t W, size_t *bytes);
 int soar_eval_image_metrics(const SoarEvalArgs *args, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- avatar playback (playback.hip, soar_amd/playback.py): what the reference's inference harness
+ * (TS/test/render_rot.py) does on the host per frame, either side of the renderer.  Both calls: the caller's stream, no allocation,
+ * no host synchronisation; compiled without FMA contraction and restated operation by operation in tests/playback_ref.py.
+ *
+ * soar_motion_resample: K key poses sampled at F times, one thread per (frame, joint), one launch.
+ *   key_pose [K][55][3] axis-angle (full_pose order), key_transl [K][3], key_expr [K][E]; t [F] in key units, clamped to [0, K - 1];
+ *   yaw [F] radians or NULL;  pose [F][55][3], transl [F][3], expr [F][E].
+ *   tc = clamp(t), i0 = floor(tc), i1 = min(i0 + 1, K - 1), u = tc - i0.  Per joint:
+ *     q(a) = (cos(|a| / 2), s a), s = sin(|a| / 2) / |a|, or 1/2 - |a|^2 / 48 when |a| < 1e-3;
+ *     dot = q0 . q1; dot < 0: q1 = -q1, dot = -dot;  dot > 0.999999: weights (1 - u, u) (normalised lerp), else with
+ *     th = acos(dot): (sin((1 - u) th), sin(u th)) / sin(th);  q = the weighted sum, divided by its length;
+ *     joint 0 with yaw: q = q (x) (cos(yaw / 2), 0, sin(yaw / 2), 0), i.e. R <- R Ry(yaw) (euler2mat(yaw, 0, 0, "syxz"));
+ *     w < 0: q = -q;  n = |(x, y, z)|;  out = k (x, y, z), k = 2 atan2(n, w) / n, or 2 + n^2 / 3 when n < 1e-3: angle in [0, pi].
+ *   u == 0 and no turn: the key's three floats are copied as they are (so is a value of transl / expr at u == 0);
+ *   transl, expr otherwise = (1 - u) v[i0] + u v[i1]. */
+int soar_motion_resample(int32_t K, int32_t F, int32_t E, const float *key_pose, const float *key_transl, const float *key_expr,
+                         const float *t, const float *yaw, float *pose, float *transl, float *expr, void *stream);
+
+/* soar_playback_finish: B rendered frames -> the byte images render_rot.py saves, one launch, every pixel's 10 floats read once.
+ *   render, normal, occ: per frame [3][H][W], mask [H][W], float32, frame b at base + b * stride (floats; the planes of a frame are
+ *   contiguous); occ may be NULL (occ_out is not written then).
+ *   rgb, normal_out, occ_out [B][H][W][4] = (the three channels, the mask), mask_out [B][H][W], uint8, contiguous.
+ *   byte(x) = (uint8) clamp(x * 255 + 0.5, 0, 255): multiply, add (no FMA), clamp, truncate -- torchvision's save_image; NaN -> 0.
+ *   normal_as_rgb != 0: the normal is n * 0.5 + 0.5 first.
+ *   Any H, W >= 1: 16-byte accesses when H W and the strides are multiples of 4 and the bases 16-byte aligned, 4-byte ones otherwise
+ *   (the float inputs and RGBA outputs must be 4-byte aligned); nothing is read or written behind a frame's last pixel.
+ *   B <= 65535, B H W <= 2^30; B == 0 is a no-op. */
+typedef struct SoarPlaybackArgs {
+    int32_t B, H, W, normal_as_rgb;
+    const float *render, *normal, *mask, *occ;
+    int64_t render_stride, normal_stride, mask_stride, occ_stride;
+    uint8_t *rgb, *normal_out, *occ_out, *mask_out;
+} SoarPlaybackArgs;
+int soar_playback_finish(const SoarPlaybackArgs *args, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

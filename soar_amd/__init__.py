@@ -8,8 +8,11 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # the geometry model ("gaussiansurfel-base") is exported here without making `import soar_amd` load torch
+    # the geometry model ("gaussiansurfel-base") and the playback entry point are exported here without making `import soar_amd` load torch
     if name == "GaussianSurfelModel":
         from .geometry import GaussianSurfelModel
         return GaussianSurfelModel
+    if name == "AvatarPlayer":
+        from .playback import AvatarPlayer
+        return AvatarPlayer
     raise AttributeError(f"module 'soar_amd' has no attribute '{name}'")

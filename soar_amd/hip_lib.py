@@ -178,6 +178,13 @@ class SoarEvalArgs(C.Structure):
                 ("gt_white", _vp), ("pred2", _vp), ("gt2", _vp), ("grid", _vp), ("metrics", _vp)]
 
 
+class SoarPlaybackArgs(C.Structure):
+    """Mirror of ``struct SoarPlaybackArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("normal_as_rgb", C.c_int32), ("render", _vp), ("normal", _vp),
+                ("mask", _vp), ("occ", _vp), ("render_stride", C.c_int64), ("normal_stride", C.c_int64), ("mask_stride", C.c_int64),
+                ("occ_stride", C.c_int64), ("rgb", _vp), ("normal_out", _vp), ("occ_out", _vp), ("mask_out", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -348,6 +355,8 @@ SIGNATURES = {
     "soar_data_step_batch": (C.c_int, [C.POINTER(SoarDataStepArgs), _vp]),
     "soar_eval_scratch_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_eval_image_metrics": (C.c_int, [C.POINTER(SoarEvalArgs), _vp, C.c_size_t, _vp]),
+    "soar_motion_resample": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8 + [_vp]),
+    "soar_playback_finish": (C.c_int, [C.POINTER(SoarPlaybackArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
