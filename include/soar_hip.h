@@ -53,7 +53,9 @@ extern "C" {
  * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail).  soar_data_mask_bbox / _crops /
  * _step_batch (+ SoarDataStepArgs: the training data module).  soar_frame_loss_partials / _pooled_partials,
  * soar_frames_geometry_warp_backward_losses (+ SoarLossFinish), soar_adam_step_at_gather: two small launches of the step plan folded
- * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation). */
+ * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation).
+ * soar_normalnet_weights_bytes / _pack_weights / _workspace_bytes / _forward (+ SoarNormalNetArgs), soar_normal_crop_boxes / _sample /
+ * _bytes: normal-map preprocessing. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1296,6 +1298,59 @@ typedef struct SoarPlaybackArgs {
     uint8_t *rgb, *normal_out, *occ_out, *mask_out;
 } SoarPlaybackArgs;
 int soar_playback_finish(const SoarPlaybackArgs *args, void *stream);
+
+/* ---- normal-map preprocessing (normalnet.hip, normal_io.hip, soar_amd/normals.py) ----
+ * Two generators of one architecture, netF on cat(image, prior_F) and netB on cat(image, prior_B) (6 input channels), inference only:
+ *   reflection pad 3, conv 7x7 6 -> ngf, IN, ReLU;  n_down x (conv 3x3 stride 2 zero pad 1, c -> 2c, IN, ReLU);
+ *   n_blocks x (x + IN(conv3x3(rpad1(ReLU(IN(conv3x3(rpad1(x))))))))  at ngf 2^n_down channels (rpad1: reflection pad 1);
+ *   n_down x (transposed conv 3x3 stride 2 pad 1 output_padding 1, c -> c / 2, IN, ReLU);  reflection pad 3, conv 7x7 ngf -> 3 + bias, tanh.
+ *   IN: InstanceNorm without affine parameters, eps 1e-5, biased variance over H x W per image and channel (sums in double, one
+ *   fixed order).  The biases of the convolutions in front of an IN cancel in it and are not part of the packed weights.
+ *   Head: n / |n|_2 over the three channels where sum_c |image_c| != 0, exactly 0 elsewhere.
+ * soar_normalnet_pack_weights packs ONE generator (soar_normalnet_weights_bytes bytes, 256-byte aligned) from `count` contiguous device
+ *   arrays in torch's layouts, in this order: first [ngf][6][7][7]; n_down x down [2c][c][3][3]; 2 n_blocks x trunk [C][C][3][3] (a
+ *   block's first, then its second); n_down x up [c][c/2][3][3] (ConvTranspose2d: [Cin][Cout]); last [3][ngf][7][7]; last bias [3].
+ *   count = 2 n_down + 2 n_blocks + 3.
+ * soar_normalnet_forward evaluates both generators; image / prior_F / prior_B [N][3][H][W] float32 at their element strides (NCHW
+ *   order), normal_F / normal_B [N][3][H][W] contiguous.  Workspace: soar_normalnet_workspace_bytes, 256-byte aligned, the caller's.
+ *   ngf: a multiple of 8, at most 512 (8192 trunk channels: the kernels' channel and K indices are int); n_down 1 .. 4; n_blocks >= 0;
+ *   H, W multiples of 2^n_down, >= 4, >= 2 at the bottom level; 0 <= N <= 65535 (0 launches nothing; the image is a grid dimension);
+ *   N H W <= 2^30.  Anything else is refused before any launch.  No atomics, no host synchronisation,
+ *   no allocation; a batch of N gives the bits of N single calls. */
+typedef struct SoarNormalNetArgs {
+    int32_t N, H, W;
+    int32_t ngf, n_down, n_blocks;
+    const float *image, *prior_F, *prior_B;
+    int64_t image_stride[4], prior_F_stride[4], prior_B_stride[4];
+    const void *weights_F, *weights_B;       /* soar_normalnet_pack_weights' outputs */
+    float *normal_F, *normal_B;
+} SoarNormalNetArgs;
+int soar_normalnet_weights_bytes(int32_t ngf, int32_t n_down, int32_t n_blocks, size_t *bytes);
+int soar_normalnet_pack_weights(int32_t ngf, int32_t n_down, int32_t n_blocks, const float *const *tensors, int32_t count, void *packed,
+                                size_t packed_bytes, void *stream);
+int soar_normalnet_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t ngf, int32_t n_down, int32_t n_blocks, size_t *bytes);
+int soar_normalnet_forward(const SoarNormalNetArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The crop in front of the networks and the byte images behind them.  images [N][H][W][3] and mask [N][H][W] are uint8 at their byte
+ * strides ((n, y, x, c) and (n, y, x): an RGBA array serves as both); a mask byte counts as m / 255.
+ * soar_normal_crop_boxes, one launch for all frames: (x0, y0, x1, y1) = the inclusive bounding box of the non-zero mask bytes;
+ *   c = (x0 + (x1 - x0) / 2, y0 + (y1 - y0) / 2), half = 1.1 max(x1 - x0, y1 - y0) / 2, boxes[n] = (c - half, c + half) in double;
+ *   normal_Ks[n] = [[S fx / (bx2 - bx1), 0, S (cx - bx1) / (bx2 - bx1)], [0, S fy / (by2 - by1), S (cy - by1) / (by2 - by1)], [0, 0, 1]]
+ *   from Ks[n] [3][3]; status[n] = 0, 1 (empty mask: the whole frame stands in as the box) or 2 (the mask is a single pixel).  Nothing
+ *   is read back: the caller looks at status where it next synchronises.
+ * soar_normal_crop_sample, one launch for all frames: sample (jy, jx) of the S x S crop sits at pixel coordinate
+ *   x = bx1 + (bx2 - bx1) jx / (S - 1), likewise y, and is the bilinear sample at (x - 1/2, y - 1/2) (grid-sample arithmetic with
+ *   align_corners = False), zeros outside the frame, of (rgb / 255 * 2 - 1) * m -> out_image [N][3][S][S] and of m -> out_mask
+ *   [N][S][S]; evaluated in double, rounded once.
+ * soar_normal_crop_bytes, one launch: out_F / out_B [N][H][W][3] = trunc(((n + 1) / 2 * mask) * 255), out_mask [N][H][W] =
+ *   trunc(mask * 255), float32 operations in that order without contraction; normal_F / normal_B [N][3][H][W], mask [N][H][W]. */
+int soar_normal_crop_boxes(int32_t N, int32_t H, int32_t W, int32_t S, const uint8_t *mask, const int64_t *mask_stride, const float *Ks,
+                           double *boxes, float *normal_Ks, int32_t *status, void *stream);
+int soar_normal_crop_sample(int32_t N, int32_t H, int32_t W, int32_t S, const uint8_t *images, const int64_t *image_stride,
+                            const uint8_t *mask, const int64_t *mask_stride, const double *boxes, float *out_image, float *out_mask,
+                            void *stream);
+int soar_normal_crop_bytes(int32_t N, int32_t H, int32_t W, const float *normal_F, const float *normal_B, const float *mask,
+                           uint8_t *out_F, uint8_t *out_B, uint8_t *out_mask, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

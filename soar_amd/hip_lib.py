@@ -185,6 +185,13 @@ class SoarPlaybackArgs(C.Structure):
                 ("occ_stride", C.c_int64), ("rgb", _vp), ("normal_out", _vp), ("occ_out", _vp), ("mask_out", _vp)]
 
 
+class SoarNormalNetArgs(C.Structure):
+    """Mirror of ``struct SoarNormalNetArgs`` (include/soar_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("ngf", C.c_int32), ("n_down", C.c_int32), ("n_blocks", C.c_int32),
+                ("image", _vp), ("prior_F", _vp), ("prior_B", _vp), ("image_stride", C.c_int64 * 4), ("prior_F_stride", C.c_int64 * 4),
+                ("prior_B_stride", C.c_int64 * 4), ("weights_F", _vp), ("weights_B", _vp), ("normal_F", _vp), ("normal_B", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -357,6 +364,13 @@ SIGNATURES = {
     "soar_eval_image_metrics": (C.c_int, [C.POINTER(SoarEvalArgs), _vp, C.c_size_t, _vp]),
     "soar_motion_resample": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8 + [_vp]),
     "soar_playback_finish": (C.c_int, [C.POINTER(SoarPlaybackArgs), _vp]),
+    "soar_normalnet_weights_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_normalnet_pack_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_normalnet_workspace_bytes": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_size_t)]),
+    "soar_normalnet_forward": (C.c_int, [C.POINTER(SoarNormalNetArgs), _vp, C.c_size_t, _vp]),
+    "soar_normal_crop_boxes": (C.c_int, [C.c_int32] * 4 + [_vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp]),
+    "soar_normal_crop_sample": (C.c_int, [C.c_int32] * 4 + [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
+    "soar_normal_crop_bytes": (C.c_int, [C.c_int32] * 3 + [_vp] * 6 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

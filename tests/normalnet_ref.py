@@ -1,0 +1,172 @@
+"""torch.nn.functional restatement of the normal-map preprocessing, written from the formulas of include/soar_hip.h:
+the two generators and their head, the crop in front (via grid_sample) and the byte conversion behind, parametrised by dtype, plus
+random He-scaled checkpoints in the reference's key layout and the inputs the tests share."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from soar_amd import normals
+
+# (ngf, n_down, n_blocks, N, H, W, seed) of the GPU tests' network cases
+CASES = {
+    "bottom2x2": (8, 4, 2, 1, 32, 32, 11),          # 2 x 2 at the bottom level; every channel count below a tile
+    "offtile": (24, 3, 2, 2, 48, 80, 12),           # channels 24 .. 192, not square, two frames
+    "workload": (8, 4, 1, 1, 512, 512, 13),         # the workload's spatial size
+}
+NORM_FLOOR = 1e-3          # pixels whose float64 three-vector is shorter than this before the normalisation are not compared per element
+
+
+def random_state_dict(ngf, n_down, n_blocks, seed=0, device="cpu", prefix="", dtype=torch.float32):
+    """He-scaled weights (std = sqrt(2 / fan_in)) and small biases under the checkpoint's keys."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    layers = normals.layer_keys(ngf, n_down, n_blocks)
+    first_up = 1 + n_down + 2 * n_blocks
+    ups = {f"model.{layers[i][0]}.weight" for i in range(first_up, first_up + n_down)}
+    for key, shape in normals.state_dict_layout(ngf, n_down, n_blocks).items():
+        if key.endswith(".weight"):
+            if key.split(".", 1)[1] in ups:             # [Cin][Cout][3][3]; a stride-2 transposed convolution sums 9 / 4 taps per output
+                fan_in = shape[0] * 9 / 4.0
+            else:
+                fan_in = shape[1] * shape[2] * shape[3]
+            t = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)
+        else:
+            t = torch.randn(shape, generator=g) * 0.1
+        sd[prefix + key] = t.to(device=device, dtype=dtype)
+    return sd
+
+
+def _inorm(x):
+    return F.instance_norm(x, eps=1e-5)
+
+
+def generator(x, sd, net, ngf, n_down, n_blocks):
+    """One generator on x [N,6,H,W]; computes in x's dtype; the biases in front of the norms are applied as the checkpoint has them."""
+    layers = normals.layer_keys(ngf, n_down, n_blocks)
+    get = lambda i, what: sd[f"{net}.model.{layers[i][0]}.{what}"].to(x)
+    li = 0
+    x = F.relu(_inorm(F.conv2d(F.pad(x, (3, 3, 3, 3), mode="reflect"), get(li, "weight"), get(li, "bias"))))
+    li += 1
+    for _ in range(n_down):
+        x = F.relu(_inorm(F.conv2d(x, get(li, "weight"), get(li, "bias"), stride=2, padding=1)))
+        li += 1
+    for _ in range(n_blocks):
+        y = F.relu(_inorm(F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), get(li, "weight"), get(li, "bias"))))
+        y = _inorm(F.conv2d(F.pad(y, (1, 1, 1, 1), mode="reflect"), get(li + 1, "weight"), get(li + 1, "bias")))
+        x = x + y
+        li += 2
+    for _ in range(n_down):
+        x = F.relu(_inorm(F.conv_transpose2d(x, get(li, "weight"), get(li, "bias"), stride=2, padding=1, output_padding=1)))
+        li += 1
+    return torch.tanh(F.conv2d(F.pad(x, (3, 3, 3, 3), mode="reflect"), get(li, "weight"), get(li, "bias")))
+
+
+def normalnet(image, prior_F, prior_B, sd, ngf, n_down, n_blocks, dtype):
+    """-> (normal_F, normal_B, raw norm F, raw norm B) in dtype: n / |n| * (sum_c |image_c| != 0), and |n| before the normalisation."""
+    image, prior_F, prior_B = image.to(dtype), prior_F.to(dtype), prior_B.to(dtype)
+    mask = (image.abs().sum(dim=1, keepdim=True) != 0).to(dtype)
+    out = []
+    for net, prior in (("netF", prior_F), ("netB", prior_B)):
+        n = generator(torch.cat([image, prior], dim=1), sd, net, ngf, n_down, n_blocks)
+        nrm = torch.norm(n, dim=1, keepdim=True)
+        out.append((torch.where(mask > 0, n / nrm, torch.zeros_like(n)), nrm))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+# the transposed convolution (3 x 3, stride 2, pad 1, output_padding 1) by output parity: along one axis the even outputs 2 y take
+# kernel row 1 at input y; the odd outputs 2 y + 1 take kernel row 2 at input y and kernel row 0 at input y + 1 (zero behind the end)
+PHASE_TAPS = {0: [(1, 0)], 1: [(2, 0), (0, 1)]}           # parity -> [(kernel index, input offset)]
+
+
+def conv_transpose_phases(x, w):
+    """x [N,Cin,H,W], w [Cin,Cout,3,3] -> [N,Cout,2H,2W] as four interleaved phases of 1 + 2 + 2 + 4 taps."""
+    N, _, H, W = x.shape
+    out = x.new_zeros((N, w.shape[1], 2 * H, 2 * W))
+    xp = F.pad(x, (0, 1, 0, 1))
+    for py in (0, 1):
+        for px in (0, 1):
+            acc = 0
+            for ky, dy in PHASE_TAPS[py]:
+                for kx, dx in PHASE_TAPS[px]:
+                    acc = acc + torch.einsum("nchw,co->nohw", xp[:, :, dy:dy + H, dx:dx + W], w[:, :, ky, kx])
+            out[:, :, py::2, px::2] = acc
+    return out
+
+
+def crop(images, masks, Ks, S=512, dtype=torch.float64):
+    """images uint8 [N,H,W,3] RGB, masks uint8 [N,H,W], Ks [N,3,3] -> (image [N,3,S,S], mask [N,1,S,S], normal_Ks [N,3,3], boxes [N,4])."""
+    N, H, W = masks.shape
+    dev = images.device
+    m = masks.to(dtype) / 255
+    img = ((images.to(dtype) / 255 * 2 - 1) * m[..., None]).permute(0, 3, 1, 2)
+    out_i, out_m, out_k, out_b = [], [], [], []
+    for n in range(N):
+        idx = torch.nonzero(masks[n])
+        if idx.numel() == 0:
+            raise ValueError(f"frame {n} has an empty mask")
+        y0, x0 = idx.min(0)[0].tolist()
+        y1, x1 = idx.max(0)[0].tolist()
+        c = torch.tensor([x0 + (x1 - x0) / 2.0, y0 + (y1 - y0) / 2.0], dtype=dtype)
+        half = max(x1 - x0, y1 - y0) * 1.1 / 2.0
+        box = torch.cat([c - half, c + half])
+        gx = torch.linspace(box[0].item(), box[2].item(), S, dtype=dtype, device=dev) / W
+        gy = torch.linspace(box[1].item(), box[3].item(), S, dtype=dtype, device=dev) / H
+        grid = torch.stack(torch.meshgrid(gx, gy, indexing="xy"), dim=-1)[None] * 2.0 - 1.0
+        out_i.append(F.grid_sample(img[n:n + 1], grid, mode="bilinear", padding_mode="zeros", align_corners=False))
+        out_m.append(F.grid_sample(m[n:n + 1, None], grid, mode="bilinear", padding_mode="zeros", align_corners=False))
+        K = Ks[n].to(dtype).cpu()
+        sx, sy = S / (box[2] - box[0]), S / (box[3] - box[1])
+        out_k.append(torch.tensor([[sx * K[0, 0], 0.0, sx * (K[0, 2] - box[0])], [0.0, sy * K[1, 1], sy * (K[1, 2] - box[1])],
+                                   [0.0, 0.0, 1.0]], dtype=dtype))
+        out_b.append(box)
+    return torch.cat(out_i), torch.cat(out_m), torch.stack(out_k).to(dev), torch.stack(out_b).to(dev)
+
+
+def to_bytes(normal, mask):
+    """[N,3,H,W], [N,1,H,W] -> uint8 [N,H,W,3], [N,H,W]: the operations in the order the kernel takes them."""
+    return (((normal + 1.0) / 2.0 * mask) * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous(), (mask[:, 0] * 255.0).to(torch.uint8)
+
+
+def _smooth(g, N, C, H, W, cells=5):
+    low = torch.rand((N, C, cells, cells), generator=g) * 2 - 1
+    return F.interpolate(low, size=(H, W), mode="bicubic", align_corners=True).clamp(-1, 1)
+
+
+def _blob(H, W, cy, cx, ry, rx):
+    y = torch.arange(H, dtype=torch.float32)[:, None]
+    x = torch.arange(W, dtype=torch.float32)[None, :]
+    return (((y - cy) / ry) ** 2 + ((x - cx) / rx) ** 2 <= 1.0).to(torch.float32)
+
+
+def make_inputs(N, H, W, seed):
+    """A smooth random image times a blob mask that touches the top and the left border, and smooth priors, zero off their own blob.
+    float32 CPU tensors [N,3,H,W]."""
+    g = torch.Generator().manual_seed(seed)
+    blob = _blob(H, W, 0.3 * H, 0.25 * W, 0.45 * H, 0.4 * W)
+    image = _smooth(g, N, 3, H, W)
+    image = torch.where(image.abs() < 1e-3, torch.full_like(image, 1e-3), image) * blob        # no accidental zeros inside the mask
+    body = _blob(H, W, 0.35 * H, 0.3 * W, 0.35 * H, 0.3 * W)
+    return image, _smooth(g, N, 3, H, W) * body, _smooth(g, N, 3, H, W) * body
+
+
+def make_case(name, device="cpu"):
+    ngf, n_down, n_blocks, N, H, W, seed = CASES[name]
+    sd = random_state_dict(ngf, n_down, n_blocks, seed=seed, device=device)
+    image, pF, pB = (t.to(device) for t in make_inputs(N, H, W, seed + 100))
+    return dict(cfg=(ngf, n_down, n_blocks), sd=sd, image=image, prior_F=pF, prior_B=pB)
+
+
+def make_frames(N=3, H=40, W=56, seed=5):
+    """uint8 frames for the crop tests: frame 0's mask lies inside the image, frame 1's box leaves it on two sides, frame 2's mask is
+    soft.  -> images [N,H,W,3], masks [N,H,W], Ks [N,3,3] (CPU)."""
+    g = torch.Generator().manual_seed(seed)
+    images = (_smooth(g, N, 3, H, W, cells=7).permute(0, 2, 3, 1) * 127.5 + 127.5).clamp(0, 255).to(torch.uint8)
+    masks = torch.zeros((N, H, W), dtype=torch.uint8)
+    masks[0] = (_blob(H, W, 20, 28, 9, 13) * 255).to(torch.uint8)
+    masks[1] = (_blob(H, W, 6, 50, 14, 9) * 255).to(torch.uint8)               # reaches the top and the right border
+    soft = _blob(H, W, 22, 24, 12, 10) * (0.35 + 0.65 * torch.rand((H, W), generator=g))
+    masks[2] = (soft * 255).to(torch.uint8)
+    Ks = torch.tensor([[60.0, 0.0, W / 2.0], [0.0, 61.0, H / 2.0], [0.0, 0.0, 1.0]]).repeat(N, 1, 1)
+    Ks[:, 0, 2] += torch.arange(N) * 0.5
+    return images.contiguous(), masks, Ks
