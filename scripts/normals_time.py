@@ -121,8 +121,8 @@ def hip_kernel_groups(net, inputs, iters):
         for _ in range(iters):
             net(*inputs)
         torch.cuda.synchronize()
-    evs = [e for e in prof.events() if "nn_" in e.name and str(getattr(e, "device_type", "")).endswith("CUDA")]
-    evs = [e for e in evs if any(k in e.name for k in ("nn_first", "nn_gemm", "nn_in_", "nn_last"))]
+    evs = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
+    evs = [e for e in evs if any(k in e.name for k in ("nn_first", "conv_gemm_kernel", "nn_in_", "nn_last"))]
     evs.sort(key=lambda e: e.time_range.start)
     per_gen = 1 + 3 + 4 * (2 * N_DOWN + 2 * N_BLOCKS) + 1
     if len(evs) != per_gen * 2 * iters:
@@ -133,7 +133,7 @@ def hip_kernel_groups(net, inputs, iters):
     for i, e in enumerate(evs):
         dur = (e.time_range.end - e.time_range.start) * 1e-3 / iters
         out[order[i % per_gen]] += dur
-        if order[i % per_gen] == "trunk" and "nn_gemm" in e.name:
+        if order[i % per_gen] == "trunk" and "conv_gemm_kernel" in e.name:
             out["trunk_gemm_only"] += dur
     return out
 

@@ -130,7 +130,7 @@ def trace_run(iters=4):
 def read_trace(path):
     """the forward GEMM launches of every iteration of trace_run, matched in order to gemm_flops"""
     with open(path) as f:
-        rows = [r for r in csv.DictReader(f) if "vae_gemm_kernel" in r["Kernel_Name"]]
+        rows = [r for r in csv.DictReader(f) if "conv_gemm_kernel" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     names = gemm_flops(N, S)
     nf = len(names)

@@ -1,0 +1,66 @@
+// conv_gemm.h -- the implicit-GEMM convolution and the weight packer that the convolutional networks share (lpips.hip, vae.hip,
+// normalnet.hip), and the small pieces every kernel on v_mfma_f32_32x32x2_f32 needs.
+#pragma once
+
+#include "soar_common.h"
+
+namespace soar {
+
+// One tap table: output (gy os + py, gx os + px) of grid row (n, gy, gx) sums, tap by tap, input (gy stride + dy, gx stride + dx)
+// times w[co][tap][ci].  A 1 x 1 convolution and a plain matrix product are a table of one entry.
+struct ConvTaps {
+    const float *w;                // B: row co at w + image wbat + co ldw, k = tap Cin + ci
+    int64_t ldw;
+    int ntaps, py, px;
+    signed char dy[9], dx[9];
+};
+// a square kernel of side x side taps, tap (ky, kx) at offset (ky + off, kx + off)
+inline void square_taps(ConvTaps &p, const float *w, int64_t ldw, int side, int off)
+{
+    p.w = w; p.ldw = ldw; p.ntaps = side * side; p.py = p.px = 0;
+    for (int t = 0; t < side * side; t++) { p.dy[t] = (signed char)(t / side + off); p.dx[t] = (signed char)(t % side + off); }
+}
+
+// y = alpha * (A B^T) + bias + res.  A row is one grid position's (tap, cin) window of x, gathered on load; nothing padded or
+// zero-dilated is ever materialised.
+struct ConvGemm {
+    const float *x;                // A: image n's pixel (iy, ix) at x + (n xim + iy Win + ix) ldx, Cin floats (a multiple of 8, 16-byte aligned)
+    int64_t ldx, xim;
+    int64_t wbat;                  // B's per-image offset (per_image only)
+    const float *bias;             // [Cout] or NULL
+    const float *res;              // indexed as y, or NULL
+    float *y;                      // image n's output pixel (oy, ox) at y + (n yim + oy Wout + ox) ldy, Cout floats
+    int64_t ldy, yim;
+    float alpha;
+    int N, Hg, Wg;                 // the grid a row walks: N Hg Wg rows, at most 2^30
+    int Hin, Win, Cin, Cout;
+    int stride, dil;               // dil = 1, or 2: the input is x zero-dilated by two (odd coordinates load zeros, even ones x at half;
+                                   //   with zero padding only)
+    int reflect;                   // outside the input: mirrored (reflect) or zero
+    int Wout, os;
+    int per_image;                 // 1: 64 x 64 tiles that never cross an image (B and the padded row count may then be per image);
+                                   // 0: tiles over the batch's flat rows, 128 x 128 where those still fill the chip
+    int nph;                       // tap tables in use: gridDim.y picks one (the phases of a transposed convolution)
+    ConvTaps ph[4];
+    int tiles_n, tiles_img;        // (the launcher's)
+};
+int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream);
+
+// torch [Cout][Cin][kk] -> fwd [Cout][kk][Cin] and, unless bwd is NULL, the data gradient's form, spatially flipped and transposed:
+// bwd[(ci kk + kk - 1 - t) ldb + co]
+int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, int kk, int64_t ldb, hipStream_t stream);
+
+inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+#if defined(__HIPCC__)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int BK = 32;             // k per chunk
+constexpr int LDSK = BK + 4;       // LDS row pitch in floats: rows 16 B apart in bank space, float4 reads conflict-free per quarter wave
+
+__device__ __forceinline__ float comp(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+// C / D of the 32 x 32 MFMA: lane l holds column l & 31; its register e is row (e & 3) + 8 (e >> 2) + 4 h with h = l >> 5
+__device__ __forceinline__ int mfma_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+__device__ __forceinline__ int mirror(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+#endif
+
+}  // namespace soar

@@ -1,0 +1,220 @@
+// conv_gemm.hip -- the implicit-GEMM convolution of the VAE encoder and the normal networks, and the three networks' weight packer
+// (conv_gemm.h).
+//
+//   conv_pack_kernel       torch [Cout][Cin][kk] -> [Cout][tap][Cin] (forward) and, where asked, spatially flipped and transposed,
+//                          [Cin][tap][ldb] (data gradient): both directions are then the same implicit GEMM
+//   conv_gemm_kernel       an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32 products): M = grid positions, N = output
+//                          channels, K = (tap, cin), tiles staged through LDS.  The A loader does strides, padding (zero or mirrored)
+//                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = alpha acc + bias + res, scattered
+//                          to the tap table's output parity
+//
+// No atomics: every output has one fixed order of summation, the same whatever the tile and the batch.
+#include "conv_gemm.h"
+
+namespace soar {
+
+namespace {
+
+__global__ void __launch_bounds__(256) conv_pack_kernel(const float *__restrict__ w, float *__restrict__ fwd, float *__restrict__ bwd,
+                                                        int Cout, int Cin, int kk, int64_t ldb)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)Cout * Cin * kk) return;
+    // e walks the torch layout [co][ci][t]
+    const int t = (int)(e % kk);
+    const int64_t r = e / kk;
+    const int ci = (int)(r % Cin), co = (int)(r / Cin);
+    const float v = w[e];
+    fwd[((size_t)co * kk + t) * Cin + ci] = v;
+    // the data gradient is the convolution of the output gradient with W'[ci][co][kk - 1 - t]
+    if (bwd) bwd[((size_t)ci * kk + (kk - 1 - t)) * ldb + co] = v;
+}
+
+// Block tile 64 WM x 64 WN, waves 2 x 2, each 32 WM x 32 WN as WM x WN MFMA blocks.  K runs flat over (tap, cin) in chunks of 32; a
+// staging thread moves groups of 8 floats, which never straddle a tap because Cin is a multiple of 8; groups behind K, rows behind M
+// and columns behind Cout are zeros.  One LDS buffer: a chunk is staged, a barrier, the next chunk's loads are issued and stay in
+// flight while the MFMAs of this one run, a barrier.
+// Lane (i, h) of a wave: row / column i of a 32 x 32 block, k half h; step s of a chunk sums k = s (h = 0) and k = 16 + s (h = 1).
+// So every output's sum runs chunk by chunk and inside a chunk k = 0, 16, 1, 17, ... whatever WM, WN and its place in the tile.
+template <int WM, int WN>
+__global__ void __launch_bounds__(256) conv_gemm_kernel(ConvGemm k)
+{
+    constexpr int BM = 64 * WM, BN = 64 * WN;
+    __shared__ float As[BM][LDSK], Bs[BN][LDSK];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const ConvTaps &ph = k.ph[blockIdx.y];
+    const int tn = (int)(blockIdx.x % (unsigned)k.tiles_n);
+    int tm = (int)(blockIdx.x / (unsigned)k.tiles_n);
+    const int hwg = k.Hg * k.Wg;
+    // the tile's rows r0 .. of image img0 on (flat: img0 = 0 and the rows run on through the batch)
+    int img0 = 0, rows = k.N * hwg;
+    if (k.per_image) { img0 = tm / k.tiles_img; tm -= img0 * k.tiles_img; rows = hwg; }
+    const int r0 = tm * BM, c0 = tn * BN;
+    const int Kp = ph.ntaps * k.Cin, nch = (Kp + BK - 1) / BK;
+    const int dm = k.dil - 1;                       // dil = 1 or 2: mask and shift of a dilated coordinate
+
+    // the staging thread's rows: tid >> 2 (+ 64 j), floats (tid & 3) * 8 .. + 8 of the chunk
+    const int srow = tid >> 2, sk = (tid & 3) * 8;
+    bool av[WM];
+    int gy[WM], gx[WM];
+    size_t abase[WM];
+#pragma unroll
+    for (int j = 0; j < WM; j++) {
+        const int r = r0 + srow + 64 * j;
+        av[j] = r < rows;
+        const int n = av[j] ? r / hwg : 0;
+        const int q = av[j] ? r - n * hwg : 0;
+        gy[j] = q / k.Wg;
+        gx[j] = q - gy[j] * k.Wg;
+        abase[j] = (size_t)(img0 + n) * k.xim;
+    }
+    const float *wrow[WN];
+    bool bv[WN];
+#pragma unroll
+    for (int j = 0; j < WN; j++) {
+        const int co = c0 + srow + 64 * j;
+        bv[j] = co < k.Cout;
+        wrow[j] = ph.w + (size_t)img0 * k.wbat + (size_t)(bv[j] ? co : 0) * ph.ldw;
+    }
+
+    float4 na[WM][2], nb[WN][2];
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto fetch = [&](int ch) {
+        const int kk = ch * BK + sk;
+        const bool kv = kk < Kp;
+        const int t = kv ? kk / k.Cin : 0;
+        const int ci = kk - t * k.Cin;
+        const int dy = ph.dy[t], dx = ph.dx[t];
+#pragma unroll
+        for (int j = 0; j < WM; j++) {
+            int iy = gy[j] * k.stride + dy, ix = gx[j] * k.stride + dx;
+            bool ok = kv && av[j];
+            ok = ok && !((iy | ix) & dm);           // dilated by two: odd coordinates are zeros, even ones (negative ones stay negative)
+            iy >>= dm; ix >>= dm;                   //   x at half
+            if (k.reflect) { iy = mirror(iy, k.Hin); ix = mirror(ix, k.Win); }
+            else ok = ok && iy >= 0 && iy < k.Hin && ix >= 0 && ix < k.Win;
+            if (ok) {
+                const float4 *s = reinterpret_cast<const float4 *>(k.x + (abase[j] + (size_t)iy * k.Win + ix) * k.ldx + ci);
+                na[j][0] = s[0];
+                na[j][1] = s[1];
+            } else {
+                na[j][0] = na[j][1] = zero4;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < WN; j++) {
+            if (kv && bv[j]) {
+                const float4 *s = reinterpret_cast<const float4 *>(wrow[j] + kk);
+                nb[j][0] = s[0];
+                nb[j][1] = s[1];
+            } else {
+                nb[j][0] = nb[j][1] = zero4;
+            }
+        }
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int j = 0; j < WM; j++) {
+            *reinterpret_cast<float4 *>(&As[srow + 64 * j][sk]) = na[j][0];
+            *reinterpret_cast<float4 *>(&As[srow + 64 * j][sk + 4]) = na[j][1];
+        }
+#pragma unroll
+        for (int j = 0; j < WN; j++) {
+            *reinterpret_cast<float4 *>(&Bs[srow + 64 * j][sk]) = nb[j][0];
+            *reinterpret_cast<float4 *>(&Bs[srow + 64 * j][sk + 4]) = nb[j][1];
+        }
+    };
+
+    const int i = lane & 31, h = lane >> 5;
+    const int wr = (wave >> 1) * 32 * WM, wc = (wave & 1) * 32 * WN;
+    f32x16 acc[WM][WN];
+#pragma unroll
+    for (int r = 0; r < WM; r++)
+#pragma unroll
+        for (int c = 0; c < WN; c++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc[r][c][e] = 0.f;
+
+    fetch(0);
+    for (int ch = 0; ch < nch; ch++) {
+        stage();
+        lds_barrier();
+        if (ch + 1 < nch) fetch(ch + 1);            // in flight while the MFMAs of this chunk run
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            float4 a4[WM], b4[WN];
+#pragma unroll
+            for (int r = 0; r < WM; r++) a4[r] = *reinterpret_cast<const float4 *>(&As[wr + r * 32 + i][h * 16 + 4 * g]);
+#pragma unroll
+            for (int c = 0; c < WN; c++) b4[c] = *reinterpret_cast<const float4 *>(&Bs[wc + c * 32 + i][h * 16 + 4 * g]);
+#pragma unroll
+            for (int s = 0; s < 4; s++)
+#pragma unroll
+                for (int r = 0; r < WM; r++)
+#pragma unroll
+                    for (int c = 0; c < WN; c++)
+                        acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(a4[r], s), comp(b4[c], s), acc[r][c], 0, 0, 0);
+        }
+        lds_barrier();
+    }
+    bool cv[WN];
+    float bias[WN];
+#pragma unroll
+    for (int c = 0; c < WN; c++) {
+        const int co = c0 + wc + c * 32 + i;
+        cv[c] = co < k.Cout;
+        bias[c] = k.bias && cv[c] ? k.bias[co] : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < WM; r++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const int row = r0 + wr + r * 32 + mfma_row(e, h);
+            if (row >= rows) continue;
+            const int n = row / hwg;
+            const int q = row - n * hwg, y = q / k.Wg, x = q - y * k.Wg;
+            const size_t base = ((size_t)(img0 + n) * k.yim + (size_t)(y * k.os + ph.py) * k.Wout + (size_t)(x * k.os + ph.px)) * k.ldy;
+#pragma unroll
+            for (int c = 0; c < WN; c++) {
+                if (!cv[c]) continue;
+                const size_t idx = base + (c0 + wc + c * 32 + i);
+                float v = acc[r][c][e] * k.alpha + bias[c];
+                if (k.res) v += k.res[idx];
+                k.y[idx] = v;
+            }
+        }
+}
+
+}  // namespace
+
+int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream)
+{
+    ConvGemm k = desc;
+    const int64_t hwg = (int64_t)k.Hg * k.Wg, M = k.N * hwg;
+    if (M == 0) return 0;
+    if (M > (int64_t(1) << 30) || k.Cin % 8 || k.nph < 1 || k.nph > 4 || (!k.per_image && k.wbat)) {
+        set_error("conv_gemm: need at most 2^30 rows, Cin a multiple of 8, 1 .. 4 tap tables, B per image only with tiles per image "
+                  "(rows=%lld, Cin=%d, nph=%d)", (long long)M, k.Cin, k.nph);
+        return 1;
+    }
+    // 128 x 128 tiles where they still fill the chip (256 compute units), 64 x 64 otherwise; the sums' order is the same
+    const int64_t big = (M + 127) / 128 * ((k.Cout + 127) / 128) * k.nph;
+    const bool big_tiles = !k.per_image && big >= 256 && k.Cout >= 128;
+    const int bt = big_tiles ? 128 : 64;
+    k.tiles_n = (k.Cout + bt - 1) / bt;
+    k.tiles_img = (int)((hwg + bt - 1) / bt);
+    const int64_t tiles = (k.per_image ? (int64_t)k.N * k.tiles_img : (M + bt - 1) / bt) * k.tiles_n;
+    if (big_tiles) hipLaunchKernelGGL((conv_gemm_kernel<2, 2>), dim3((unsigned)tiles, (unsigned)k.nph), dim3(256), 0, stream, k);
+    else hipLaunchKernelGGL((conv_gemm_kernel<1, 1>), dim3((unsigned)tiles, (unsigned)k.nph), dim3(256), 0, stream, k);
+    SOAR_LAUNCH_OK("conv_gemm", stream, 0);
+    return 0;
+}
+
+int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, int kk, int64_t ldb, hipStream_t stream)
+{
+    hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks((int64_t)Cout * Cin * kk)), dim3(256), 0, stream, w, fwd, bwd, Cout, Cin, kk, ldb);
+    SOAR_LAUNCH_OK("conv_pack", stream, 0);
+    return 0;
+}
+
+}  // namespace soar

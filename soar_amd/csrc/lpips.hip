@@ -1,7 +1,7 @@
 // lpips.hip -- LPIPS-VGG (soar_amd/lpips.py): lpips 0.1, net='vgg', eval mode, as include/soar_hip.h and DESIGN.md 9e state it.
 //
-//   lpips_pack_kernel        torch [Cout][Cin][3][3] -> [Cout][tap][Cin] (forward) and, spatially flipped and transposed,
-//                            [Cin][tap][Cout] (data gradient): both directions are then the same implicit GEMM
+//   (conv_pack_kernel        conv_gemm.hip: torch [Cout][Cin][3][3] -> [Cout][tap][Cin] (forward) and, spatially flipped and
+//                            transposed, [Cin][tap][Cout] (data gradient): both directions are then the same implicit GEMM)
 //   lpips_first_kernel       conv1_1: scaling layer on load (strided NCHW input, zero padding in scaled space), 27 -> 64, bias, ReLU
 //   lpips_conv_kernel        conv3x3 pad 1 on NHWC activations as an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32 products):
 //                            M = pixels, N = output channels, K = 9 Cin ordered (tap, cin).  A wave owns WM x WN blocks of 32 x 32
@@ -17,7 +17,7 @@
 //
 // No atomics: every value and gradient has one fixed order of summation (bitwise reproducible).  No host synchronisation, no
 // allocation.
-#include "soar_common.h"
+#include "conv_gemm.h"
 
 namespace soar {
 
@@ -108,23 +108,6 @@ WsLayout ws_layout(const Dims &d, int grads)
     }
     L.total = off == 0 ? ALIGN : off;
     return L;
-}
-
-// ---- weight packing ----
-__global__ void __launch_bounds__(256) lpips_pack_kernel(const float *__restrict__ w, float *__restrict__ fwd, float *__restrict__ bwd,
-                                                         int Cout, int Cin)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = (int64_t)Cout * Cin * 9;
-    if (e >= n) return;
-    // e walks the torch layout [co][ci][t]
-    const int t = (int)(e % 9);
-    const int64_t r = e / 9;
-    const int ci = (int)(r % Cin), co = (int)(r / Cin);
-    const float v = w[e];
-    fwd[((size_t)co * 9 + t) * Cin + ci] = v;
-    // the data gradient is the convolution of the output gradient with W'[ci][co][8 - t]
-    bwd[((size_t)ci * 9 + (8 - t)) * Cout + co] = v;
 }
 
 // ---- conv1_1 with the scaling layer ----
@@ -218,9 +201,6 @@ struct ConvK {
     int64_t M;
     int H, W, Cin, Cout, epi;
 };
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float comp(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 
 // Lane l of a wave: row / column i = l & 31 of every 32 x 32 block, k half h = l >> 5.  In a chunk of 32 k (one tap, 32 input
 // channels) step s of the MFMA sums k = s (h = 0) and k = 16 + s (h = 1), so that a lane's operands are 16 contiguous floats.
@@ -306,7 +286,6 @@ __global__ void __launch_bounds__(256) lpips_conv_kernel(ConvK k)
 #pragma unroll
             for (int j = 0; j < 4; j++) b[c][j] = bn[c][j];
     }
-    // C / D: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int c = 0; c < WN; c++) {
         const int co = tn * 32 * WN + c * 32 + i;
@@ -315,7 +294,7 @@ __global__ void __launch_bounds__(256) lpips_conv_kernel(ConvK k)
         for (int r = 0; r < WM; r++)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                const int64_t p = p0 + r * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int64_t p = p0 + r * 32 + mfma_row(e, h);
                 if (p >= k.M) continue;
                 const size_t idx = (size_t)p * k.Cout + co;
                 float v = acc[r][c][e];
@@ -502,8 +481,6 @@ __global__ void __launch_bounds__(256) lpips_gate_kernel(GateK k)
 }
 
 // ---- host side ----
-inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
-
 int launch_conv(const ConvK &k, hipStream_t stream)
 {
     // the widest wave tile that still gives every SIMD (1024) two waves
@@ -577,10 +554,8 @@ extern "C" int soar_lpips_pack_weights(const SoarLpipsWeights *w, void *packed, 
         const size_t n = (size_t)COUT[i] * CIN[i] * 9;
         if (i == 0) {
             SOAR_HIP_OK(hipMemcpyAsync(P + L.fwd[0], w->conv_w[0], n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        } else {
-            hipLaunchKernelGGL(lpips_pack_kernel, dim3(blocks((int64_t)n)), dim3(256), 0, stream, w->conv_w[i], P + L.fwd[i], P + L.bwd[i],
-                               COUT[i], CIN[i]);
-            SOAR_LAUNCH_OK("lpips_pack", stream, 0);
+        } else if (launch_conv_pack(w->conv_w[i], P + L.fwd[i], P + L.bwd[i], COUT[i], CIN[i], 9, COUT[i], stream)) {
+            return 1;
         }
         SOAR_HIP_OK(hipMemcpyAsync(P + L.bias[i], w->conv_b[i], COUT[i] * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }

@@ -1,14 +1,13 @@
 // normalnet.hip -- the normal-map networks of the preprocessing stage (soar_amd/normals.py): two pix2pixHD global generators,
 // netF on [image, prior_F] and netB on [image, prior_B], inference only, as include/soar_hip.h and DESIGN.md 9l state them.
 //
-//   nn_pack_kernel         torch [Cout][Cin][k][k] -> [Cout][tap][Cin]
+//   (conv_pack_kernel      conv_gemm.hip: torch [Cout][Cin][k][k] -> [Cout][tap][Cin])
 //   nn_pack_up_kernel      the transposed convolution's torch [Cin][Cout][3][3] -> its four output-parity phases, each
 //                          [Cout][tap of the phase][Cin] (1 + 2 + 2 + 4 taps)
 //   nn_first_kernel        reflection pad 3 + conv 7x7, 6 -> ngf, on the VALU: reads the caller's strided NCHW planes, writes NHWC
-//   nn_gemm_kernel         every other convolution but the last: an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32 products),
-//                          M = pixels of the whole batch, N = output channels, K = (tap, cin), tiles staged through LDS.  The A loader
-//                          does the padding as index arithmetic: zero (stride-2 convolutions, the phases of the transposed one) or
-//                          mirrored (the residual trunk); nothing padded or zero-dilated is ever materialised
+//   (conv_gemm_kernel      conv_gemm.hip: every other convolution but the last, as the shared implicit GEMM with M = pixels of the
+//                          whole batch.  Its A loader does the padding as index arithmetic: zero (stride-2 convolutions, the phases
+//                          of the transposed one) or mirrored (the residual trunk))
 //   nn_in_partial_kernel   InstanceNorm statistics: per (image, chunk of pixels, channel) sum and sum of squares in double
 //   nn_in_final_kernel     ... the chunks added in order -> mean, 1 / sqrt(biased variance + 1e-5)
 //   nn_in_apply_kernel     y = relu((x - mean) rstd), or y = res + (x - mean) rstd at the end of a residual block
@@ -17,7 +16,7 @@
 // A convolution bias in front of an InstanceNorm without affine parameters cancels in (x - mean): those biases are not read.
 // No atomics: every output has one fixed order of summation, the same whatever the tile and the batch (a batch of N is bit-equal to
 // N single calls).  No host synchronisation, no allocation.
-#include "soar_common.h"
+#include "conv_gemm.h"
 
 namespace soar {
 
@@ -123,19 +122,7 @@ WsLayout ws_layout(const Cfg &c, int N, int H, int W)
     return L;
 }
 
-inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
-__device__ __forceinline__ int mirror(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
-
 // ---- weight packing ----
-__global__ void __launch_bounds__(256) nn_pack_kernel(const float *__restrict__ w, float *__restrict__ out, int Cout, int Cin, int kk)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)Cout * Cin * kk) return;
-    const int t = (int)(e % kk);
-    const int64_t r = e / kk;
-    const int ci = (int)(r % Cin), co = (int)(r / Cin);
-    out[((size_t)co * kk + t) * Cin + ci] = w[e];
-}
 struct PackUpK {
     const float *w;         // torch ConvTranspose2d: [Cin][Cout][3][3]
     float *out[4];
@@ -191,167 +178,6 @@ __global__ void __launch_bounds__(256) nn_first_kernel(FirstK k)
     float4 *dst = reinterpret_cast<float4 *>(k.y + (size_t)p * k.ngf + co0);
     dst[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
     dst[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
-}
-
-// ---- the implicit GEMM ----
-struct Phase {
-    const float *w;                // [Cout][ntaps][Cin]
-    int ntaps, py, px;
-    signed char dy[9], dx[9];
-};
-struct GemmK {
-    const float *x;                // [N][Hin][Win][Cin]
-    float *y;                      // [N][Hout][Wout][Cout]
-    int64_t M;                     // rows: N Hg Wg
-    int Hg, Wg;                    // the grid a row walks: row (n, gy, gx) reads input (gy stride + dy, gx stride + dx) per tap
-    int Hin, Win, Cin, Cout;       //   and writes output (gy os + py, gx os + px)
-    int stride, reflect;           // outside the input: mirrored (reflect) or zero
-    int Hout, Wout, os;
-    int tiles_n;
-    Phase ph[4];                   // blockIdx.y picks the phase
-};
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int BK = 32;
-constexpr int LDSK = BK + 4;       // row pitch in floats: rows 16 B apart in bank space, float4 reads conflict-free per quarter wave
-
-__device__ __forceinline__ float comp(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
-
-// Block tile 64 WM x 64 WN, waves 2 x 2, each 32 WM x 32 WN as WM x WN MFMA blocks.  K runs flat over (tap, cin) in chunks of 32; a
-// staging thread moves groups of 8 floats, which never straddle a tap because Cin is a multiple of 8; groups behind K are zeros.
-// Lane (i, h) of a wave: row / column i of a 32 x 32 block, k half h; step s of a chunk sums k = s (h = 0) and k = 16 + s (h = 1).
-// So every output's sum runs chunk by chunk and inside a chunk k = 0, 16, 1, 17, ... whatever WM, WN and its place in the tile.
-template <int WM, int WN>
-__global__ void __launch_bounds__(256) nn_gemm_kernel(GemmK k)
-{
-    constexpr int BM = 64 * WM, BN = 64 * WN;
-    __shared__ float As[BM][LDSK], Bs[BN][LDSK];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const Phase &ph = k.ph[blockIdx.y];
-    const int tn = (int)(blockIdx.x % (unsigned)k.tiles_n);
-    const int64_t tm = blockIdx.x / (unsigned)k.tiles_n;
-    const int64_t r0 = tm * BM;
-    const int c0 = tn * BN;
-    const int Kp = ph.ntaps * k.Cin, nch = (Kp + BK - 1) / BK;
-    const int64_t hwg = (int64_t)k.Hg * k.Wg;
-
-    // the staging thread's rows: tid >> 2 (+ 64 j), floats (tid & 3) * 8 .. + 8 of the chunk
-    const int srow = tid >> 2, sk = (tid & 3) * 8;
-    bool av[WM];
-    int gy[WM], gx[WM];
-    size_t abase[WM];
-#pragma unroll
-    for (int j = 0; j < WM; j++) {
-        const int64_t r = r0 + srow + 64 * j;
-        av[j] = r < k.M;
-        const int64_t n = av[j] ? r / hwg : 0;
-        const int q = av[j] ? (int)(r - n * hwg) : 0;
-        gy[j] = q / k.Wg;
-        gx[j] = q - gy[j] * k.Wg;
-        abase[j] = (size_t)n * k.Hin * k.Win;
-    }
-    const float *wrow[WN];
-    bool bv[WN];
-#pragma unroll
-    for (int j = 0; j < WN; j++) {
-        const int co = c0 + srow + 64 * j;
-        bv[j] = co < k.Cout;
-        wrow[j] = ph.w + (size_t)(bv[j] ? co : 0) * Kp;
-    }
-
-    float4 na[WM][2], nb[WN][2];
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto fetch = [&](int ch) {
-        const int kk = ch * BK + sk;
-        const bool kv = kk < Kp;
-        const int t = kv ? kk / k.Cin : 0;
-        const int ci = kk - t * k.Cin;
-        const int dy = ph.dy[t], dx = ph.dx[t];
-#pragma unroll
-        for (int j = 0; j < WM; j++) {
-            int iy = gy[j] * k.stride + dy, ix = gx[j] * k.stride + dx;
-            bool ok = kv && av[j];
-            if (k.reflect) { iy = mirror(iy, k.Hin); ix = mirror(ix, k.Win); }
-            else ok = ok && iy >= 0 && iy < k.Hin && ix >= 0 && ix < k.Win;
-            if (ok) {
-                const float4 *s = reinterpret_cast<const float4 *>(k.x + (abase[j] + (size_t)iy * k.Win + ix) * k.Cin + ci);
-                na[j][0] = s[0];
-                na[j][1] = s[1];
-            } else {
-                na[j][0] = na[j][1] = zero4;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < WN; j++) {
-            if (kv && bv[j]) {
-                const float4 *s = reinterpret_cast<const float4 *>(wrow[j] + kk);
-                nb[j][0] = s[0];
-                nb[j][1] = s[1];
-            } else {
-                nb[j][0] = nb[j][1] = zero4;
-            }
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < WM; j++) {
-            *reinterpret_cast<float4 *>(&As[srow + 64 * j][sk]) = na[j][0];
-            *reinterpret_cast<float4 *>(&As[srow + 64 * j][sk + 4]) = na[j][1];
-        }
-#pragma unroll
-        for (int j = 0; j < WN; j++) {
-            *reinterpret_cast<float4 *>(&Bs[srow + 64 * j][sk]) = nb[j][0];
-            *reinterpret_cast<float4 *>(&Bs[srow + 64 * j][sk + 4]) = nb[j][1];
-        }
-    };
-
-    const int i = lane & 31, h = lane >> 5;
-    const int wr = (wave >> 1) * 32 * WM, wc = (wave & 1) * 32 * WN;
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int r = 0; r < WM; r++)
-#pragma unroll
-        for (int c = 0; c < WN; c++)
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[r][c][e] = 0.f;
-
-    fetch(0);
-    for (int ch = 0; ch < nch; ch++) {
-        stage();
-        lds_barrier();
-        if (ch + 1 < nch) fetch(ch + 1);            // in flight while the MFMAs of this chunk run
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            float4 a4[WM], b4[WN];
-#pragma unroll
-            for (int r = 0; r < WM; r++) a4[r] = *reinterpret_cast<const float4 *>(&As[wr + r * 32 + i][h * 16 + 4 * g]);
-#pragma unroll
-            for (int c = 0; c < WN; c++) b4[c] = *reinterpret_cast<const float4 *>(&Bs[wc + c * 32 + i][h * 16 + 4 * g]);
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-                for (int r = 0; r < WM; r++)
-#pragma unroll
-                    for (int c = 0; c < WN; c++)
-                        acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(a4[r], s), comp(b4[c], s), acc[r][c], 0, 0, 0);
-        }
-        lds_barrier();
-    }
-    // C / D: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int r = 0; r < WM; r++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int64_t row = r0 + wr + r * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (row >= k.M) continue;
-            const int64_t n = row / hwg;
-            const int q = (int)(row - n * hwg), y = q / k.Wg, x = q - y * k.Wg;
-            float *dst = k.y + (((size_t)n * k.Hout + (size_t)(y * k.os + ph.py)) * k.Wout + (size_t)(x * k.os + ph.px)) * k.Cout;
-#pragma unroll
-            for (int c = 0; c < WN; c++) {
-                const int co = c0 + wc + c * 32 + i;
-                if (co < k.Cout) dst[co] = acc[r][c][e];
-            }
-        }
 }
 
 // ---- InstanceNorm ----
@@ -491,23 +317,6 @@ __global__ void __launch_bounds__(256) nn_last_kernel(LastK k)
 }
 
 // ---- host side ----
-int launch_gemm(GemmK &k, int nph, int num_tiles_big_enough, hipStream_t stream)
-{
-    // 128 x 128 tiles where they still fill the chip (256 compute units), 64 x 64 otherwise; the sums' order is the same
-    const int64_t big = (k.M + 127) / 128 * ((k.Cout + 127) / 128) * nph;
-    if (big >= num_tiles_big_enough && k.Cout >= 128) {
-        k.tiles_n = (k.Cout + 127) / 128;
-        const int64_t tiles = (k.M + 127) / 128 * k.tiles_n;
-        hipLaunchKernelGGL((nn_gemm_kernel<2, 2>), dim3((unsigned)tiles, (unsigned)nph), dim3(256), 0, stream, k);
-    } else {
-        k.tiles_n = (k.Cout + 63) / 64;
-        const int64_t tiles = (k.M + 63) / 64 * k.tiles_n;
-        hipLaunchKernelGGL((nn_gemm_kernel<1, 1>), dim3((unsigned)tiles, (unsigned)nph), dim3(256), 0, stream, k);
-    }
-    SOAR_LAUNCH_OK("nn_gemm", stream, 0);
-    return 0;
-}
-
 int instance_norm(const float *x, const float *res, float *y, int N, int64_t hw, int C, double *part, float *stats, hipStream_t stream)
 {
     InK k{};
@@ -523,10 +332,17 @@ int instance_norm(const float *x, const float *res, float *y, int N, int64_t hw,
     return 0;
 }
 
-void conv_taps(Phase &p, const float *w)
+// one convolution over the batch's flat rows: grid Hg x Wg, input (gy stride + dy, gx stride + dx), output (gy os + py, gx os + px)
+ConvGemm conv_k(const float *x, float *y, int N, int Hin, int Win, int Cin, int Cout, int Hg, int Wg, int stride, int os, int reflect)
 {
-    p.w = w; p.ntaps = 9; p.py = p.px = 0;
-    for (int t = 0; t < 9; t++) { p.dy[t] = (signed char)(t / 3 - 1); p.dx[t] = (signed char)(t % 3 - 1); }
+    ConvGemm k{};
+    k.x = x; k.ldx = Cin; k.xim = (int64_t)Hin * Win;
+    k.y = y; k.ldy = Cout; k.yim = (int64_t)Hg * os * Wg * os; k.Wout = Wg * os; k.os = os;
+    k.alpha = 1.f;
+    k.N = N; k.Hg = Hg; k.Wg = Wg; k.Hin = Hin; k.Win = Win; k.Cin = Cin; k.Cout = Cout;
+    k.stride = stride; k.dil = 1; k.reflect = reflect;
+    k.nph = 1;
+    return k;
 }
 
 int run_generator(const Cfg &c, const SoarNormalNetArgs *a, const float *prior, const int64_t *prior_stride, const float *P, float *out,
@@ -551,50 +367,41 @@ int run_generator(const Cfg &c, const SoarNormalNetArgs *a, const float *prior, 
 
     for (int i = 0; i < c.n_down; i++) {
         const int nxt = (cur + 1) % 3;
-        GemmK k{};
-        k.x = buf[cur]; k.y = buf[nxt];
-        k.Hin = H; k.Win = W; k.Cin = C; k.Cout = 2 * C;
-        k.Hg = k.Hout = H / 2; k.Wg = k.Wout = W / 2; k.os = 1; k.stride = 2; k.reflect = 0;
-        k.M = (int64_t)N * k.Hg * k.Wg;
-        conv_taps(k.ph[0], P + WL.down[i]);
-        if (launch_gemm(k, 1, 256, stream)) return 1;
+        ConvGemm k = conv_k(buf[cur], buf[nxt], N, H, W, C, 2 * C, H / 2, W / 2, 2, 1, 0);
+        square_taps(k.ph[0], P + WL.down[i], 9 * C, 3, -1);
+        if (launch_conv_gemm(k, stream)) return 1;
         H /= 2; W /= 2; C *= 2;
         if (instance_norm(buf[nxt], nullptr, buf[nxt], N, (int64_t)H * W, C, part, stats, stream)) return 1;
         cur = nxt;
     }
     for (int b = 0; b < c.n_blocks; b++) {
         const int t1 = (cur + 1) % 3, t2 = (cur + 2) % 3;
-        GemmK k{};
-        k.Hin = k.Hg = k.Hout = H; k.Win = k.Wg = k.Wout = W; k.Cin = k.Cout = C; k.os = 1; k.stride = 1; k.reflect = 1;
-        k.M = (int64_t)N * H * W;
-        k.x = buf[cur]; k.y = buf[t1];
-        conv_taps(k.ph[0], P + WL.block(2 * b));
-        if (launch_gemm(k, 1, 256, stream)) return 1;
+        ConvGemm k = conv_k(buf[cur], buf[t1], N, H, W, C, C, H, W, 1, 1, 1);
+        square_taps(k.ph[0], P + WL.block(2 * b), 9 * C, 3, -1);
+        if (launch_conv_gemm(k, stream)) return 1;
         if (instance_norm(buf[t1], nullptr, buf[t1], N, (int64_t)H * W, C, part, stats, stream)) return 1;
         k.x = buf[t1]; k.y = buf[t2];
-        conv_taps(k.ph[0], P + WL.block(2 * b + 1));
-        if (launch_gemm(k, 1, 256, stream)) return 1;
+        square_taps(k.ph[0], P + WL.block(2 * b + 1), 9 * C, 3, -1);
+        if (launch_conv_gemm(k, stream)) return 1;
         if (instance_norm(buf[t2], buf[cur], buf[t2], N, (int64_t)H * W, C, part, stats, stream)) return 1;
         cur = t2;
     }
     for (int i = 0; i < c.n_down; i++) {
         const int nxt = (cur + 1) % 3;
-        GemmK k{};
-        k.x = buf[cur]; k.y = buf[nxt];
-        k.Hin = k.Hg = H; k.Win = k.Wg = W; k.Cin = C; k.Cout = C / 2;
-        k.Hout = 2 * H; k.Wout = 2 * W; k.os = 2; k.stride = 1; k.reflect = 0;
-        k.M = (int64_t)N * H * W;
+        ConvGemm k = conv_k(buf[cur], buf[nxt], N, H, W, C, C / 2, H, W, 1, 2, 0);
+        k.nph = 4;
         for (int ph = 0; ph < 4; ph++) {
-            Phase &p = k.ph[ph];
+            ConvTaps &p = k.ph[ph];
             p.w = P + WL.up[i][ph];
             p.py = ph >> 1; p.px = ph & 1;
             int ky[2], dy[2], kx[2], dx[2];
             const int ny = phase_axis_taps(p.py, ky, dy), nx = phase_axis_taps(p.px, kx, dx);
             p.ntaps = ny * nx;
+            p.ldw = (int64_t)p.ntaps * C;
             for (int ty = 0; ty < ny; ty++)
                 for (int tx = 0; tx < nx; tx++) { p.dy[ty * nx + tx] = (signed char)dy[ty]; p.dx[ty * nx + tx] = (signed char)dx[tx]; }
         }
-        if (launch_gemm(k, 4, 256, stream)) return 1;
+        if (launch_conv_gemm(k, stream)) return 1;
         H *= 2; W *= 2; C /= 2;
         if (instance_norm(buf[nxt], nullptr, buf[nxt], N, (int64_t)H * W, C, part, stats, stream)) return 1;
         cur = nxt;
@@ -638,11 +445,7 @@ extern "C" int soar_normalnet_pack_weights(int32_t ngf, int32_t n_down, int32_t 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     float *P = static_cast<float *>(packed);
     int ti = 0;
-    auto pack = [&](const float *w, float *dst, int cout, int cin, int kk) -> int {
-        hipLaunchKernelGGL(nn_pack_kernel, dim3(blocks((int64_t)cout * cin * kk)), dim3(256), 0, stream, w, dst, cout, cin, kk);
-        SOAR_LAUNCH_OK("nn_pack", stream, 0);
-        return 0;
-    };
+    auto pack = [&](const float *w, float *dst, int cout, int cin, int kk) { return launch_conv_pack(w, dst, nullptr, cout, cin, kk, 0, stream); };
     if (pack(tensors[ti++], P + L.first, ngf, CIN0, 49)) return 1;
     for (int i = 0; i < n_down; i++)
         if (pack(tensors[ti++], P + L.down[i], ngf << (i + 1), ngf << i, 9)) return 1;

@@ -1,16 +1,13 @@
 // vae.hip -- the Stable-Diffusion-2.1 VAE encoder (ldm AutoencoderKL, encoder + quant_conv) and the SDS guidance's loss tail
 // (soar_amd/sds.py), as include/soar_hip.h and DESIGN.md 9f state them.
 //
-//   vae_pack_kernel        torch [Cout][Cin][kk] -> [Cout][tap][Cin] (forward) and, spatially flipped and transposed,
-//                          [Cin][tap][Cout] (data gradient)
-//   vae_gemm_kernel        every convolution with Cin >= 128 and the attention's products: an implicit GEMM on
-//                          v_mfma_f32_32x32x2_f32 (exact f32 products), M = output pixels of one image, N = output channels,
-//                          K = taps x Cin ordered (tap, cin).  The four waves of a workgroup share a 64-pixel x 64-channel block tile
-//                          staged through LDS, 32 k at a time, double-buffered (each operand element is fetched from memory once per
-//                          workgroup instead of once per wave).  Taps: 1 x 1, 3 x 3 pad 1, 3 x 3 stride 2 (ldm's Downsample: pad
-//                          right / bottom by one), and the data gradient of the latter as a 3 x 3 convolution over the zero-dilated
-//                          output gradient (never materialised: odd dilated coordinates load zeros).  B may be per image (attention).
-//                          Epilogue: y = alpha acc + bias + res
+//   (conv_pack_kernel      conv_gemm.hip: torch [Cout][Cin][kk] -> [Cout][tap][Cin] (forward) and, spatially flipped and transposed,
+//                          [Cin][tap][Cout] (data gradient))
+//   (conv_gemm_kernel      conv_gemm.hip: every convolution with Cin >= 128 and the attention's products, as the shared implicit GEMM
+//                          with M = output pixels of one image, in 64 x 64 tiles.  Taps: 1 x 1, 3 x 3 pad 1, 3 x 3 stride 2 (ldm's
+//                          Downsample: pad right / bottom by one), and the data gradient of the latter as a 3 x 3 convolution over
+//                          the zero-dilated output gradient (never materialised: odd dilated coordinates load zeros).  B may be per
+//                          image (attention).  Epilogue: y = alpha acc + bias + res)
 //   vae_first_kernel       conv_in with the bilinear resize (align_corners=False, torch's source-index arithmetic) and x * 2 - 1 on
 //                          load, reading the caller's strides
 //   vae_gn_partial_kernel  GroupNorm (32 groups) sums per image and chunk of 256 pixels in double; forward: sum x, sum x^2; backward:
@@ -33,7 +30,7 @@
 //
 // No atomics: every value and gradient has one fixed order of summation, independent of N (bitwise reproducible, N = 4 equals four
 // N = 1 calls).  No host synchronisation, no allocation.  Offsets are size_t.
-#include "soar_common.h"
+#include "conv_gemm.h"
 
 namespace soar {
 
@@ -201,145 +198,6 @@ WsLayout ws_layout(const Dims &d)
     L.mid2.x = L.attn_out;
     L.total = off == 0 ? ALIGN : off;
     return L;
-}
-
-// ---- weight packing ----
-// w: torch [Cout][Cin][kk]; fwd[(co kk + t) Cin + ci]; bwd[(ci kk + kk - 1 - t) ldb + co]
-__global__ void __launch_bounds__(256) vae_pack_kernel(const float *__restrict__ w, float *__restrict__ fwd, float *__restrict__ bwd,
-                                                       int Cout, int Cin, int kk, int64_t ldb)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = (int64_t)Cout * Cin * kk;
-    if (e >= n) return;
-    const int t = (int)(e % kk);
-    const int64_t r = e / kk;
-    const int ci = (int)(r % Cin), co = (int)(r / Cin);
-    const float v = w[e];
-    fwd[((size_t)co * kk + t) * Cin + ci] = v;
-    bwd[((size_t)ci * kk + (kk - 1 - t)) * ldb + co] = v;
-}
-
-// ---- the implicit GEMM ----
-struct GemmK {
-    const float *x;        // A: image i's rows at x + i xim ldx; a row is one (input) pixel's Cin channels
-    int64_t ldx, xim;
-    const float *w;        // B: row co at w + i wbat + co ldw, k = tap Cin + ci
-    int64_t ldw, wbat;
-    const float *bias;     // [Cout] or NULL
-    const float *res;      // [.. ldy] or NULL, indexed as y
-    float *y;              // image i's row r at y + (i yim + r) ldy
-    int64_t ldy, yim;
-    float alpha;
-    int N, Hin, Win, Hout, Wout, Cin, Cout;
-    int taps, stride, off, dil;   // taps 1: A row = output row; taps 9: input (oy stride + ky + off, ...), in dilated space if dil = 2
-};
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int BM = 64, BN = 64, BK = 32;
-constexpr int LDSK = BK + 4;           // row pitch in floats: rows 16 B apart in bank space, float4 reads conflict-free per quarter
-
-// Block tile 64 x 64, waves 2 x 2 of 32 x 32 each.  Lane (i, h) of a wave: row / column i of its 32 x 32 block, k half h; step s of
-// the MFMA sums k = s (h = 0) and k = 16 + s (h = 1) of the chunk, so the order of every output's sum is fixed: chunk by chunk
-// (tap-major, then cin), within a chunk k = 0, 16, 1, 17, ... -- whatever the tile or N.
-// Staging: thread t loads row t >> 2 of A and of B, floats (t & 3) * 8 .. + 8 of the chunk, two float4 each, for the next chunk while
-// the MFMAs of this one run.
-__global__ void __launch_bounds__(256) vae_gemm_kernel(GemmK k)
-{
-    __shared__ float As[2][BM][LDSK], Bs[2][BN][LDSK];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int Mi = k.Hout * k.Wout;
-    const int tpi = (Mi + BM - 1) / BM, ntn = k.Cout / BN;
-    const int64_t tile = blockIdx.x;
-    const int tn = (int)(tile % ntn);
-    const int64_t rest = tile / ntn;
-    const int tm = (int)(rest % tpi);
-    const int img = (int)(rest / tpi);
-    const int r0 = tm * BM, c0 = tn * BN;
-
-    // the staging thread's row
-    const int srow = tid >> 2, sk = (tid & 3) * 8;
-    const int ar = r0 + srow;
-    const bool av = ar < Mi;
-    const int oy = av ? ar / k.Wout : 0, ox = av ? ar - (ar / k.Wout) * k.Wout : 0;
-    const float *xb = k.x + (size_t)img * k.xim * k.ldx;
-    const float *wb = k.w + (size_t)img * k.wbat + (size_t)(c0 + srow) * k.ldw + sk;
-    const int cpt = k.Cin / BK, nch = k.taps * cpt;
-
-    float4 na[2], nb[2];
-    auto fetch = [&](int ch) {
-        const int t = ch / cpt;
-        const int ci = (ch - t * cpt) * BK + sk;
-        const float *src = nullptr;
-        if (av) {
-            if (k.taps == 1) {
-                src = xb + (size_t)ar * k.ldx + ci;
-            } else {
-                int iy = oy * k.stride + t / 3 + k.off, ix = ox * k.stride + t % 3 + k.off;
-                bool ok = true;
-                if (k.dil == 2) {
-                    ok = iy >= 0 && ix >= 0 && !(iy & 1) && !(ix & 1);
-                    iy >>= 1; ix >>= 1;
-                }
-                ok = ok && iy >= 0 && iy < k.Hin && ix >= 0 && ix < k.Win;
-                if (ok) src = xb + ((size_t)iy * k.Win + ix) * k.ldx + ci;
-            }
-        }
-        if (src) {
-            na[0] = *reinterpret_cast<const float4 *>(src);
-            na[1] = *reinterpret_cast<const float4 *>(src + 4);
-        } else {
-            na[0] = na[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        const float *ws = wb + (size_t)ch * BK;
-        nb[0] = *reinterpret_cast<const float4 *>(ws);
-        nb[1] = *reinterpret_cast<const float4 *>(ws + 4);
-    };
-    auto stage = [&](int buf) {
-        *reinterpret_cast<float4 *>(&As[buf][srow][sk]) = na[0];
-        *reinterpret_cast<float4 *>(&As[buf][srow][sk + 4]) = na[1];
-        *reinterpret_cast<float4 *>(&Bs[buf][srow][sk]) = nb[0];
-        *reinterpret_cast<float4 *>(&Bs[buf][srow][sk + 4]) = nb[1];
-    };
-
-    const int i = lane & 31, h = lane >> 5;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[e] = 0.f;
-
-    fetch(0);
-    stage(0);
-    __syncthreads();
-    for (int ch = 0; ch < nch; ch++) {
-        const int buf = ch & 1;
-        if (ch + 1 < nch) fetch(ch + 1);
-        const float *ap = &As[buf][wr + i][h * 16], *bp = &Bs[buf][wc + i][h * 16];
-        float4 a4[4], b4[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            a4[j] = *reinterpret_cast<const float4 *>(ap + 4 * j);
-            b4[j] = *reinterpret_cast<const float4 *>(bp + 4 * j);
-        }
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            const float av_ = s % 4 == 0 ? a4[s / 4].x : s % 4 == 1 ? a4[s / 4].y : s % 4 == 2 ? a4[s / 4].z : a4[s / 4].w;
-            const float bv_ = s % 4 == 0 ? b4[s / 4].x : s % 4 == 1 ? b4[s / 4].y : s % 4 == 2 ? b4[s / 4].z : b4[s / 4].w;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av_, bv_, acc, 0, 0, 0);
-        }
-        if (ch + 1 < nch) stage(buf ^ 1);
-        __syncthreads();
-    }
-    // C / D: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-    const int co = c0 + wc + i;
-    const float bias = k.bias ? k.bias[co] : 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const int r = r0 + wr + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (r >= Mi) continue;
-        const size_t idx = ((size_t)img * k.yim + r) * k.ldy + co;
-        float v = acc[e] * k.alpha + bias;
-        if (k.res) v += k.res[idx];
-        k.y[idx] = v;
-    }
 }
 
 // ---- GroupNorm ----
@@ -967,18 +825,6 @@ __global__ void __launch_bounds__(LOSS_THREADS) sds_loss_kernel(SdsK k)
 }
 
 // ---- host side ----
-inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
-
-int launch_gemm(const GemmK &k, hipStream_t stream)
-{
-    const int64_t Mi = (int64_t)k.Hout * k.Wout;
-    const int64_t tiles = (int64_t)k.N * ((Mi + BM - 1) / BM) * (k.Cout / BN);
-    if (tiles == 0) return 0;
-    hipLaunchKernelGGL(vae_gemm_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, k);
-    SOAR_LAUNCH_OK("vae_gemm", stream, 0);
-    return 0;
-}
-
 struct Ctx {
     Dims d;
     WsLayout L;
@@ -990,17 +836,18 @@ struct Ctx {
     const float *R(size_t off) const { return P + off; }
 };
 
-// conv over NHWC activations: 3 x 3 pad 1 (taps 9) or 1 x 1, stride 1, at level lev
-GemmK conv_k(const Ctx &c, int lev, const float *x, int Cin, const float *w, int Cout, int taps, const float *bias, const float *res, float *y)
+// conv over NHWC activations: side x side taps at offset off (3 x 3 pad 1: off = -1), stride 1, at level lev
+ConvGemm conv_k(const Ctx &c, int lev, const float *x, int Cin, const float *w, int Cout, int side, int off, const float *bias,
+                const float *res, float *y)
 {
-    GemmK k{};
+    ConvGemm k{};
     const int S = c.d.S[lev];
     k.x = x; k.ldx = Cin; k.xim = (int64_t)S * S;
-    k.w = w; k.ldw = (int64_t)taps * Cin; k.wbat = 0;
     k.bias = bias; k.res = res; k.y = y; k.ldy = Cout; k.yim = (int64_t)S * S;
     k.alpha = 1.f;
-    k.N = c.d.N; k.Hin = S; k.Win = S; k.Hout = S; k.Wout = S; k.Cin = Cin; k.Cout = Cout;
-    k.taps = taps; k.stride = 1; k.off = -1; k.dil = 1;
+    k.N = c.d.N; k.Hin = S; k.Win = S; k.Hg = S; k.Wg = S; k.Wout = S; k.os = 1; k.Cin = Cin; k.Cout = Cout;
+    k.stride = 1; k.dil = 1; k.per_image = 1; k.nph = 1;
+    square_taps(k.ph[0], w, (int64_t)side * side * Cin, side, off);
     return k;
 }
 
@@ -1046,29 +893,27 @@ int rb_forward(const Ctx &c, int lev, const RB &b, const RBws &s, float *out)
     const float *x = c.F(s.x);
     float *tmp = c.F(c.L.tmp), *h1 = c.F(s.h1);
     if (gn_forward(c, x, hw, b.cin, c.R(b.n1g), c.R(b.n1b), c.F(s.st1), tmp, 1)) return 1;
-    if (launch_gemm(conv_k(c, lev, tmp, b.cin, c.R(b.c1f), b.cout, 9, c.R(b.c1b), nullptr, h1), c.stream)) return 1;
+    if (launch_conv_gemm(conv_k(c, lev, tmp, b.cin, c.R(b.c1f), b.cout, 3, -1, c.R(b.c1b), nullptr, h1), c.stream)) return 1;
     if (gn_forward(c, h1, hw, b.cout, c.R(b.n2g), c.R(b.n2b), c.F(s.st2), tmp, 1)) return 1;
     const float *res = x;
     if (b.cin != b.cout) {
-        GemmK k = conv_k(c, lev, x, b.cin, c.R(b.ninf), b.cout, 1, c.R(b.ninb), nullptr, out);
-        k.off = 0;
-        if (launch_gemm(k, c.stream)) return 1;
+        ConvGemm k = conv_k(c, lev, x, b.cin, c.R(b.ninf), b.cout, 1, 0, c.R(b.ninb), nullptr, out);
+        if (launch_conv_gemm(k, c.stream)) return 1;
         res = out;
     }
-    return launch_gemm(conv_k(c, lev, tmp, b.cout, c.R(b.c2f), b.cout, 9, c.R(b.c2b), res, out), c.stream);
+    return launch_conv_gemm(conv_k(c, lev, tmp, b.cout, c.R(b.c2f), b.cout, 3, -1, c.R(b.c2b), res, out), c.stream);
 }
 // g: gradient of the block's output (kept); writes the gradient of its input into gx.  t1 / t2: scratch at the level's size
 int rb_backward(const Ctx &c, int lev, const RB &b, const RBws &s, const float *g, float *gx, float *t1, float *t2)
 {
     const int64_t hw = (int64_t)c.d.S[lev] * c.d.S[lev];
-    if (launch_gemm(conv_k(c, lev, g, b.cout, c.R(b.c2r), b.cout, 9, nullptr, nullptr, t1), c.stream)) return 1;
+    if (launch_conv_gemm(conv_k(c, lev, g, b.cout, c.R(b.c2r), b.cout, 3, -1, nullptr, nullptr, t1), c.stream)) return 1;
     if (gn_backward(c, c.F(s.h1), hw, b.cout, c.R(b.n2g), c.R(b.n2b), c.F(s.st2), t1, nullptr, t1, 1)) return 1;
-    if (launch_gemm(conv_k(c, lev, t1, b.cout, c.R(b.c1r), b.cin, 9, nullptr, nullptr, t2), c.stream)) return 1;
+    if (launch_conv_gemm(conv_k(c, lev, t1, b.cout, c.R(b.c1r), b.cin, 3, -1, nullptr, nullptr, t2), c.stream)) return 1;
     const float *res = g;
     if (b.cin != b.cout) {
-        GemmK k = conv_k(c, lev, g, b.cout, c.R(b.ninr), b.cin, 1, nullptr, nullptr, t1);
-        k.off = 0;
-        if (launch_gemm(k, c.stream)) return 1;
+        ConvGemm k = conv_k(c, lev, g, b.cout, c.R(b.ninr), b.cin, 1, 0, nullptr, nullptr, t1);
+        if (launch_conv_gemm(k, c.stream)) return 1;
         res = t1;
     }
     return gn_backward(c, c.F(s.x), hw, b.cin, c.R(b.n1g), c.R(b.n1b), c.F(s.st1), t2, res, gx, 1);
@@ -1084,15 +929,15 @@ int transpose(const Ctx &c, const float *x, int64_t ld, int R, int C, int c0, fl
     return 0;
 }
 // a product of per-image row-major operands: y[i] (rows M, ldy) = alpha x[i] (M x K, ldx) B[i]^T with B[i] rows Cout x K at ldw
-GemmK mm_k(const Ctx &c, const float *x, int64_t ldx, int64_t xim, int M, int K, const float *w, int64_t ldw, int64_t wbat, int Cout,
-           float *y, int64_t ldy, int64_t yim)
+ConvGemm mm_k(const Ctx &c, const float *x, int64_t ldx, int64_t xim, int M, int K, const float *w, int64_t ldw, int64_t wbat, int Cout,
+              float *y, int64_t ldy, int64_t yim)
 {
-    GemmK k{};
-    k.x = x; k.ldx = ldx; k.xim = xim;
-    k.w = w; k.ldw = ldw; k.wbat = wbat;
+    ConvGemm k{};
+    k.x = x; k.ldx = ldx; k.xim = xim; k.wbat = wbat;
     k.y = y; k.ldy = ldy; k.yim = yim; k.alpha = 1.f;
-    k.N = c.d.N; k.Hin = 1; k.Win = M; k.Hout = 1; k.Wout = M; k.Cin = K; k.Cout = Cout;
-    k.taps = 1; k.stride = 1; k.off = 0; k.dil = 1;
+    k.N = c.d.N; k.Hin = 1; k.Win = M; k.Hg = 1; k.Wg = M; k.Wout = M; k.os = 1; k.Cin = K; k.Cout = Cout;
+    k.stride = 1; k.dil = 1; k.per_image = 1; k.nph = 1;
+    square_taps(k.ph[0], w, ldw, 1, 0);
     return k;
 }
 
@@ -1104,24 +949,24 @@ int attn_forward(const Ctx &c)
     float *tmp = c.F(c.L.tmp), *qkv = c.F(c.L.qkv), *P = c.F(c.L.P), *vT = c.F(c.L.vT), *O = c.F(c.L.O);
     if (gn_forward(c, x, T, CMID, c.R(c.W.an_g), c.R(c.W.an_b), c.F(c.L.an_st), tmp, 0)) return 1;
     if (Tp != T) SOAR_HIP_OK(hipMemsetAsync(qkv, 0, (size_t)d.N * Tp * C3 * sizeof(float), c.stream));
-    GemmK k = mm_k(c, tmp, CMID, T, T, CMID, c.R(c.W.qkv_f), CMID, 0, C3, qkv, C3, Tp);
+    ConvGemm k = mm_k(c, tmp, CMID, T, T, CMID, c.R(c.W.qkv_f), CMID, 0, C3, qkv, C3, Tp);
     k.bias = c.R(c.W.qkv_b);
-    if (launch_gemm(k, c.stream)) return 1;
+    if (launch_conv_gemm(k, c.stream)) return 1;
     // scores into the dP buffer, then P
     float *Sc = c.F(c.L.dP);
     k = mm_k(c, qkv, C3, Tp, Tp, CMID, qkv + CMID, C3, (int64_t)Tp * C3, Tp, Sc, Tp, Tp);
     k.alpha = 1.f / sqrtf((float)CMID);
-    if (launch_gemm(k, c.stream)) return 1;
+    if (launch_conv_gemm(k, c.stream)) return 1;
     SmK sm{};
     sm.s = Sc; sm.out = P; sm.rows = (int64_t)d.N * Tp; sm.T = T; sm.Tp = Tp;
     hipLaunchKernelGGL(vae_softmax_kernel, dim3((unsigned)((sm.rows + 3) / 4)), dim3(256), 0, c.stream, sm);
     SOAR_LAUNCH_OK("vae_softmax", c.stream, 0);
     if (transpose(c, qkv, C3, Tp, CMID, 2 * CMID, vT)) return 1;
-    if (launch_gemm(mm_k(c, P, Tp, Tp, Tp, Tp, vT, Tp, (int64_t)CMID * Tp, CMID, O, CMID, Tp), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, P, Tp, Tp, Tp, Tp, vT, Tp, (int64_t)CMID * Tp, CMID, O, CMID, Tp), c.stream)) return 1;
     k = mm_k(c, O, CMID, Tp, T, CMID, c.R(c.W.p_f), CMID, 0, CMID, c.F(c.L.attn_out), CMID, T);
     k.bias = c.R(c.W.p_b);
     k.res = x;
-    return launch_gemm(k, c.stream);
+    return launch_conv_gemm(k, c.stream);
 }
 // g: gradient of the attention block's output; writes the gradient of its input into gx (t: scratch)
 int attn_backward(const Ctx &c, const float *g, float *gx, float *t)
@@ -1131,25 +976,25 @@ int attn_backward(const Ctx &c, const float *g, float *gx, float *t)
     const float *qkv = c.F(c.L.qkv), *P = c.F(c.L.P);
     float *dO = c.F(c.L.dO), *dOT = c.F(c.L.dOT), *dP = c.F(c.L.dP), *XT = c.F(c.L.XT), *dqkv = c.F(c.L.dqkv);
     if (Tp != T) SOAR_HIP_OK(hipMemsetAsync(dO, 0, (size_t)d.N * Tp * CMID * sizeof(float), c.stream));
-    if (launch_gemm(mm_k(c, g, CMID, T, T, CMID, c.R(c.W.p_r), CMID, 0, CMID, dO, CMID, Tp), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, g, CMID, T, T, CMID, c.R(c.W.p_r), CMID, 0, CMID, dO, CMID, Tp), c.stream)) return 1;
     // dV = P^T dO
     if (transpose(c, P, Tp, Tp, Tp, 0, XT)) return 1;
     if (transpose(c, dO, CMID, Tp, CMID, 0, dOT)) return 1;
-    if (launch_gemm(mm_k(c, XT, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv + 2 * CMID, C3, Tp), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, XT, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv + 2 * CMID, C3, Tp), c.stream)) return 1;
     // dP = dO V^T, dS in place
-    if (launch_gemm(mm_k(c, dO, CMID, Tp, Tp, CMID, qkv + 2 * CMID, C3, (int64_t)Tp * C3, Tp, dP, Tp, Tp), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, dO, CMID, Tp, Tp, CMID, qkv + 2 * CMID, C3, (int64_t)Tp * C3, Tp, dP, Tp, Tp), c.stream)) return 1;
     SmK sm{};
     sm.s = P; sm.dp = dP; sm.out = dP; sm.rows = (int64_t)d.N * Tp; sm.T = T; sm.Tp = Tp; sm.alpha = 1.f / sqrtf((float)CMID);
     hipLaunchKernelGGL(vae_softmax_bwd_kernel, dim3((unsigned)((sm.rows + 3) / 4)), dim3(256), 0, c.stream, sm);
     SOAR_LAUNCH_OK("vae_softmax_bwd", c.stream, 0);
     // dQ = dS K, dK = dS^T Q
     if (transpose(c, qkv, C3, Tp, CMID, CMID, dOT)) return 1;
-    if (launch_gemm(mm_k(c, dP, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv, C3, Tp), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, dP, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv, C3, Tp), c.stream)) return 1;
     if (transpose(c, dP, Tp, Tp, Tp, 0, XT)) return 1;
     if (transpose(c, qkv, C3, Tp, CMID, 0, dOT)) return 1;
-    if (launch_gemm(mm_k(c, XT, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv + CMID, C3, Tp), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, XT, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv + CMID, C3, Tp), c.stream)) return 1;
     // d(normed input) = [dQ dK dV] [Wq; Wk; Wv], then the GroupNorm (no SiLU) + the residual
-    if (launch_gemm(mm_k(c, dqkv, C3, Tp, T, C3, c.R(c.W.qkv_r), C3, 0, CMID, t, CMID, T), c.stream)) return 1;
+    if (launch_conv_gemm(mm_k(c, dqkv, C3, Tp, T, C3, c.R(c.W.qkv_r), C3, 0, CMID, t, CMID, T), c.stream)) return 1;
     return gn_backward(c, c.F(c.L.mid1_out), T, CMID, c.R(c.W.an_g), c.R(c.W.an_b), c.F(c.L.an_st), t, g, gx, 0);
 }
 
@@ -1212,11 +1057,8 @@ extern "C" int soar_vae_pack_weights(const float *raw, size_t raw_floats, void *
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     float *P = static_cast<float *>(packed);
     SOAR_HIP_OK(hipMemcpyAsync(P, raw, L.raw_total * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    auto pack = [&](size_t src, size_t fwd, size_t bwd, int Cout, int Cin, int kk, int64_t ldb) -> int {
-        const int64_t n = (int64_t)Cout * Cin * kk;
-        hipLaunchKernelGGL(vae_pack_kernel, dim3(blocks(n)), dim3(256), 0, stream, raw + src, P + fwd, P + bwd, Cout, Cin, kk, ldb);
-        SOAR_LAUNCH_OK("vae_pack", stream, 0);
-        return 0;
+    auto pack = [&](size_t src, size_t fwd, size_t bwd, int Cout, int Cin, int kk, int64_t ldb) {
+        return launch_conv_pack(raw + src, P + fwd, P + bwd, Cout, Cin, kk, ldb, stream);
     };
     auto pack_rb = [&](const RB &b) -> int {
         if (pack(b.c1w, b.c1f, b.c1r, b.cout, b.cin, 9, b.cout)) return 1;
@@ -1274,10 +1116,10 @@ extern "C" int soar_vae_forward(const SoarVaeArgs *a, void *workspace, size_t wo
         for (int j = 0; j < 2; j++)
             if (rb_forward(c, l, c.W.rb[l][j], c.L.rb[l][j], c.F(c.L.rb_out[l][j]))) return 1;
         if (l == 3) break;
-        GemmK k = conv_k(c, l, c.F(c.L.rb_out[l][1]), LEVC[l], c.R(c.W.df[l]), LEVC[l], 9, c.R(c.W.db[l]), nullptr, c.F(c.L.down[l]));
-        k.Hout = k.Wout = d.S[l + 1]; k.yim = (int64_t)d.S[l + 1] * d.S[l + 1];
-        k.stride = 2; k.off = 0;                      // pad right / bottom by one: the bounds check loads the zeros
-        if (launch_gemm(k, c.stream)) return 1;
+        ConvGemm k = conv_k(c, l, c.F(c.L.rb_out[l][1]), LEVC[l], c.R(c.W.df[l]), LEVC[l], 3, 0, c.R(c.W.db[l]), nullptr, c.F(c.L.down[l]));
+        k.Hg = k.Wg = k.Wout = d.S[l + 1]; k.yim = (int64_t)d.S[l + 1] * d.S[l + 1];
+        k.stride = 2;                                 // taps at 0 .. 2: pad right / bottom by one, the bounds check loads the zeros
+        if (launch_conv_gemm(k, c.stream)) return 1;
     }
     if (rb_forward(c, 3, c.W.mid1, c.L.mid1, c.F(c.L.mid1_out))) return 1;
     if (attn_forward(c)) return 1;
@@ -1333,10 +1175,10 @@ extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t w
         if (l < 3) {
             // the downsample's data gradient: a 3 x 3 pad-2-top-left convolution over the zero-dilated gradient (the padded row and
             // column are never produced)
-            GemmK k = conv_k(c, l, G[0], LEVC[l], c.R(c.W.dr[l]), LEVC[l], 9, nullptr, nullptr, G[1]);
+            ConvGemm k = conv_k(c, l, G[0], LEVC[l], c.R(c.W.dr[l]), LEVC[l], 3, -2, nullptr, nullptr, G[1]);
             k.Hin = k.Win = d.S[l + 1]; k.xim = (int64_t)d.S[l + 1] * d.S[l + 1];
-            k.off = -2; k.dil = 2;
-            if (launch_gemm(k, c.stream)) return 1;
+            k.dil = 2;
+            if (launch_conv_gemm(k, c.stream)) return 1;
             rot();
         }
         for (int j = 1; j >= 0; j--) {

@@ -13,6 +13,9 @@ CASES = {
     "bottom2x2": (8, 4, 2, 1, 32, 32, 11),          # 2 x 2 at the bottom level; every channel count below a tile
     "offtile": (24, 3, 2, 2, 48, 80, 12),           # channels 24 .. 192, not square, two frames
     "workload": (8, 4, 1, 1, 512, 512, 13),         # the workload's spatial size
+    # 130 x 126 at the bottom level: M = 32760 at N = 2 is 256 tiles of 128 x 128 (the last one 120 rows), so the down convolution
+    # and the trunk take the big tile; a single frame (128 tiles) takes 64 x 64
+    "tiles128": (64, 1, 1, 2, 260, 252, 14),
 }
 NORM_FLOOR = 1e-3          # pixels whose float64 three-vector is shorter than this before the normalisation are not compared per element
 
