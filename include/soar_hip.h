@@ -55,7 +55,8 @@ extern "C" {
  * soar_frames_geometry_warp_backward_losses (+ SoarLossFinish), soar_adam_step_at_gather: two small launches of the step plan folded
  * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation).
  * soar_normalnet_weights_bytes / _pack_weights / _workspace_bytes / _forward (+ SoarNormalNetArgs), soar_normal_crop_boxes / _sample /
- * _bytes: normal-map preprocessing. */
+ * _bytes: normal-map preprocessing.  soar_selftest_conv_gemm / _conv_pack (+ SoarConvGemmArgs, SoarConvGemmTaps): the shared
+ * implicit-GEMM convolution and its weight packer by themselves, for the tests. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -815,6 +816,55 @@ int soar_selftest_affine_scan(const float *m64_dev, const float *b64_dev, float 
 /* ---- device self-test of the blend kernels' exp: out_dev[i] = the kernels' exp(x[i]), expf_dev[i] = the device math
  * library's expf(x[i]) (what the reference's `exp(power)` becomes when built for this GPU); equal bit for bit on [-87, 0]. */
 int soar_selftest_exp(const float *x_dev, int32_t n, float *out_dev, float *expf_dev, void *stream);
+
+/* ---- the shared implicit-GEMM convolution and the weight packer by themselves (csrc/conv_gemm.h): what the VAE
+ * encoder, the normal networks and LPIPS reach only through whole networks, for tests/test_conv_gemm_*.py.
+ * SoarConvGemmTaps / SoarConvGemmArgs mirror ConvTaps / ConvGemm of csrc/conv_gemm.h field by field (the launcher's tiles_* left out).
+ * One tap table: output (gy os + py, gx os + px) of grid row (n, gy, gx) sums, tap by tap, input (gy stride + dy, gx stride + dx)
+ * times w[co][tap][ci]: row co of B at w + image wbat + co ldw, k = tap Cin + ci.  y = alpha (A B^T) + bias + res:
+ *   x      image n's pixel (iy, ix) at x + (n xim + iy Win + ix) ldx, Cin floats (Cin a multiple of 8)
+ *   wbat   B's offset per image (per_image only)
+ *   bias   [Cout] or NULL; res: indexed as y, or NULL
+ *   y      image n's output pixel (oy, ox) at y + (n yim + oy Wout + ox) ldy, Cout floats
+ *   N, Hg, Wg   the grid a row walks: N Hg Wg rows, at most 2^30
+ *   dil    1, or 2: the input is x zero-dilated by two (odd coordinates load zeros, even ones x at half; zero padding only)
+ *   reflect     outside the input: mirrored once (-i, 2 (n - 1) - i), or zero
+ *   per_image   1: 64 x 64 tiles that never cross an image; 0: tiles over the batch's flat rows, 128 x 128 where those still fill
+ *               the chip and Cout >= 128
+ *   nph    tap tables in use, 1 .. 4 (the phases of a transposed convolution)
+ * soar_selftest_conv_gemm hands the descriptor to the networks' own launcher and writes the side of the tile that launcher picks (64
+ * or 128) to *tile_out.  The launcher refuses, with nothing launched: more than 2^30 rows; Cin no multiple of 8; nph outside
+ * 1 .. 4; wbat without per_image; dil not 1 or 2, or 2 with reflect; stride, os, Cout, Hin or Win below 1; NULL x, y or a table's w;
+ * x or w off 16 bytes, ldx, ldw or wbat no multiple of 4; ntaps outside 1 .. 9; py or px outside [0, os); with reflect, a coordinate
+ * gy stride + dy outside [-(Hin - 1), 2 (Hin - 1)], likewise along x.  N Hg Wg == 0 is a no-op.
+ * soar_selftest_conv_pack: torch [Cout][Cin][kk] -> fwd [Cout][kk][Cin] and, unless bwd is NULL, the data gradient's form, spatially
+ * flipped and transposed: bwd[(ci kk + kk - 1 - t) ldb + co] (ldb >= Cout; the columns behind Cout are left alone). */
+typedef struct SoarConvGemmTaps {
+    const float *w;
+    int64_t ldw;
+    int32_t ntaps, py, px;
+    int8_t dy[9], dx[9];
+} SoarConvGemmTaps;
+typedef struct SoarConvGemmArgs {
+    const float *x;
+    int64_t ldx, xim;
+    int64_t wbat;
+    const float *bias;
+    const float *res;
+    float *y;
+    int64_t ldy, yim;
+    float alpha;
+    int32_t N, Hg, Wg;
+    int32_t Hin, Win, Cin, Cout;
+    int32_t stride, dil;
+    int32_t reflect;
+    int32_t Wout, os;
+    int32_t per_image;
+    int32_t nph;
+    SoarConvGemmTaps ph[4];
+} SoarConvGemmArgs;
+int soar_selftest_conv_gemm(const SoarConvGemmArgs *args, int32_t *tile_out, void *stream);
+int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb, void *stream);
 
 /* ---- mesh export (mesh.hip, soar_amd/mesh.py; DESIGN.md "Mesh export").  Not part of the training step.
  * soar_tsdf_integrate: fuses n_views (1..64) rendered depth / opacity planes [n_views][H][W] into the TSDF of a dense grid

@@ -44,7 +44,13 @@ struct ConvGemm {
     ConvTaps ph[4];
     int tiles_n, tiles_img;        // (the launcher's)
 };
+// Refuses (set_error, 1, nothing launched) a descriptor the kernel cannot run: more than 2^30 rows; Cin no multiple of 8; nph outside
+// 1 .. 4; wbat without per_image; dil not 1 or 2, or 2 with reflect; stride, os, Cout, Hin or Win below 1; x, y or a table's w NULL; x
+// or w off 16 bytes, or ldx, ldw, wbat no multiple of 4 (the loads are float4); a table with ntaps outside 1 .. 9 or py, px outside
+// [0, os); with reflect, a coordinate gy stride + dy outside [-(Hin - 1), 2 (Hin - 1)] (mirror() reflects once), likewise along x.
 int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream);
+// the side of the tile launch_conv_gemm picks for desc: 128 or 64
+int conv_gemm_tile(const ConvGemm &desc);
 
 // torch [Cout][Cin][kk] -> fwd [Cout][kk][Cin] and, unless bwd is NULL, the data gradient's form, spatially flipped and transposed:
 // bwd[(ci kk + kk - 1 - t) ldb + co]

@@ -8,6 +8,8 @@
 //                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = alpha acc + bias + res, scattered
 //                          to the tap table's output parity
 //
+// The launcher refuses the descriptors the kernel cannot run (conv_gemm.h); soar_selftest_conv_gemm / _conv_pack at the end of the
+// file reach the launcher and the packer by themselves (tests/test_conv_gemm_*.py).
 // No atomics: every output has one fixed order of summation, the same whatever the tile and the batch.
 #include "conv_gemm.h"
 
@@ -185,22 +187,79 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(ConvGemm k)
         }
 }
 
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// what the kernel takes for granted of a descriptor with rows (conv_gemm.h); false and set_error where it does not hold
+bool check_desc(const ConvGemm &k, int64_t M)
+{
+    if (k.N < 0 || k.Hg < 0 || k.Wg < 0 || M > (int64_t(1) << 30) || k.Cin < 8 || k.Cin % 8 || k.nph < 1 || k.nph > 4 || (!k.per_image && k.wbat)) {
+        set_error("conv_gemm: need at most 2^30 rows, Cin a multiple of 8, 1 .. 4 tap tables, B per image only with tiles per image "
+                  "(rows=%lld, Cin=%d, nph=%d)", (long long)M, k.Cin, k.nph);
+        return false;
+    }
+    if ((k.dil != 1 && k.dil != 2) || (k.dil == 2 && k.reflect)) {
+        set_error("conv_gemm: dil must be 1, or 2 with zero padding (dil=%d, reflect=%d)", k.dil, k.reflect);
+        return false;
+    }
+    if (k.stride < 1 || k.os < 1 || k.Cout < 1 || k.Hin < 1 || k.Win < 1) {
+        set_error("conv_gemm: stride, os, Cout, Hin and Win must be at least 1 (stride=%d, os=%d, Cout=%d, Hin=%d, Win=%d)", k.stride, k.os,
+                  k.Cout, k.Hin, k.Win);
+        return false;
+    }
+    if (!k.x || !k.y) { set_error("conv_gemm: NULL %s", k.x ? "y" : "x"); return false; }
+    if (!aligned16(k.x) || k.ldx % 4 || k.wbat % 4) {
+        set_error("conv_gemm: x must be 16-byte aligned, ldx and wbat multiples of 4: the loads are float4 (x=%p, ldx=%lld, wbat=%lld)",
+                  (const void *)k.x, (long long)k.ldx, (long long)k.wbat);
+        return false;
+    }
+    for (int p = 0; p < k.nph; p++) {
+        const ConvTaps &t = k.ph[p];
+        if (t.ntaps < 1 || t.ntaps > 9) { set_error("conv_gemm: tap table %d: ntaps must be 1 .. 9 (got %d)", p, t.ntaps); return false; }
+        if (t.py < 0 || t.py >= k.os || t.px < 0 || t.px >= k.os) {
+            set_error("conv_gemm: tap table %d: py and px must lie in [0, os) (py=%d, px=%d, os=%d)", p, t.py, t.px, k.os);
+            return false;
+        }
+        if (!t.w) { set_error("conv_gemm: tap table %d: NULL w", p); return false; }
+        if (!aligned16(t.w) || t.ldw % 4) {
+            set_error("conv_gemm: tap table %d: w must be 16-byte aligned and ldw a multiple of 4: the loads are float4 (w=%p, ldw=%lld)", p,
+                      (const void *)t.w, (long long)t.ldw);
+            return false;
+        }
+        if (!k.reflect) continue;
+        // mirror() reflects once: a coordinate further out than the image is wide would land outside it again
+        int dy0 = t.dy[0], dy1 = t.dy[0], dx0 = t.dx[0], dx1 = t.dx[0];
+        for (int i = 1; i < t.ntaps; i++) {
+            dy0 = t.dy[i] < dy0 ? t.dy[i] : dy0; dy1 = t.dy[i] > dy1 ? t.dy[i] : dy1;
+            dx0 = t.dx[i] < dx0 ? t.dx[i] : dx0; dx1 = t.dx[i] > dx1 ? t.dx[i] : dx1;
+        }
+        const int64_t y1 = (int64_t)(k.Hg - 1) * k.stride + dy1, x1 = (int64_t)(k.Wg - 1) * k.stride + dx1;
+        if (dy0 < -(k.Hin - 1) || y1 > 2 * (int64_t)(k.Hin - 1) || dx0 < -(k.Win - 1) || x1 > 2 * (int64_t)(k.Win - 1)) {
+            set_error("conv_gemm: tap table %d: reflect mirrors once: rows %d .. %lld of a %d-row input, columns %d .. %lld of a %d-column "
+                      "input must lie in [-(n - 1), 2 (n - 1)]", p, dy0, (long long)y1, k.Hin, dx0, (long long)x1, k.Win);
+            return false;
+        }
+    }
+    return true;
+}
+
 }  // namespace
+
+// 128 x 128 tiles where they still fill the chip (256 compute units), 64 x 64 otherwise; the sums' order is the same
+int conv_gemm_tile(const ConvGemm &k)
+{
+    const int64_t M = (int64_t)k.N * k.Hg * k.Wg;
+    const int64_t big = (M + 127) / 128 * ((k.Cout + 127) / 128) * k.nph;
+    return !k.per_image && big >= 256 && k.Cout >= 128 ? 128 : 64;
+}
 
 int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream)
 {
     ConvGemm k = desc;
     const int64_t hwg = (int64_t)k.Hg * k.Wg, M = k.N * hwg;
     if (M == 0) return 0;
-    if (M > (int64_t(1) << 30) || k.Cin % 8 || k.nph < 1 || k.nph > 4 || (!k.per_image && k.wbat)) {
-        set_error("conv_gemm: need at most 2^30 rows, Cin a multiple of 8, 1 .. 4 tap tables, B per image only with tiles per image "
-                  "(rows=%lld, Cin=%d, nph=%d)", (long long)M, k.Cin, k.nph);
-        return 1;
-    }
-    // 128 x 128 tiles where they still fill the chip (256 compute units), 64 x 64 otherwise; the sums' order is the same
-    const int64_t big = (M + 127) / 128 * ((k.Cout + 127) / 128) * k.nph;
-    const bool big_tiles = !k.per_image && big >= 256 && k.Cout >= 128;
-    const int bt = big_tiles ? 128 : 64;
+    if (!check_desc(k, M)) return 1;
+    const int bt = conv_gemm_tile(k);
+    const bool big_tiles = bt == 128;
     k.tiles_n = (k.Cout + bt - 1) / bt;
     k.tiles_img = (int)((hwg + bt - 1) / bt);
     const int64_t tiles = (k.per_image ? (int64_t)k.N * k.tiles_img : (M + bt - 1) / bt) * k.tiles_n;
@@ -218,3 +277,34 @@ int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, 
 }
 
 }  // namespace soar
+
+// ---- the launcher and the packer by themselves (tests/test_conv_gemm_*.py) ----
+extern "C" int soar_selftest_conv_gemm(const SoarConvGemmArgs *a, int32_t *tile_out, void *stream_)
+{
+    if (!a || !tile_out) { soar::set_error("soar_selftest_conv_gemm: NULL %s", a ? "tile_out" : "args"); return 1; }
+    soar::ConvGemm k{};
+    k.x = a->x; k.ldx = a->ldx; k.xim = a->xim; k.wbat = a->wbat;
+    k.bias = a->bias; k.res = a->res; k.y = a->y; k.ldy = a->ldy; k.yim = a->yim; k.alpha = a->alpha;
+    k.N = a->N; k.Hg = a->Hg; k.Wg = a->Wg; k.Hin = a->Hin; k.Win = a->Win; k.Cin = a->Cin; k.Cout = a->Cout;
+    k.stride = a->stride; k.dil = a->dil; k.reflect = a->reflect; k.Wout = a->Wout; k.os = a->os;
+    k.per_image = a->per_image; k.nph = a->nph;
+    for (int p = 0; p < 4; p++) {
+        const SoarConvGemmTaps &s = a->ph[p];
+        soar::ConvTaps &t = k.ph[p];
+        t.w = s.w; t.ldw = s.ldw; t.ntaps = s.ntaps; t.py = s.py; t.px = s.px;
+        for (int i = 0; i < 9; i++) { t.dy[i] = s.dy[i]; t.dx[i] = s.dx[i]; }
+    }
+    *tile_out = soar::conv_gemm_tile(k);
+    return soar::launch_conv_gemm(k, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb,
+                                       void *stream_)
+{
+    if (!w || !fwd || Cout < 1 || Cin < 1 || kk < 1 || (bwd && ldb < Cout)) {
+        soar::set_error("soar_selftest_conv_pack: need w, fwd, positive sizes and ldb >= Cout (Cout=%d, Cin=%d, kk=%d, ldb=%lld)", Cout, Cin,
+                        kk, (long long)ldb);
+        return 1;
+    }
+    return soar::launch_conv_pack(w, fwd, bwd, Cout, Cin, kk, ldb, static_cast<hipStream_t>(stream_));
+}

@@ -192,6 +192,21 @@ class SoarNormalNetArgs(C.Structure):
                 ("prior_B_stride", C.c_int64 * 4), ("weights_F", _vp), ("weights_B", _vp), ("normal_F", _vp), ("normal_B", _vp)]
 
 
+class SoarConvGemmTaps(C.Structure):
+    """Mirror of ``struct SoarConvGemmTaps`` (include/soar_hip.h)."""
+    _fields_ = [("w", _vp), ("ldw", C.c_int64), ("ntaps", C.c_int32), ("py", C.c_int32), ("px", C.c_int32), ("dy", C.c_int8 * 9),
+                ("dx", C.c_int8 * 9)]
+
+
+class SoarConvGemmArgs(C.Structure):
+    """Mirror of ``struct SoarConvGemmArgs`` (include/soar_hip.h)."""
+    _fields_ = [("x", _vp), ("ldx", C.c_int64), ("xim", C.c_int64), ("wbat", C.c_int64), ("bias", _vp), ("res", _vp), ("y", _vp),
+                ("ldy", C.c_int64), ("yim", C.c_int64), ("alpha", C.c_float), ("N", C.c_int32), ("Hg", C.c_int32), ("Wg", C.c_int32),
+                ("Hin", C.c_int32), ("Win", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("stride", C.c_int32), ("dil", C.c_int32),
+                ("reflect", C.c_int32), ("Wout", C.c_int32), ("os", C.c_int32), ("per_image", C.c_int32), ("nph", C.c_int32),
+                ("ph", SoarConvGemmTaps * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -279,6 +294,8 @@ SIGNATURES = {
                                                   C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "soar_selftest_exp": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "soar_selftest_affine_scan": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "soar_selftest_conv_gemm": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.POINTER(C.c_int32), _vp]),
+    "soar_selftest_conv_pack": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp]),
     "soar_prof_enable": (C.c_int, [C.c_int]),
     "soar_prof_reset": (C.c_int, []),
     "soar_prof_stage_count": (C.c_int, []),
