@@ -1402,6 +1402,57 @@ int soar_normal_crop_sample(int32_t N, int32_t H, int32_t W, int32_t S, const ui
 int soar_normal_crop_bytes(int32_t N, int32_t H, int32_t W, const float *normal_F, const float *normal_B, const float *mask,
                            uint8_t *out_F, uint8_t *out_B, uint8_t *out_mask, void *stream);
 
+/* ---- SMPL-X keypoint fitting (smplify.hip, soar_amd/smplify.py) ----
+ * The SMPLify objective of the reference's preprocessing (preproc/utils.py:626-685) and the gradient of its sum, for N frames.
+ * SoarSmplifyRig: the part of the body model the objective reads.  J = 55 joints in SMPL-X order (global, 21 body, jaw, two eyes,
+ *   15 + 15 hand joints; parents[j] < j, parents[0] < 0); NB = NBS + NE shape and expression directions (<= 64); VS gathered
+ *   vertices (<= 256); P model points (<= 160), each either a joint (pt_kind 0, pt_idx[p][0] = joint) or a weighted sum of up to
+ *   three gathered vertices (pt_kind 1: a selected vertex with weights (1, 0, 0), a landmark with its barycentric coordinates),
+ *   written to keypoint pt_dst[p] of 137.  Every pointer is device memory; the indices are the caller's to check
+ *   (soar_amd.smplify.KeypointRig does, on the host): the kernels trust them.
+ * SoarSmplifyArgs: rotations of the optimised joints as 6-D vectors (two rows, Gram-Schmidt), jaw and eyes as rotation vectors;
+ *   *0 are the initial values of the preserve term.  kp_scale = w_kp / (NF 137 2), pose_scale[k] = w_preserve / (NF J_k),
+ *   row_scale = w_preserve / NF, smooth_scale[k] = w_smooth / ((N - 1) J_k) (0 for N = 1), NF: the frame count the means divide by.
+ *   Outputs: g_* the gradient of the sum of the three losses ([N][1|21|15|15][6], [NBS], [N][3]), loss[3] = (kp, preserve,
+ *   smooth), weighted; kps [N][137][2] the projected keypoints or NULL.  Scratch: frame_betas [N][NBS], frame_loss [N][2].
+ * soar_smplify_objective: two launches -- one workgroup per frame for the forward and the adjoint of the per-frame part, then one
+ *   workgroup for the smooth term (a thread per (frame, joint) reads both neighbours) and the sums over frames in a fixed order.
+ *   No atomics, no host synchronisation, no allocation; two calls give the same bits, and a frame's keypoint and preserve
+ *   gradients depend neither on N nor on its place (for a given NF).  grads = 0: only loss[0] and kps are computed (one launch).
+ * soar_smplify_target_scales: per frame the larger side of the bounding box of the keypoints (x img_w, y img_h, confidence)
+ *   [N][137][3] with confidence above 0.3; -1 for a frame that has none. */
+typedef struct SoarSmplifyRig {
+    int32_t J, NBS, NE, VS, P, pad_;
+    const float *J_template;      /* [J][3]      J_regressor v_template */
+    const float *J_dirs;          /* [J][3][NB]  J_regressor shapedirs */
+    const int32_t *parents;       /* [J] */
+    const float *v_template;      /* [VS][3] */
+    const float *shapedirs;       /* [VS][3][NB] */
+    const float *posedirs;        /* [(J - 1) 9][VS 3] */
+    const float *lbs_weights;     /* [VS][J] */
+    const int32_t *pt_kind;       /* [P] */
+    const int32_t *pt_idx;        /* [P][3] */
+    const float *pt_w;            /* [P][3] */
+    const int32_t *pt_dst;        /* [P], distinct, in [0, 137) */
+    const float *kp_mask;         /* [137] */
+} SoarSmplifyRig;
+typedef struct SoarSmplifyArgs {
+    int32_t N, ignore_hands, grads, pad_;
+    const float *global_orient, *body_pose, *left_hand_pose, *right_hand_pose, *betas, *transl, *jaw_pose, *leye_pose, *reye_pose,
+        *expression;
+    const float *global_orient0, *body_pose0, *left_hand_pose0, *right_hand_pose0, *betas0, *transl0, *jaw_pose0, *leye_pose0,
+        *reye_pose0, *expression0;
+    const float *Ks;              /* [N][3][3] */
+    const float *w2c;             /* [4][4], rows 0 .. 2 are read */
+    const float *target_kps;      /* [N][137][3]: x / img_w, y / img_h, confidence */
+    const float *target_scales;   /* [N] */
+    float img_w, img_h, sigma, kp_scale, pose_scale[4], row_scale, w_preserve, smooth_scale[4];
+    float *g_global_orient, *g_body_pose, *g_left_hand_pose, *g_right_hand_pose, *g_betas, *g_transl, *loss, *kps;
+    float *frame_betas, *frame_loss;
+} SoarSmplifyArgs;
+int soar_smplify_objective(const SoarSmplifyRig *rig, const SoarSmplifyArgs *args, void *stream);
+int soar_smplify_target_scales(int32_t N, const float *target_kps, float img_w, float img_h, float *scales, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

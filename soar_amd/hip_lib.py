@@ -207,6 +207,27 @@ class SoarConvGemmArgs(C.Structure):
                 ("ph", SoarConvGemmTaps * 4)]
 
 
+class SoarSmplifyRig(C.Structure):
+    """Mirror of ``struct SoarSmplifyRig`` (include/soar_hip.h)."""
+    _fields_ = [("J", C.c_int32), ("NBS", C.c_int32), ("NE", C.c_int32), ("VS", C.c_int32), ("P", C.c_int32), ("pad_", C.c_int32),
+                ("J_template", _vp), ("J_dirs", _vp), ("parents", _vp), ("v_template", _vp), ("shapedirs", _vp), ("posedirs", _vp),
+                ("lbs_weights", _vp), ("pt_kind", _vp), ("pt_idx", _vp), ("pt_w", _vp), ("pt_dst", _vp), ("kp_mask", _vp)]
+
+
+_SMPLIFY_PARAMS = ("global_orient", "body_pose", "left_hand_pose", "right_hand_pose", "betas", "transl", "jaw_pose", "leye_pose", "reye_pose",
+                   "expression")
+
+
+class SoarSmplifyArgs(C.Structure):
+    """Mirror of ``struct SoarSmplifyArgs`` (include/soar_hip.h)."""
+    _fields_ = ([("N", C.c_int32), ("ignore_hands", C.c_int32), ("grads", C.c_int32), ("pad_", C.c_int32)]
+                + [(k, _vp) for k in _SMPLIFY_PARAMS] + [(k + "0", _vp) for k in _SMPLIFY_PARAMS]
+                + [("Ks", _vp), ("w2c", _vp), ("target_kps", _vp), ("target_scales", _vp),
+                   ("img_w", C.c_float), ("img_h", C.c_float), ("sigma", C.c_float), ("kp_scale", C.c_float), ("pose_scale", C.c_float * 4),
+                   ("row_scale", C.c_float), ("w_preserve", C.c_float), ("smooth_scale", C.c_float * 4)]
+                + [("g_" + k, _vp) for k in _SMPLIFY_PARAMS[:6]] + [("loss", _vp), ("kps", _vp), ("frame_betas", _vp), ("frame_loss", _vp)])
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -388,6 +409,8 @@ SIGNATURES = {
     "soar_normal_crop_boxes": (C.c_int, [C.c_int32] * 4 + [_vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp]),
     "soar_normal_crop_sample": (C.c_int, [C.c_int32] * 4 + [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     "soar_normal_crop_bytes": (C.c_int, [C.c_int32] * 3 + [_vp] * 6 + [_vp]),
+    "soar_smplify_objective": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyArgs), _vp]),
+    "soar_smplify_target_scales": (C.c_int, [C.c_int32, _vp, C.c_float, C.c_float, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

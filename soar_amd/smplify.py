@@ -1,0 +1,456 @@
+"""SMPL-X keypoint fitting: the SMPLify objective and its gradient in HIP (csrc/smplify.hip), driven by torch's L-BFGS.
+
+What the reference's ``preproc/compute_smplx.py`` does between the SMPLer-X estimates and ``params.pth``
+(``SMPLify``, preproc/utils.py:593-982): all N frames of a video are refined at once against 137 OpenPose keypoints, with two
+L-BFGS stages (body, then body and hands).  Every closure evaluation there is the full 10 475-vertex body model through autograd;
+here it is two launches:
+
+* ``KeypointRig``: the part of the body model the objective reads -- the 55 joints, and the distinct vertices behind the selected
+  vertices and the landmark triangles (each once), with their rows of ``v_template``, ``shapedirs``, ``posedirs`` and
+  ``lbs_weights``, and ``J_regressor @ v_template`` / ``J_regressor @ shapedirs``.  The joint-to-keypoint tables (``src_inds``,
+  ``dst_inds``, ``kp_mask``) are the caller's: the product ships no default for them.
+* ``smplify_objective``: the three weighted losses and the gradient of their sum.
+* ``project_keypoints``, ``target_scales``: forward-only by-products.
+* ``SMPLify(rig).fit``: the reference's two stages with ``torch.optim.LBFGS`` (plumbing); ``save_params`` writes ``params.pth``;
+  ``load_keypoints`` / ``load_smplerx`` read the inputs.
+
+Departures from the reference: the optimised rotations enter the body model as matrices (the reference's
+rotmat -> rotvec -> Rodrigues detour is the identity map); N = 1 gives a smooth term of 0, not NaN; landmarks are static rows
+only -- the reference picks the 17 contour landmarks per frame by the head's yaw, here they are 17 further rows of
+``lmk_faces_idx`` / ``lmk_bary_coords`` (``from_body_model`` appends the frontal row of ``dynamic_lmk_*`` when the body has one);
+a body model with a non-zero ``pose_mean`` is refused.  HIP only; there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import glob
+import json
+import os
+from typing import Dict, NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import hip_lib
+from .hip_lib import check
+
+N_KEYPOINTS = 137
+N_JOINTS = 55
+MAX_VERTICES, MAX_POINTS, MAX_SHAPE_DIRS, MAX_DEPTH = 256, 160, 64, 32      # smplify.hip
+POSE_KEYS = ("global_orient", "body_pose", "left_hand_pose", "right_hand_pose")
+POSE_JOINTS = {"global_orient": 1, "body_pose": 21, "left_hand_pose": 15, "right_hand_pose": 15}
+GRAD_KEYS = POSE_KEYS + ("betas", "transl")
+FIXED_KEYS = ("jaw_pose", "leye_pose", "reye_pose", "expression")
+PARAM_KEYS = GRAD_KEYS + FIXED_KEYS
+STAGE_KEYS = (("betas", "body_pose", "global_orient", "transl"),
+              ("betas", "body_pose", "global_orient", "left_hand_pose", "right_hand_pose", "transl"))
+
+
+def _hip(t, name: str) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name} is on '{where}': soar_amd.smplify runs on HIP devices only; there is no CPU fallback")
+
+
+def _stream(device: torch.device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _ints(x, name: str) -> torch.Tensor:
+    t = torch.as_tensor(np.asarray(x.detach().cpu()) if isinstance(x, torch.Tensor) else np.asarray(x))
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"{name} must hold integers (got {t.dtype})")
+    return t.to(torch.int64)
+
+
+def _in_range(t: torch.Tensor, hi: int, name: str) -> None:
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= hi):
+        bad = t[(t < 0) | (t >= hi)]
+        raise ValueError(f"{name}: index {int(bad[0])} is outside [0, {hi})")
+
+
+class KeypointRig:
+    """The sub-model of an SMPL-X body that the keypoint objective reads; see the module docstring.
+
+    ``faces [F,3]``, ``lmk_faces_idx [L]``, ``lmk_bary_coords [L,3]``, ``extra_joints_idxs [NX]`` (the vertex selector's ids).
+    Model point ``s`` of ``src_inds`` is joint ``s`` for ``s < 55``, selected vertex ``s - 55`` below ``55 + NX``, landmark
+    ``s - 55 - NX`` above; ``dst_inds`` the OpenPose keypoint it is written to (distinct); ``kp_mask [137]``.  Every index is
+    checked here, on the host: the kernels trust the tables."""
+
+    def __init__(self, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, faces, lmk_faces_idx, lmk_bary_coords,
+                 extra_joints_idxs, src_inds, dst_inds, kp_mask, device="cuda"):
+        f = lambda x: torch.as_tensor(x).detach().to("cpu", torch.float32)
+        vt, sd, pd, Jreg, lw, bary, mask = (f(x) for x in (v_template, shapedirs, posedirs, J_regressor, lbs_weights, lmk_bary_coords, kp_mask))
+        par, fc, lf, ex = _ints(parents, "parents"), _ints(faces, "faces"), _ints(lmk_faces_idx, "lmk_faces_idx"), _ints(extra_joints_idxs, "extra_joints_idxs")
+        src, dst = _ints(src_inds, "src_inds").reshape(-1), _ints(dst_inds, "dst_inds").reshape(-1)
+        V, J = vt.shape[0], par.numel()
+        if J != N_JOINTS:
+            raise ValueError(f"the body model must have the {N_JOINTS} SMPL-X joints (got {J})")
+        if vt.shape != (V, 3) or sd.dim() != 3 or sd.shape[:2] != (V, 3) or pd.shape != ((J - 1) * 9, V * 3) or Jreg.shape != (J, V) \
+                or lw.shape != (V, J):
+            raise ValueError(f"bad body model: v_template {tuple(vt.shape)}, shapedirs {tuple(sd.shape)}, posedirs {tuple(pd.shape)}, "
+                             f"J_regressor {tuple(Jreg.shape)}, lbs_weights {tuple(lw.shape)}")
+        NB = sd.shape[2]
+        if not 1 <= NB <= MAX_SHAPE_DIRS:
+            raise ValueError(f"shapedirs has {NB} directions; 1 .. {MAX_SHAPE_DIRS} are supported")
+        if int(par[0]) >= 0 or bool((par[1:] < 0).any()) or bool((par[1:] >= torch.arange(1, J)).any()):
+            raise ValueError("parents: need parents[0] < 0 and 0 <= parents[j] < j")
+        depth = [0] * J
+        for j in range(1, J):
+            depth[j] = depth[int(par[j])] + 1
+        if max(depth) >= MAX_DEPTH:
+            raise ValueError(f"the kinematic tree is {max(depth)} deep; below {MAX_DEPTH} is supported")
+        if fc.dim() != 2 or fc.shape[1] != 3 or bary.shape != (lf.numel(), 3) or lf.dim() != 1 or ex.dim() != 1:
+            raise ValueError(f"bad shapes: faces {tuple(fc.shape)}, lmk_faces_idx {tuple(lf.shape)}, lmk_bary_coords {tuple(bary.shape)}")
+        _in_range(fc, V, "faces")
+        _in_range(lf, fc.shape[0], "lmk_faces_idx")
+        _in_range(ex, V, "extra_joints_idxs")
+        NX, L = ex.numel(), lf.numel()
+        if src.shape != dst.shape or src.numel() > MAX_POINTS:
+            raise ValueError(f"src_inds and dst_inds must have one length, at most {MAX_POINTS} (got {src.numel()} and {dst.numel()})")
+        _in_range(src, J + NX + L, "src_inds")
+        _in_range(dst, N_KEYPOINTS, "dst_inds")
+        if dst.unique().numel() != dst.numel():
+            raise ValueError("dst_inds: a keypoint is written twice")
+        if mask.shape != (N_KEYPOINTS,):
+            raise ValueError(f"kp_mask must be [{N_KEYPOINTS}] (got {tuple(mask.shape)})")
+
+        tri = fc[lf]                                                          # [L,3]
+        used = torch.unique(torch.cat([ex, tri.reshape(-1)]))                 # ascending, each vertex once
+        if used.numel() == 0:
+            used = torch.zeros(1, dtype=torch.int64)
+        if used.numel() > MAX_VERTICES:
+            raise ValueError(f"the selector and the landmarks read {used.numel()} distinct vertices; at most {MAX_VERTICES} are supported")
+        pos = torch.full((V,), -1, dtype=torch.int64)
+        pos[used] = torch.arange(used.numel())
+        P = src.numel()
+        kind, idx, w = torch.zeros(P, dtype=torch.int32), torch.zeros(P, 3, dtype=torch.int32), torch.zeros(P, 3)
+        for p, s in enumerate(src.tolist()):
+            if s < J:
+                idx[p, 0], w[p, 0] = s, 1.0
+            elif s < J + NX:
+                kind[p], idx[p], w[p, 0] = 1, int(pos[ex[s - J]]), 1.0
+            else:
+                kind[p], idx[p], w[p] = 1, pos[tri[s - J - NX]].to(torch.int32), bary[s - J - NX]
+        self.device = torch.device(device)
+        _hip(torch.empty(0, device=self.device), "the rig's device")
+        d = lambda x: x.contiguous().to(self.device)
+        self.J, self.NB, self.V, self.VS, self.P, self.NX, self.L = J, NB, V, int(used.numel()), P, NX, L
+        self.vertex_ids = used
+        self.J_template, self.J_dirs = d(Jreg @ vt), d(torch.einsum("jv,vkl->jkl", Jreg, sd))
+        self.parents = d(par.to(torch.int32))
+        self.v_template, self.shapedirs, self.lbs_weights = d(vt[used]), d(sd[used]), d(lw[used])
+        self.posedirs = d(pd.reshape(-1, V, 3)[:, used].reshape(-1, used.numel() * 3))
+        self.pt_kind, self.pt_idx, self.pt_w, self.pt_dst = d(kind), d(idx), d(w), d(dst.to(torch.int32))
+        self.kp_mask = d(mask)
+        self.src_inds, self.dst_inds = src, dst
+
+    @classmethod
+    def from_body_model(cls, body, src_inds, dst_inds, kp_mask, device="cuda") -> "KeypointRig":
+        """From an ``smplx``-style body object: ``v_template, shapedirs (+ expr_dirs), posedirs, J_regressor, parents, lbs_weights,
+        faces_tensor, lmk_faces_idx, lmk_bary_coords, vertex_joint_selector.extra_joints_idxs``.  A body with
+        ``dynamic_lmk_faces_idx [79,17]`` / ``dynamic_lmk_bary_coords [79,17,3]`` gets their frontal row (yaw 0) appended as 17
+        static landmarks."""
+        pm = getattr(body, "pose_mean", None)
+        if pm is not None and bool((torch.as_tensor(pm) != 0).any()):
+            raise ValueError("the body model has a non-zero pose_mean (flat_hand_mean=False): create it with flat_hand_mean=True")
+        sd = torch.as_tensor(body.shapedirs)
+        ed = getattr(body, "expr_dirs", None)
+        if ed is not None:
+            sd = torch.cat([sd, torch.as_tensor(ed).to(sd)], dim=-1)
+        lf, lb = torch.as_tensor(body.lmk_faces_idx).reshape(-1), torch.as_tensor(body.lmk_bary_coords).reshape(-1, 3)
+        df, db = getattr(body, "dynamic_lmk_faces_idx", None), getattr(body, "dynamic_lmk_bary_coords", None)
+        if df is not None and db is not None:
+            lf, lb = torch.cat([lf, torch.as_tensor(df)[0].to(lf)]), torch.cat([lb, torch.as_tensor(db)[0].to(lb)])
+        return cls(body.v_template, sd, body.posedirs, body.J_regressor, body.parents, body.lbs_weights, body.faces_tensor, lf, lb,
+                   body.vertex_joint_selector.extra_joints_idxs, src_inds, dst_inds, kp_mask, device)
+
+    def _struct(self, NBS: int, NE: int) -> hip_lib.SoarSmplifyRig:
+        p = lambda t: t.data_ptr()
+        return hip_lib.SoarSmplifyRig(self.J, NBS, NE, self.VS, self.P, 0, p(self.J_template), p(self.J_dirs), p(self.parents),
+                                      p(self.v_template), p(self.shapedirs), p(self.posedirs), p(self.lbs_weights), p(self.pt_kind) if self.P else None,
+                                      p(self.pt_idx) if self.P else None, p(self.pt_w) if self.P else None,
+                                      p(self.pt_dst) if self.P else None, p(self.kp_mask))
+
+
+class SmplifyResult(NamedTuple):
+    losses: torch.Tensor               # [3] float32: kp, preserve, smooth, weighted
+    grads: Dict[str, torch.Tensor]     # the gradient of the sum, in the shapes of the parameters
+    frame_betas: torch.Tensor          # [N,NBS]: every frame's share of the betas gradient (keypoint term)
+
+
+def _prepare(rig: KeypointRig, params, name: str):
+    """float32 contiguous tensors on the rig's device (any strides are accepted), in the kernels' shapes."""
+    out = {}
+    for k in PARAM_KEYS:
+        if k not in params:
+            raise ValueError(f"{name} lacks '{k}'")
+        _hip(params[k], f"{name}['{k}']")
+        out[k] = params[k].detach().to(device=rig.device, dtype=torch.float32).contiguous()
+    N = out["transl"].shape[0]
+    for k in POSE_KEYS:
+        if out[k].numel() != N * POSE_JOINTS[k] * 6:
+            raise ValueError(f"{name}['{k}'] must be [{N},{POSE_JOINTS[k]},6] 6-D rotations (got {tuple(out[k].shape)})")
+    for k in ("transl", "jaw_pose", "leye_pose", "reye_pose"):
+        if out[k].shape != (N, 3):
+            raise ValueError(f"{name}['{k}'] must be [{N},3] (got {tuple(out[k].shape)})")
+    if out["betas"].dim() != 2 or out["betas"].shape[0] != 1 or out["expression"].dim() != 2 or out["expression"].shape[0] != N \
+            or out["betas"].shape[1] + out["expression"].shape[1] != rig.NB:
+        raise ValueError(f"{name}: betas must be [1,NBS] and expression [{N},NE] with NBS + NE = {rig.NB} "
+                         f"(got {tuple(out['betas'].shape)} and {tuple(out['expression'].shape)})")
+    return out, N
+
+
+def _camera(rig, N, Ks, w2c):
+    _hip(Ks, "Ks")
+    f = lambda x: x.detach().to(device=rig.device, dtype=torch.float32).contiguous()
+    Ks, w2c = f(Ks), f(w2c)
+    if Ks.shape != (N, 3, 3) or w2c.shape != (4, 4):
+        raise ValueError(f"Ks must be [{N},3,3] and w2c [4,4] (got {tuple(Ks.shape)} and {tuple(w2c.shape)})")
+    return Ks, w2c
+
+
+def _launch(rig, p, p0, N, Ks, w2c, img_wh, target, scales, weights, sigma, ignore_hands, norm_frames, grads, kps):
+    dev = rig.device
+    NBS, NE = p["betas"].shape[1], p["expression"].shape[1]
+    NF = float(N if norm_frames is None else norm_frames)
+    if NF <= 0:
+        raise ValueError("norm_frames must be positive")
+    a = hip_lib.SoarSmplifyArgs()
+    a.N, a.ignore_hands, a.grads = N, int(bool(ignore_hands)), int(grads)
+    for k in PARAM_KEYS:
+        setattr(a, k, p[k].data_ptr() if p[k].numel() else None)
+        if p0 is not None:
+            setattr(a, k + "0", p0[k].data_ptr() if p0[k].numel() else None)
+    a.Ks, a.w2c, a.target_kps, a.target_scales = Ks.data_ptr(), w2c.data_ptr(), target.data_ptr(), scales.data_ptr()
+    wk, wp, ws = (float(w) for w in weights)
+    a.img_w, a.img_h, a.sigma = float(img_wh[0]), float(img_wh[1]), float(sigma)
+    a.kp_scale, a.row_scale, a.w_preserve = wk / (NF * N_KEYPOINTS * 2), wp / NF, wp
+    for i, k in enumerate(POSE_KEYS):
+        a.pose_scale[i] = wp / (NF * POSE_JOINTS[k])
+        a.smooth_scale[i] = ws / ((N - 1) * POSE_JOINTS[k]) if N > 1 else 0.0
+    out = None
+    if grads:
+        g = {k: torch.empty_like(p[k]) for k in GRAD_KEYS}
+        loss = torch.empty(3, dtype=torch.float32, device=dev)
+        fb = torch.empty(N, NBS, dtype=torch.float32, device=dev)
+        fl = torch.empty(N, 2, dtype=torch.float32, device=dev)
+        for k in GRAD_KEYS:
+            setattr(a, "g_" + k, g[k].data_ptr())
+        a.loss, a.frame_betas, a.frame_loss = loss.data_ptr(), fb.data_ptr(), fl.data_ptr()
+        out = SmplifyResult(loss, g, fb)
+    if kps is not None:
+        a.kps = kps.data_ptr()
+    rs = rig._struct(NBS, NE)
+    with torch.cuda.device(dev):
+        check(hip_lib.lib().soar_smplify_objective(C.byref(rs), C.byref(a), _stream(dev)), "soar_smplify_objective")
+    return out
+
+
+@torch.no_grad()
+def smplify_objective(rig: KeypointRig, params, init_params, Ks, w2c, img_wh, target_kps, target_scales,
+                      weights: Sequence[float] = (100.0, 60.0, 10000.0), sigma: float = 100.0, ignore_hands: bool = False,
+                      norm_frames: Optional[int] = None) -> SmplifyResult:
+    """``SMPLify.forward`` of the reference and the gradient of the sum of its three losses, in two launches.
+
+    ``params`` / ``init_params``: ``global_orient [N,1,6], body_pose [N,21,6], left_hand_pose / right_hand_pose [N,15,6]`` (6-D
+    rotations), ``betas [1,NBS]``, ``transl [N,3]``, and the fixed ``jaw_pose, leye_pose, reye_pose [N,3]`` (rotation vectors) and
+    ``expression [N,NE]``.  ``Ks [N,3,3]``, ``w2c [4,4]``, ``img_wh = (w, h)``, ``target_kps [N,137,3]`` (x / w, y / h, confidence),
+    ``target_scales [N]`` (``target_scales()``), ``weights`` = (kp, preserve, smooth).  ``ignore_hands`` zeroes the confidences
+    ``25:-70`` (stage one).  ``norm_frames``: the frame count the keypoint and preserve means divide by when the batch is a
+    part of a longer sequence (default N): with it a frame's keypoint and preserve gradients are the same bits alone and in the
+    batch.  Deterministic; nothing is read back."""
+    p, N = _prepare(rig, params, "params")
+    p0, N0 = _prepare(rig, init_params, "init_params")
+    if N0 != N or p0["betas"].shape != p["betas"].shape:
+        raise ValueError("params and init_params disagree in shape")
+    Ks, w2c = _camera(rig, N, Ks, w2c)
+    _hip(target_kps, "target_kps")
+    f = lambda x: x.detach().to(device=rig.device, dtype=torch.float32).contiguous()
+    target, scales = f(target_kps), f(target_scales)
+    if target.shape != (N, N_KEYPOINTS, 3) or scales.shape != (N,):
+        raise ValueError(f"target_kps must be [{N},{N_KEYPOINTS},3] and target_scales [{N}] (got {tuple(target.shape)}, {tuple(scales.shape)})")
+    if N == 0:
+        raise ValueError("no frames")
+    res = _launch(rig, p, p0, N, Ks, w2c, img_wh, target, scales, weights, sigma, ignore_hands, norm_frames, True, None)
+    return SmplifyResult(res.losses, {k: res.grads[k].view(params[k].shape) for k in GRAD_KEYS}, res.frame_betas)
+
+
+@torch.no_grad()
+def project_keypoints(rig: KeypointRig, params, Ks, w2c) -> torch.Tensor:
+    """The projected OpenPose keypoints [N,137,2] of the body model (pixels; the divisor is ``z.clamp(min=1e-5)``)."""
+    p, N = _prepare(rig, params, "params")
+    Ks, w2c = _camera(rig, N, Ks, w2c)
+    kps = torch.empty(N, N_KEYPOINTS, 2, dtype=torch.float32, device=rig.device)
+    if N:
+        dummy = torch.ones(N, N_KEYPOINTS, 3, dtype=torch.float32, device=rig.device)
+        _launch(rig, p, None, N, Ks, w2c, (1.0, 1.0), dummy, dummy[:, 0, 0].contiguous(), (0.0, 0.0, 0.0), 1.0, False, None, False, kps)
+    return kps
+
+
+def target_scales(target_kps: torch.Tensor, img_wh) -> torch.Tensor:
+    """[N]: per frame the larger side, in pixels, of the bounding box of the keypoints with confidence above 0.3
+    (``get_target_scales``).  Raises for a frame that has none."""
+    _hip(target_kps, "target_kps")
+    t = target_kps.detach().to(torch.float32).contiguous()
+    if t.dim() != 3 or t.shape[1:] != (N_KEYPOINTS, 3):
+        raise ValueError(f"target_kps must be [N,{N_KEYPOINTS},3] (got {tuple(t.shape)})")
+    out = torch.empty(t.shape[0], dtype=torch.float32, device=t.device)
+    if t.shape[0]:
+        with torch.cuda.device(t.device):
+            check(hip_lib.lib().soar_smplify_target_scales(t.shape[0], t.data_ptr(), float(img_wh[0]), float(img_wh[1]), out.data_ptr(),
+                                                           _stream(t.device)), "soar_smplify_target_scales")
+        bad = (out < 0).nonzero()
+        if bad.numel():
+            raise ValueError(f"frame {int(bad[0])} has no keypoint with confidence above 0.3")
+    return out
+
+
+# ---- rotations on the host side of the optimiser (plumbing) -----------------------------------------------------------------------
+
+def rotvec_to_rotmat(rv: torch.Tensor) -> torch.Tensor:
+    t = torch.linalg.norm(rv, dim=-1)
+    small = t < 1e-4
+    ts = torch.where(small, torch.ones_like(t), t)
+    A = torch.where(small, 1.0 - t * t / 6.0, torch.sin(ts) / ts)[..., None, None]
+    B = torch.where(small, 0.5 - t * t / 24.0, (1.0 - torch.cos(ts)) / (ts * ts))[..., None, None]
+    x, y, z = rv[..., 0], rv[..., 1], rv[..., 2]
+    o = torch.zeros_like(x)
+    K = torch.stack((o, -z, y, z, o, -x, -y, x, o), -1).reshape(rv.shape[:-1] + (3, 3))
+    return torch.eye(3, dtype=rv.dtype, device=rv.device) + A * K + B * (K @ K)
+
+
+def rotation_6d_to_matrix(d6: torch.Tensor) -> torch.Tensor:
+    a1, a2 = d6[..., :3], d6[..., 3:]
+    b1 = torch.nn.functional.normalize(a1, dim=-1)
+    b2 = torch.nn.functional.normalize(a2 - (b1 * a2).sum(-1, keepdim=True) * b1, dim=-1)
+    return torch.stack((b1, b2, torch.cross(b1, b2, dim=-1)), dim=-2)
+
+
+def rotmat_to_rotvec(R: torch.Tensor) -> torch.Tensor:
+    """Through the unit quaternion (largest of the four candidates), shortest arc: good at every angle."""
+    m = R
+    d0, d1, d2 = m[..., 0, 0], m[..., 1, 1], m[..., 2, 2]
+    cand = torch.stack([
+        torch.stack([1 + d0 + d1 + d2, m[..., 2, 1] - m[..., 1, 2], m[..., 0, 2] - m[..., 2, 0], m[..., 1, 0] - m[..., 0, 1]], -1),
+        torch.stack([m[..., 2, 1] - m[..., 1, 2], 1 + d0 - d1 - d2, m[..., 0, 1] + m[..., 1, 0], m[..., 0, 2] + m[..., 2, 0]], -1),
+        torch.stack([m[..., 0, 2] - m[..., 2, 0], m[..., 0, 1] + m[..., 1, 0], 1 - d0 + d1 - d2, m[..., 1, 2] + m[..., 2, 1]], -1),
+        torch.stack([m[..., 1, 0] - m[..., 0, 1], m[..., 0, 2] + m[..., 2, 0], m[..., 1, 2] + m[..., 2, 1], 1 - d0 - d1 + d2], -1)], -2)
+    best = torch.stack([1 + d0 + d1 + d2, 1 + d0 - d1 - d2, 1 - d0 + d1 - d2, 1 - d0 - d1 + d2], -1).argmax(-1)
+    q = torch.gather(cand, -2, best[..., None, None].expand(best.shape + (1, 4)))[..., 0, :]
+    q = torch.nn.functional.normalize(q, dim=-1)
+    q = torch.where(q[..., :1] < 0, -q, q)
+    s = torch.linalg.norm(q[..., 1:], dim=-1)
+    angle = 2.0 * torch.atan2(s, q[..., 0])
+    scale = torch.where(s < 1e-6, torch.full_like(s, 2.0), angle / s.clamp(min=1e-30))
+    return q[..., 1:] * scale[..., None]
+
+
+# ---- the fit --------------------------------------------------------------------------------------------------------------------
+
+class SMPLify:
+    """The reference's ``SMPLify`` with its defaults; ``fit`` runs its two L-BFGS stages on the HIP closure."""
+
+    def __init__(self, rig: KeypointRig, lr=1.0, max_iters=20, body_steps=20, hand_steps=40, kp_weight=100.0, preserve_weight=60.0,
+                 smooth_weight=10000.0, sigma=100.0, objective=None, scales=None, dtype=torch.float32):
+        self.rig, self.lr, self.max_iters, self.body_steps, self.hand_steps = rig, lr, max_iters, body_steps, hand_steps
+        self.weights, self.sigma = (kp_weight, preserve_weight, smooth_weight), sigma
+        # tests drive the same fit by a torch restatement of the objective, in another dtype or on the CPU
+        self.objective = objective if objective is not None else smplify_objective
+        self.scales = scales if scales is not None else target_scales
+        self.dtype = dtype
+        self.loss_dict: Dict[str, float] = {}
+        self.evaluations = 0
+
+    def make_closure(self, params, init_params, names, Ks, w2c, img_wh, target_kps, scales, ignore_hands):
+        """The closure of one stage: one ``smplify_objective`` call that writes ``.grad`` of the stage's parameters ``names`` and
+        of no other."""
+        def closure():
+            res = self.objective(self.rig, params, init_params, Ks, w2c, img_wh, target_kps, scales, self.weights, self.sigma, ignore_hands)
+            for k in names:
+                params[k].grad = res.grads[k].view(params[k].shape)
+            self.last = res
+            self.evaluations += 1
+            return res.losses.sum()
+        return closure
+
+    def fit(self, init_params, Ks, w2c, img_wh, target_kps) -> Dict[str, torch.Tensor]:
+        """``init_params``: rotation vectors as SMPLer-X gives them (``global_orient [N,3], body_pose [N,63], left_hand_pose /
+        right_hand_pose [N,45], jaw_pose / leye_pose / reye_pose [N,3]``), ``betas [N|1,NBS]`` (their mean is the one shared
+        row), ``expression [N,NE]``, ``transl [N,3]``.  Returns the refined parameters in the same form, ``global_orient [N,3]``
+        and ``betas [1,NBS]``."""
+        dev = self.rig.device
+        f = lambda x: torch.as_tensor(x).detach().to(device=dev, dtype=self.dtype)
+        init = {}
+        for k in PARAM_KEYS:
+            v = f(init_params[k])
+            if k in POSE_KEYS:
+                v = rotation_6d_from_rotvec(v.reshape(v.shape[0], -1, 3))
+            elif k == "betas":
+                v = v.mean(0, keepdim=True)
+            init[k] = v.contiguous()
+        params = {k: v.clone().requires_grad_(k in GRAD_KEYS) for k, v in init.items()}
+        target = f(target_kps)
+        scales = self.scales(target, img_wh)
+        Ks, w2c = f(Ks), f(w2c)
+        for names, steps, ignore_hands in ((STAGE_KEYS[0], self.body_steps, True), (STAGE_KEYS[1], self.hand_steps, False)):
+            for k in GRAD_KEYS:
+                params[k].grad = torch.zeros_like(params[k])              # parameters outside the stage's list keep a zero gradient
+            opt = torch.optim.LBFGS([params[k] for k in names], lr=self.lr, max_iter=self.max_iters, line_search_fn="strong_wolfe")
+            closure = self.make_closure(params, init, names, Ks, w2c, img_wh, target, scales, ignore_hands)
+            for _ in range(steps):
+                opt.step(closure)
+            if steps:
+                self.loss_dict = dict(zip(("kp", "preserve", "smooth"), self.last.losses.tolist()))
+        out = {}
+        with torch.no_grad():
+            for k, v in params.items():
+                out[k] = rotmat_to_rotvec(rotation_6d_to_matrix(v)).reshape(v.shape[0], -1) if k in POSE_KEYS else v.detach().clone()
+        self.params_6d = {k: v.detach() for k, v in params.items()}
+        return out
+
+
+def rotation_6d_from_rotvec(rv: torch.Tensor) -> torch.Tensor:
+    """[..., 3] rotation vectors -> [..., 6]: the first two rows of the rotation matrix."""
+    m = rotvec_to_rotmat(rv)
+    return m[..., :2, :].clone().reshape(m.shape[:-2] + (6,))
+
+
+def save_params(path: str, params, Ks, w2c, img_wh) -> None:
+    """``params.pth`` with the reference's keys: the ten parameter tensors, ``Ks``, ``w2c`` (CPU tensors) and ``img_wh`` (a tuple)."""
+    out = {k: torch.as_tensor(params[k]).detach().cpu() for k in PARAM_KEYS}
+    out.update(Ks=torch.as_tensor(Ks).detach().cpu(), w2c=torch.as_tensor(w2c).detach().cpu(), img_wh=tuple(int(x) for x in img_wh))
+    torch.save(out, path)
+
+
+def load_keypoints(kp_dir: str) -> np.ndarray:
+    """[N,137,3] float32 from a directory of OpenPose JSON files (sorted by name): body 25, left hand 21, right hand 21, face 70 of the
+    first person, (x, y, confidence) in pixels."""
+    out = []
+    for path in sorted(glob.glob(os.path.join(kp_dir, "*.json"))):
+        with open(path) as fh:
+            person = json.load(fh)["people"][0]
+        out.append(np.array(person["pose_keypoints_2d"] + person["hand_left_keypoints_2d"] + person["hand_right_keypoints_2d"]
+                            + person["face_keypoints_2d"], dtype=np.float32).reshape(-1, 3))
+    if not out:
+        raise FileNotFoundError(f"no *.json under {kp_dir}")
+    kp = np.stack(out, axis=0)
+    if kp.shape[1:] != (N_KEYPOINTS, 3):
+        raise ValueError(f"expected {N_KEYPOINTS} keypoints per frame (got {kp.shape[1]})")
+    return kp
+
+
+def load_smplerx(result_dir: str, device="cpu") -> Dict[str, torch.Tensor]:
+    """The SMPLer-X estimates ``00000_0.npz, 00001_0.npz, ...`` as the dict ``fit`` takes, in the reference's shapes:
+    ``betas [N,10], global_orient [N,3], body_pose [N,63], left_hand_pose / right_hand_pose [N,45], jaw_pose / leye_pose / reye_pose
+    [N,3], expression [N,10], transl [N,3]``."""
+    N = len(glob.glob(os.path.join(result_dir, "*_0.npz")))
+    if N == 0:
+        raise FileNotFoundError(f"no *_0.npz under {result_dir}")
+    data = [np.load(os.path.join(result_dir, f"{i:05d}_0.npz")) for i in range(N)]
+    out = {}
+    for k in PARAM_KEYS:
+        rows = [torch.from_numpy(d[k].astype(np.float32)) for d in data]
+        out[k] = (torch.stack([r.reshape(-1) for r in rows]) if k in ("body_pose", "left_hand_pose", "right_hand_pose")
+                  else torch.cat([r.reshape(1, -1) for r in rows])).to(device)
+    return out
