@@ -56,7 +56,8 @@ extern "C" {
  * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation).
  * soar_normalnet_weights_bytes / _pack_weights / _workspace_bytes / _forward (+ SoarNormalNetArgs), soar_normal_crop_boxes / _sample /
  * _bytes: normal-map preprocessing.  soar_selftest_conv_gemm / _conv_pack (+ SoarConvGemmArgs, SoarConvGemmTaps): the shared
- * implicit-GEMM convolution and its weight packer by themselves, for the tests. */
+ * implicit-GEMM convolution and its weight packer by themselves, for the tests.  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
+ * normal priors (a triangle-mesh rasterizer). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1452,6 +1453,35 @@ typedef struct SoarSmplifyArgs {
 } SoarSmplifyArgs;
 int soar_smplify_objective(const SoarSmplifyRig *rig, const SoarSmplifyArgs *args, void *stream);
 int soar_smplify_target_scales(int32_t N, const float *target_kps, float img_w, float img_h, float *scales, void *stream);
+
+/* ---- SMPL-X normal priors: an indexed triangle mesh drawn as a normal map (prior.hip, soar_amd/prior.py) ----
+ * N frames of one topology: faces [F][3] (indices in [0, V): the caller's to check, soar_amd.prior.MeshTopology does, on the host)
+ * and the vertex-to-corner table csr_offsets [V + 1], csr_corners [3 F] (3 face + corner of every corner that names the vertex,
+ * ascending).  Every pointer is device memory but verts_stride (host, three element strides of verts [N][V][3]).
+ * soar_prior_vertex_setup, one launch: per (frame, vertex) p = R v + t from w2c ([4][4], or [N][4][4] with w2c_per_frame != 0;
+ *   rows 0 .. 2 are read), x = fx p.x / p.z + cx, y = fy p.y / p.z + cy with Ks [N][3][3] in un-contracted float32,
+ *   snapped [N][V][2] = rint(256 (x, y)), inv_z [N][V] = 1 / p.z, normals [N][V][3] = R normalize(sum of the un-normalised cross
+ *   products (v1 - v0) x (v2 - v0) of the vertex's faces), normalize(x) = x / max(|x|, 1e-12).  A vertex with p.z <= 1e-6 or more
+ *   than 2^20 pixels from the origin has snapped = (INT32_MIN, INT32_MIN) and inv_z = 0.
+ * soar_prior_face_boxes, one launch: boxes [N][F][4] int16 = the first and last pixel column and the first and last row whose sample
+ *   (256 j + 128) lies inside the face's snapped bounding box, clamped to int16; (32767, -32768, 32767, -32768) for a face with an
+ *   invalid vertex, of zero snapped area, or whose box holds no sample.  8 bytes a face instead of three indices and three vertices:
+ *   what every tile of the raster launch reads of every face.
+ * soar_prior_raster, one launch: both views of every frame from those arrays.  Pixel (i, j) is sampled at snapped
+ *   (256 j + 128, 256 i + 128); exact int64 edge functions, ties on an edge by the edge's direction (towards +y, or along +x, owns
+ *   it, on the face with vertices 1 and 2 swapped when its snapped area is negative); no culling; a face with an invalid vertex or
+ *   of zero snapped area covers nothing.  b_k = float(e_k) / float(A), q = sum b_k inv_z_k; view 0 keeps the largest q, view 1 the
+ *   smallest, the smaller face index among equal q.  prior [N][2][3][H][W] = normalize(sum (b_k inv_z_k) n_k), as (x, -y, -z) when
+ *   opengl != 0, exactly 0 off the mesh; mask [N][2][H][W] 1 / 0; face [N][2][H][W] the winner or -1.  H, W <= 4096.
+ * No float atomics, no host synchronisation, no allocation; the output does not depend on the order of execution, and a frame's
+ * output depends neither on N nor on its place. */
+int soar_prior_vertex_setup(int32_t N, int32_t V, int32_t F, const float *verts, const int64_t *verts_stride, const float *w2c,
+                            int32_t w2c_per_frame, const float *Ks, const int32_t *faces, const int32_t *csr_offsets,
+                            const int32_t *csr_corners, int32_t *snapped, float *inv_z, float *normals, void *stream);
+int soar_prior_face_boxes(int32_t N, int32_t V, int32_t F, const int32_t *faces, const int32_t *snapped, int16_t *boxes, void *stream);
+int soar_prior_raster(int32_t N, int32_t V, int32_t F, int32_t H, int32_t W, int32_t opengl, const int32_t *faces, const int32_t *snapped,
+                      const float *inv_z, const float *normals, const int16_t *boxes, float *prior, uint8_t *mask, int32_t *face,
+                      void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

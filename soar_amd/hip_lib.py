@@ -411,6 +411,9 @@ SIGNATURES = {
     "soar_normal_crop_bytes": (C.c_int, [C.c_int32] * 3 + [_vp] * 6 + [_vp]),
     "soar_smplify_objective": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyArgs), _vp]),
     "soar_smplify_target_scales": (C.c_int, [C.c_int32, _vp, C.c_float, C.c_float, _vp, _vp]),
+    "soar_prior_vertex_setup": (C.c_int, [C.c_int32] * 3 + [_vp, C.POINTER(C.c_int64), _vp, C.c_int32] + [_vp] * 7 + [_vp]),
+    "soar_prior_face_boxes": (C.c_int, [C.c_int32] * 3 + [_vp] * 3 + [_vp]),
+    "soar_prior_raster": (C.c_int, [C.c_int32] * 6 + [_vp] * 8 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None
