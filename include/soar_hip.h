@@ -786,7 +786,8 @@ typedef struct SoarAdamRow {
 int soar_adam_step(int32_t n_rows, const SoarAdamRow *rows_host, double beta1, double beta2, double eps, void *state_dev, void *stream);
 /* The same update with the step number (1, 2, ...) kept by the caller, as torch.optim.Adam keeps it: the bias corrections are worked
  * out on the host in double precision, there is no device counter and no launch to advance it.  Several calls with the same `step`
- * update further rows of that step.  Not inside a captured graph (a replay would repeat the step number). */
+ * update further rows of that step.  Not inside a captured graph (a replay would repeat the step number).
+ * 1 <= step <= INT32_MAX; a larger step is refused with an error (it is not truncated), here and in soar_adam_step_at_gather. */
 int soar_adam_step_at(int32_t n_rows, const SoarAdamRow *rows, double beta1, double beta2, double eps, int64_t step, void *stream);
 /* soar_adam_step_at and soar_gather_step_inputs_ids (same arguments, same results) in ONE launch: the gather depends on nothing the
  * update writes, its n_frames workgroups ride behind the update's.  The first launch of a training step's prologue. */

@@ -179,20 +179,14 @@ static int adam_step_at(int32_t n_rows, const SoarAdamRow *rows_host, double bet
         set_error("soar_adam_step_at: 0 <= n_rows <= %d, rows must be given, step >= 1", ADAM_MAX_ROWS);
         return 1;
     }
-    AdamTable tab;
-    tab.n = n_rows;
-    int64_t blocks = 0;
-    for (int r = 0; r < n_rows; r++) {
-        const SoarAdamRow &w = rows_host[r];
-        if (w.count < 0 || (w.count && (!w.param || !w.grad || !w.exp_avg || !w.exp_avg_sq))) {
-            set_error("soar_adam_step_at: row %d has a NULL pointer or a negative count", r);
-            return 1;
-        }
-        tab.row[r] = w;
-        tab.first_block[r] = blocks;
-        blocks += (w.count + 1023) / 1024;
+    // the kernel's state holds the step as int32 (its `step <= 0` guard would skip every row of a truncated, negative one)
+    if (step > INT32_MAX) {
+        set_error("soar_adam_step_at: step %lld does not fit the 32-bit step counter (at most %d)", (long long)step, INT32_MAX);
+        return 1;
     }
-    for (int r = n_rows; r <= ADAM_MAX_ROWS; r++) tab.first_block[r] = blocks;
+    AdamTable tab;
+    int64_t blocks = 0;
+    if (!adam_fill(tab, n_rows, rows_host, ADAM_MAX_ROWS, blocks, "soar_adam_step_at")) return 1;
     AdamState st;
     st.step = (int32_t)step;
     st.bias_correction1 = (float)(1.0 - pow(beta1, (double)step));

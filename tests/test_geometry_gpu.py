@@ -425,9 +425,11 @@ def _groups_for_torch(m):
     return [{"params": list(g["params"]), "lr": g["lr"], "name": g["name"]} for g in m.optimizer.param_groups]
 
 
-def test_one_launch_adam_matches_torch_adam_over_all_groups(world):
+@pytest.mark.parametrize("P", [2000, 1997, 1998, 1999])
+def test_one_launch_adam_matches_torch_adam_over_all_groups(world, P):
+    """(P past 2000: surfel counts that are no multiple of four -- the leaves' rows end inside a float4 of the wide table's kernel)"""
     w = world
-    m = make_model(w, dict(position_lr_init=1.6e-5, position_lr_final=1.6e-6, position_lr_max_steps=1000), P=2000, seed=1)
+    m = make_model(w, dict(position_lr_init=1.6e-5, position_lr_final=1.6e-6, position_lr_max_steps=1000), P=P, seed=1)
     m.training_setup()
     ours = [p for g in m.optimizer.param_groups for p in g["params"]]
     assert len(ours) == 27

@@ -120,8 +120,8 @@ _AV = dict(P=3000, W=160, H=128, frames=[0, 1, 2, 3],
            lam=dict(recon=1.0, mask=1.0, normal=1.0, occ=0.1))
 
 
-def _avatar_scene():
-    P, W, H = _AV["P"], _AV["W"], _AV["H"]
+def _avatar_scene(P=None):
+    P, W, H = _AV["P"] if P is None else P, _AV["W"], _AV["H"]
     body, poses, cam = syn.make_body_model(0, V=2048), syn.make_pose_sequence(4, 0), syn.make_camera(W, H)
     seq = AvatarSequence(syn.make_surfels(P, 0), body, poses, cam, DEV)
     seq.occ.requires_grad_(True)
@@ -130,12 +130,12 @@ def _avatar_scene():
     return seq, dict(seq.leaves(), occ=seq.occ), cam, bg, pool
 
 
-def _avatar_plan_steps(steps):
+def _avatar_plan_steps(steps, P=None):
     """`steps` training steps of FrameStepPlan(loss="avatar") + optim.FusedAdam: per-step losses, first-step gradients, per-step leaves."""
     from soar_amd import optim, rasterizer
     from soar_amd.frame_dp import FlatGradBuffer
     from soar_amd.step_plan import FrameStepPlan
-    seq, leaves, cam, bg, pool = _avatar_scene()
+    seq, leaves, cam, bg, pool = _avatar_scene(P)
     flat = FlatGradBuffer(leaves)
     with torch.no_grad():
         seq.render_frames(_AV["frames"], bg, with_occ=True)
@@ -152,11 +152,11 @@ def _avatar_plan_steps(steps):
     return losses_, grads, snaps
 
 
-def _avatar_composed_steps(steps):
+def _avatar_composed_steps(steps, P=None):
     """The same steps composed from the autograd pieces of the plugin path: lbs_warp, GaussianRasterizer twice, the post-op functions
     (TS/renderer/diff_gaussian_rasterizer.py:292-303), losses.avatar_stage_loss + loss_occ, torch.optim.Adam."""
     from scenes import avatar_frame_loss
-    seq, leaves, cam, bg, pool = _avatar_scene()
+    seq, leaves, cam, bg, pool = _avatar_scene(P)
     lr = _AV["lr"]
     opt = torch.optim.Adam([{"params": [leaves[n]], "lr": lr[n]} for n in lr], lr=0.0, eps=1e-15)
     losses_, grads, snaps = [], None, []
