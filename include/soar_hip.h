@@ -1484,6 +1484,29 @@ int soar_prior_raster(int32_t N, int32_t V, int32_t F, int32_t H, int32_t W, int
                       const float *inv_z, const float *normals, const int16_t *boxes, float *prior, uint8_t *mask, int32_t *face,
                       void *stream);
 
+/* ---- mask clean-up: union of the segmenter's candidates, 5 x 5 open / close, largest component (masks.hip, soar_amd/masks.py;
+ * DESIGN.md 9o) ----
+ * N frames per call.  cand [N][K][H][W], K >= 1, contiguous: dtype 0 = uint8 / bool (non-zero is set), dtype 1 = float32
+ * (value > threshold is set: 0.0, -0.0 and NaN are unset at threshold 0).  A pixel of the union is set where any candidate is.
+ * OPEN (erode, dilate) then CLOSE (dilate, erode) with the 5 x 5 all-ones element, centre anchor, one iteration; an erosion reads
+ * positions outside the image as set, a dilation as unset (OpenCV's default border value), each operation on its own input.
+ * The largest component: 8-connectivity; a component's label is the smallest raster index y W + x of its pixels; the largest area
+ * wins, the smallest label among equal areas.  out [N][H][W] uint8 in {0, 1}.  stats [N][4] int32 = union_area, cleaned_area,
+ * n_components, kept_area (soar_masks_open_close leaves the last two 0; soar_masks_largest_component gives the input's area in the
+ * first two).  A frame whose cleaned mask is empty gives zeros and n_components = 0.
+ * soar_masks_open_close: the union, the four operations and the popcounts in one launch, one launch for the bytes.
+ * soar_masks_largest_component: mask [N][H][W] uint8 (non-zero is set) -> pack, six launches of labelling and selection.
+ * soar_masks_clean: both; the cleaned bit-plane stays in the workspace.  Seven launches and two memsets whatever the images hold.
+ * Integer arithmetic and integer atomics only: two calls give the same bits.  No host synchronisation, no allocation; the
+ * workspace (soar_masks_workspace_bytes, 256-byte aligned) is 4 bytes a pixel plus a bit a pixel.  H W < 2^31, N <= 65535. */
+int soar_masks_workspace_bytes(int32_t N, int32_t H, int32_t W, size_t *bytes);
+int soar_masks_open_close(int32_t N, int32_t K, int32_t H, int32_t W, const void *cand, int32_t dtype, float threshold, uint8_t *out,
+                          int32_t *stats, void *workspace, size_t workspace_bytes, void *stream);
+int soar_masks_largest_component(int32_t N, int32_t H, int32_t W, const uint8_t *mask, uint8_t *out, int32_t *stats, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int soar_masks_clean(int32_t N, int32_t K, int32_t H, int32_t W, const void *cand, int32_t dtype, float threshold, uint8_t *out,
+                     int32_t *stats, void *workspace, size_t workspace_bytes, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

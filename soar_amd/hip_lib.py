@@ -414,6 +414,10 @@ SIGNATURES = {
     "soar_prior_vertex_setup": (C.c_int, [C.c_int32] * 3 + [_vp, C.POINTER(C.c_int64), _vp, C.c_int32] + [_vp] * 7 + [_vp]),
     "soar_prior_face_boxes": (C.c_int, [C.c_int32] * 3 + [_vp] * 3 + [_vp]),
     "soar_prior_raster": (C.c_int, [C.c_int32] * 6 + [_vp] * 8 + [_vp]),
+    "soar_masks_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
+    "soar_masks_open_close": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "soar_masks_largest_component": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "soar_masks_clean": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
