@@ -1507,6 +1507,60 @@ int soar_masks_largest_component(int32_t N, int32_t H, int32_t W, const uint8_t 
 int soar_masks_clean(int32_t N, int32_t K, int32_t H, int32_t W, const void *cand, int32_t dtype, float threshold, uint8_t *out,
                      int32_t *stats, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the training step's remaining image terms (step_terms.hip, soar_amd/step_losses.py) ----
+ * Current stream, no synchronisation, no read-back, no atomics: two calls give the same bits.  Every image is planar float32 and
+ * 4-byte aligned; 16-byte accesses where the planes allow them, under the rule of soar_cos_loss / soar_masked_l1, whose values and
+ * gradients these have bit for bit on the same images.  scratch: soar_step_terms_scratch_bytes() bytes, 8-byte aligned.
+ *
+ * soar_consistency_loss: cos_loss(a, b, mask = None, thrsh, weight) view by view over B <= 8 views [3,H,W] that lie a_stride /
+ *   b_stride floats apart (>= 3 H W): stats [B][2] = {mean of 1 - cos over the view's selected pixels (NaN when none), their
+ *   count}.  One launch and a finishing launch.  The backward gives BOTH gradients [B][3][H][W] in one launch: of a with b's
+ *   values and of b with a's, each scaled by upstream_dev[view] / max(count, 1).  H W <= 2^28. */
+int soar_step_terms_scratch_bytes(size_t *bytes);
+int soar_consistency_loss(int32_t B, int32_t H, int32_t W, const float *a, int64_t a_stride, const float *b, int64_t b_stride,
+                          float cos_thrsh, float weight, float *stats, float *scratch, void *stream);
+int soar_consistency_loss_backward(int32_t B, int32_t H, int32_t W, const float *a, int64_t a_stride, const float *b, int64_t b_stride,
+                                   float cos_thrsh, float weight, const float *stats, const float *upstream_dev, float *dL_da,
+                                   float *dL_db, void *stream);
+/* soar_normal_view_terms: the front and back normal views of the video frame (TS/system/gaussian_surfel_mvdream.py:332-399).
+ *   normal: `views` (1: front only, 2) rendered views [3,R,R], normal_stride floats apart; mask0 [R,R] the front view's mask image;
+ *   gt_F, gt_B [3,R,R] (gt_B NULL with views = 1); gt_mask [R,R] float.  sel = gt_mask > 1e-5.
+ *   mode 1: values [3] = {0.2 cos_loss(view 0, gt_F, sel, 0), 0.2 cos_loss(view 1, gt_B, sel, 0), mean|mask0 - gt_mask|}, stats [6] the
+ *   three {loss, count} pairs behind them, lpips_in [2 views][3][R][R] (16-byte aligned) = ((x * m) - 0.5) * 2 of the rendered views,
+ *   then of the targets: m is the float gt_mask for the front view and (float)sel for the back view, as the reference has it.
+ *   mode 2 (after mode 1, same stats): g_normal [views][3][R][R] = up[v] times the 0.2 cos term's gradient + (g_lpips * 2) * m
+ *   (g_lpips [views][3][R][R], the upstream of the rendered views' LPIPS inputs, or NULL); g_mask0 [R,R] = up[2] times the L1
+ *   term's.  up [3]: device.  One launch (mode 1: and a finishing launch).  R R <= 2^28. */
+typedef struct SoarNormalViewArgs {
+    int32_t R, views;
+    const float *normal;
+    int64_t normal_stride;
+    const float *mask0, *gt_F, *gt_B, *gt_mask;
+    float *values, *stats, *lpips_in, *scratch;
+    const float *up, *g_lpips;
+    float *g_normal, *g_mask0;
+} SoarNormalViewArgs;
+int soar_normal_view_terms(const SoarNormalViewArgs *args, int32_t mode, void *stream);
+/* soar_frame_extra_terms: occ [3,H,W] planes, gt_mask [H,W]; gt_rgb and rand_bg through element strides {channel, pixel} (any
+ *   layout whose rows follow each other: interleaved, planar, a broadcast colour with pixel stride 0).
+ *   stats [2] = {mean of 1 - occ over the three channels of the pixels with gt_mask > 0 (float64 sums; NaN when none), the number of
+ *   those elements}; blended [3,H,W] = gt_rgb * m + rand_bg * (1 - m), each operation rounded once.
+ *   The backward: g_occ [3,H,W] = -(up[0] / stats[1]) at the selected pixels, 0 elsewhere.  H W <= 2^28.
+ * soar_abs_mean: stats [2] = {mean|x| (float64 sums), n}; the backward: sign(x) * (upstream / n), sign(0) = 0.  n <= 2^30. */
+typedef struct SoarFrameExtraArgs {
+    int32_t H, W;
+    const float *occ, *gt_rgb, *gt_mask, *rand_bg;
+    int64_t rgb_stride[2], bg_stride[2];
+    float *stats, *blended;
+    void *scratch;
+    const float *up;
+    float *g_occ;
+} SoarFrameExtraArgs;
+int soar_frame_extra_terms(const SoarFrameExtraArgs *args, void *stream);
+int soar_frame_extra_terms_backward(const SoarFrameExtraArgs *args, void *stream);
+int soar_abs_mean(int64_t n, const float *x, float *stats, void *scratch, void *stream);
+int soar_abs_mean_backward(int64_t n, const float *x, const float *upstream_dev, float *dL_dx, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

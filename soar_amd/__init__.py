@@ -8,11 +8,14 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # the geometry model ("gaussiansurfel-base") and the playback entry point are exported here without making `import soar_amd` load torch
+    # the geometry model ("gaussiansurfel-base"), the playback entry point and the training system are exported here without making `import soar_amd` load torch
     if name == "GaussianSurfelModel":
         from .geometry import GaussianSurfelModel
         return GaussianSurfelModel
     if name == "AvatarPlayer":
         from .playback import AvatarPlayer
         return AvatarPlayer
+    if name == "SurfelMVDreamSystem":
+        from .system import SurfelMVDreamSystem
+        return SurfelMVDreamSystem
     raise AttributeError(f"module 'soar_amd' has no attribute '{name}'")

@@ -8,6 +8,7 @@
 // Both are means over a data-dependent selection: the forward kernel leaves {sum, count} per workgroup, a finish kernel
 // folds them; the backward kernel reads the count and the upstream scalar from device memory (no host round trip).
 #include "soar_common.h"
+#include "loss_pixel.h"       // the cosine arithmetic, the load helpers and the reductions (shared with step_terms.hip)
 
 #include <cstdint>
 
@@ -25,31 +26,6 @@ struct LossArgs {
     const float *upstream;             // backward: d L / d loss (device scalar) or nullptr (= 1)
     float *grad;                       // backward out [C,n]
 };
-
-__device__ __forceinline__ void block_sum2(float s, float c, float *partials)
-{
-    __shared__ float red[4][2];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); c += __shfl_xor(c, off); }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        partials[2 * blockIdx.x + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    }
-}
-
-// V = 4: four consecutive pixels per thread and trip through 16-byte loads / stores (pixel count a multiple of 4, planes 16-byte
-// aligned: every image of the path); V = 1: any size
-template <int V> struct PixVec;
-template <> struct PixVec<4> { typedef float4 F; typedef uchar4 M; };
-template <> struct PixVec<1> { typedef float F; typedef uint8_t M; };
-__device__ __forceinline__ void unpack(const float4 &v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-__device__ __forceinline__ void unpack(const float &v, float (&o)[1]) { o[0] = v; }
-__device__ __forceinline__ void unpack(const uchar4 &v, bool (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-__device__ __forceinline__ void unpack(const uint8_t &v, bool (&o)[1]) { o[0] = v; }
-__device__ __forceinline__ float4 pack(const float (&o)[4]) { return make_float4(o[0], o[1], o[2], o[3]); }
-__device__ __forceinline__ float pack(const float (&o)[1]) { return o[0]; }
 
 template <bool BACKWARD, int V>
 __global__ void __launch_bounds__(256) masked_l1_kernel(Batch<LossArgs> batch)
@@ -111,7 +87,7 @@ __global__ void __launch_bounds__(256) cos_loss_kernel(Batch<LossArgs> batch)
             unpack(reinterpret_cast<const F *>(a.b + (size_t)c * a.n)[p], y);
 #pragma unroll
             for (int k = 0; k < V; k++) {
-                cs[k] += (x[k] * 2.f - 1.f) * (y[k] * 2.f - 1.f) * a.weight;
+                cos_accumulate(cs[k], x[k], y[k], a.weight);
                 if (c < 3) gt[c][k] = y[k];
             }
         }
@@ -124,7 +100,7 @@ __global__ void __launch_bounds__(256) cos_loss_kernel(Batch<LossArgs> batch)
 #pragma unroll
                 for (int k = 0; k < V; k++) {
                     const float y = c < 3 ? gt[c < 3 ? c : 0][k] : a.b[(size_t)c * a.n + (size_t)p * V + k];
-                    g[k] = sel[k] ? -2.f * a.weight * (y * 2.f - 1.f) * scale : 0.f;
+                    g[k] = sel[k] ? cos_grad_value(a.weight, y, scale) : 0.f;
                 }
                 reinterpret_cast<F *>(a.grad + (size_t)c * a.n)[p] = pack(g);
             }
@@ -153,25 +129,9 @@ struct MeanFinishArgs {
 __global__ void __launch_bounds__(256) mean_finish_kernel(Batch<MeanFinishArgs> batch)
 {
     const MeanFinishArgs &fa = batch.v[blockIdx.y];
-    const float *partials = fa.partials;
-    const int nblocks = fa.nblocks;
-    const float per = fa.per;
-    float *stats = fa.stats;
-    __shared__ float red[4][2];
-    float s = 0.f, c = 0.f;
-    for (int k = threadIdx.x; k < nblocks; k += 256) { s += partials[2 * k]; c += partials[2 * k + 1]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); c += __shfl_xor(c, off); }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float st = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]), ct = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        stats[0] = st / (ct * per);
-        stats[1] = ct;
-    }
+    mean_finish_block(fa.partials, fa.nblocks, fa.per, fa.stats);
 }
 
-constexpr int LOSS_BLOCKS = 1024;
 
 // ---- the avatar stage's per-pixel losses in ONE pass over the images (round 4) --------------------------------------------------
 // masked L1 of the colours, L1 of the mask image, cosine loss of the normals, masked L1 of the occlusion image against 1
@@ -295,7 +255,7 @@ __global__ void __launch_bounds__(256) avatar_pixel_kernel(Batch<AvatarArgs> bat
                 }
 #pragma unroll
                 for (int k = 0; k < V; k++) {
-                    cs[k] += (x[k] * 2.f - 1.f) * (y[k] * 2.f - 1.f) * a.cos_weight;
+                    cos_accumulate(cs[k], x[k], y[k], a.cos_weight);
                     gt[c][k] = y[k];
                 }
             }
@@ -309,7 +269,7 @@ __global__ void __launch_bounds__(256) avatar_pixel_kernel(Batch<AvatarArgs> bat
                     float g[V];
 #pragma unroll
                     for (int k = 0; k < V; k++) {
-                        g[k] = seln[k] ? -2.f * a.cos_weight * (gt[c][k] * 2.f - 1.f) * sc_cos : 0.f;
+                        g[k] = seln[k] ? cos_grad_value(a.cos_weight, gt[c][k], sc_cos) : 0.f;
                         if (a.normal_raw) {
                             const float h = g[k] * 0.5f;
                             g[k] = opaque[k] ? (c == 0 ? h : -h) : 0.f;

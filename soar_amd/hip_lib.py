@@ -228,6 +228,20 @@ class SoarSmplifyArgs(C.Structure):
                 + [("g_" + k, _vp) for k in _SMPLIFY_PARAMS[:6]] + [("loss", _vp), ("kps", _vp), ("frame_betas", _vp), ("frame_loss", _vp)])
 
 
+class SoarNormalViewArgs(C.Structure):
+    """Mirror of ``struct SoarNormalViewArgs`` (include/soar_hip.h)."""
+    _fields_ = [("R", C.c_int32), ("views", C.c_int32), ("normal", _vp), ("normal_stride", C.c_int64), ("mask0", _vp), ("gt_F", _vp),
+                ("gt_B", _vp), ("gt_mask", _vp), ("values", _vp), ("stats", _vp), ("lpips_in", _vp), ("scratch", _vp), ("up", _vp),
+                ("g_lpips", _vp), ("g_normal", _vp), ("g_mask0", _vp)]
+
+
+class SoarFrameExtraArgs(C.Structure):
+    """Mirror of ``struct SoarFrameExtraArgs`` (include/soar_hip.h)."""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("occ", _vp), ("gt_rgb", _vp), ("gt_mask", _vp), ("rand_bg", _vp),
+                ("rgb_stride", C.c_int64 * 2), ("bg_stride", C.c_int64 * 2), ("stats", _vp), ("blended", _vp), ("scratch", _vp), ("up", _vp),
+                ("g_occ", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -418,6 +432,15 @@ SIGNATURES = {
     "soar_masks_open_close": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
     "soar_masks_largest_component": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "soar_masks_clean": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "soar_step_terms_scratch_bytes": (C.c_int, [C.POINTER(C.c_size_t)]),
+    "soar_consistency_loss": (C.c_int, [C.c_int32] * 3 + [_vp, C.c_int64, _vp, C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "soar_consistency_loss_backward": (C.c_int, [C.c_int32] * 3 + [_vp, C.c_int64, _vp, C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp, _vp,
+                                                 _vp]),
+    "soar_normal_view_terms": (C.c_int, [C.POINTER(SoarNormalViewArgs), C.c_int32, _vp]),
+    "soar_frame_extra_terms": (C.c_int, [C.POINTER(SoarFrameExtraArgs), _vp]),
+    "soar_frame_extra_terms_backward": (C.c_int, [C.POINTER(SoarFrameExtraArgs), _vp]),
+    "soar_abs_mean": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp]),
+    "soar_abs_mean_backward": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -8,3 +8,4 @@ from .. import background  # noqa: F401,E402  (registers "gaussiandreamer-backgr
 # registers "gaussiansurfel-base", so that registry.find() knows every name once the plugin package is imported (as the background
 # above); geometry itself asks for .registry only, which is already loaded at this point
 from .. import geometry  # noqa: F401,E402
+from .. import system  # noqa: F401,E402  (registers "gaussiansurfel-mvdream-system")
