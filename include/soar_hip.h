@@ -1453,6 +1453,28 @@ typedef struct SoarSmplifyArgs {
     float *frame_betas, *frame_loss;
 } SoarSmplifyArgs;
 int soar_smplify_objective(const SoarSmplifyRig *rig, const SoarSmplifyArgs *args, void *stream);
+/* SoarSmplifyBody, soar_smplify_objective_body: the same objective for the body model the reference creates (use_face_contour=True,
+ *   flat_hand_mean=False).  The rig's gathered arrays (v_template, shapedirs, posedirs, lbs_weights) then hold VU rows: the rig's
+ *   VS static rows first, then the vertices of all 79 rows of the contour table (any count: only a frame's active set, VS +
+ *   3 L_dyn <= 256 slots, is held on chip; posedirs rows are VU 3 long).  Per frame the row is chosen from R = the world rotation of
+ *   joint `neck` (root ... neck, pose mean included): e = atan2(-R[2][0], sqrt(R[0][0]^2 + R[1][0]^2)), y = rint(min(-e 180/pi,
+ *   39)) (half to even), row = y if y >= 0, 78 if y < -39, else 39 - y.  Contour landmark l then is sum_k dyn_bary[row][l][k] x vertex
+ *   row dyn_vrow[row][l][k], and replaces the weights and indices of model point dyn_point[l] (a pt_kind 1 entry of the rig; -1: the
+ *   landmark feeds no keypoint).  The row is not differentiated.  rows_out [N] int32 or NULL receives the rows (written only with L_dyn > 0).
+ *   pose_mean [55][3]: joint j with bit j of mean_mask set enters the body model as rodrigues(log(R_j) + mean_j) (optimised joints;
+ *   log by the axial vector and atan2, a series below |a| = 1e-3, specified for angles up to 3.0 rad) or rodrigues(v_j + mean_j)
+ *   (jaw, eyes); the other joints take the direct path.  The preserve and smooth terms are unchanged.  L_dyn = 0 and mean_mask = 0
+ *   runs soar_smplify_objective itself.  Refuses N <= 0.  Same launches, same no-atomics guarantees as soar_smplify_objective. */
+typedef struct SoarSmplifyBody {
+    int32_t L_dyn, n_rows, neck, VU;   /* contour landmarks (<= 17, 0: none), table rows (79), the neck joint, gathered rows */
+    const int32_t *dyn_vrow;      /* [79][L_dyn][3] rows of the gathered arrays, in [0, VU) */
+    const float *dyn_bary;        /* [79][L_dyn][3] */
+    const int32_t *dyn_point;     /* [L_dyn] model point in [0, P) or -1 */
+    const float *pose_mean;       /* [55][3] or NULL with mean_mask = 0 */
+    uint64_t mean_mask;
+    int32_t *rows_out;            /* [N] or NULL */
+} SoarSmplifyBody;
+int soar_smplify_objective_body(const SoarSmplifyRig *rig, const SoarSmplifyBody *body, const SoarSmplifyArgs *args, void *stream);
 int soar_smplify_target_scales(int32_t N, const float *target_kps, float img_w, float img_h, float *scales, void *stream);
 
 /* ---- SMPL-X normal priors: an indexed triangle mesh drawn as a normal map (prior.hip, soar_amd/prior.py) ----

@@ -15,6 +15,22 @@
 // preserve gradients depend on nothing but the frame's own inputs and the scales.
 // The reference sends every optimised rotation through rotmat -> rotvec -> batch_rodrigues before lbs(); that is the identity map
 // and is skipped.  Jaw and eyes are rotation vectors and go through batch_rodrigues (soar_rodrigues.h) as there.
+//
+// smplify_frame_kernel<true> (soar_smplify_objective_body) adds the two things SMPLX.forward does for the model the reference
+// creates (use_face_contour=True, flat_hand_mean=False); smplify_frame_kernel<false> is the kernel above, statement for statement.
+//   Contour landmarks: after the chain the workgroup computes the table row from Rw[neck] (rot_mat_to_euler and the rounding of
+//   find_dynamic_lmk_idx_and_bcoords, lbs.py:82-99) and fills smap[slot] -> row of the gathered arrays: slots 0 .. VS-1 are the
+//   static rows themselves, slot VS + 3 l + k is corner k of contour landmark l in the chosen row.  The gathered arrays hold the
+//   union of all 79 rows (VU rows, any count); a frame's active set, VS + 3 L_dyn <= 256 slots, lives in LDS as before, and every
+//   loop over vertices (blend shapes, correctives, skinning, their adjoints, the betas partial) reads device memory through
+//   smap.  The row is not differentiated.
+//   Pose mean: a joint whose bit is set in mean_mask enters the body model as rodrigues(log(R) + mean_j) (R from Gram-Schmidt for an
+//   optimised joint; for jaw and eyes the mean is added to the rotation vector).  log: a = vee(R - R^T) / 2, s = |a|,
+//   c = (tr R - 1) / 2, v = a atan2(s, c) / s; for s < 1e-3 with c > 0 the series 1 + s^2/6 + 3 s^4/40 of asin(s)/s (the next term
+//   is below 5e-20), so v = 0 with a finite gradient at R = I.  Specified for angles up to 3.0 rad: towards pi, s -> 0 divides.
+//   The adjoint runs Rodrigues' adjoint, then log's, then Gram-Schmidt's.  The preserve and smooth terms read the 6-D vectors.
+#include <type_traits>
+
 #include "soar_common.h"
 #include "soar_rodrigues.h"
 
@@ -87,6 +103,78 @@ __device__ __forceinline__ void rot6d_backward(const float *x, const float *g, f
     }
 }
 
+// ---- the pose mean's detour: log, and the adjoints of log and of rodrigues<3> ----
+constexpr float LOG_SERIES = 1e-3f;
+
+__device__ __forceinline__ void so3_log(const float *R, float *v)
+{
+    const float a[3] = {0.5f * (R[7] - R[5]), 0.5f * (R[2] - R[6]), 0.5f * (R[3] - R[1])};
+    const float c = 0.5f * (R[0] + R[4] + R[8] - 1.f);
+    const float s2 = dot3(a, a), s = sqrtf(s2);
+    const float f = (s < LOG_SERIES && c > 0.f) ? fmaf(s2, fmaf(s2, 0.075f, 1.f / 6.f), 1.f) : atan2f(s, c) / fmaxf(s, 1e-30f);
+    for (int k = 0; k < 3; k++) v[k] = a[k] * f;
+}
+
+// gv [3] -> gR [9] (overwritten)
+__device__ __forceinline__ void so3_log_backward(const float *R, const float *gv, float *gR)
+{
+    const float a[3] = {0.5f * (R[7] - R[5]), 0.5f * (R[2] - R[6]), 0.5f * (R[3] - R[1])};
+    const float c = 0.5f * (R[0] + R[4] + R[8] - 1.f);
+    const float s2 = dot3(a, a), s = sqrtf(s2);
+    float f, fs, fc;                       // f, (df/ds) / s, df/dc
+    if (s < LOG_SERIES && c > 0.f) {
+        f = fmaf(s2, fmaf(s2, 0.075f, 1.f / 6.f), 1.f);
+        fs = fmaf(s2, 0.3f, 1.f / 3.f);
+        fc = 0.f;
+    } else {
+        const float den = fmaf(s, s, c * c);
+        f = atan2f(s, c) / fmaxf(s, 1e-30f);
+        fs = s2 > 0.f ? (c / den - f) / s2 : 0.f;
+        fc = den > 0.f ? -1.f / den : 0.f;
+    }
+    const float gf = dot3(a, gv);
+    const float ga[3] = {fmaf(a[0], gf * fs, f * gv[0]), fmaf(a[1], gf * fs, f * gv[1]), fmaf(a[2], gf * fs, f * gv[2])};
+    const float gc = 0.5f * (gf * fc);
+    gR[0] = gc; gR[4] = gc; gR[8] = gc;
+    gR[7] = 0.5f * ga[0]; gR[5] = -0.5f * ga[0];
+    gR[2] = 0.5f * ga[1]; gR[6] = -0.5f * ga[1];
+    gR[3] = 0.5f * ga[2]; gR[1] = -0.5f * ga[2];
+}
+
+// the adjoint of rodrigues<3> (soar_rodrigues.h): g [9] -> gv [3]
+__device__ __forceinline__ void rodrigues_backward(const float *v, const float *g, float *gv)
+{
+    const float e[3] = {v[0] + 1e-8f, v[1] + 1e-8f, v[2] + 1e-8f};
+    const float angle = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    const float rx = v[0] / angle, ry = v[1] / angle, rz = v[2] / angle;
+    const float sn = sinf(angle), cn = cosf(angle), cs = 1.f - cn;
+    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+    float gsn = 0.f, gcs = 0.f, gK[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            float kk = 0.f, t = 0.f;
+            for (int m = 0; m < 3; m++) {
+                kk += K[r * 3 + m] * K[m * 3 + c];
+                t += g[r * 3 + m] * K[c * 3 + m] + K[m * 3 + r] * g[m * 3 + c];     // g K^T + K^T g
+            }
+            gsn = fmaf(g[r * 3 + c], K[r * 3 + c], gsn);
+            gcs = fmaf(g[r * 3 + c], kk, gcs);
+            gK[r * 3 + c] = fmaf(cs, t, sn * g[r * 3 + c]);
+        }
+    const float gr[3] = {gK[7] - gK[5], gK[2] - gK[6], gK[3] - gK[1]};
+    const float gang = fmaf(gsn, cn, gcs * sn) - dot3(gr, v) / (angle * angle);
+    for (int k = 0; k < 3; k++) gv[k] = gr[k] / angle + gang * (e[k] / angle);
+}
+
+// the table row of find_dynamic_lmk_idx_and_bcoords from the neck's world rotation R (row-major)
+__device__ __forceinline__ int contour_row(const float *R, int n_rows)
+{
+    const float e = atan2f(-R[6], sqrtf(fmaf(R[0], R[0], R[3] * R[3])));
+    const int y = (int)rintf(fminf(-e * 180.f / 3.14159265358979323846f, 39.f));      // half to even, as torch.round
+    const int row = y >= 0 ? y : (y < -39 ? 78 : 39 - y);
+    return min(row, n_rows - 1);
+}
+
 // C = A B (3x3 row-major)
 __device__ __forceinline__ void mm3(const float *A, const float *B, float *C)
 {
@@ -121,6 +209,13 @@ struct FrameArgs {
     SoarSmplifyRig rig;
     SoarSmplifyArgs a;
 };
+struct BodyFrameArgs {
+    SoarSmplifyRig rig;
+    SoarSmplifyArgs a;
+    SoarSmplifyBody b;
+};
+constexpr int S_DYN_ROWS = 79;      // rows of the contour table
+constexpr int S_MAX_DYN = 17;       // contour landmarks
 
 __device__ __forceinline__ const float *pose_ptr(const SoarSmplifyArgs &a, int key, bool init)
 {
@@ -152,12 +247,20 @@ __device__ __forceinline__ float row_norm(const float *p, const float *p0, int n
     return nrm;
 }
 
-__global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
+// BODY: per-frame contour landmarks and the pose mean (SoarSmplifyBody).  Without it VS counts the gathered rows and the slots
+// alike; with it rig.VS is the static rows' count, VS below the frame's active slots and PS3 the row length of posedirs.
+template <bool BODY>
+__global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(std::conditional_t<BODY, BodyFrameArgs, FrameArgs> fa)
 {
     const SoarSmplifyRig &rig = fa.rig;
     const SoarSmplifyArgs &a = fa.a;
     const int n = blockIdx.x, tid = threadIdx.x;
-    const int NB = rig.NBS + rig.NE, VS = rig.VS, VS3 = rig.VS * 3, P = rig.P;
+    int VS_ = rig.VS, PS3_ = rig.VS * 3;
+    if constexpr (BODY) { VS_ = rig.VS + 3 * fa.b.L_dyn; PS3_ = fa.b.VU * 3; }
+    const int NB = rig.NBS + rig.NE, VS = VS_, VS3 = VS_ * 3, PS3 = PS3_, P = rig.P;
+    __shared__ int smap[BODY ? S_MAX_VS : 1];       // slot -> row of the gathered arrays
+    auto row_of = [&](int slot) -> int { if constexpr (BODY) return smap[slot]; else return slot; };
+    auto col_of = [&](int col) -> int { if constexpr (BODY) return smap[col / 3] * 3 + col % 3; else return col; };
 
     __shared__ float coef[S_MAX_NB];
     __shared__ float Rl[SJ][9], Rw[SJ][9], Jr[SJ][3], tw[SJ][3], At[SJ][3];
@@ -186,10 +289,29 @@ __global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
             float x[6];
             const float *src = pose_ptr(a, key, false) + ((size_t)n * key_joints(key) + jk) * 6;
             for (int c = 0; c < 6; c++) x[c] = src[c];
-            rot6d(x, Rl[tid]);
+            bool direct = true;
+            if constexpr (BODY) {
+                if ((fa.b.mean_mask >> tid) & 1ull) {              // rodrigues(log(R) + mean)
+                    float R6[9], v[3];
+                    rot6d(x, R6);
+                    so3_log(R6, v);
+                    for (int c = 0; c < 3; c++) v[c] += fa.b.pose_mean[tid * 3 + c];
+                    rodrigues<3>(v, Rl[tid]);
+                    direct = false;
+                }
+            }
+            if (direct) rot6d(x, Rl[tid]);
         } else {
             const float *src = (tid == 22 ? a.jaw_pose : (tid == 23 ? a.leye_pose : a.reye_pose)) + (size_t)n * 3;
-            rodrigues<3>(src, Rl[tid]);
+            bool direct = true;
+            if constexpr (BODY) {
+                if ((fa.b.mean_mask >> tid) & 1ull) {
+                    const float v[3] = {src[0] + fa.b.pose_mean[tid * 3], src[1] + fa.b.pose_mean[tid * 3 + 1], src[2] + fa.b.pose_mean[tid * 3 + 2]};
+                    rodrigues<3>(v, Rl[tid]);
+                    direct = false;
+                }
+            }
+            if (direct) rodrigues<3>(src, Rl[tid]);
         }
     }
     for (int p = tid; p < P; p += S_THREADS) {
@@ -246,19 +368,36 @@ __global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
             At[tid][r] = W[r * 4 + 3] - fmaf(W[r * 4 + 2], Jr[tid][2], fmaf(W[r * 4 + 1], Jr[tid][1], W[r * 4] * Jr[tid][0]));
         }
     }
+    if constexpr (BODY) {
+        // ---- the contour landmarks' row: every thread derives it from Rw[neck]; the slot map and the landmarks' point entries ----
+        __syncthreads();
+        const SoarSmplifyBody &b = fa.b;
+        const int row = b.L_dyn > 0 ? contour_row(Rw[b.neck], S_DYN_ROWS) : 0;
+        if (tid < rig.VS) smap[tid] = tid;
+        if (tid < b.L_dyn * 3) {
+            const int l = tid / 3, k = tid % 3, slot = rig.VS + tid;
+            const size_t at = ((size_t)row * b.L_dyn + l) * 3 + k;
+            smap[slot] = b.dyn_vrow[at];
+            const int p = b.dyn_point[l];
+            if (p >= 0) { pti[p][k] = slot; ptw[p][k] = b.dyn_bary[at]; }
+        }
+        if (tid == 0 && b.rows_out && b.L_dyn > 0) b.rows_out[n] = row;
+        __syncthreads();
+    }
     // ---- shape blend and pose correctives of the gathered vertices: a thread per (vertex, component) column ----
     for (int col = tid; col < VS3; col += S_THREADS) {
+        const int gcol = col_of(col);
         float sh = 0.f;
-        const float *sd = rig.shapedirs + (size_t)col * NB;
+        const float *sd = rig.shapedirs + (size_t)gcol * NB;
         for (int l = 0; l < NB; l++) sh = fmaf(coef[l], sd[l], sh);
-        const float *pd = rig.posedirs + col;
+        const float *pd = rig.posedirs + gcol;
         float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;                 // three chains, joined in a fixed order
         for (int k = 0; k < SFEAT; k += 3) {
-            acc0 = fmaf(feat[k], pd[(size_t)k * VS3], acc0);
-            acc1 = fmaf(feat[k + 1], pd[(size_t)(k + 1) * VS3], acc1);
-            acc2 = fmaf(feat[k + 2], pd[(size_t)(k + 2) * VS3], acc2);
+            acc0 = fmaf(feat[k], pd[(size_t)k * PS3], acc0);
+            acc1 = fmaf(feat[k + 1], pd[(size_t)(k + 1) * PS3], acc1);
+            acc2 = fmaf(feat[k + 2], pd[(size_t)(k + 2) * PS3], acc2);
         }
-        (&vposed[0][0])[col] = ((acc0 + acc1) + acc2) + (rig.v_template[col] + sh);
+        (&vposed[0][0])[col] = ((acc0 + acc1) + acc2) + (rig.v_template[gcol] + sh);
     }
     __syncthreads();
 
@@ -266,7 +405,7 @@ __global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
     if (tid < VS) {
         float T[12];
         for (int c = 0; c < 12; c++) T[c] = 0.f;
-        const float *w = rig.lbs_weights + (size_t)tid * SJ;
+        const float *w = rig.lbs_weights + (size_t)row_of(tid) * SJ;
         for (int j = 0; j < SJ; j++) {
             const float wj = w[j];
             for (int r = 0; r < 3; r++) {
@@ -400,16 +539,16 @@ __global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
     for (int i = tid; i < SJ * 12; i += S_THREADS) {
         const int j = i / 12, e = i % 12;
         float s = 0.f;
-        for (int v = 0; v < VS; v++) s = fmaf(rig.lbs_weights[(size_t)v * SJ + j], Ts[v][e], s);
+        for (int v = 0; v < VS; v++) s = fmaf(rig.lbs_weights[(size_t)row_of(v) * SJ + j], Ts[v][e], s);
         gA[j][e] = s;
     }
     // pose correctives: the gradient of feature k is row k of posedirs against the gradient of v_posed -- a wave per row
     {
         const int wave = tid >> 6, lane = tid & 63;
         for (int k = wave; k < SFEAT; k += S_THREADS / 64) {
-            const float *pd = rig.posedirs + (size_t)k * VS3;
+            const float *pd = rig.posedirs + (size_t)k * PS3;
             float s = 0.f;
-            for (int col = lane; col < VS3; col += 64) s = fmaf(pd[col], (&vposed[0][0])[col], s);
+            for (int col = lane; col < VS3; col += 64) s = fmaf(pd[col_of(col)], (&vposed[0][0])[col], s);
             for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
             if (lane == 0) feat[k] = s;
         }
@@ -475,6 +614,16 @@ __global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
             const float *src = pose_ptr(a, key, false) + at, *src0 = pose_ptr(a, key, true) + at;
             float x[6], x0[6], gx[6], gp[6];
             for (int c = 0; c < 6; c++) { x[c] = src[c]; x0[c] = src0[c]; }
+            if constexpr (BODY) {
+                if ((fa.b.mean_mask >> tid) & 1ull) {              // back through rodrigues(log(R6) + mean)
+                    float R6[9], v[3], gv[3];
+                    rot6d(x, R6);
+                    so3_log(R6, v);
+                    for (int c = 0; c < 3; c++) v[c] += fa.b.pose_mean[tid * 3 + c];
+                    rodrigues_backward(v, gR, gv);
+                    so3_log_backward(R6, gv, gR);
+                }
+            }
             rot6d_backward(x, gR, gx);
             preserve += a.pose_scale[key] * row_norm(x, x0, 6, a.pose_scale[key], gp);
             float *dst = grad_ptr(a, key) + at;
@@ -494,7 +643,7 @@ __global__ void __launch_bounds__(S_THREADS) smplify_frame_kernel(FrameArgs fa)
         const int per = (VS3 + 7) / 8, c0 = q * per, c1 = min(VS3, c0 + per);
         for (int l = l0; l < rig.NBS; l += 32) {
             float s = 0.f;
-            for (int col = c0; col < c1; col++) s = fmaf(rig.shapedirs[(size_t)col * NB + l], (&vposed[0][0])[col], s);
+            for (int col = c0; col < c1; col++) s = fmaf(rig.shapedirs[(size_t)col_of(col) * NB + l], (&vposed[0][0])[col], s);
             bpart[q][l] = s;
         }
     }
@@ -670,8 +819,72 @@ extern "C" int soar_smplify_objective(const SoarSmplifyRig *rig, const SoarSmpli
     FrameArgs fa;
     fa.rig = r;
     fa.a = a;
-    hipLaunchKernelGGL(smplify_frame_kernel, dim3(a.N), dim3(S_THREADS), 0, stream, fa);
+    hipLaunchKernelGGL(smplify_frame_kernel<false>, dim3(a.N), dim3(S_THREADS), 0, stream, fa);
     SOAR_LAUNCH_OK("smplify_frame", stream, 0);
+    if (a.grads) {
+        hipLaunchKernelGGL(smplify_finish_kernel, dim3(1), dim3(F_THREADS), 0, stream, a, r.NBS);
+        SOAR_LAUNCH_OK("smplify_finish", stream, 0);
+    }
+    return 0;
+}
+
+extern "C" int soar_smplify_objective_body(const SoarSmplifyRig *rig, const SoarSmplifyBody *body, const SoarSmplifyArgs *args, void *stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!rig || !body || !args) { set_error("soar_smplify_objective_body: NULL rig / body / args"); return 1; }
+    const SoarSmplifyRig &r = *rig;
+    const SoarSmplifyBody &b = *body;
+    const SoarSmplifyArgs &a = *args;
+    if (a.N <= 0) { set_error("soar_smplify_objective_body: N=%d: need at least one frame", a.N); return 1; }
+    if (b.L_dyn < 0 || b.L_dyn > S_MAX_DYN || (b.L_dyn > 0 && (b.n_rows != S_DYN_ROWS || b.neck < 0 || b.neck >= SJ))) {
+        set_error("soar_smplify_objective_body: need 0 <= L_dyn <= %d, and with L_dyn > 0 n_rows = %d and 0 <= neck < %d (L_dyn=%d n_rows=%d neck=%d)",
+                  S_MAX_DYN, S_DYN_ROWS, SJ, b.L_dyn, b.n_rows, b.neck);
+        return 1;
+    }
+    if (r.VS < 1 || r.VS + 3 * b.L_dyn > S_MAX_VS || b.VU < r.VS) {
+        set_error("soar_smplify_objective_body: %d static slots + 3 x %d contour slots exceed the %d a frame may use, or the union VU=%d is below "
+                  "the static rows", r.VS, b.L_dyn, S_MAX_VS, b.VU);
+        return 1;
+    }
+    if ((b.L_dyn > 0 && (!b.dyn_vrow || !b.dyn_bary || !b.dyn_point)) || (b.mean_mask != 0 && !b.pose_mean) || (b.mean_mask >> SJ) != 0) {
+        set_error("soar_smplify_objective_body: NULL contour table or pose_mean, or a mean_mask bit past joint %d", SJ - 1);
+        return 1;
+    }
+    if (b.L_dyn == 0 && b.mean_mask == 0) {                       // nothing to add: the static kernel, its bits
+        if (b.VU != r.VS) { set_error("soar_smplify_objective_body: without a contour table VU=%d must equal VS=%d", b.VU, r.VS); return 1; }
+        return soar_smplify_objective(rig, args, stream_);
+    }
+    // the remaining checks are soar_smplify_objective's, on a rig whose VS is the static rows' count
+    if (r.J != SJ || r.NBS < 1 || r.NE < 0 || r.NBS + r.NE > S_MAX_NB || r.P < 0 || r.P > S_MAX_P) {
+        set_error("soar_smplify_objective_body: need J = %d, 1 <= NBS, NBS + NE <= %d, 0 <= P <= %d (J=%d NBS=%d NE=%d P=%d)",
+                  SJ, S_MAX_NB, S_MAX_P, r.J, r.NBS, r.NE, r.P);
+        return 1;
+    }
+    if (a.N > 0x7fffffff / (SKP * 3)) { set_error("soar_smplify_objective_body: N=%d out of range", a.N); return 1; }
+    if (!r.J_template || !r.J_dirs || !r.parents || !r.v_template || !r.shapedirs || !r.posedirs || !r.lbs_weights || !r.kp_mask
+        || (r.P > 0 && (!r.pt_kind || !r.pt_idx || !r.pt_w || !r.pt_dst))) {
+        set_error("soar_smplify_objective_body: NULL rig table");
+        return 1;
+    }
+    if (!a.global_orient || !a.body_pose || !a.left_hand_pose || !a.right_hand_pose || !a.betas || !a.transl || !a.jaw_pose || !a.leye_pose
+        || !a.reye_pose || (r.NE > 0 && !a.expression) || !a.Ks || !a.w2c || !a.target_kps || !a.target_scales) {
+        set_error("soar_smplify_objective_body: NULL input");
+        return 1;
+    }
+    if (a.grads && (!a.global_orient0 || !a.body_pose0 || !a.left_hand_pose0 || !a.right_hand_pose0 || !a.betas0 || !a.transl0 || !a.jaw_pose0
+                    || !a.leye_pose0 || !a.reye_pose0 || (r.NE > 0 && !a.expression0) || !a.g_global_orient || !a.g_body_pose
+                    || !a.g_left_hand_pose || !a.g_right_hand_pose || !a.g_betas || !a.g_transl || !a.loss || !a.frame_betas || !a.frame_loss)) {
+        set_error("soar_smplify_objective_body: NULL initial value, gradient or scratch pointer");
+        return 1;
+    }
+    if (!a.grads && !a.kps && !a.frame_loss) { set_error("soar_smplify_objective_body: nothing to compute (grads = 0, kps = NULL)"); return 1; }
+    if (!(a.sigma > 0.f)) { set_error("soar_smplify_objective_body: sigma must be positive"); return 1; }
+    BodyFrameArgs fa;
+    fa.rig = r;
+    fa.a = a;
+    fa.b = b;
+    hipLaunchKernelGGL(smplify_frame_kernel<true>, dim3(a.N), dim3(S_THREADS), 0, stream, fa);
+    SOAR_LAUNCH_OK("smplify_frame_body", stream, 0);
     if (a.grads) {
         hipLaunchKernelGGL(smplify_finish_kernel, dim3(1), dim3(F_THREADS), 0, stream, a, r.NBS);
         SOAR_LAUNCH_OK("smplify_finish", stream, 0);

@@ -228,6 +228,12 @@ class SoarSmplifyArgs(C.Structure):
                 + [("g_" + k, _vp) for k in _SMPLIFY_PARAMS[:6]] + [("loss", _vp), ("kps", _vp), ("frame_betas", _vp), ("frame_loss", _vp)])
 
 
+class SoarSmplifyBody(C.Structure):
+    """Mirror of ``struct SoarSmplifyBody`` (include/soar_hip.h)."""
+    _fields_ = [("L_dyn", C.c_int32), ("n_rows", C.c_int32), ("neck", C.c_int32), ("VU", C.c_int32), ("dyn_vrow", _vp), ("dyn_bary", _vp),
+                ("dyn_point", _vp), ("pose_mean", _vp), ("mean_mask", C.c_uint64), ("rows_out", _vp)]
+
+
 class SoarNormalViewArgs(C.Structure):
     """Mirror of ``struct SoarNormalViewArgs`` (include/soar_hip.h)."""
     _fields_ = [("R", C.c_int32), ("views", C.c_int32), ("normal", _vp), ("normal_stride", C.c_int64), ("mask0", _vp), ("gt_F", _vp),
@@ -424,6 +430,7 @@ SIGNATURES = {
     "soar_normal_crop_sample": (C.c_int, [C.c_int32] * 4 + [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     "soar_normal_crop_bytes": (C.c_int, [C.c_int32] * 3 + [_vp] * 6 + [_vp]),
     "soar_smplify_objective": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyArgs), _vp]),
+    "soar_smplify_objective_body": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyBody), C.POINTER(SoarSmplifyArgs), _vp]),
     "soar_smplify_target_scales": (C.c_int, [C.c_int32, _vp, C.c_float, C.c_float, _vp, _vp]),
     "soar_prior_vertex_setup": (C.c_int, [C.c_int32] * 3 + [_vp, C.POINTER(C.c_int64), _vp, C.c_int32] + [_vp] * 7 + [_vp]),
     "soar_prior_face_boxes": (C.c_int, [C.c_int32] * 3 + [_vp] * 3 + [_vp]),

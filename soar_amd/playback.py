@@ -212,10 +212,13 @@ class AvatarPlayer:
 
     ``geometry``: a ``GaussianSurfelModel`` or anything with the duck type of render_rot.py:16-51 (``CheckpointSurfels``);
     ``guidance``: the ``SMPLGuidance`` whose stored frames the turntable starts from; ``renderer``: a ``"gaussiansurfel-rasterizer"``
-    plugin instance over ``geometry`` (made with its defaults when None)."""
+    plugin instance over ``geometry`` (made with its defaults when None).  ``pose_mean [165]`` (the guidance's own when None): the
+    body model's mean pose; pose dicts hold offsets from it, as ``params.pth`` does, and the motion is made on offset + mean."""
 
-    def __init__(self, geometry, guidance, renderer=None, use_explicit: bool = False):
+    def __init__(self, geometry, guidance, renderer=None, use_explicit: bool = False, pose_mean=None):
         self.geometry, self.guidance = geometry, guidance
+        pose_mean = getattr(guidance, "pose_mean", None) if pose_mean is None else pose_mean
+        self.pose_mean = None if pose_mean is None else torch.as_tensor(pose_mean, dtype=torch.float32).reshape(1, 165).to(guidance.device)
         if getattr(geometry, "smpl_guidance", None) is None:
             geometry.smpl_guidance = guidance
         if renderer is None:
@@ -249,12 +252,15 @@ class AvatarPlayer:
         z = lambda n: torch.zeros((K, n), device=dev)
         get = lambda k, n: parms[k].to(dev).reshape(K, n) if parms.get(k) is not None else z(n)
         pose = torch.cat([get(k, n) for k, n in zip(POSE_KEYS, POSE_WIDTHS)], dim=1)
+        if self.pose_mean is not None:
+            pose = pose + self.pose_mean
         expr = parms.get("expression")
         expr = z(10) if expr is None else expr.to(dev).reshape(-1, expr.shape[-1]).expand(K, -1)
         return pose, get("transl", 3), expr, parms["betas"].to(dev)[:1]
 
-    @staticmethod
-    def _pose_dict(pose, transl, expr, betas) -> Dict[str, torch.Tensor]:
+    def _pose_dict(self, pose, transl, expr, betas) -> Dict[str, torch.Tensor]:
+        if self.pose_mean is not None:
+            pose = pose - self.pose_mean                                      # back to offsets: ``_keys_of`` adds the mean again
         d = _split_pose(pose)
         d.update(betas=betas, transl=transl, expression=expr)
         return d

@@ -158,22 +158,24 @@ def render_normal_priors(topo: MeshTopology, verts: torch.Tensor, w2c, Ks, img_w
     return out
 
 
-def full_pose(params: Mapping[str, torch.Tensor]) -> torch.Tensor:
+def full_pose(params: Mapping[str, torch.Tensor], pose_mean=None) -> torch.Tensor:
     """``[N,165]`` rotation vectors in SMPL-X joint order (global, 21 body, jaw, two eyes, 15 + 15 hand joints) from the parameter
-    dict ``SMPLify.fit`` returns and ``save_params`` writes."""
+    dict ``SMPLify.fit`` returns and ``save_params`` writes.  ``pose_mean [165]``: the body model's mean pose, added as
+    ``SMPLX.forward`` adds it (the parameters are offsets from it)."""
     N = params["body_pose"].shape[0]
     keys = ("global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")
-    return torch.cat([params[k].reshape(N, -1) for k in keys], dim=1)
+    pose = torch.cat([params[k].reshape(N, -1) for k in keys], dim=1)
+    return pose if pose_mean is None else pose + torch.as_tensor(pose_mean).reshape(1, -1).to(pose)
 
 
 @torch.no_grad()
 def body_normal_priors(body, params: Mapping[str, torch.Tensor], normal_Ks, w2c, topo: MeshTopology, img_wh=(512, 512),
-                       space: str = "opengl") -> Dict[str, torch.Tensor]:
+                       space: str = "opengl", pose_mean=None) -> Dict[str, torch.Tensor]:
     """The priors of N fitted frames: ``params`` as ``SMPLify.fit`` returns them (rotation vectors, ``betas [1|N,NBS]``,
     ``expression [N,NE]``, ``transl [N,3]``; device tensors), ``body`` as ``body.smplx_vertices`` takes it, ``normal_Ks [N,3,3]`` of
-    ``crop_frames``.  Returns ``render_normal_priors``' dict plus ``verts [N,V,3]``."""
+    ``crop_frames``, ``pose_mean`` as ``full_pose`` takes it.  Returns ``render_normal_priors``' dict plus ``verts [N,V,3]``."""
     from .body import smplx_vertices
-    pose = full_pose(params)
+    pose = full_pose(params, pose_mean)
     _hip(pose, "params")
     N = pose.shape[0]
     betas = params["betas"].reshape(-1, params["betas"].shape[-1])

@@ -27,7 +27,7 @@ _POSE_KEYS = ("global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose"
 
 class SMPLGuidance:
     def __init__(self, body, smpl_parms: Dict[str, torch.Tensor], device="cuda", leg_angle: float = 30.0, faces=None,
-                 num_subdiv: int = 2, pose_correctives: bool = False, generator: Optional[torch.Generator] = None):
+                 num_subdiv: int = 2, pose_correctives: bool = False, generator: Optional[torch.Generator] = None, pose_mean=None):
         """smpl_parms: betas [1,10], expression [F,10], global_orient [F,3], body_pose [F,63], jaw/leye/reye_pose [F,3],
         left/right_hand_pose [F,45], transl [F,3]  (the keys TS/utils/smpl.py:571-587 reads).
 
@@ -41,8 +41,12 @@ class SMPLGuidance:
         (``body.smplx_vertices``: shape blend, pose-corrective blend shapes, skinning, ``transl``), which is what the reference's
         ``cano_smpl.vertices`` are (:510).  The default stays False because ``cano_vertices`` without the correctives are what
         this class has always computed and what its blend weights, tests and recorded results were made with; the two differ
-        by about 1e-3 on the synthetic body."""
+        by about 1e-3 on the synthetic body.
+
+        ``pose_mean [165]``: the body model's mean pose (``flat_hand_mean=False``); the stored rotation vectors are offsets from
+        it and ``_full_pose`` adds it, as ``SMPLX.forward`` does.  The canonical pose is taken as it stands."""
         self.device = torch.device(device)
+        self.pose_mean = None if pose_mean is None else torch.as_tensor(pose_mean, dtype=torch.float32).reshape(1, 165).to(self.device)
         self.smpl_parms = {k: v.to(self.device) for k, v in smpl_parms.items()}
         self._jt = JointTransformer(body.v_template, body.shapedirs, body.J_regressor, body.parents).to(self.device)
         self.ori_lbs = body.lbs_weights.to(self.device)[None]
@@ -83,8 +87,9 @@ class SMPLGuidance:
     def _full_pose(self, parms):
         z = lambda n: torch.zeros(1, n, device=self.device)
         get = lambda k, n: parms[k].reshape(1, -1) if k in parms and parms[k] is not None else z(n)
-        return torch.cat([get("global_orient", 3), get("body_pose", 63), get("jaw_pose", 3), get("leye_pose", 3),
+        pose = torch.cat([get("global_orient", 3), get("body_pose", 63), get("jaw_pose", 3), get("leye_pose", 3),
                           get("reye_pose", 3), get("left_hand_pose", 45), get("right_hand_pose", 45)], dim=1)
+        return pose if self.pose_mean is None else pose + self.pose_mean
 
     def _select(self, smpl_parms_in=None, idx=None, zero_out=False):
         """Pose parameters of one frame, following the branches of __call__ (:567-599)."""

@@ -14,11 +14,17 @@ here it is two launches:
 * ``SMPLify(rig).fit``: the reference's two stages with ``torch.optim.LBFGS`` (plumbing); ``save_params`` writes ``params.pth``;
   ``load_keypoints`` / ``load_smplerx`` read the inputs.
 
-Departures from the reference: the optimised rotations enter the body model as matrices (the reference's
-rotmat -> rotvec -> Rodrigues detour is the identity map); N = 1 gives a smooth term of 0, not NaN; landmarks are static rows
-only -- the reference picks the 17 contour landmarks per frame by the head's yaw, here they are 17 further rows of
-``lmk_faces_idx`` / ``lmk_bary_coords`` (``from_body_model`` appends the frontal row of ``dynamic_lmk_*`` when the body has one);
-a body model with a non-zero ``pose_mean`` is refused.  HIP only; there is no CPU path.
+The body model the reference creates (``use_face_contour=True``, ``flat_hand_mean=False``) is opt-in, and both halves run in the
+kernel (``soar_smplify_objective_body``): ``from_body_model(..., dynamic_contour=True)`` keeps the 79-row contour table and the
+kernel picks every frame's row by the yaw of the neck's world rotation, as ``find_dynamic_lmk_idx_and_bcoords`` does;
+``use_pose_mean=True`` keeps a non-zero ``pose_mean``, and the joints it touches enter the body model as
+``rodrigues(log(R) + mean)``, so the hand rotation vectors ``fit`` returns are offsets from the hands' mean pose, as the reference's
+``params.pth`` stores them.  The defaults are the static rig: the frontal row appended as 17 static landmarks, and a non-zero
+``pose_mean`` refused.
+
+Departures from the reference: joints without a mean enter the body model as matrices (the reference's
+rotmat -> rotvec -> Rodrigues detour is the identity map there); N = 1 gives a smooth term of 0, not NaN; the log map is specified
+for angles up to 3.0 rad.  HIP only; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -37,6 +43,8 @@ from .hip_lib import check
 N_KEYPOINTS = 137
 N_JOINTS = 55
 MAX_VERTICES, MAX_POINTS, MAX_SHAPE_DIRS, MAX_DEPTH = 256, 160, 64, 32      # smplify.hip
+CONTOUR_ROWS, MAX_CONTOUR, MAX_UNION = 79, 17, 1 << 20                      # the contour table; the gathered rows of a rig with one
+NECK_JOINT = 12
 POSE_KEYS = ("global_orient", "body_pose", "left_hand_pose", "right_hand_pose")
 POSE_JOINTS = {"global_orient": 1, "body_pose": 21, "left_hand_pose": 15, "right_hand_pose": 15}
 GRAD_KEYS = POSE_KEYS + ("betas", "transl")
@@ -75,10 +83,17 @@ class KeypointRig:
     ``faces [F,3]``, ``lmk_faces_idx [L]``, ``lmk_bary_coords [L,3]``, ``extra_joints_idxs [NX]`` (the vertex selector's ids).
     Model point ``s`` of ``src_inds`` is joint ``s`` for ``s < 55``, selected vertex ``s - 55`` below ``55 + NX``, landmark
     ``s - 55 - NX`` above; ``dst_inds`` the OpenPose keypoint it is written to (distinct); ``kp_mask [137]``.  Every index is
-    checked here, on the host: the kernels trust the tables."""
+    checked here, on the host: the kernels trust the tables.
+
+    ``dynamic_lmk_faces_idx [79,LD]`` / ``dynamic_lmk_bary_coords [79,LD,3]`` (LD <= 17): the contour table.  Landmark
+    ``L + l`` (model point ``55 + NX + L + l``) is then contour landmark ``l`` of the row the kernel picks per frame from the world
+    rotation of ``neck_joint``.  The gathered arrays hold the static vertices first (``VS`` of them), then the table's distinct
+    vertices (``VU`` rows in all, at most ``MAX_UNION``); what is limited to 256 is a frame's active set, ``VS + 3 LD`` slots.
+    ``pose_mean [165]``: added to the joints' rotation vectors before the body model (module docstring); all zero is no mean."""
 
     def __init__(self, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, faces, lmk_faces_idx, lmk_bary_coords,
-                 extra_joints_idxs, src_inds, dst_inds, kp_mask, device="cuda"):
+                 extra_joints_idxs, src_inds, dst_inds, kp_mask, device="cuda", dynamic_lmk_faces_idx=None,
+                 dynamic_lmk_bary_coords=None, neck_joint=NECK_JOINT, pose_mean=None):
         f = lambda x: torch.as_tensor(x).detach().to("cpu", torch.float32)
         vt, sd, pd, Jreg, lw, bary, mask = (f(x) for x in (v_template, shapedirs, posedirs, J_regressor, lbs_weights, lmk_bary_coords, kp_mask))
         par, fc, lf, ex = _ints(parents, "parents"), _ints(faces, "faces"), _ints(lmk_faces_idx, "lmk_faces_idx"), _ints(extra_joints_idxs, "extra_joints_idxs")
@@ -106,9 +121,29 @@ class KeypointRig:
         _in_range(lf, fc.shape[0], "lmk_faces_idx")
         _in_range(ex, V, "extra_joints_idxs")
         NX, L = ex.numel(), lf.numel()
+        LD = 0
+        if (dynamic_lmk_faces_idx is None) != (dynamic_lmk_bary_coords is None):
+            raise ValueError("dynamic_lmk_faces_idx and dynamic_lmk_bary_coords come together")
+        if dynamic_lmk_faces_idx is not None:
+            df, db = _ints(dynamic_lmk_faces_idx, "dynamic_lmk_faces_idx"), f(dynamic_lmk_bary_coords)
+            if df.dim() != 2 or df.shape[0] != CONTOUR_ROWS or not 1 <= df.shape[1] <= MAX_CONTOUR or db.shape != tuple(df.shape) + (3,):
+                raise ValueError(f"bad shapes: dynamic_lmk_faces_idx {tuple(df.shape)} must be [{CONTOUR_ROWS},1..{MAX_CONTOUR}] and "
+                                 f"dynamic_lmk_bary_coords {tuple(db.shape)} the same with a trailing 3")
+            _in_range(df, fc.shape[0], "dynamic_lmk_faces_idx")
+            neck_joint = int(neck_joint)
+            if not 0 <= neck_joint < J:
+                raise ValueError(f"neck_joint {neck_joint} is outside [0, {J})")
+            LD = df.shape[1]
+        mean = None
+        if pose_mean is not None:
+            mean = f(pose_mean).reshape(-1)
+            if mean.numel() != J * 3:
+                raise ValueError(f"pose_mean must hold {J * 3} values (got {mean.numel()})")
+            if not bool(torch.isfinite(mean).all()):
+                raise ValueError("pose_mean is not finite")
         if src.shape != dst.shape or src.numel() > MAX_POINTS:
             raise ValueError(f"src_inds and dst_inds must have one length, at most {MAX_POINTS} (got {src.numel()} and {dst.numel()})")
-        _in_range(src, J + NX + L, "src_inds")
+        _in_range(src, J + NX + L + LD, "src_inds")
         _in_range(dst, N_KEYPOINTS, "dst_inds")
         if dst.unique().numel() != dst.numel():
             raise ValueError("dst_inds: a keypoint is written twice")
@@ -121,49 +156,88 @@ class KeypointRig:
             used = torch.zeros(1, dtype=torch.int64)
         if used.numel() > MAX_VERTICES:
             raise ValueError(f"the selector and the landmarks read {used.numel()} distinct vertices; at most {MAX_VERTICES} are supported")
+        VS = int(used.numel())
+        if LD and VS + 3 * LD > MAX_VERTICES:
+            raise ValueError(f"a frame's active set is {VS} static vertices + 3 x {LD} contour corners = {VS + 3 * LD} slots; at most "
+                             f"{MAX_VERTICES} are supported")
         pos = torch.full((V,), -1, dtype=torch.int64)
         pos[used] = torch.arange(used.numel())
+        rows = used                                                           # the gathered rows: static first, then the table's
+        if LD:
+            dtri = fc[df]                                                     # [79,LD,3]
+            dused = torch.unique(dtri.reshape(-1))
+            if VS + dused.numel() > MAX_UNION:
+                raise ValueError(f"the contour table reads {dused.numel()} distinct vertices; at most {MAX_UNION - VS} are supported")
+            dpos = torch.full((V,), -1, dtype=torch.int64)
+            dpos[dused] = VS + torch.arange(dused.numel())
+            rows = torch.cat([used, dused])
         P = src.numel()
         kind, idx, w = torch.zeros(P, dtype=torch.int32), torch.zeros(P, 3, dtype=torch.int32), torch.zeros(P, 3)
+        dyn_point = torch.full((max(LD, 1),), -1, dtype=torch.int32)
         for p, s in enumerate(src.tolist()):
             if s < J:
                 idx[p, 0], w[p, 0] = s, 1.0
             elif s < J + NX:
                 kind[p], idx[p], w[p, 0] = 1, int(pos[ex[s - J]]), 1.0
-            else:
+            elif s < J + NX + L:
                 kind[p], idx[p], w[p] = 1, pos[tri[s - J - NX]].to(torch.int32), bary[s - J - NX]
+            else:                                                             # a contour landmark: the kernel fills slots and weights
+                l = s - J - NX - L
+                if int(dyn_point[l]) >= 0:
+                    raise ValueError(f"src_inds: contour landmark {l} (model point {s}) is named twice")
+                kind[p], dyn_point[l] = 1, p
+                idx[p] = torch.arange(VS + 3 * l, VS + 3 * l + 3, dtype=torch.int32)
         self.device = torch.device(device)
         _hip(torch.empty(0, device=self.device), "the rig's device")
         d = lambda x: x.contiguous().to(self.device)
-        self.J, self.NB, self.V, self.VS, self.P, self.NX, self.L = J, NB, V, int(used.numel()), P, NX, L
+        self.J, self.NB, self.V, self.VS, self.P, self.NX, self.L = J, NB, V, VS, P, NX, L
+        self.LD, self.VU, self.neck_joint = LD, int(rows.numel()), neck_joint
         self.vertex_ids = used
         self.J_template, self.J_dirs = d(Jreg @ vt), d(torch.einsum("jv,vkl->jkl", Jreg, sd))
         self.parents = d(par.to(torch.int32))
-        self.v_template, self.shapedirs, self.lbs_weights = d(vt[used]), d(sd[used]), d(lw[used])
-        self.posedirs = d(pd.reshape(-1, V, 3)[:, used].reshape(-1, used.numel() * 3))
+        self.v_template, self.shapedirs, self.lbs_weights = d(vt[rows]), d(sd[rows]), d(lw[rows])
+        self.posedirs = d(pd.reshape(-1, V, 3)[:, rows].reshape(-1, rows.numel() * 3))
+        self.dyn_vrow = d(dpos[dtri].to(torch.int32)) if LD else None
+        self.dyn_bary, self.dyn_point = (d(db), d(dyn_point)) if LD else (None, None)
+        self.mean_mask = 0
+        if mean is not None:
+            for j in torch.nonzero((mean.reshape(J, 3) != 0).any(1)).reshape(-1).tolist():
+                self.mean_mask |= 1 << j
+        self.pose_mean = d(mean) if mean is not None else None
         self.pt_kind, self.pt_idx, self.pt_w, self.pt_dst = d(kind), d(idx), d(w), d(dst.to(torch.int32))
         self.kp_mask = d(mask)
         self.src_inds, self.dst_inds = src, dst
 
     @classmethod
-    def from_body_model(cls, body, src_inds, dst_inds, kp_mask, device="cuda") -> "KeypointRig":
+    def from_body_model(cls, body, src_inds, dst_inds, kp_mask, device="cuda", dynamic_contour=False, use_pose_mean=False) -> "KeypointRig":
         """From an ``smplx``-style body object: ``v_template, shapedirs (+ expr_dirs), posedirs, J_regressor, parents, lbs_weights,
         faces_tensor, lmk_faces_idx, lmk_bary_coords, vertex_joint_selector.extra_joints_idxs``.  A body with
         ``dynamic_lmk_faces_idx [79,17]`` / ``dynamic_lmk_bary_coords [79,17,3]`` gets their frontal row (yaw 0) appended as 17
-        static landmarks."""
+        static landmarks; with ``dynamic_contour=True`` the table is kept and indexed per frame (the neck joint is
+        ``neck_kin_chain[0]``, or 12).  ``use_pose_mean=True`` keeps the body's ``pose_mean [165]``; the default refuses a
+        non-zero one."""
         pm = getattr(body, "pose_mean", None)
-        if pm is not None and bool((torch.as_tensor(pm) != 0).any()):
-            raise ValueError("the body model has a non-zero pose_mean (flat_hand_mean=False): create it with flat_hand_mean=True")
+        if not use_pose_mean:
+            if pm is not None and bool((torch.as_tensor(pm) != 0).any()):
+                raise ValueError("the body model has a non-zero pose_mean (flat_hand_mean=False): create it with flat_hand_mean=True")
+            pm = None
         sd = torch.as_tensor(body.shapedirs)
         ed = getattr(body, "expr_dirs", None)
         if ed is not None:
             sd = torch.cat([sd, torch.as_tensor(ed).to(sd)], dim=-1)
         lf, lb = torch.as_tensor(body.lmk_faces_idx).reshape(-1), torch.as_tensor(body.lmk_bary_coords).reshape(-1, 3)
         df, db = getattr(body, "dynamic_lmk_faces_idx", None), getattr(body, "dynamic_lmk_bary_coords", None)
-        if df is not None and db is not None:
+        kw = {}
+        if dynamic_contour:
+            if df is None or db is None:
+                raise ValueError("dynamic_contour=True needs a body with dynamic_lmk_faces_idx and dynamic_lmk_bary_coords")
+            chain = getattr(body, "neck_kin_chain", None)
+            neck = int(torch.as_tensor(chain).reshape(-1)[0]) if chain is not None and len(chain) else NECK_JOINT
+            kw = dict(dynamic_lmk_faces_idx=df, dynamic_lmk_bary_coords=db, neck_joint=neck)
+        elif df is not None and db is not None:
             lf, lb = torch.cat([lf, torch.as_tensor(df)[0].to(lf)]), torch.cat([lb, torch.as_tensor(db)[0].to(lb)])
         return cls(body.v_template, sd, body.posedirs, body.J_regressor, body.parents, body.lbs_weights, body.faces_tensor, lf, lb,
-                   body.vertex_joint_selector.extra_joints_idxs, src_inds, dst_inds, kp_mask, device)
+                   body.vertex_joint_selector.extra_joints_idxs, src_inds, dst_inds, kp_mask, device, pose_mean=pm, **kw)
 
     def _struct(self, NBS: int, NE: int) -> hip_lib.SoarSmplifyRig:
         p = lambda t: t.data_ptr()
@@ -172,11 +246,23 @@ class KeypointRig:
                                       p(self.pt_idx) if self.P else None, p(self.pt_w) if self.P else None,
                                       p(self.pt_dst) if self.P else None, p(self.kp_mask))
 
+    @property
+    def body_path(self) -> bool:
+        """Whether the objective goes through ``soar_smplify_objective_body``: a contour table or a mean (which runs the static
+        kernel itself when there is no table and the mean is all zero)."""
+        return bool(self.LD) or self.pose_mean is not None
+
+    def _body_struct(self, rows_out) -> hip_lib.SoarSmplifyBody:
+        p = lambda t: t.data_ptr() if t is not None else None
+        return hip_lib.SoarSmplifyBody(self.LD, CONTOUR_ROWS, self.neck_joint, self.VU, p(self.dyn_vrow), p(self.dyn_bary), p(self.dyn_point),
+                                       p(self.pose_mean) if self.mean_mask else None, self.mean_mask, p(rows_out))
+
 
 class SmplifyResult(NamedTuple):
     losses: torch.Tensor               # [3] float32: kp, preserve, smooth, weighted
     grads: Dict[str, torch.Tensor]     # the gradient of the sum, in the shapes of the parameters
     frame_betas: torch.Tensor          # [N,NBS]: every frame's share of the betas gradient (keypoint term)
+    contour_rows: Optional[torch.Tensor] = None     # [N] int32: the contour table's row of every frame; None on the static path
 
 
 def _prepare(rig: KeypointRig, params, name: str):
@@ -243,7 +329,14 @@ def _launch(rig, p, p0, N, Ks, w2c, img_wh, target, scales, weights, sigma, igno
         a.kps = kps.data_ptr()
     rs = rig._struct(NBS, NE)
     with torch.cuda.device(dev):
-        check(hip_lib.lib().soar_smplify_objective(C.byref(rs), C.byref(a), _stream(dev)), "soar_smplify_objective")
+        if rig.body_path:
+            rows = torch.empty(N, dtype=torch.int32, device=dev) if rig.LD else None
+            bs = rig._body_struct(rows)
+            check(hip_lib.lib().soar_smplify_objective_body(C.byref(rs), C.byref(bs), C.byref(a), _stream(dev)), "soar_smplify_objective_body")
+            if out is not None:
+                out = out._replace(contour_rows=rows)
+        else:
+            check(hip_lib.lib().soar_smplify_objective(C.byref(rs), C.byref(a), _stream(dev)), "soar_smplify_objective")
     return out
 
 
@@ -273,7 +366,7 @@ def smplify_objective(rig: KeypointRig, params, init_params, Ks, w2c, img_wh, ta
     if N == 0:
         raise ValueError("no frames")
     res = _launch(rig, p, p0, N, Ks, w2c, img_wh, target, scales, weights, sigma, ignore_hands, norm_frames, True, None)
-    return SmplifyResult(res.losses, {k: res.grads[k].view(params[k].shape) for k in GRAD_KEYS}, res.frame_betas)
+    return SmplifyResult(res.losses, {k: res.grads[k].view(params[k].shape) for k in GRAD_KEYS}, res.frame_betas, res.contour_rows)
 
 
 @torch.no_grad()
