@@ -46,7 +46,8 @@ extern "C" {
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
  * soar_mesh_filter_bytes / _components, soar_mesh_simplify_bytes / _count / soar_mesh_simplify, soar_mesh_attr_transfer[_bytes],
- * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes], soar_mesh_close_holes[_bytes] (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
+ * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes], soar_mesh_close_holes[_bytes], soar_mesh_atlas_bytes / _levels / _place,
+ * soar_mesh_texels_bytes / soar_mesh_texel_offsets / soar_mesh_texels / soar_mesh_texture_write (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
@@ -972,6 +973,47 @@ int soar_mesh_close_holes_bytes(int32_t V, int32_t F, size_t *bytes);
 int soar_mesh_close_holes(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t max_hole_edges, void *workspace,
                           size_t workspace_bytes, float *verts_out, int32_t *faces_out, int32_t *loop_edges_out, int64_t *counts_host,
                           void *stream);
+/* The texture atlas of the exported mesh (mesh_texture.hip, soar_amd/texture.py; DESIGN.md 9b, "Texture atlas" states the layout).
+ * Every face gets half of a square cell of side s texels, s a power of two in [4, texture_size / 2]; the cells stand one behind the
+ * other, largest first, on the Morton curve of the image's 4 x 4 texel units.  texture_size is a power of two in [16, 16384];
+ * 1 <= V <= 2^30, 1 <= F <= 2^28; every workspace is the caller's, 256-byte aligned, sized by its _bytes query; a size, pointer or
+ * workspace that is refused is refused before any launch.  Integer atomics only: bit-reproducible.
+ * soar_mesh_atlas_levels: the float32 area of every face (0.5 sqrt of the squared cross product of its two edges from corner 0,
+ *   every operation rounded as written, the square root correctly rounded), its level = the number of the n_ladder <= 1024 ascending
+ *   thresholds ladder[] (device) that are <= area, kept in the workspace (its first F int32 words; -1: no area), and hist_host[n_ladder + 2] = the faces of every level 0 .. n_ladder, then the faces whose
+ *   area is not a positive finite number.  One stream synchronisation; a face naming a vertex outside [0, V) is refused there.
+ * soar_mesh_atlas_place: with the workspace soar_mesh_atlas_levels filled for the same faces and ladder.  Side of a face:
+ *   q = floor((level + scale_step) / 8), s = 4 for q < 2 (and for the faces without an area), texture_size / 2 for
+ *   q >= log2(texture_size / 2), else 2^q.  Order: decreasing s, then face index; the r-th face of a size takes half r % 2 (0: lower)
+ *   of that size's cell r / 2.  Writes cell_out [F][4] = {x0, y0, s, half} (image texels, row 0 at the top), uv_out [3 F][2] (OBJ
+ *   convention, v = 0 at the bottom; the corners sit on texel centres) and uv_faces_out [F][3] = {3 f, 3 f + 1, 3 f + 2}.  A
+ *   scale_step whose cells do not fit the image is refused (one stream synchronisation) before anything is written.
+ * soar_mesh_texel_offsets: checks every cell (a power-of-two square in [4, texture_size / 2], aligned to its side, inside the image)
+ *   and every face, and enumerates the texels the faces own, face after face: a lower half owns the local texels with
+ *   a + b <= s - 1, an upper half those with a + b >= s.  total_host = their number; the ranges stay in the workspace.  One stream
+ *   synchronisation; bad cells or faces are refused there, and nothing else of this group runs on them.  Cells are checked ONE BY
+ *   ONE: that two cells of a hand-made atlas overlap is noticed only when the texels owned exceed T^2.  Overlapping cells that
+ *   pass are written twice, in the enumeration's order: in bounds and repeatable, but not an atlas.  soar_mesh_atlas_place's are disjoint.
+ * soar_mesh_texels: for the texels first .. first + count - 1 of that enumeration, pos_out [count][3] = b0 v0 + b1 v1 + b2 v2 with
+ *   the barycentrics of the texel centre in UV space (from the integers a, b and m = s - 3; negative weights clamped to 0 and the
+ *   three divided by their sum) and addr_out [count] = y * texture_size + x.  A position that is not finite is written as the origin
+ *   and its address as ~addr.  owner_img [T^2], bary_img [T^2][3], position_img [T^2][3]: optional images of the face, the weights
+ *   and the unmodified position of every texel visited.
+ * soar_mesh_texture_write: texture_out [T^2][3] bytes = floor(255 c + 0.5) of color [count][3] clamped to [0, 1] at the addresses
+ *   soar_mesh_texels wrote (1 <= count <= T^2), zero at a flagged (~addr) one; color_img [T^2][3] optionally receives the floats behind the bytes. */
+int soar_mesh_atlas_bytes(int32_t F, size_t *bytes);
+int soar_mesh_atlas_levels(int32_t V, int32_t F, const float *verts, const int32_t *faces, const float *ladder, int32_t n_ladder,
+                           void *workspace, size_t workspace_bytes, int64_t *hist_host, void *stream);
+int soar_mesh_atlas_place(int32_t F, int32_t texture_size, int32_t n_ladder, int32_t scale_step, void *workspace, size_t workspace_bytes,
+                          float *uv_out, int32_t *uv_faces_out, int32_t *cell_out, void *stream);
+int soar_mesh_texels_bytes(int32_t F, size_t *bytes);
+int soar_mesh_texel_offsets(int32_t V, int32_t F, int32_t texture_size, const int32_t *faces, const int32_t *cell, void *workspace,
+                            size_t workspace_bytes, int64_t *total_host, void *stream);
+int soar_mesh_texels(int32_t V, int32_t F, int32_t texture_size, const float *verts, const int32_t *faces, const int32_t *cell,
+                     const void *workspace, size_t workspace_bytes, int64_t first, int32_t count, float *pos_out, int32_t *addr_out,
+                     int32_t *owner_img, float *bary_img, float *position_img, void *stream);
+int soar_mesh_texture_write(int32_t count, int32_t texture_size, const int32_t *addr, const float *color, uint8_t *texture_out,
+                            float *color_img, void *stream);
 
 /* ---- the surfels' attribute field (field.hip, soar_amd/field.py; DESIGN.md "Attribute field"): the reference's HashMLPSDFField
  * (TS/geometry/sdf_fields.py:41-219) with nerfstudio's torch HashEncoding / MLP semantics.  Two multiresolution hash encodings of

@@ -46,6 +46,8 @@ EXTRA_FLAGS = {
     "mesh_attr.hip": ["-ffp-contract=off"],
     # the new vertices' float64 sums are restated operation by operation (tests/mesh_holes_ref.py)
     "mesh_holes.hip": ["-ffp-contract=off"],
+    # face areas decide the atlas' integer layout, and barycentrics and positions are restated operation by operation (tests/texture_ref.py)
+    "mesh_texture.hip": ["-ffp-contract=off"],
     # the background's composite must equal torch's three separate operations bit for bit
     "envmap.hip": ["-ffp-contract=off"],
     # exactly zero gradients where a difference is exactly zero, and values that do not depend on what the compiler fuses
@@ -73,7 +75,7 @@ EXTRA_FLAGS = {
 }
 SOURCES = ["api.hip", "rast_preprocess.hip", "rast_binning.hip", "rast_tilebin.hip", "rast_blockmask.hip", "rast_render_fwd.hip", "rast_render_bwd.hip",
            "rast_geom_bwd.hip", "lbs.hip", "lbs_knn.hip", "frame_loss.hip", "postops.hip", "ssim.hip", "image_losses.hip", "smplx_joints.hip", "densify.hip", "optim.hip", "view.hip",
-           "mesh.hip", "mesh_simplify.hip", "mesh_attr.hip", "mesh_holes.hip", "field.hip", "envmap.hip", "conv_gemm.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip", "playback.hip",
+           "mesh.hip", "mesh_simplify.hip", "mesh_attr.hip", "mesh_holes.hip", "mesh_texture.hip", "field.hip", "envmap.hip", "conv_gemm.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip", "playback.hip",
            "normalnet.hip", "normal_io.hip", "smplify.hip", "prior.hip", "masks.hip", "step_terms.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(_HERE, "..", "include", "soar_hip.h")]
 

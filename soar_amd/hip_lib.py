@@ -386,6 +386,14 @@ SIGNATURES = {
     "soar_mesh_close_holes_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_mesh_close_holes": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp,
                                         C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_atlas_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_atlas_levels": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_atlas_place": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "soar_mesh_texels_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_texel_offsets": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_texels": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int32, _vp, _vp,
+                                   _vp, _vp, _vp, _vp]),
+    "soar_mesh_texture_write": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "soar_field_workspace_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_field_forward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp]),
     "soar_field_backward": (C.c_int, [C.POINTER(SoarFieldArgs), _vp, C.c_size_t, _vp]),

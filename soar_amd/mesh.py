@@ -26,6 +26,8 @@ sphere, the depth is fused into a truncated signed-distance volume and its zero 
   and the mesh in any number of poses with the existing warp and normal kernels: one export, many frames.
 * ``export_avatar``: all of it in the reference's order, from canonical surfels to mesh, colours, quality, normals and weights;
   ``save_obj`` / ``save_ply`` / ``save_skinned`` write them.
+* ``build_atlas`` / ``bake_texture`` / ``save_textured_obj`` (soar_amd/texture.py, csrc/mesh_texture.hip): a per-face texture atlas baked
+  from the surfels' colours, and the OBJ + MTL + PNG writer; ``export_avatar(texture_size=...)`` runs them ("Texture atlas").
 
 Every output is deterministic: the same input gives the same tensors bit for bit.  HIP only; there is no CPU path.
 """
@@ -660,7 +662,8 @@ def _check_surfels(means3D, rotations, scales, opacities, colors) -> None:
 def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: torch.Tensor, resolution: int = 256,
                   decimate_target: Optional[int] = DECIMATE_TARGET, quality_thresh: Optional[float] = None,
                   smooth_steps: int = SMOOTH_STEPS, k: int = ATTR_K, K: int = 30, n_views: int = 48, image_size: int = 1024,
-                  group: int = 8, use_explicit: bool = False, max_hole_edges: Optional[int] = None) -> dict:
+                  group: int = 8, use_explicit: bool = False, max_hole_edges: Optional[int] = None,
+                  texture_size: Optional[int] = None) -> dict:
     """A coloured, animatable mesh from CANONICAL-space surfels in one call -> ``dict(mesh, color, quality, normals, weights)``.
 
     ``model_or_tensors``: the tuple ``(means3D [P,3], rotations [P,4], scales [P,3] with z = -1e10, opacities [P,1], colors [P,3]
@@ -676,8 +679,18 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
 
     ``max_hole_edges``: None (the default) closes nothing and returns exactly what this function returned before it had the
     argument.  A number closes the holes of at most that many edges that the pruning (or the extraction) left, before the smoothing,
-    and the dict gains ``closed`` (``close_holes``' second result); 300 is recommended, the reference's ``maxholesize``."""
+    and the dict gains ``closed`` (``close_holes``' second result); 300 is recommended, the reference's ``maxholesize``.
+
+    ``texture_size``: None (the default) returns exactly that dict.  A power of two adds ``atlas`` (``build_atlas`` of the final,
+    smoothed mesh) and ``texture`` (``bake_texture`` from the same surfel colours and ``k`` as the vertex colours), for
+    ``save_textured_obj``; the texture belongs to the faces, so it rides along with every ``pose_mesh`` pose.  A size that is not a
+    power of two in [16, 16384] is refused before anything runs.  Whether the size holds the mesh (``F <= T^2 / 8``: 1024 for the
+    default budget of 100 000 faces) is known only once the mesh exists: the ``ValueError`` then names the smallest size that does
+    and carries the finished dict, without ``atlas`` and ``texture``, as its ``result``, so that ``build_atlas`` can be called on
+    ``result["mesh"]`` with that size instead of exporting again."""
     from . import body
+    if texture_size is not None:
+        texture._check_size(texture_size)                     # a malformed size is refused before the export, not after it
     means3D, rotations, scales, opacities, colors = _surfel_tensors(model_or_tensors, bool(use_explicit))
     _check_surfels(means3D, rotations, scales, opacities, colors)
     for t, name in ((means3D, "means3D"), (rotations, "rotations"), (scales, "scales"), (opacities, "opacities"), (colors, "colors")):
@@ -700,6 +713,14 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
     out = dict(mesh=m, color=color, quality=quality, normals=normals, weights=weights)
     if closed is not None:
         out["closed"] = closed
+    if texture_size is not None:
+        try:
+            out["atlas"] = build_atlas(m, texture_size)
+        except ValueError as e:                               # too many faces for this size: known only now; the export is not lost
+            err = ValueError(f"{e}; the export itself is done: this exception's `result` is the dict without atlas and texture")
+            err.result = out
+            raise err from e
+        out["texture"] = bake_texture(m, out["atlas"], means3D, colors, k)
     return out
 
 
@@ -792,3 +813,11 @@ def save_skinned(path_npz: str, mesh: Mesh, weights: torch.Tensor, colors: torch
             buf = io.BytesIO()
             np.lib.format.write_array(buf, np.ascontiguousarray(arr), allow_pickle=False)
             zf.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue())
+
+
+# ---- texture atlas (soar_amd/texture.py, csrc/mesh_texture.hip) -------------------------------------------------------------------
+
+from . import texture  # noqa: E402
+from .texture import Atlas, bake_texture, build_atlas, save_textured_obj  # noqa: E402,F401
+
+assert (texture.ATTR_K, texture.ATTR_MAX_K) == (ATTR_K, ATTR_MAX_K)
