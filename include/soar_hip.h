@@ -58,7 +58,8 @@ extern "C" {
  * soar_normalnet_weights_bytes / _pack_weights / _workspace_bytes / _forward (+ SoarNormalNetArgs), soar_normal_crop_boxes / _sample /
  * _bytes: normal-map preprocessing.  soar_selftest_conv_gemm / _conv_pack (+ SoarConvGemmArgs, SoarConvGemmTaps): the shared
  * implicit-GEMM convolution and its weight packer by themselves, for the tests.  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
- * normal priors (a triangle-mesh rasterizer). */
+ * normal priors (a triangle-mesh rasterizer).  soar_rast_backward_plan_loss (+ SoarBackwardLoss),
+ * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -513,6 +514,46 @@ int soar_frame_loss_pooled_partials(int32_t W, int32_t H, const float *color, co
                                     float w_color, float w_mask, float w_normal, float w_depth, float *loss_out, float *scratch,
                                     float *dL_dcolor, float *dL_dnormal, float *dL_ddepth, float *dL_dopac, const void *image_buffer,
                                     const float *background, int32_t normalize_depth, SoarLossFinish *finish_out, void *stream);
+
+/* ---- the frame loss inside the backward blend's launch (the batched eager step plan).  soar_rast_backward_plan with a loss record in
+ * place of the four gradient planes: soar_frame_loss[_pooled]_partials + soar_rast_backward_plan as ONE launch, without the
+ * gradient planes' round trip through memory.
+ *   - the blend computes dL/dcolor, dL/dnormal, dL/ddepth, dL/dopac of a pixel in its prologue, from the forward's color / opac
+ *     planes and the frame's targets, with soar_frame_loss's expressions (the same bits; only pixels with contributors matter);
+ *   - the loss's value pass runs as extra workgroups ("riders") of the same launch: bandwidth work next to issue-bound work.  They
+ *     leave one partial sum per WAVEFRONT of soar_frame_loss's grid in wave_sums; *finish_out (host memory) describes them for
+ *     soar_frames_geometry_warp_backward_wave_losses, which adds the four wavefronts of a workgroup first and then goes on in
+ *     soar_frame_loss's order: loss_out receives soar_frame_loss's bits there.  loss_out is NOT written by this call.
+ * The image buffer, background and normalize_depth of the loss are those of the call (image_buffer, prm->bg_dev,
+ * prm->cfg_normalize_depth).  target_*: explicit planes (set_index_dev = NULL), or all three = a resident pool [n_sets][7][H*W] and
+ * set_index_dev a device integer, as in soar_frame_loss_pooled.  Batch-safe.  Needs P > 0 and num_rendered > 0 (the binning
+ * capacity): with nothing to launch the riders would have no launch to ride in.  Everything else is soar_rast_backward_plan. */
+#define SOAR_BACKWARD_LOSS_SCRATCH_FLOATS (4 * SOAR_FRAME_LOSS_SCRATCH_FLOATS)
+typedef struct SoarBackwardLoss {
+    const float *color, *normal, *depth, *opac;                     /* the forward's outputs */
+    const float *target_color, *target_mask, *target_normal;
+    const int32_t *set_index_dev;
+    int32_t n_sets;
+    float w_color, w_mask, w_normal, w_depth;
+    float *loss_out;                                                /* [1]: handed on in *finish_out */
+    float *wave_sums;                                               /* [SOAR_BACKWARD_LOSS_SCRATCH_FLOATS] */
+} SoarBackwardLoss;
+int soar_rast_backward_plan_loss(const SoarRastParams *prm, int32_t region,
+                                 const float *means3D, const int32_t *radii, const float *shs,
+                                 const float *colors_precomp, const float *scales, const float *rotations,
+                                 const float *cov3D_precomp,
+                                 const void *geom_buffer, const void *binning_buffer, const void *image_buffer,
+                                 int64_t num_rendered, const SoarBackwardLoss *loss,
+                                 float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity, float *dL_dmeans3D,
+                                 float *dL_dcov3D, float *dL_dsh, float *dL_dscales, float *dL_drotations,
+                                 float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos,
+                                 void *workspace, size_t workspace_bytes, SoarLossFinish *finish_out,
+                                 void *stream);
+/* soar_frames_geometry_warp_backward_losses for finish[] records of soar_rast_backward_plan_loss (per-wavefront partials) */
+int soar_frames_geometry_warp_backward_wave_losses(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot,
+                                                   const float *weights, const float *joint_mats, int32_t P, int32_t J, const float *scales,
+                                                   float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors, float *dL_docc,
+                                                   const SoarLossFinish *finish, void *stream);
 
 /* ---- the same terms in ONE pass over the images (round 4, ABI 6): masked L1 of the colours over `sel`, L1 of the mask image over
  * every pixel, cosine loss of the normals over `sel_normal`, and -- when `occ` is given -- masked L1 of the occlusion image against 1

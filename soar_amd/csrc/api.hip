@@ -810,6 +810,61 @@ int soar_rast_backward_plan(const SoarRastParams *prm, int32_t region, const flo
                          workspace_bytes, nullptr, nullptr, nullptr, 3, region, stream_);
 }
 
+// soar_rast_backward_plan with the frame loss inside the blend's launch (rast_render_bwd.hip: launch_render_backward_loss)
+int soar_rast_backward_plan_loss(const SoarRastParams *prm, int32_t region, const float *means3D, const int32_t *radii, const float *shs,
+                                 const float *colors_precomp, const float *scales, const float *rotations, const float *cov3D_precomp,
+                                 const void *geom_buffer, const void *binning_buffer, const void *image_buffer, int64_t num_rendered,
+                                 const SoarBackwardLoss *loss, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                                 float *dL_dmeans3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscales, float *dL_drotations,
+                                 float *dL_dviewmat, float *dL_dprojmat, float *dL_dcampos, void *workspace, size_t workspace_bytes,
+                                 SoarLossFinish *finish_out, void *stream_)
+{
+    const char *who = "soar_rast_backward_plan_loss";
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (region != 1 && region != 2) { set_error("%s: region is 1 or 2, got %d", who, region); return 1; }
+    if (check_params(prm)) return 1;
+    if (!loss || !finish_out) { set_error("%s: loss / finish_out is NULL", who); return 1; }
+    if (!loss->color || !loss->normal || !loss->depth || !loss->opac || !loss->target_color || !loss->target_mask || !loss->target_normal ||
+        !loss->loss_out || !loss->wave_sums) {
+        set_error("%s: the loss record has a NULL pointer", who);
+        return 1;
+    }
+    if (loss->set_index_dev && loss->n_sets <= 0) { set_error("%s: a pool needs n_sets > 0", who); return 1; }
+    if (!prm->bg_dev) { set_error("%s: needs the background colour (prm->bg_dev)", who); return 1; }
+    if (prm->P <= 0 || num_rendered <= 0) { set_error("%s: needs P > 0 and num_rendered > 0 (the launch the loss rides in)", who); return 1; }
+    if (!dL_dviewmat || !dL_dprojmat || !dL_dcampos) { set_error("camera gradient pointers must not be NULL"); return 1; }
+    if (check_aligned(geom_buffer, "geom_buffer") || check_aligned(image_buffer, "image_buffer") || check_aligned(workspace, "workspace") ||
+        check_aligned(binning_buffer, "binning_buffer"))
+        return 1;
+    size_t need = 0;
+    soar_rast_backward_workspace_bytes(prm->P, &need);
+    if (workspace_bytes < need - ALIGN) { set_error("workspace too small: %zu < %zu", workspace_bytes, need); return 1; }
+    if (!means3D || !radii || !dL_dmeans2D || !dL_dcolors || !dL_dopacity || !dL_dmeans3D || !dL_dcov3D || !dL_dscales || !dL_drotations) {
+        set_error("%s: a required pointer is NULL", who);
+        return 1;
+    }
+    if (prm->M > 0 && shs && !dL_dsh) { set_error("dL_dsh is NULL but SHs are in use"); return 1; }
+    (void)colors_precomp;
+    GeomBuf g;
+    ImageBuf img;
+    BinBuf b;
+    carve_geom(const_cast<void *>(geom_buffer), prm->P, prm->M, &g);
+    carve_image(const_cast<void *>(image_buffer), prm->W, prm->H, &img);
+    carve_binning(const_cast<void *>(binning_buffer), num_rendered, &b);
+    float *acc = static_cast<float *>(workspace);
+    const bool wide = (prm->debug & 2) != 0;
+    double *acc64 = wide ? reinterpret_cast<double *>(static_cast<char *>(workspace) + align_up(sizeof(float) * ACC_STRIDE * (size_t)prm->P))
+                         : nullptr;
+    const ZeroRange zr[4] = {{wide ? (void *)acc64 : (void *)acc, (wide ? sizeof(double) : sizeof(float)) * ACC_STRIDE * (size_t)prm->P},
+                             {dL_dviewmat, 16 * sizeof(float)}, {dL_dprojmat, 16 * sizeof(float)}, {dL_dcampos, 3 * sizeof(float)}};
+    if (launch_zero_ranges(zr, 4, stream)) return 1;
+    if (launch_render_backward_loss(*prm, g, b, img, *loss, acc, acc64, region, finish_out, stream)) return 1;
+    if ((prm->debug & 8) != 0) return 0;       // the rows stay in the workspace for soar_frames_geometry_warp_backward[_wave_losses]
+    return launch_geometry_backward(*prm, means3D, radii, shs, scales, rotations, cov3D_precomp, g, acc, dL_dmeans2D, dL_dcolors, dL_dopacity,
+                                    dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos,
+                                    /*zero_camera_grads=*/false, stream, nullptr);
+}
+
 int soar_rast_backward_occ_plan(const SoarRastParams *prm, int32_t region, const float *means3D, const int32_t *radii, const float *shs,
                                 const float *colors_precomp, const float *scales, const float *rotations,
                                 const float *cov3D_precomp, const void *geom_buffer, const void *binning_buffer,

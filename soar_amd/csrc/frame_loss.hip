@@ -6,110 +6,21 @@
 // the same structure: per-pixel terms averaged over the image).  In eager torch this is ~25 full-image kernels per
 // frame; here every pixel is read once and its four gradient planes are written once.
 #include "soar_common.h"
+#include "frame_loss_terms.h"
 #include "loss_finish.h"
-
-#include <type_traits>
 
 namespace soar {
 
 namespace {
 
-struct LossArgs {
-    int n;                       // pixels
-    const float *color, *normal, *depth, *opac;            // [3,n] [3,n] [n] [n]
-    const float *t_color, *t_mask, *t_normal;              // [3,n] [n] [3,n]
-    float wc, wm, wn, wd;
-    float *dcolor, *dnormal, *ddepth, *dopac;
-    float *sums;                 // [gridDim.x][4] per-workgroup un-normalised sums of the four terms
-    const int *set_index;        // optional: the targets are set (*set_index mod n_sets) of a resident pool [n_sets][7][n]
-    int n_sets;
-    const float *bg;             // optional [3] (with n_contrib): background colour of the forward blend that wrote the images --
-                                 // pixels nothing contributed to are not read, their values are the blend's background constants
-    int normalize_depth;
-    const uint32_t *n_contrib;   // optional [n]: the forward blend's contributor count; gradients of pixels nothing contributed to
-                                 // are never read by the backward blend (its walk starts at n_contrib) and are not written
-    const uint32_t *bg_tiles;    // optional (with n_contrib; ImageBuf::bg_tiles): 1 = the 16x16 tile had no list, all its counts are 0 --
-    int W, gx;                   // its 1 KB of counts is not read either (80 % of the tiles of a frame of one person)
-};
-
-__device__ __forceinline__ float sign_of(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// V = 4: float4 accesses (planes of a [3,n] tensor are 16-byte aligned only when n % 4 == 0); V = 1: any image size
-template <int V> struct Vec;
-template <> struct Vec<4> { typedef float4 type; };
-template <> struct Vec<1> { typedef float type; };
-__device__ __forceinline__ float4 ld(const float4 *p, int i) { return p[i]; }
-__device__ __forceinline__ float4 ld(const float *p, int i) { return make_float4(p[i], 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void st(float4 *p, int i, float4 v) { p[i] = v; }
-__device__ __forceinline__ void st(float *p, int i, float4 v) { p[i] = v.x; }
-__device__ __forceinline__ bool any_contrib(const uint4 *p, int i) { const uint4 v = p[i]; return (v.x | v.y | v.z | v.w) != 0u; }
-__device__ __forceinline__ bool any_contrib(const uint32_t *p, int i) { return p[i] != 0u; }
-
+// LossArgs, the pixel arithmetic and the walk of a thread: frame_loss_terms.h (shared with the backward blend's loss form)
 template <int V>
 __global__ void __launch_bounds__(256) frame_loss_kernel(Batch<LossArgs> batch)
 {
     LossArgs a = batch.v[blockIdx.y];                 // (a copy: the pooled form points it at its frame's target planes)
-    typedef typename Vec<V>::type T;
-    const int nv = a.n / V;
-    if (a.set_index) {           // frame data resident in HBM: pick this frame's planes (colour 3, mask 1, normal 3)
-        const float *set = a.t_color + (size_t)((unsigned)*a.set_index % (unsigned)a.n_sets) * 7u * (size_t)a.n;
-        a.t_color = set; a.t_mask = set + 3 * (size_t)a.n; a.t_normal = set + 4 * (size_t)a.n;
-    }
+    loss_pick_target_set(a);
     float s_c = 0.f, s_m = 0.f, s_n = 0.f, s_d = 0.f;
-    const float gc = a.wc / (3.f * a.n), gm = a.wm / a.n, gn = a.wn / (3.f * a.n), gd = a.wd / a.n;
-    const float4 pad = V == 4 ? make_float4(1.f, 1.f, 1.f, 1.f) : make_float4(1.f, 0.f, 0.f, 0.f);   // lanes that exist
-    typedef typename std::conditional<V == 4, uint4, uint32_t>::type U;
-    // what the blend writes where nothing contributed (T = 1; forward.cu:618-633, the same expressions as its epilogue)
-    const float Tc = (float)(1 - 0.000001);
-    const bool known = a.n_contrib && a.bg;
-    float bgc[3] = {0.f, 0.f, 0.f};
-    if (known) { bgc[0] = 0.f + Tc * a.bg[0]; bgc[1] = 0.f + Tc * a.bg[1]; bgc[2] = 0.f + Tc * a.bg[2]; }
-    const float bg_depth = a.normalize_depth ? 0.f / (1.f - Tc) : 0.f + Tc * 10.f, bg_opac = 1.f - Tc;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
-        bool wr = true;                                                                                // someone will read the gradients
-        if (a.n_contrib) {
-            bool empty_tile = false;
-            if (a.bg_tiles) {
-                const int p = i * V, y = p / a.W, x = p - y * a.W;
-                empty_tile = a.bg_tiles[(y >> 4) * a.gx + (x >> 4)] != 0u;
-            }
-            wr = !empty_tile && any_contrib(reinterpret_cast<const U *>(a.n_contrib), i);
-        }
-        const bool rd = wr || !known;                                                                  // the images have to be read
-        float4 nsum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            const float4 c = rd ? ld(reinterpret_cast<const T *>(a.color + (size_t)ch * a.n), i) : make_float4(bgc[ch], bgc[ch], bgc[ch], bgc[ch]);
-            const float4 t = ld(reinterpret_cast<const T *>(a.t_color + (size_t)ch * a.n), i);
-            const float4 d = make_float4(c.x - t.x, c.y - t.y, c.z - t.z, c.w - t.w);
-            s_c += (fabsf(d.x) + fabsf(d.y)) + (fabsf(d.z) + fabsf(d.w));
-            if (wr) st(reinterpret_cast<T *>(a.dcolor + (size_t)ch * a.n), i,
-                       make_float4(gc * sign_of(d.x), gc * sign_of(d.y), gc * sign_of(d.z), gc * sign_of(d.w)));
-            const float4 nr = rd ? ld(reinterpret_cast<const T *>(a.normal + (size_t)ch * a.n), i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            // (where nothing was rendered the normal image is exactly 0: its product with the target adds +-0 to the sum whatever the
-            // (finite) target is -- the target's 12 bytes per pixel of the 85 % background of a frame are not read: 25 of the launch's
-            // 86 MB per 1080p frame)
-            const float4 nt = rd ? ld(reinterpret_cast<const T *>(a.t_normal + (size_t)ch * a.n), i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            nsum.x += nr.x * nt.x; nsum.y += nr.y * nt.y; nsum.z += nr.z * nt.z; nsum.w += nr.w * nt.w;
-            if (wr) st(reinterpret_cast<T *>(a.dnormal + (size_t)ch * a.n), i, make_float4(gn * nt.x, gn * nt.y, gn * nt.z, gn * nt.w));
-        }
-        s_n += (nsum.x + nsum.y) + (nsum.z + nsum.w);
-        const float4 o = rd ? ld(reinterpret_cast<const T *>(a.opac), i) : make_float4(bg_opac, bg_opac, bg_opac, bg_opac);
-        const float4 m = ld(reinterpret_cast<const T *>(a.t_mask), i);
-        const float4 e = make_float4(o.x - m.x, o.y - m.y, o.z - m.z, o.w - m.w);
-        s_m += (fabsf(e.x) + fabsf(e.y)) + (fabsf(e.z) + fabsf(e.w));
-        if (wr) st(reinterpret_cast<T *>(a.dopac), i, make_float4(gm * sign_of(e.x), gm * sign_of(e.y), gm * sign_of(e.z), gm * sign_of(e.w)));
-        const float4 dp = rd ? ld(reinterpret_cast<const T *>(a.depth), i) : make_float4(bg_depth, bg_depth, bg_depth, bg_depth);
-        s_d += (dp.x + dp.y) + (dp.z + dp.w);
-        if (wr) st(reinterpret_cast<T *>(a.ddepth), i, make_float4(gd * pad.x, gd * pad.y, gd * pad.z, gd * pad.w));
-    }
+    frame_loss_walk<V, true>(a, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, s_c, s_m, s_n, s_d);
     __shared__ float part[4][4];
     s_c = wave_sum(s_c); s_m = wave_sum(s_m); s_n = wave_sum(s_n); s_d = wave_sum(s_d);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -228,10 +139,9 @@ static int frame_loss_launch(int32_t W, int32_t H, const float *color, const flo
         if (W % 4 == 0) a.bg_tiles = img.bg_tiles;       // (four consecutive pixels of the flat planes lie in one tile)
     }
     StageTimer timer(ST_FRAME_LOSS, stream);
-    const bool vec4 = (a.n & 3) == 0 && (((uintptr_t)a.n_contrib | (uintptr_t)color | (uintptr_t)normal | (uintptr_t)depth | (uintptr_t)opac | (uintptr_t)target_color |
-                                          (uintptr_t)target_mask | (uintptr_t)target_normal | (uintptr_t)dL_dcolor | (uintptr_t)dL_dnormal |
-                                          (uintptr_t)dL_ddepth | (uintptr_t)dL_dopac) & 15) == 0;
-    const int blocks = min(SOAR_FRAME_LOSS_SCRATCH_FLOATS / 4, max(1, (a.n / (vec4 ? 4 : 1) + 255) / 256));
+    bool vec4;
+    int blocks;
+    frame_loss_grid(a, vec4, blocks);
     if (vec4) SOAR_LAUNCH_BATCHED(frame_loss_kernel<4>, dim3(blocks), dim3(256), 0, stream, a);
     else SOAR_LAUNCH_BATCHED(frame_loss_kernel<1>, dim3(blocks), dim3(256), 0, stream, a);
     if (finish_out) {

@@ -480,6 +480,7 @@ struct TailOut {
 // needs the value.  The kernel boundary in front of this launch is the ordering; n = 0: no such workgroups.
 struct TailLosses {
     int n, first_block;
+    int per_wave;                    // 1: v[].sums4 holds a partial per wavefront of the loss's grid (soar_rast_backward_plan_loss)
     SoarLossFinish v[MAX_BATCH];
 };
 #ifndef SOAR_TAIL_WPE
@@ -491,7 +492,8 @@ __global__ void __launch_bounds__(WARP_THREADS) __attribute__((amdgpu_waves_per_
     static_assert(WARP_THREADS == 256 && WARP_NF * TAIL_C * WAVE * sizeof(float) >= 256 * sizeof(float4), "loss_finish_sum: 256 threads, 4 KB of LDS");
     if (losses.n && (int)blockIdx.x >= losses.first_block) {             // (uniform: a whole workgroup)
         const SoarLossFinish &l = losses.v[(int)blockIdx.x - losses.first_block];
-        loss_finish_sum(l.sums4, l.blocks, l.n, l.w_color, l.w_mask, l.w_normal, l.w_depth, l.loss_out, reinterpret_cast<float4 *>(wtile));
+        if (losses.per_wave) loss_finish_sum<true>(l.sums4, l.blocks, l.n, l.w_color, l.w_mask, l.w_normal, l.w_depth, l.loss_out, reinterpret_cast<float4 *>(wtile));
+        else loss_finish_sum(l.sums4, l.blocks, l.n, l.w_color, l.w_mask, l.w_normal, l.w_depth, l.loss_out, reinterpret_cast<float4 *>(wtile));
         return;
     }
     float *red = wtile + WAVE * a.J;                             // [WARP_NF][TAIL_C][WAVE]
@@ -755,13 +757,34 @@ int soar_frames_geometry_warp_backward(int32_t n, const SoarFrameTail *frames, c
                                                      dL_dcolors, dL_docc, nullptr, stream_);
 }
 
+static int frames_tail(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot, const float *weights, const float *joint_mats,
+                       int32_t P, int32_t J, const float *scales, float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors,
+                       float *dL_docc, const SoarLossFinish *finish, bool per_wave, const char *who, void *stream_);
+
 int soar_frames_geometry_warp_backward_losses(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot,
                                               const float *weights, const float *joint_mats, int32_t P, int32_t J, const float *scales,
                                               float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors, float *dL_docc,
                                               const SoarLossFinish *finish, void *stream_)
 {
+    return frames_tail(n, frames, xyz, rot, weights, joint_mats, P, J, scales, dL_dxyz, dL_drot, dL_dscales, dL_dcolors, dL_docc, finish, false,
+                       finish ? "soar_frames_geometry_warp_backward_losses" : "soar_frames_geometry_warp_backward", stream_);
+}
+
+int soar_frames_geometry_warp_backward_wave_losses(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot,
+                                                   const float *weights, const float *joint_mats, int32_t P, int32_t J, const float *scales,
+                                                   float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors, float *dL_docc,
+                                                   const SoarLossFinish *finish, void *stream_)
+{
+    if (!finish) { set_error("soar_frames_geometry_warp_backward_wave_losses: finish is NULL"); return 1; }
+    return frames_tail(n, frames, xyz, rot, weights, joint_mats, P, J, scales, dL_dxyz, dL_drot, dL_dscales, dL_dcolors, dL_docc, finish, true,
+                       "soar_frames_geometry_warp_backward_wave_losses", stream_);
+}
+
+static int frames_tail(int32_t n, const SoarFrameTail *frames, const float *xyz, const float *rot, const float *weights, const float *joint_mats,
+                       int32_t P, int32_t J, const float *scales, float *dL_dxyz, float *dL_drot, float *dL_dscales, float *dL_dcolors,
+                       float *dL_docc, const SoarLossFinish *finish, bool per_wave, const char *who, void *stream_)
+{
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const char *who = finish ? "soar_frames_geometry_warp_backward_losses" : "soar_frames_geometry_warp_backward";
     if (n < 1 || n > MAX_BATCH || !frames) { set_error("%s: 1 <= n <= %d frames", who, MAX_BATCH); return 1; }
     if (!weights) { set_error("%s: needs the blend weights", who); return 1; }
     if (warp_check(xyz, rot, weights, joint_mats, P, J)) return 1;
@@ -792,11 +815,12 @@ int soar_frames_geometry_warp_backward_losses(int32_t n, const SoarFrameTail *fr
     TailLosses losses{};
     const int blocks = (P + WAVE - 1) / WAVE;
     if (finish) {
-        losses.n = n; losses.first_block = blocks;
+        losses.n = n; losses.first_block = blocks; losses.per_wave = per_wave ? 1 : 0;
         for (int f = 0; f < n; f++) {
             const SoarLossFinish &l = finish[f];
             if (!l.sums4 || !l.loss_out || l.blocks < 1 || l.blocks > SOAR_FRAME_LOSS_SCRATCH_FLOATS / 4 || l.n < 1) {
-                set_error("%s: frame %d: finish[] is not what soar_frame_loss_partials left", who, f);
+                set_error("%s: frame %d: finish[] is not what %s left", who, f,
+                          per_wave ? "soar_rast_backward_plan_loss" : "soar_frame_loss_partials");
                 return 1;
             }
             losses.v[f] = l;

@@ -17,6 +17,7 @@
 // transpose-reduce (rounds 1-2: 395 us per 4-frame launch) and lane = entry inside a workgroup that stages the tile's list
 // (352 us); this file holds the form that replaced them (298-306 us).
 #include "soar_common.h"
+#include "frame_loss_terms.h"
 
 #include <atomic>
 #include <type_traits>
@@ -86,27 +87,46 @@ struct Splat {
     float x, y, A, B, C, opacity, depth, plane_a, plane_b, r, g, b, nx, ny, nz;
 };
 
+// LOSS (soar_rast_backward_plan_loss): the upstream gradients are those of the frame loss (frame_loss.hip), made here from the forward's
+// colour / opacity planes and the frame's targets with that kernel's own expressions (frame_loss_terms.h) -- nobody writes or reads
+// the eight gradient planes.  The four factors are wave-uniform and arrive in scalar registers.
+struct PixelLoss {
+    const float *color, *opac, *t_color, *t_mask, *t_normal;
+    LossScales k;
+};
 // Every load issued at once (waiting for n_contrib first and only then asking for the eight gradient planes is two round trips to
 // memory in a row at the start of every wavefront).  What a pixel without contributors holds in the
 // gradient planes may be anything (producers may leave it unwritten): selected away, never multiplied.
-__device__ __forceinline__ void load_pixel_at_once(const BwdArgs &a, int px, int py, bool inside, PixelConsts &c, PixelState &s)
+template <bool LOSS>
+__device__ __forceinline__ void load_pixel_at_once(const BwdArgs &a, const PixelLoss &l, int px, int py, bool inside, PixelConsts &c, PixelState &s)
 {
     const size_t hw = (size_t)a.H * a.W;
     const size_t pix = inside ? (size_t)a.W * py + px : 0;
     const uint32_t last = a.n_contrib[pix];
     const float Tf = a.final_T[pix];
     const float Df = a.normalize_depth ? a.final_D[pix] : 0.f;
-    const float g0 = a.dL_dcolor[pix], g1 = a.dL_dcolor[hw + pix], g2 = a.dL_dcolor[2 * hw + pix];
-    const float n0 = a.dL_dnormal[pix], n1 = a.dL_dnormal[hw + pix], n2 = a.dL_dnormal[2 * hw + pix];
-    const float gd = a.dL_ddepth[pix], go = a.dL_dopac[pix];
-    const float gs = a.grad_scale ? *a.grad_scale : 1.f;
+    float g0, g1, g2, n0, n1, n2, gd, go, gs;
+    if constexpr (LOSS) {
+        const float c0 = l.color[pix], c1 = l.color[hw + pix], c2 = l.color[2 * hw + pix], o = l.opac[pix];
+        const float t0 = l.t_color[pix], t1 = l.t_color[hw + pix], t2 = l.t_color[2 * hw + pix], m = l.t_mask[pix];
+        const float nt0 = l.t_normal[pix], nt1 = l.t_normal[hw + pix], nt2 = l.t_normal[2 * hw + pix];
+        g0 = loss_grad_l1(l.k.gc, c0 - t0); g1 = loss_grad_l1(l.k.gc, c1 - t1); g2 = loss_grad_l1(l.k.gc, c2 - t2);
+        n0 = loss_grad_dot(l.k.gn, nt0); n1 = loss_grad_dot(l.k.gn, nt1); n2 = loss_grad_dot(l.k.gn, nt2);
+        gd = loss_grad_dot(l.k.gd, 1.f); go = loss_grad_l1(l.k.gm, o - m);
+        gs = 1.f;
+    } else {
+        g0 = a.dL_dcolor[pix]; g1 = a.dL_dcolor[hw + pix]; g2 = a.dL_dcolor[2 * hw + pix];
+        n0 = a.dL_dnormal[pix]; n1 = a.dL_dnormal[hw + pix]; n2 = a.dL_dnormal[2 * hw + pix];
+        gd = a.dL_ddepth[pix]; go = a.dL_dopac[pix];
+        gs = a.grad_scale ? *a.grad_scale : 1.f;
+    }
     c.fx = (float)px; c.fy = (float)py;
     c.last = inside ? last : 0u;                                              // :604
     const bool on = c.last != 0u;
     const float T_final = inside ? Tf : 0.f;
     const float D_final = inside ? Df : 0.f;
     c.dC0 = on ? gs * g0 : 0.f; c.dC1 = on ? gs * g1 : 0.f; c.dC2 = on ? gs * g2 : 0.f;
-    const float gn = a.normal_scale ? *a.normal_scale : 1.f;
+    const float gn = !LOSS && a.normal_scale ? *a.normal_scale : 1.f;
     c.dN0 = on ? gs * (gn * n0) : 0.f; c.dN1 = on ? gs * (gn * n1) : 0.f; c.dN2 = on ? gs * (gn * n2) : 0.f;
     c.dD = on ? gs * gd : 0.f;
     const float dO = on ? gs * go : 0.f;
@@ -436,10 +456,11 @@ __device__ __forceinline__ float lane_value(float v, int lane) { return __int_as
 //     pixel loop cost sixteen registers and with them 36 bytes of scratch per lane -- more than the hidden round trip was worth);
 //   * the sums of batch n leave through LDS (16 atomic wave-instructions of four whole rows) at the start of batch n + 1, BEHIND that
 //     batch's gather: the wait for the gather of batch n + 2 then finds the atomics in front of it a whole pixel loop old.
-template <bool WIDE, bool OCC, int REGION>
-__device__ __forceinline__ void backward_block(const BwdArgs &a, const int rank, const int blk, float4 (*pixc)[5], uint32_t *ring,
+template <bool WIDE, bool OCC, int REGION, bool LOSS>
+__device__ __forceinline__ void backward_block(const BwdArgs &a, const PixelLoss &pl, const int rank, const int blk, float4 (*pixc)[5], uint32_t *ring,
                                                uint32_t *list, float *xpose, uint32_t *xgid)
 {
+    static_assert(!(LOSS && OCC), "the loss form has no occlusion chain");
     const int lane = threadIdx.x & 63;
     constexpr int NC = OCC ? 14 : 13, XS = OCC ? 15 : 13;       // components of a row that leave; stride of a row in `xpose`
     constexpr int NPIX = 16 * REGION;
@@ -490,7 +511,7 @@ __device__ __forceinline__ void backward_block(const BwdArgs &a, const int rank,
         To_final = tf;
         G_occ = last_o != 0u ? (three ? (g0 + g1) + g2 : g0) : 0.f;
     }
-    load_pixel_at_once(a, px, py, inside, c, st);
+    load_pixel_at_once<LOSS>(a, pl, px, py, inside, c, st);
     const uint32_t vLast = OCC ? max(c.last, last_o) : c.last;       // how deep the pixel's walk starts (the occlusion chain skips the
     const uint32_t deepest = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(vLast));     // back-facing entries: it may outlive the main one)
     if (deepest == 0u) return;
@@ -882,8 +903,9 @@ __device__ __forceinline__ void backward_block(const BwdArgs &a, const int rank,
 #endif
 // one wavefront per workgroup: a finished block frees its slot at once.  Grid = 16 x ranks; the 16 blocks of a tile are
 // consecutive workgroups of one XCD (its L2 holds the tile's records), ranks dealt round-robin to the XCDs.
-template <bool WIDE, bool OCC, int REGION>
-__device__ __forceinline__ void backward_blocks(const BwdArgs &a, int bx)
+// bx, grid_x: this workgroup's place among the blend's grid_x workgroups (a multiple of 8; the launch may hold others: the loss form's riders)
+template <bool WIDE, bool OCC, int REGION, bool LOSS = false>
+__device__ __forceinline__ void backward_blocks(const BwdArgs &a, int bx, unsigned grid_x, const PixelLoss &pl = PixelLoss())
 {
     constexpr int NPIX = 16 * REGION;
     __shared__ float4 pixc[NPIX][5];                       // per pixel: {fx, fy, dC0, dC1 | dC2, dN0, dN1, dN2 | dD, dD_ch, tail terms, last |
@@ -895,16 +917,16 @@ __device__ __forceinline__ void backward_blocks(const BwdArgs &a, int bx)
     const int xcd = bx & 7, kth = bx >> 3;
     constexpr int PER_TILE = 16 / REGION;                    // wavefronts per tile
     const int rank0 = (kth / PER_TILE) * 8 + xcd, blk = (kth % PER_TILE) * REGION;
-    const int stride = (int)(gridDim.x / PER_TILE);          // ranks per pass of the grid (a multiple of 8)
+    const int stride = (int)(grid_x / PER_TILE);             // ranks per pass of the grid (a multiple of 8)
     const int n_work = (int)a.tile_order[(a.ntiles + 7) / 8 * 8];
-    for (int rank = rank0; rank < n_work; rank += stride) backward_block<WIDE, OCC, REGION>(a, rank, blk, pixc, ring, list, xpose, xgid);
+    for (int rank = rank0; rank < n_work; rank += stride) backward_block<WIDE, OCC, REGION, LOSS>(a, pl, rank, blk, pixc, ring, list, xpose, xgid);
 }
 template <bool WIDE, int REGION>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SOAR_BWD_BLK_WPE, 8))) render_backward_blocks_kernel(Batch<BwdArgs> batch)
 {
     int frame, bx;
     batch_interleave(frame, bx);
-    backward_blocks<WIDE, false, REGION>(batch.v[frame], bx);
+    backward_blocks<WIDE, false, REGION>(batch.v[frame], bx, gridDim.x);
 }
 // ... with the fused occlusion chain walked in the same pass (soar_rast_backward_occ): a few registers more than the 128 that four
 // wavefronts per SIMD allow
@@ -913,7 +935,84 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8)))
 {
     int frame, bx;
     batch_interleave(frame, bx);
-    backward_blocks<WIDE, true, REGION>(batch.v[frame], bx);
+    backward_blocks<WIDE, true, REGION>(batch.v[frame], bx, gridDim.x);
+}
+
+
+// ================================================================================================
+// the loss form: the blend makes its own upstream gradients, the frame loss's value pass rides in the launch
+// ================================================================================================
+// soar_rast_backward_plan_loss.  The frame loss (frame_loss.hip) is a streaming pass at the memory system's rate, the blend is bound
+// by instruction issue and the request rate of its atomics and uses about a quarter of that rate: one launch holds both.
+//   * the blend's workgroups: backward_blocks<.., LOSS> -- the pixel prologue reads the forward's colour / opacity planes and the
+//     frame's targets instead of eight gradient planes nobody has written;
+//   * the riders: workgroups of one wavefront that do what the wavefronts of frame_loss_kernel<V>'s grid do minus the gradient
+//     stores.  Rider r takes the wavefronts r per, r per + 1, ... of that grid (wavefront w = workgroup w / 4, threads 64 (w % 4) ..)
+//     and leaves ONE partial {colour, mask, normal, depth} per wavefront in l.sums[w]; the tail of the step
+//     (soar_frames_geometry_warp_backward_wave_losses) adds the four of a workgroup as that kernel does and goes on in its order.
+//     Nothing in this launch reads what a rider writes: the kernel boundary in front of the tail is the ordering.
+// Where the riders sit in the dispatch order (place) and how many wavefronts each takes (per) are arguments of the launch:
+// SOAR_BWD_LOSS_RIDERS="place:per" (development A/B; profiles/r09_ab_loss_in_backward.txt has the measurements behind the default).
+struct BwdLossArgs {
+    BwdArgs b;
+    LossArgs l;                  // (no gradient planes; sums: the per-wavefront partials)
+    int blend_blocks;            // workgroups of the blend, a multiple of 8
+    int rider_blocks;            // riders, padded to a multiple of 8 (the padding has nothing to do)
+    int loss_blocks;             // workgroups of the frame_loss_kernel grid the riders stand in for
+    int per;                     // wavefronts of that grid per rider
+    int place;                   // 0: riders behind the blend's workgroups, 1: in front, 2: dealt in between, eight at a time
+    int vec4;                    // the loss's V = 4 form
+};
+static_assert(sizeof(Batch<BwdLossArgs>) <= 4096, "kernel arguments: at most 4 KB");
+
+__device__ __forceinline__ void loss_rider(const BwdLossArgs &A, int r)
+{
+    LossArgs a = A.l;
+    loss_pick_target_set(a);
+    const int lane = threadIdx.x & 63, n_waves = 4 * A.loss_blocks, stride = A.loss_blocks * 256;
+    for (int k = 0; k < A.per; k++) {
+        const int w = r * A.per + k;                     // (wave-uniform)
+        if (w >= n_waves) break;
+        float s_c = 0.f, s_m = 0.f, s_n = 0.f, s_d = 0.f;
+        const int first = (w >> 2) * 256 + (w & 3) * 64 + lane;
+        if (A.vec4) frame_loss_walk<4, false>(a, first, stride, s_c, s_m, s_n, s_d);
+        else frame_loss_walk<1, false>(a, first, stride, s_c, s_m, s_n, s_d);
+        s_c = wave_sum(s_c); s_m = wave_sum(s_m); s_n = wave_sum(s_n); s_d = wave_sum(s_d);
+        if (lane == 0) reinterpret_cast<float4 *>(a.sums)[w] = make_float4(s_c, s_m, s_n, s_d);
+    }
+}
+
+template <bool WIDE, int REGION>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SOAR_BWD_BLK_WPE, 8))) render_backward_blocks_loss_kernel(Batch<BwdLossArgs> batch)
+{
+    int frame, bx;
+    batch_interleave(frame, bx);
+    const BwdLossArgs &A = batch.v[frame];
+    // who am I (uniform per workgroup): groups of eight workgroups -- one per XCD -- are riders or blend as a whole
+    const int grp = bx >> 3, g_blend = A.blend_blocks >> 3, g_rider = A.rider_blocks >> 3;
+    int rider_grp = -1, blend_grp = grp;
+    if (A.place == 0) {
+        if (grp >= g_blend) rider_grp = grp - g_blend;
+    } else if (A.place == 1) {
+        if (grp < g_rider) rider_grp = grp; else blend_grp = grp - g_rider;
+    } else {
+        const int total = g_blend + g_rider;
+        // (riders spread evenly over the groups; the products stay far below 2^31: at most 8192 + 1024 groups x 1024)
+        const int before = (int)((unsigned)(grp * g_rider) / (unsigned)total), upto = (int)((unsigned)((grp + 1) * g_rider) / (unsigned)total);
+        if (upto > before) rider_grp = before; else blend_grp = grp - before;
+    }
+    if (rider_grp >= 0) {
+        loss_rider(A, rider_grp * 8 + (bx & 7));
+        return;
+    }
+    LossArgs t = A.l;
+    loss_pick_target_set(t);
+    PixelLoss pl;
+    pl.color = t.color; pl.opac = t.opac; pl.t_color = t.t_color; pl.t_mask = t.t_mask; pl.t_normal = t.t_normal;
+    const LossScales k = loss_scales(t);
+    auto uniform = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    pl.k.gc = uniform(k.gc); pl.k.gm = uniform(k.gm); pl.k.gn = uniform(k.gn); pl.k.gd = uniform(k.gd);
+    backward_blocks<WIDE, false, REGION, true>(A.b, blend_grp * 8 + (bx & 7), (unsigned)A.blend_blocks, pl);
 }
 
 }  // namespace
@@ -949,6 +1048,78 @@ int launch_backward_blend(const BwdArgs &a, bool wide, bool blend, bool occ, hip
     return 0;
 }
 }  // namespace
+
+namespace {
+template <int REGION>
+int launch_backward_blend_loss(BwdLossArgs &A, bool wide, hipStream_t stream)
+{
+    const int grid_ranks = blend_grid_ranks(A.b.ntiles);
+    A.blend_blocks = (16 / REGION) * min((A.b.ntiles + 7) / 8 * 8, grid_ranks);
+    const dim3 grid((unsigned)(A.blend_blocks + A.rider_blocks));
+    if (wide) SOAR_LAUNCH_BATCHED((render_backward_blocks_loss_kernel<true, REGION>), grid, dim3(64), 0, stream, A);
+    else SOAR_LAUNCH_BATCHED((render_backward_blocks_loss_kernel<false, REGION>), grid, dim3(64), 0, stream, A);
+    g_blend_frames[REGION - 1].fetch_add(1, std::memory_order_relaxed);
+    return 0;
+}
+// SOAR_BWD_LOSS_RIDERS="place:per" (read once): where the riders sit and how many of the loss grid's wavefronts each takes
+void rider_knobs(int &place, int &per)
+{
+    static const struct Knobs {
+        int place = 0, per = 4;
+        Knobs()
+        {
+            const char *e = getenv("SOAR_BWD_LOSS_RIDERS");
+            int a = 0, b = 0;
+            if (e && sscanf(e, "%d:%d", &a, &b) == 2 && a >= 0 && a <= 2 && b >= 1 && b <= 64) { place = a; per = b; }
+        }
+    } knobs;
+    place = knobs.place; per = knobs.per;
+}
+}  // namespace
+
+int launch_render_backward_loss(const SoarRastParams &prm, const GeomBuf &g, const BinBuf &b, const ImageBuf &img, const SoarBackwardLoss &loss,
+                                float *acc, double *acc64, int region, SoarLossFinish *finish_out, hipStream_t stream)
+{
+    if (region != 1 && region != 2) { set_error("render_backward_loss: region is 1 (single blocks) or 2 (pairs), got %d", region); return 1; }
+    BwdLossArgs A{};
+    BwdArgs &a = A.b;
+    a.occ_planes = 3;
+    a.W = prm.W; a.H = prm.H;
+    a.gx = (prm.W + TILE - 1) / TILE; a.gy = (prm.H + TILE - 1) / TILE;
+    a.ntiles = a.gx * a.gy;
+    a.normalize_depth = prm.cfg_normalize_depth;
+    a.ranges = img.ranges; a.tile_order = img.tile_order; a.order_rec = img.order_rec; a.point_list = b.vals_sorted; a.rec = g.rec; a.bg = prm.bg_dev;
+    a.final_T = img.final_T; a.final_D = img.final_D; a.n_contrib = img.n_contrib;
+    a.acc = acc; a.acc64 = acc64;
+    a.masks = b.block_masks; a.mask_plane = b.mask_plane;
+    // the loss's arguments as soar_frame_loss[_pooled] sets them up for these outputs and this image buffer
+    LossArgs &l = A.l;
+    l.n = prm.W * prm.H;
+    l.color = loss.color; l.normal = loss.normal; l.depth = loss.depth; l.opac = loss.opac;
+    l.t_color = loss.target_color; l.t_mask = loss.target_mask; l.t_normal = loss.target_normal;
+    l.wc = loss.w_color; l.wm = loss.w_mask; l.wn = loss.w_normal; l.wd = loss.w_depth;
+    l.sums = loss.wave_sums;
+    l.set_index = loss.set_index_dev; l.n_sets = loss.n_sets;
+    l.W = prm.W; l.gx = a.gx;
+    l.bg = prm.bg_dev; l.normalize_depth = prm.cfg_normalize_depth;
+    l.n_contrib = img.n_contrib;
+    if (prm.W % 4 == 0) l.bg_tiles = img.bg_tiles;       // (four consecutive pixels of the flat planes lie in one tile)
+    bool vec4;
+    frame_loss_grid(l, vec4, A.loss_blocks);
+    A.vec4 = vec4 ? 1 : 0;
+    rider_knobs(A.place, A.per);
+    A.rider_blocks = ((4 * A.loss_blocks + A.per - 1) / A.per + 7) / 8 * 8;
+    StageTimer timer(ST_RENDER_BWD, stream);
+    if (region == 2 ? launch_backward_blend_loss<2>(A, acc64 != nullptr, stream) : launch_backward_blend_loss<1>(A, acc64 != nullptr, stream)) return 1;
+    if (acc64) {
+        NarrowArgs na;
+        na.n = (size_t)prm.P * ACC_STRIDE; na.wide = acc64; na.narrow = acc;
+        SOAR_LAUNCH_BATCHED(narrow_rows_kernel, dim3((unsigned)((na.n + 255) / 256)), dim3(256), 0, stream, na);
+    }
+    *finish_out = SoarLossFinish{loss.wave_sums, loss.loss_out, A.loss_blocks, l.n, loss.w_color, loss.w_mask, loss.w_normal, loss.w_depth};
+    SOAR_LAUNCH_OK("render_backward_loss", stream, prm.debug & 1);
+    return 0;
+}
 
 void render_backward_region_counts(long long *single_blocks, long long *pairs)
 {

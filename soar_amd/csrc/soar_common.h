@@ -449,6 +449,10 @@ int launch_render_backward(const SoarRastParams &prm, const GeomBuf &g, const Bi
                            const float *dL_dcolor, const float *dL_dnormal, const float *dL_ddepth, const float *dL_dopac,
                            const float *grad_scale, float *acc, double *acc64, bool blend, const float *dL_dout_occ, float *dL_docc,
                            const float *normal_scale, int occ_planes, int region, hipStream_t stream);
+// the blend with the frame loss's gradients made in its pixel prologue and the loss's value pass as riders of the launch
+// (soar_rast_backward_plan_loss; *finish_out: what the tail of the step needs to finish the value from the riders' partials)
+int launch_render_backward_loss(const SoarRastParams &prm, const GeomBuf &g, const BinBuf &b, const ImageBuf &img, const SoarBackwardLoss &loss,
+                                float *acc, double *acc64, int region, SoarLossFinish *finish_out, hipStream_t stream);
 // frames whose backward blend was issued with a wavefront per 4 x 4 block / per pair of blocks, since the library was loaded
 void render_backward_region_counts(long long *single_blocks, long long *pairs);
 int launch_geometry_backward(const SoarRastParams &prm, const float *means3D, const int32_t *radii, const float *shs,

@@ -76,6 +76,16 @@ class SoarLossFinish(C.Structure):
                 ("w_normal", C.c_float), ("w_depth", C.c_float)]
 
 
+BACKWARD_LOSS_SCRATCH_FLOATS = 4 * FRAME_LOSS_SCRATCH_FLOATS   # SOAR_BACKWARD_LOSS_SCRATCH_FLOATS: SoarBackwardLoss.wave_sums
+
+
+class SoarBackwardLoss(C.Structure):
+    """Mirror of ``struct SoarBackwardLoss`` (include/soar_hip.h): the loss record of soar_rast_backward_plan_loss."""
+    _fields_ = [("color", _vp), ("normal", _vp), ("depth", _vp), ("opac", _vp), ("target_color", _vp), ("target_mask", _vp),
+                ("target_normal", _vp), ("set_index_dev", _vp), ("n_sets", C.c_int32), ("w_color", C.c_float), ("w_mask", C.c_float),
+                ("w_normal", C.c_float), ("w_depth", C.c_float), ("loss_out", _vp), ("wave_sums", _vp)]
+
+
 class SoarViewArgs(C.Structure):
     """Mirror of ``struct SoarViewArgs`` (include/soar_hip.h)."""
     _fields_ = [("rast", SoarRastParams), ("focal_k00", C.c_float), ("focal_k11", C.c_float), ("back", C.c_int32), ("pad_", C.c_int32),
@@ -273,6 +283,8 @@ SIGNATURES = {
                                + [_vp] * 12 + [_vp, C.c_size_t, _vp]),
     "soar_rast_backward_plan": (C.c_int, [C.POINTER(SoarRastParams), C.c_int32] + [_vp] * 7 + [_vp, _vp, _vp, C.c_int64] + [_vp] * 4
                                 + [_vp] * 11 + [_vp, C.c_size_t, _vp]),
+    "soar_rast_backward_plan_loss": (C.c_int, [C.POINTER(SoarRastParams), C.c_int32] + [_vp] * 7 + [_vp, _vp, _vp, C.c_int64] + [_vp]
+                                     + [_vp] * 11 + [_vp, C.c_size_t, _vp, _vp]),
     "soar_rast_backward_occ_plan": (C.c_int, [C.POINTER(SoarRastParams), C.c_int32] + [_vp] * 7 + [_vp, _vp, _vp, C.c_int64] + [_vp] * 6
                                     + [C.c_int32] + [_vp] * 12 + [_vp, C.c_size_t, _vp]),
     "soar_rast_backward_region_counts": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -301,6 +313,7 @@ SIGNATURES = {
     "soar_rast_backward_rows": (C.c_int, [_vp] * 22),
     "soar_frames_geometry_warp_backward": (C.c_int, [C.c_int32, _vp] + [_vp] * 4 + [C.c_int32, C.c_int32] + [_vp] * 7),
     "soar_frames_geometry_warp_backward_losses": (C.c_int, [C.c_int32, _vp] + [_vp] * 4 + [C.c_int32, C.c_int32] + [_vp] * 8),
+    "soar_frames_geometry_warp_backward_wave_losses": (C.c_int, [C.c_int32, _vp] + [_vp] * 4 + [C.c_int32, C.c_int32] + [_vp] * 8),
     "soar_dist2_knn3": (C.c_int, [_vp, C.c_int32, _vp, _vp]),
     "soar_depth2normal": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     "soar_depth2normal_backward": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp,

@@ -191,6 +191,16 @@ class FrameStepPlan:
         self.loss_in_tail = fold and self.fused_tail and loss == "synthetic" and os.environ.get("SOAR_PLAN_LOSS_IN_TAIL", "1") != "0"
         if self.loss_in_tail:
             self._loss_finish = (hip_lib.SoarLossFinish * self.n)()        # written by every step's loss calls, read by its tail call
+        # The frame loss inside the backward blend's launch (soar_rast_backward_plan_loss, csrc/rast_render_bwd.hip): the blend makes
+        # the loss's pixel gradients in its own prologue -- gC / gN / gD / gO are neither written nor read --, the loss's value pass
+        # rides in the same launch as extra workgroups that leave a partial per wavefront of soar_frame_loss's grid, and the tail adds
+        # them up in that kernel's order (the same bits in `losses`).  The chain is geometry, render, backward.  On exactly where
+        # loss_in_tail is; SOAR_PLAN_LOSS_IN_BACKWARD=0: the chain with the loss launch again (profiles/r09_ab_loss_in_backward.txt).
+        self.loss_in_backward = self.loss_in_tail and os.environ.get("SOAR_PLAN_LOSS_IN_BACKWARD", "1") != "0"
+        if self.loss_in_backward:
+            self._loss_records = (hip_lib.SoarBackwardLoss * self.n)()
+            for v in self.views:
+                v["wave_sums"] = torch.empty((hip_lib.BACKWARD_LOSS_SCRATCH_FLOATS,), **f)
         self.gather_in_adam = fold and self.n <= 8 and os.environ.get("SOAR_PLAN_GATHER_IN_ADAM", "1") != "0"
         self._call_cache = {}
         self.optimizer = None                     # see _run_eager
@@ -448,6 +458,30 @@ class FrameStepPlan:
                                                 stream), "backward")
         self._call(("backward", i, stream), build)
 
+    def _f_backward_loss(self, i: int, stream: int) -> None:
+        """loss and rasterizer backward of frame i as one call (``loss_in_backward``): the partial sums stay in v["wave_sums"], the
+        epilogue's launch writes losses[i] (soar_frames_geometry_warp_backward_wave_losses)"""
+        def build():
+            L, s, v = self.L, self.seq, self.views[i]
+            r = self._loss_records[i]
+            r.color, r.normal, r.depth, r.opac = ptr(v["color"]), ptr(v["normal"]), ptr(v["depth"]), ptr(v["opac"])
+            if self.pool is not None:
+                r.target_color = r.target_mask = r.target_normal = ptr(self.pool)
+                r.set_index_dev, r.n_sets = ptr(self.frame_sel[i]), int(self.pool.shape[0])
+            else:
+                r.target_color, r.target_mask, r.target_normal = (ptr(t) for t in self.targets)
+                r.set_index_dev, r.n_sets = None, 1
+            r.w_color, r.w_mask, r.w_normal, r.w_depth = self.weights
+            r.loss_out, r.wave_sums = ptr(self.losses[i]), ptr(v["wave_sums"])
+            return (L.soar_rast_backward_plan_loss, (C.byref(self.ctx.params), self.bwd_region, ptr(v["xyz_p"]), ptr(v["radii"]), None,
+                                                     ptr(s.colors.detach()), ptr(s.scales.detach()), ptr(v["rot_p"]), None, ptr(v["geom"]),
+                                                     ptr(v["binning"]), ptr(v["img"]), self.capacity, C.addressof(r), ptr(v["g_means2D"]),
+                                                     ptr(self.g_colors[i]), ptr(v["g_opacity"]), ptr(v["g_means3D"]), ptr(v["g_cov3D"]), None,
+                                                     ptr(self.g_scales[i]), ptr(v["g_rot_p"]), ptr(v["g_view"]), ptr(v["g_proj"]),
+                                                     ptr(v["g_campos"]), ptr(v["work"]), v["work"].numel(),
+                                                     C.addressof(self._loss_finish[i]), stream), "backward_loss")
+        self._call(("backward_loss", i, stream), build)
+
     def _f_backward_occ(self, i: int, stream: int) -> None:
         """the rasterizer backward with the fused occlusion chain taken along (soar_rast_backward_occ_plan): dL/docc of the frame without a
         walk of its own"""
@@ -505,6 +539,8 @@ class FrameStepPlan:
                 for i in frames:
                     v = self.views[i]
                     torch.add(torch.dot(v["terms"], self.av_coef), v["occ_terms"][0] * self.av_occ_up[0], out=self.losses[i])
+        elif self.loss_in_backward:
+            batch((self._f_geometry, self._f_render, self._f_backward_loss))
         else:
             batch((self._f_geometry, self._f_render, self._f_loss, self._f_backward))
         for i in frames:
@@ -525,7 +561,8 @@ class FrameStepPlan:
             # calls stopped behind their blends (SoarRastParams.debug bit 3), their accumulation rows wait in the workspaces
             occ = ptr(fv["occ"]) if (self.loss_kind == "avatar" and "occ" in fv) else None
             if self.loss_in_tail:
-                check(L.soar_frames_geometry_warp_backward_losses(self.n, self._tail_frames, ptr(s.xyz.detach()), ptr(s.rot.detach()),
+                tail = L.soar_frames_geometry_warp_backward_wave_losses if self.loss_in_backward else L.soar_frames_geometry_warp_backward_losses
+                check(tail(self.n, self._tail_frames, ptr(s.xyz.detach()), ptr(s.rot.detach()),
                                                                   ptr(self.blend_weights), ptr(self.mats), self.P, J, ptr(s.scales.detach()),
                                                                   ptr(fv["xyz"]), ptr(fv["rot"]), ptr(fv["scales"]), ptr(fv["colors"]), occ,
                                                                   self._loss_finish, stream), "frames_geometry_warp_backward_losses")
