@@ -1476,7 +1476,7 @@ def test_avatar_stage_loss_is_the_composed_losses_in_one_node(hw):
     assert out["depth"].grad is None and out["curv"].grad is None and out["render"].grad.abs().sum() > 0
 
 
-@pytest.mark.parametrize("hw,with_occ", [((128, 200), True), ((540, 960), True), ((64, 96), False)])
+@pytest.mark.parametrize("hw,with_occ", [((128, 200), True), ((540, 960), True), ((64, 96), False), ((1026, 1024), True)])
 def test_avatar_pixel_losses_in_one_pass_equal_the_separate_kernels(hw, with_occ):
     """soar_avatar_pixel_losses (colour L1 + mask L1 + cosine loss + occlusion L1 against 1, one read of every image) against
     soar_masked_l1 / soar_cos_loss and their backwards: the same values and counts bit for bit, the same gradient planes, the
