@@ -1666,6 +1666,59 @@ int soar_frame_extra_terms_backward(const SoarFrameExtraArgs *args, void *stream
 int soar_abs_mean(int64_t n, const float *x, float *stats, void *scratch, void *stream);
 int soar_abs_mean_backward(int64_t n, const float *x, const float *upstream_dev, float *dL_dx, void *stream);
 
+/* ---- SMPLify fit inspection: keypoint and body-normal strips (fitviz.hip, soar_amd/fitviz.py) ----
+ * Current stream, no synchronisation, no allocation, no atomics; integer and un-contracted float32 arithmetic: two calls give the
+ * same bits, and a frame's output depends neither on N nor on its place.  Every pointer is device memory but verts_stride (host).
+ * N == 0 returns 0 without touching a pointer.
+ *
+ * soar_fitviz_yaw_views: verts [N][V][3] through three element strides, pivot [N][3], R [n_views - 1][3][3] ->
+ *   out [N][n_views][V][3].  View 0 is verts, bit for bit.  View k >= 1: d = v - p, and component i is
+ *   ((R[k-1][i][0] d0 + R[k-1][i][1] d1) + R[k-1][i][2] d2) + p_i, every operation rounded once.  1 <= n_views <= 16.
+ *
+ * soar_fitviz_strip: per frame a strip [H][5 W][3] uint8 of five panels H x W (or, with half != 0, [H / 2][(5 W) / 2][3]).
+ *   Keypoints: target_px, fit_px [N][K][2] float32 pixels (x, y); kp_mask [K] uint8.  The centre of keypoint k is
+ *   ((int)x, (int)y), truncated toward zero, and is drawn iff kp_mask[k] != 0, both coordinates are finite with |coord| < 2^20,
+ *   and both integers are >= 1.  A disc covers pixel p iff dx dx + dy dy <= r r + 1 (r = radius, 1 .. 8).
+ *   Limbs: limbs [L][2] int32 keypoint indices (a, b) with limb_rgb [L][3]; a limb is drawn in a set iff both of its keypoints
+ *   are drawn in that set (an index outside [0, K) draws nothing).  With d = b - a, L2 = d . d, s = (p - a) . d, exact in integers:
+ *   if 0 < s < L2, p is covered iff 4 cross(p - a, d)^2 <= t^2 L2; else iff 4 |p - e|^2 <= t^2, e = a when s <= 0 and b otherwise
+ *   (t = thickness, 1 .. 64; a limb of length 0 is its end test).
+ *   Panel 0: black; then, the last writer winning, the target set's limbs, its discs (target_rgb), the fit set's limbs, its discs
+ *   (fit_rgb); limbs in the order of the table, discs in the order of the keypoints.  Drawing is clipped to the panel.  With imgs
+ *   ([N][H][W][3] uint8 through four element strides; or NULL) every channel becomes rint(0.6f c + 0.4f img): two float32
+ *   products, one float32 sum, half to even, clamped to 0 .. 255.
+ *   Panels 2, 3, 4: yaw views 0, 1, 2 of prior [N][3][2][3][H][W] / mask [N][3][2][H][W] (soar_prior_raster's outputs for the 3 N
+ *   bodies of soar_fitviz_yaw_views; only the front view, index 0 of the axis of 2, is read): where mask != 0 channel c is
+ *   (uint8)((n_c * 0.5f + 0.5f) * 255.0f), clamped to 0 .. 255 and truncated; 0 elsewhere.
+ *   Panel 1: panel 2 blended with imgs by the rule of panel 0; panel 2 itself without imgs.
+ *   half: output pixel (i, j) is (a + b + c + d + 2) >> 2, per channel, of the full strip's pixels (2 i .. 2 i + 1, 2 j .. 2 j + 1);
+ *   an odd last row or column of the full strip is dropped.  H, W <= 4096, K <= 512, L <= 512, N <= 65535.
+ *
+ * soar_fitviz_residuals: fit_px, target_px [N][K][2], conf [N][K], kp_mask [K] -> out [N][3] float32 = {count, mean, max} over
+ *   the keypoints with kp_mask != 0, conf > thresh and four finite coordinates, of dist = sqrtf(dx dx + dy dy) (float32, every
+ *   operation rounded once).  A keypoint outside the selection enters as 0.  Lane l of 64 adds its keypoints l, l + 64, ... in that
+ *   order, then six butterfly steps x[l] += x[l ^ off], off = 32, 16, ..., 1; mean = sum / (float)count; a frame with none
+ *   gives 0, 0, 0.  K <= 512. */
+typedef struct SoarFitvizStripArgs {
+    int32_t N, H, W, K, L;
+    int32_t radius, thickness, half;
+    const float *target_px, *fit_px;
+    const uint8_t *kp_mask;
+    const int32_t *limbs;             /* [L][2] or NULL with L = 0 */
+    const uint8_t *limb_rgb;          /* [L][3] */
+    const uint8_t *imgs;              /* or NULL */
+    int64_t imgs_stride[4];           /* elements: frame, row, column, channel */
+    const float *prior;
+    const uint8_t *mask;
+    uint8_t target_rgb[4], fit_rgb[4];   /* r, g, b, unused */
+    uint8_t *out;
+} SoarFitvizStripArgs;
+int soar_fitviz_yaw_views(int32_t N, int32_t V, int32_t n_views, const float *verts, const int64_t *verts_stride, const float *pivot,
+                          const float *R, float *out, void *stream);
+int soar_fitviz_strip(const SoarFitvizStripArgs *args, void *stream);
+int soar_fitviz_residuals(int32_t N, int32_t K, const float *fit_px, const float *target_px, const float *conf, const uint8_t *kp_mask,
+                          float thresh, float *out, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

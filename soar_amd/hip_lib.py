@@ -195,6 +195,14 @@ class SoarPlaybackArgs(C.Structure):
                 ("occ_stride", C.c_int64), ("rgb", _vp), ("normal_out", _vp), ("occ_out", _vp), ("mask_out", _vp)]
 
 
+class SoarFitvizStripArgs(C.Structure):
+    """Mirror of ``struct SoarFitvizStripArgs`` (include/soar_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("L", C.c_int32), ("radius", C.c_int32),
+                ("thickness", C.c_int32), ("half", C.c_int32), ("target_px", _vp), ("fit_px", _vp), ("kp_mask", _vp), ("limbs", _vp),
+                ("limb_rgb", _vp), ("imgs", _vp), ("imgs_stride", C.c_int64 * 4), ("prior", _vp), ("mask", _vp),
+                ("target_rgb", C.c_uint8 * 4), ("fit_rgb", C.c_uint8 * 4), ("out", _vp)]
+
+
 class SoarNormalNetArgs(C.Structure):
     """Mirror of ``struct SoarNormalNetArgs`` (include/soar_hip.h)."""
     _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("ngf", C.c_int32), ("n_down", C.c_int32), ("n_blocks", C.c_int32),
@@ -469,6 +477,9 @@ SIGNATURES = {
     "soar_frame_extra_terms_backward": (C.c_int, [C.POINTER(SoarFrameExtraArgs), _vp]),
     "soar_abs_mean": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp]),
     "soar_abs_mean_backward": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp]),
+    "soar_fitviz_yaw_views": (C.c_int, [C.c_int32] * 3 + [_vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
+    "soar_fitviz_strip": (C.c_int, [C.POINTER(SoarFitvizStripArgs), _vp]),
+    "soar_fitviz_residuals": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -467,11 +467,26 @@ class SMPLify:
             return res.losses.sum()
         return closure
 
-    def fit(self, init_params, Ks, w2c, img_wh, target_kps) -> Dict[str, torch.Tensor]:
+    @staticmethod
+    def _rotvec_params(params) -> Dict[str, torch.Tensor]:
+        """The parameters in the form ``fit`` returns: rotation vectors for the 6-D poses, detached copies of the rest."""
+        out = {}
+        with torch.no_grad():
+            for k, v in params.items():
+                out[k] = rotmat_to_rotvec(rotation_6d_to_matrix(v)).reshape(v.shape[0], -1) if k in POSE_KEYS else v.detach().clone()
+        return out
+
+    def fit(self, init_params, Ks, w2c, img_wh, target_kps, visual=None) -> Dict[str, torch.Tensor]:
         """``init_params``: rotation vectors as SMPLer-X gives them (``global_orient [N,3], body_pose [N,63], left_hand_pose /
         right_hand_pose [N,45], jaw_pose / leye_pose / reye_pose [N,3]``), ``betas [N|1,NBS]`` (their mean is the one shared
         row), ``expression [N,NE]``, ``transl [N,3]``.  Returns the refined parameters in the same form, ``global_orient [N,3]``
-        and ``betas [1,NBS]``."""
+        and ``betas [1,NBS]``.
+
+        ``visual``: a ``fitviz.FitVisualizer`` (any callable ``(name, params, Ks, w2c, img_wh, target_kps)``; its ``debug``
+        attribute is read), called at the reference's moments with the current parameters in the returned form: ``"1_000"`` before
+        the first body step, ``"1_{i:03d}"`` after body step ``i`` and ``"2_{i:03d}"`` after hand step ``i`` -- a stage's last step,
+        or every fifth with ``visual.debug``.  It sees copies: neither ``.grad`` nor the optimizer's state is touched.  With None
+        (the default) ``fit`` makes exactly the calls it made without the argument."""
         dev = self.rig.device
         f = lambda x: torch.as_tensor(x).detach().to(device=dev, dtype=self.dtype)
         init = {}
@@ -486,19 +501,20 @@ class SMPLify:
         target = f(target_kps)
         scales = self.scales(target, img_wh)
         Ks, w2c = f(Ks), f(w2c)
-        for names, steps, ignore_hands in ((STAGE_KEYS[0], self.body_steps, True), (STAGE_KEYS[1], self.hand_steps, False)):
+        for stage, names, steps, ignore_hands in ((1, STAGE_KEYS[0], self.body_steps, True), (2, STAGE_KEYS[1], self.hand_steps, False)):
             for k in GRAD_KEYS:
                 params[k].grad = torch.zeros_like(params[k])              # parameters outside the stage's list keep a zero gradient
             opt = torch.optim.LBFGS([params[k] for k in names], lr=self.lr, max_iter=self.max_iters, line_search_fn="strong_wolfe")
             closure = self.make_closure(params, init, names, Ks, w2c, img_wh, target, scales, ignore_hands)
-            for _ in range(steps):
+            if visual is not None and stage == 1:
+                visual("1_000", self._rotvec_params(params), Ks, w2c, img_wh, target)
+            for i in range(steps):
                 opt.step(closure)
+                if visual is not None and ((i + 1) % 5 == 0 if getattr(visual, "debug", False) else i == steps - 1):
+                    visual(f"{stage}_{i:03d}", self._rotvec_params(params), Ks, w2c, img_wh, target)
             if steps:
                 self.loss_dict = dict(zip(("kp", "preserve", "smooth"), self.last.losses.tolist()))
-        out = {}
-        with torch.no_grad():
-            for k, v in params.items():
-                out[k] = rotmat_to_rotvec(rotation_6d_to_matrix(v)).reshape(v.shape[0], -1) if k in POSE_KEYS else v.detach().clone()
+        out = self._rotvec_params(params)
         self.params_6d = {k: v.detach() for k, v in params.items()}
         return out
 
