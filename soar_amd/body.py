@@ -22,7 +22,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import hip_lib
-from .hip_lib import check, ptr
+from .hip_lib import _bytes, check, ptr
 
 WEIGHTINGS = {"angle": 0, "area": 1, "uniform": 2}       # SOAR_NORMALS_*
 
@@ -43,12 +43,11 @@ def _stream(device: torch.device) -> int:
 
 
 def _workspace(F: int, device: torch.device) -> Tuple[torch.Tensor, int]:
-    nb = C.c_size_t(0)
-    check(hip_lib.lib().soar_mesh_workspace_bytes(int(F), C.byref(nb)), "soar_mesh_workspace_bytes")
-    buf = torch.empty(max(int(nb.value), 256), dtype=torch.uint8, device=device)
+    nb = _bytes(hip_lib.lib().soar_mesh_workspace_bytes, "soar_mesh_workspace_bytes", int(F))
+    buf = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
     if buf.data_ptr() % 256:
         raise RuntimeError("device allocation is not 256-byte aligned")
-    return buf, int(nb.value)
+    return buf, nb
 
 
 def _mesh_args(verts: torch.Tensor, faces: torch.Tensor):

@@ -15,12 +15,9 @@
 //   * vertex normals        : (vertex, corner) pairs radix-sorted, every vertex adds its corners' weighted unit face normals in
 //     ascending corner order -- no float atomics, bit-reproducible.
 //   * surfel frames         : ux = normalize(uz x rand), uy = normalize(uz x ux), [ux uy uz] -> quaternion (soar_quat.h).
-#include "soar_common.h"
+#include "mesh_common.h"
 #include "soar_quat.h"
 #include "soar_rodrigues.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace soar {
 
@@ -152,27 +149,18 @@ struct MeshBuf {
 size_t carve_mesh(MeshBuf &b, void *base, size_t F)
 {
     const size_t N = 3 * (F > 0 ? F : 1);
-    b.sort_bytes = 0;
-    (void)rocprim::radix_sort_keys((void *)nullptr, b.sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, N, 0u, 64u, (hipStream_t)0);
-    b.scan_bytes = 0;
-    (void)rocprim::exclusive_scan((void *)nullptr, b.scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)0, N,
-                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
-    size_t off = 0;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t bytes) {
-        void *r = p ? p + off : nullptr;
-        off += align_up(bytes);
-        return r;
-    };
-    b.keys = static_cast<uint64_t *>(take(N * 8));
-    b.keys_sorted = static_cast<uint64_t *>(take(N * 8));
-    b.ukeys = static_cast<uint64_t *>(take(N * 8));
-    b.head = static_cast<uint32_t *>(take(N * 4));
-    b.uid = static_cast<uint32_t *>(take(N * 4));
-    b.totals = static_cast<uint32_t *>(take(256));
-    b.sort_temp = take(b.sort_bytes);
-    b.scan_temp = take(b.scan_bytes);
-    return off;
+    Carver c(base);
+    b.keys = c.take<uint64_t>(N);
+    b.keys_sorted = c.take<uint64_t>(N);
+    b.ukeys = c.take<uint64_t>(N);
+    b.head = c.take<uint32_t>(N);
+    b.uid = c.take<uint32_t>(N);
+    b.totals = c.take<uint32_t>(64);
+    b.sort_bytes = sort_keys_temp_bytes<uint64_t>(N, 64u);
+    b.scan_bytes = scan_temp_bytes<uint32_t>(N);
+    b.sort_temp = c.take<char>(b.sort_bytes);
+    b.scan_temp = c.take<char>(b.scan_bytes);
+    return c.bytes();
 }
 
 __device__ __forceinline__ uint64_t edge_key(int a, int b)
@@ -187,8 +175,8 @@ __global__ void __launch_bounds__(256) edge_keys_kernel(int V, int F, const int 
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    const bool ok = a >= 0 && a < V && b >= 0 && b < V && c >= 0 && c < V;
+    int a, b, c;
+    const bool ok = face_corners(V, faces, f, a, b, c);
     if (!ok) totals[1] = 1u;
     keys[3 * f] = ok ? edge_key(a, b) : 0ull;
     keys[3 * f + 1] = ok ? edge_key(b, c) : 0ull;
@@ -345,17 +333,8 @@ __global__ void __launch_bounds__(256) vertex_frames_kernel(int P, const float *
 
 int mesh_workspace_ok(const char *what, int32_t F, const void *workspace, size_t workspace_bytes, MeshBuf &b)
 {
-    if (!workspace || ((uintptr_t)workspace & 255)) {
-        set_error("%s: NULL workspace or workspace not 256-byte aligned", what);
-        return 1;
-    }
-    const size_t need = carve_mesh(b, nullptr, (size_t)F);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, need %zu (soar_mesh_workspace_bytes)", what, workspace_bytes, need);
-        return 1;
-    }
-    carve_mesh(b, const_cast<void *>(workspace), (size_t)F);
-    return 0;
+    const size_t need = carve_mesh(b, const_cast<void *>(workspace), (size_t)F);
+    return workspace_ok(what, workspace, workspace_bytes, need, "soar_mesh_workspace_bytes") ? 0 : 1;
 }
 
 constexpr int32_t MAX_FACES = 0x7fffffff / 12;      // 12 F ints of child faces and 3 F corner ids stay in int32
@@ -423,11 +402,9 @@ extern "C" int soar_mesh_subdivide_edges(int32_t V, int32_t F, const int32_t *fa
     SOAR_HIP_OK(hipMemsetAsync(b.totals, 0, 8, stream));
     hipLaunchKernelGGL(edge_keys_kernel, gf, blk, 0, stream, V, F, faces, b.keys, b.totals);
     SOAR_LAUNCH_OK("edge_keys", stream, 0);
-    size_t bytes = b.sort_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_keys(b.sort_temp, bytes, b.keys, b.keys_sorted, (size_t)N, 0u, 64u, stream));
+    SOAR_HIP_OK(sort_keys(b.sort_temp, b.sort_bytes, b.keys, b.keys_sorted, (size_t)N, 64u, stream));
     hipLaunchKernelGGL(head_kernel, gn, blk, 0, stream, N, b.keys_sorted, b.head);
-    bytes = b.scan_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.head, b.uid, (uint32_t)0, (size_t)N, rocprim::plus<uint32_t>(), stream));
+    SOAR_HIP_OK(exclusive_scan_sum(b.scan_temp, b.scan_bytes, b.head, b.uid, (size_t)N, stream));
     hipLaunchKernelGGL(compact_kernel, gn, blk, 0, stream, N, b.keys_sorted, b.head, b.uid, b.ukeys, b.totals);
     SOAR_LAUNCH_OK("edge_compact", stream, 0);
     uint32_t tot[2] = {0, 0};
@@ -477,8 +454,7 @@ extern "C" int soar_mesh_vertex_normals(int32_t V, int32_t F, const float *verts
         SOAR_HIP_OK(hipMemsetAsync(b.totals, 0, 8, stream));
         hipLaunchKernelGGL(corner_keys_kernel, dim3((F + 255) / 256), dim3(256), 0, stream, V, F, faces, b.keys, b.totals);
         SOAR_LAUNCH_OK("corner_keys", stream, 0);
-        size_t bytes = b.sort_bytes;
-        SOAR_HIP_OK(rocprim::radix_sort_keys(b.sort_temp, bytes, b.keys, b.keys_sorted, (size_t)N, 0u, 64u, stream));
+        SOAR_HIP_OK(sort_keys(b.sort_temp, b.sort_bytes, b.keys, b.keys_sorted, (size_t)N, 64u, stream));
         // the gather reads vertices by these indices: nothing is gathered before they are known to be in range
         uint32_t tot[2] = {0, 0};
         SOAR_HIP_OK(hipMemcpyAsync(tot, b.totals, 8, hipMemcpyDeviceToHost, stream));

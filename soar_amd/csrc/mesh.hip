@@ -11,18 +11,17 @@
 //   mc_emit_kernel         writes the vertices (index coordinates) and the triangles (mcubes_table.h, gen_mcubes_table.py)
 //   filt_* kernels         union-find over the faces' edges (atomicMin hooking: the root of a component is its least vertex
 //                          id, whatever the order of the hooks), face counts and bounding boxes per component (integer atomics
-//                          on an order-preserving encoding of the coordinates), keep flags, two scans, compaction
+//                          on an order-preserving encoding of the coordinates), keep flags; compact_mesh (mesh_common.h) then
+//                          scans the flags and writes the kept vertices and faces
 //
 // Host read-backs: soar_mc_count and soar_mesh_filter_components read their totals back (one stream synchronisation each) to
 // size the outputs.  This is the export path, not the training step; the launch functions allocate nothing.
 // Built with -ffp-contract=off: the vertex positions and the fused signed distances follow an IEEE evaluation of the
 // expressions as written, which the CPU restatements in tests/ reproduce.
-#include "soar_common.h"
+#include "mesh_common.h"
 #include "preprocess_point.h"
 
 #include <climits>
-
-#include <rocprim/device/device_scan.hpp>
 
 #define SOAR_MC_TABLE_SPACE __constant__
 #include "mcubes_table.h"
@@ -90,25 +89,16 @@ struct McBuf {
     size_t scan_bytes;
 };
 
-inline size_t mc_scan_bytes(size_t N)
-{
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan((void *)nullptr, bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, N > 0 ? N : 1,
-                                  rocprim::plus<uint64_t>(), (hipStream_t)0);
-    return bytes;
-}
-
 inline size_t carve_mc(McBuf &b, void *base, size_t N)
 {
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.packed = reinterpret_cast<uint64_t *>(take(N * 8));
-    b.offs = reinterpret_cast<uint64_t *>(take(N * 8));
-    b.info = reinterpret_cast<uint16_t *>(take(N * 2));
-    b.totals = reinterpret_cast<uint64_t *>(take(8));
-    b.scan_bytes = mc_scan_bytes(N);
-    b.scan_temp = take(b.scan_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    Carver c(base);
+    b.packed = c.take<uint64_t>(N);
+    b.offs = c.take<uint64_t>(N);
+    b.info = c.take<uint16_t>(N);
+    b.totals = c.take<uint64_t>(1);
+    b.scan_bytes = scan_temp_bytes<uint64_t>(N > 0 ? N : 1);
+    b.scan_temp = c.take<char>(b.scan_bytes);
+    return c.bytes();
 }
 
 struct McArgs {
@@ -203,55 +193,27 @@ struct FiltBuf {
     int32_t *bbox;         // [V][6] ordered-int min xyz, max xyz per component
     int32_t *gbox;         // [6] the whole mesh's
     uint8_t *ref;          // [V] vertex used by a face
-    uint32_t *vkeep, *voff;  // [V]
-    uint32_t *fkeep, *foff;  // [F]
-    uint32_t *totals;      // [3] kept vertices, kept faces, faces with an index out of range
-    void *scan_temp;
-    size_t scan_bytes;
+    CompactBuf c;          // keep flags, their scans, totals ([2]: faces with an index out of range)
 };
-
-inline size_t filt_scan_bytes(size_t n)
-{
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan((void *)nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)0, n > 0 ? n : 1,
-                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
-    return bytes;
-}
 
 inline size_t carve_filt(FiltBuf &b, void *base, size_t V, size_t F)
 {
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.parent = reinterpret_cast<int32_t *>(take(V * 4));
-    b.fcount = reinterpret_cast<int32_t *>(take(V * 4));
-    b.bbox = reinterpret_cast<int32_t *>(take(V * 24));
-    b.gbox = reinterpret_cast<int32_t *>(take(24));
-    b.ref = reinterpret_cast<uint8_t *>(take(V));
-    b.vkeep = reinterpret_cast<uint32_t *>(take(V * 4));
-    b.voff = reinterpret_cast<uint32_t *>(take(V * 4));
-    b.fkeep = reinterpret_cast<uint32_t *>(take(F * 4));
-    b.foff = reinterpret_cast<uint32_t *>(take(F * 4));
-    b.totals = reinterpret_cast<uint32_t *>(take(12));
-    const size_t sv = filt_scan_bytes(V), sf = filt_scan_bytes(F);
-    b.scan_bytes = sv > sf ? sv : sf;
-    b.scan_temp = take(b.scan_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    Carver c(base);
+    b.parent = c.take<int32_t>(V);
+    b.fcount = c.take<int32_t>(V);
+    b.bbox = c.take<int32_t>(V * 6);
+    b.gbox = c.take<int32_t>(6);
+    b.ref = c.take<uint8_t>(V);
+    const size_t sv = scan_temp_bytes<uint32_t>(V > 0 ? V : 1), sf = scan_temp_bytes<uint32_t>(F > 0 ? F : 1);
+    carve_compact(c, b.c, V, F, sv > sf ? sv : sf);
+    return c.bytes();
 }
-
-// floats as ints whose signed order is the floats' order
-__device__ __forceinline__ int ford(float f)
-{
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-
-__device__ __forceinline__ float fdec(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
 __global__ void __launch_bounds__(256) filt_init_kernel(int V, FiltBuf b)
 {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v == 0) {
-        for (int k = 0; k < 3; k++) { b.gbox[k] = INT_MAX; b.gbox[3 + k] = INT_MIN; b.totals[k] = 0; }
+        for (int k = 0; k < 3; k++) { b.gbox[k] = INT_MAX; b.gbox[3 + k] = INT_MIN; b.c.totals[k] = 0; }
     }
     if (v >= V) return;
     b.parent[v] = v;
@@ -288,9 +250,9 @@ __global__ void __launch_bounds__(256) filt_hook_kernel(int V, int F, const int3
 {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
-    const int a = faces[(size_t)f * 3], c1 = faces[(size_t)f * 3 + 1], c2 = faces[(size_t)f * 3 + 2];
-    if (a < 0 || a >= V || c1 < 0 || c1 >= V || c2 < 0 || c2 >= V) {
-        atomicAdd(b.totals + 2, 1u);                      // reported by the host; the face is ignored
+    int a, c1, c2;
+    if (!face_corners(V, faces, f, a, c1, c2)) {
+        atomicAdd(b.c.totals + 2, 1u);                    // reported by the host; the face is ignored
         return;
     }
     b.ref[a] = 1;
@@ -311,33 +273,13 @@ __global__ void __launch_bounds__(256) filt_label_kernel(int V, FiltBuf b)
     b.parent[v] = r;
 }
 
-__device__ __forceinline__ int wave_max_i(int x)
-{
-    for (int m = 32; m >= 1; m >>= 1) x = max(x, __shfl_xor(x, m));
-    return x;
-}
-
-__device__ __forceinline__ int wave_min_i(int x)
-{
-    for (int m = 32; m >= 1; m >>= 1) x = min(x, __shfl_xor(x, m));
-    return x;
-}
-
-__device__ __forceinline__ int wave_sum_i(int x)
-{
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
-
 // faces per component.  Almost every wave of faces lies in one component: then ONE atomic per wave (Guideline 12)
 __global__ void __launch_bounds__(256) filt_face_stats_kernel(int V, int F, const int32_t *__restrict__ faces, FiltBuf b)
 {
     const int f = blockIdx.x * 256 + threadIdx.x;
     int lab = -1;
-    if (f < F) {
-        const int a = faces[(size_t)f * 3], c1 = faces[(size_t)f * 3 + 1], c2 = faces[(size_t)f * 3 + 2];
-        if (a >= 0 && a < V && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V) lab = b.parent[a];
-    }
+    int a, c1, c2;
+    if (f < F && face_corners(V, faces, f, a, c1, c2)) lab = b.parent[a];
     const int top = wave_max_i(lab);
     if (__all(lab == top || lab < 0)) {
         const int n = wave_sum_i(lab >= 0 ? 1 : 0);
@@ -407,36 +349,16 @@ __global__ void __launch_bounds__(256) filt_keep_verts_kernel(int V, int min_fac
         const int lab = b.parent[v];
         keep = b.fcount[lab] >= min_faces && !(box_diag(b.bbox + (size_t)lab * 6) < min_diag_frac * box_diag(b.gbox));
     }
-    b.vkeep[v] = keep;
+    b.c.vkeep[v] = keep;
 }
 
 __global__ void __launch_bounds__(256) filt_keep_faces_kernel(int V, int F, const int32_t *__restrict__ faces, FiltBuf b)
 {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
-    const int a = faces[(size_t)f * 3], c1 = faces[(size_t)f * 3 + 1], c2 = faces[(size_t)f * 3 + 2];
-    const bool ok = a >= 0 && a < V && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V;
-    b.fkeep[f] = ok ? b.vkeep[a] : 0u;          // the three corners share a component
-}
-
-__global__ void filt_totals_kernel(int V, int F, FiltBuf b)
-{
-    b.totals[0] = b.voff[V - 1] + b.vkeep[V - 1];
-    b.totals[1] = b.foff[F - 1] + b.fkeep[F - 1];
-}
-
-__global__ void __launch_bounds__(256) filt_write_kernel(int V, int F, const float *__restrict__ verts, const int32_t *__restrict__ faces,
-                                                         FiltBuf b, float *__restrict__ verts_out, int32_t *__restrict__ faces_out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < V && b.vkeep[i]) {
-        const size_t o = b.voff[i];
-        for (int k = 0; k < 3; k++) verts_out[o * 3 + k] = verts[(size_t)i * 3 + k];
-    }
-    if (i < F && b.fkeep[i]) {
-        const size_t o = b.foff[i];
-        for (int k = 0; k < 3; k++) faces_out[o * 3 + k] = (int32_t)b.voff[faces[(size_t)i * 3 + k]];
-    }
+    int a, c1, c2;
+    const bool ok = face_corners(V, faces, f, a, c1, c2);
+    b.c.fkeep[f] = ok ? b.c.vkeep[a] : 0u;      // the three corners share a component
 }
 
 inline bool grid_ok(const char *what, int32_t X, int32_t Y, int32_t Z)
@@ -488,35 +410,24 @@ extern "C" int soar_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z, size_t *
     return 0;
 }
 
-static int mc_check(const char *what, int32_t X, int32_t Y, int32_t Z, const float *values, void *workspace, size_t workspace_bytes)
+static int mc_check(const char *what, int32_t X, int32_t Y, int32_t Z, const float *values, void *workspace, size_t workspace_bytes, McBuf &b)
 {
     if (!grid_ok(what, X, Y, Z)) return 1;
-    if (!values || !workspace || ((uintptr_t)workspace & 255)) {
-        set_error("%s: NULL argument or workspace not 256-byte aligned", what);
-        return 1;
-    }
-    McBuf b;
-    const size_t need = carve_mc(b, nullptr, (size_t)X * Y * Z);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, need %zu (soar_mc_workspace_bytes)", what, workspace_bytes, need);
-        return 1;
-    }
-    return 0;
+    if (!values) { set_error("%s: NULL argument", what); return 1; }
+    return workspace_ok(what, workspace, workspace_bytes, carve_mc(b, workspace, (size_t)X * Y * Z), "soar_mc_workspace_bytes") ? 0 : 1;
 }
 
 extern "C" int soar_mc_count(int32_t X, int32_t Y, int32_t Z, const float *values, const uint8_t *valid, float level, void *workspace,
                              size_t workspace_bytes, int64_t *counts_host, void *stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (mc_check("soar_mc_count", X, Y, Z, values, workspace, workspace_bytes)) return 1;
+    McBuf b;
+    if (mc_check("soar_mc_count", X, Y, Z, values, workspace, workspace_bytes, b)) return 1;
     if (!counts_host) { set_error("soar_mc_count: NULL counts_host"); return 1; }
     const int N = X * Y * Z;
-    McBuf b;
-    carve_mc(b, workspace, (size_t)N);
     const McArgs a = {X, Y, Z, level, values, valid};
     hipLaunchKernelGGL(mc_count_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, a, b.packed, b.info);
-    size_t bytes = b.scan_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.packed, b.offs, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), stream));
+    SOAR_HIP_OK(exclusive_scan_sum(b.scan_temp, b.scan_bytes, b.packed, b.offs, (size_t)N, stream));
     hipLaunchKernelGGL(mc_totals_kernel, dim3(1), dim3(1), 0, stream, N, b.packed, b.offs, b.totals);
     SOAR_LAUNCH_OK("mc_count", stream, 0);
     uint64_t tot = 0;
@@ -536,11 +447,10 @@ extern "C" int soar_mc_emit(int32_t X, int32_t Y, int32_t Z, const float *values
                             size_t workspace_bytes, float *verts, int32_t *faces, void *stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (mc_check("soar_mc_emit", X, Y, Z, values, const_cast<void *>(workspace), workspace_bytes)) return 1;
+    McBuf b;
+    if (mc_check("soar_mc_emit", X, Y, Z, values, const_cast<void *>(workspace), workspace_bytes, b)) return 1;
     if (!verts || !faces) { set_error("soar_mc_emit: NULL verts / faces"); return 1; }
     const int N = X * Y * Z;
-    McBuf b;
-    carve_mc(b, const_cast<void *>(workspace), (size_t)N);
     const McArgs a = {X, Y, Z, level, values, valid};
     hipLaunchKernelGGL(mc_emit_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, a, b.offs, b.info, verts, faces);
     SOAR_LAUNCH_OK("mc_emit", stream, 0);
@@ -561,18 +471,12 @@ extern "C" int soar_mesh_filter_components(int32_t V, int32_t F, const float *ve
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (V <= 0 || F <= 0) { set_error("soar_mesh_filter_components: need V > 0 and F > 0 (V=%d, F=%d)", V, F); return 1; }
-    if (!verts || !faces || !workspace || !verts_out || !faces_out || !counts_host || ((uintptr_t)workspace & 255)) {
-        set_error("soar_mesh_filter_components: NULL argument or workspace not 256-byte aligned");
-        return 1;
-    }
+    if (!verts || !faces || !verts_out || !faces_out || !counts_host) { set_error("soar_mesh_filter_components: NULL argument"); return 1; }
     FiltBuf b;
-    const size_t need = carve_filt(b, nullptr, (size_t)V, (size_t)F);
-    if (workspace_bytes < need) {
-        set_error("soar_mesh_filter_components: workspace of %zu bytes, need %zu (soar_mesh_filter_bytes)", workspace_bytes, need);
+    if (!workspace_ok("soar_mesh_filter_components", workspace, workspace_bytes, carve_filt(b, workspace, (size_t)V, (size_t)F),
+                      "soar_mesh_filter_bytes"))
         return 1;
-    }
-    carve_filt(b, workspace, (size_t)V, (size_t)F);
-    const dim3 gv((V + 255) / 256), gf((F + 255) / 256), gm(((V > F ? V : F) + 255) / 256), blk(256);
+    const dim3 gv((V + 255) / 256), gf((F + 255) / 256), blk(256);
     hipLaunchKernelGGL(filt_init_kernel, gv, blk, 0, stream, V, b);
     hipLaunchKernelGGL(filt_hook_kernel, gf, blk, 0, stream, V, F, faces, b);
     hipLaunchKernelGGL(filt_label_kernel, gv, blk, 0, stream, V, b);
@@ -581,18 +485,5 @@ extern "C" int soar_mesh_filter_components(int32_t V, int32_t F, const float *ve
     hipLaunchKernelGGL(filt_keep_verts_kernel, gv, blk, 0, stream, V, min_faces, min_diag_frac, b);
     hipLaunchKernelGGL(filt_keep_faces_kernel, gf, blk, 0, stream, V, F, faces, b);
     SOAR_LAUNCH_OK("mesh_filter_stats", stream, 0);
-    size_t bytes = b.scan_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.vkeep, b.voff, (uint32_t)0, (size_t)V, rocprim::plus<uint32_t>(), stream));
-    bytes = b.scan_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.fkeep, b.foff, (uint32_t)0, (size_t)F, rocprim::plus<uint32_t>(), stream));
-    hipLaunchKernelGGL(filt_totals_kernel, dim3(1), dim3(1), 0, stream, V, F, b);
-    hipLaunchKernelGGL(filt_write_kernel, gm, blk, 0, stream, V, F, verts, faces, b, verts_out, faces_out);
-    SOAR_LAUNCH_OK("mesh_filter_write", stream, 0);
-    uint32_t tot[3] = {0, 0, 0};
-    SOAR_HIP_OK(hipMemcpyAsync(tot, b.totals, 12, hipMemcpyDeviceToHost, stream));
-    SOAR_HIP_OK(hipStreamSynchronize(stream));
-    if (tot[2]) { set_error("soar_mesh_filter_components: %u faces name a vertex outside [0, %d)", tot[2], V); return 1; }
-    counts_host[0] = tot[0];
-    counts_host[1] = tot[1];
-    return 0;
+    return compact_mesh("soar_mesh_filter_components", V, F, verts, faces, b.c, verts_out, faces_out, nullptr, counts_host, stream);
 }

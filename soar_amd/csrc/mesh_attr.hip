@@ -23,17 +23,15 @@
 //   smooth_step_kernel     one lane per vertex, one Jacobi step: S = the sum of the row's positions in row order (a border vertex
 //                          adds only the neighbours that stand once), P' = (P + S) / (n + 1), n the number of terms; n = 0 keeps P.
 //                          Gathers only, no float atomics: two runs give the same bits.
-//   prune_* kernels        keep flags (a vertex goes when quality > thresh, a face when it touches one), two scans, compaction
-//                          in input order, re-indexed faces and the map keep[new] = old.
+//   prune_flags_kernel     keep flags (a vertex goes when quality > thresh, a face when it touches one); compact_mesh
+//                          (mesh_common.h) then does the two scans and the compaction in input order: re-indexed faces and the
+//                          map keep[new] = old.
 //
 // Host read-backs (one stream synchronisation each): soar_mesh_attr_transfer and soar_mesh_adjacency read back the number of
 // indices / faces they had to refuse, soar_mesh_prune that and its totals.  This is the export path, not the training step; the
 // launch functions allocate nothing and keep no device state.  Built with -ffp-contract=off: the sums and squares are IEEE
 // evaluations of the expressions as written, which tests/mesh_attr_ref.py restates.
-#include "soar_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "mesh_common.h"
 
 namespace soar {
 
@@ -87,15 +85,13 @@ struct AdjBuf {
 size_t carve_adj(AdjBuf &b, void *base, size_t F)
 {
     const size_t N = 6 * (F > 0 ? F : 1);
-    b.sort_bytes = 0;
-    (void)rocprim::radix_sort_keys((void *)nullptr, b.sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, N, 0u, 64u, (hipStream_t)0);
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.keys = reinterpret_cast<uint64_t *>(take(N * 8));
-    b.keys_sorted = reinterpret_cast<uint64_t *>(take(N * 8));
-    b.bad = reinterpret_cast<uint32_t *>(take(4));
-    b.sort_temp = take(b.sort_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    Carver c(base);
+    b.keys = c.take<uint64_t>(N);
+    b.keys_sorted = c.take<uint64_t>(N);
+    b.bad = c.take<uint32_t>(1);
+    b.sort_bytes = sort_keys_temp_bytes<uint64_t>(N, 64u);
+    b.sort_temp = c.take<char>(b.sort_bytes);
+    return c.bytes();
 }
 
 __global__ void __launch_bounds__(256) adj_keys_kernel(int V, int F, const int32_t *__restrict__ faces, uint64_t *__restrict__ keys,
@@ -180,71 +176,26 @@ __global__ void __launch_bounds__(256) smooth_step_kernel(int V, int nnz, const 
     dst[(size_t)v * 3 + 2] = n ? (pz + sz) / d : pz;
 }
 
-__global__ void __launch_bounds__(256) copy_floats_kernel(size_t n, const float *__restrict__ src, float *__restrict__ dst)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
 // ---- pruning -----------------------------------------------------------------------------------------------------------------
 
-struct PruneBuf {
-    uint32_t *vkeep, *voff;     // [V]
-    uint32_t *fkeep, *foff;     // [F]
-    uint32_t *totals;           // [0] vertices kept, [1] faces kept, [2] faces naming a vertex outside [0, V)
-    void *scan_temp;
-    size_t scan_bytes;
-};
-
-size_t carve_prune(PruneBuf &b, void *base, size_t V, size_t F)
+size_t carve_prune(CompactBuf &b, void *base, size_t V, size_t F)
 {
     const size_t M = V > F ? V : F;
-    b.scan_bytes = 0;
-    (void)rocprim::exclusive_scan((void *)nullptr, b.scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)0, M > 0 ? M : 1,
-                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.vkeep = reinterpret_cast<uint32_t *>(take(V * 4));
-    b.voff = reinterpret_cast<uint32_t *>(take(V * 4));
-    b.fkeep = reinterpret_cast<uint32_t *>(take((F > 0 ? F : 1) * 4));
-    b.foff = reinterpret_cast<uint32_t *>(take((F > 0 ? F : 1) * 4));
-    b.totals = reinterpret_cast<uint32_t *>(take(12));
-    b.scan_temp = take(b.scan_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    Carver c(base);
+    carve_compact(c, b, V, F, scan_temp_bytes<uint32_t>(M > 0 ? M : 1));
+    return c.bytes();
 }
 
 __global__ void __launch_bounds__(256) prune_flags_kernel(int V, int F, const int32_t *__restrict__ faces, const float *__restrict__ quality,
-                                                          float thresh, PruneBuf b)
+                                                          float thresh, CompactBuf b)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < V) b.vkeep[i] = quality[i] > thresh ? 0u : 1u;            // (a NaN quality is not above the threshold: kept)
     if (i < F) {
-        const int a = faces[(size_t)i * 3], c1 = faces[(size_t)i * 3 + 1], c2 = faces[(size_t)i * 3 + 2];
-        const bool ok = a >= 0 && a < V && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V;
+        int a, c1, c2;
+        const bool ok = face_corners(V, faces, i, a, c1, c2);
         if (!ok) atomicAdd(b.totals + 2, 1u);
         b.fkeep[i] = ok && !(quality[a] > thresh) && !(quality[c1] > thresh) && !(quality[c2] > thresh) ? 1u : 0u;
-    }
-}
-
-__global__ void prune_totals_kernel(int V, int F, PruneBuf b)
-{
-    b.totals[0] = b.voff[V - 1] + b.vkeep[V - 1];
-    b.totals[1] = F > 0 ? b.foff[F - 1] + b.fkeep[F - 1] : 0u;
-}
-
-__global__ void __launch_bounds__(256) prune_write_kernel(int V, int F, const float *__restrict__ verts, const int32_t *__restrict__ faces,
-                                                          PruneBuf b, float *__restrict__ verts_out, int32_t *__restrict__ faces_out,
-                                                          int32_t *__restrict__ keep_out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < V && b.vkeep[i]) {
-        const size_t o = b.voff[i];
-        for (int k = 0; k < 3; k++) verts_out[o * 3 + k] = verts[(size_t)i * 3 + k];
-        keep_out[o] = i;
-    }
-    if (i < F && b.fkeep[i]) {                        // (a kept face has its three corners in range and kept)
-        const size_t o = b.foff[i];
-        for (int k = 0; k < 3; k++) faces_out[o * 3 + k] = (int32_t)b.voff[faces[(size_t)i * 3 + k]];
     }
 }
 
@@ -254,13 +205,6 @@ bool sizes_ok(const char *what, int32_t V, int32_t F)
         set_error("%s: need 1 <= V <= 2^30 and 0 <= F <= 2^28 (V=%d, F=%d)", what, V, F);
         return false;
     }
-    return true;
-}
-
-bool workspace_ok(const char *what, const void *workspace, size_t have, size_t need)
-{
-    if (!workspace || ((uintptr_t)workspace & 255)) { set_error("%s: NULL workspace or workspace not 256-byte aligned", what); return false; }
-    if (have < need) { set_error("%s: workspace of %zu bytes, need %zu (ask the call's _bytes query)", what, have, need); return false; }
     return true;
 }
 
@@ -288,7 +232,7 @@ extern "C" int soar_mesh_attr_transfer(int32_t V, int32_t N, int32_t K, const fl
     if (K < 1 || K > ATTR_MAXK) { set_error("soar_mesh_attr_transfer: need 1 <= K <= %d (K=%d)", ATTR_MAXK, K); return 1; }
     if (V < 1 || V > ATTR_MAX_V || N < 1) { set_error("soar_mesh_attr_transfer: need 1 <= V <= 2^30 and N >= 1 (V=%d, N=%d)", V, N); return 1; }
     if (!verts || !points || !colors || !idx || !color_out || !quality_out) { set_error("soar_mesh_attr_transfer: NULL argument"); return 1; }
-    if (!workspace_ok("soar_mesh_attr_transfer", workspace, workspace_bytes, 256)) return 1;
+    if (!workspace_ok("soar_mesh_attr_transfer", workspace, workspace_bytes, 256, "soar_mesh_attr_transfer_bytes")) return 1;
     uint32_t *bad = static_cast<uint32_t *>(workspace);
     SOAR_HIP_OK(hipMemsetAsync(bad, 0, 4, stream));
     hipLaunchKernelGGL(attr_transfer_kernel, dim3((V + 255) / 256), dim3(256), 0, stream, V, N, K, verts, points, colors, idx, color_out,
@@ -317,15 +261,13 @@ extern "C" int soar_mesh_adjacency(int32_t V, int32_t F, const int32_t *faces, v
     if (!sizes_ok("soar_mesh_adjacency", V, F)) return 1;
     if (!row_start || !border || (F > 0 && (!faces || !nbr))) { set_error("soar_mesh_adjacency: NULL argument"); return 1; }
     AdjBuf b;
-    if (!workspace_ok("soar_mesh_adjacency", workspace, workspace_bytes, carve_adj(b, nullptr, (size_t)F))) return 1;
-    carve_adj(b, workspace, (size_t)F);
+    if (!workspace_ok("soar_mesh_adjacency", workspace, workspace_bytes, carve_adj(b, workspace, (size_t)F), "soar_mesh_adjacency_bytes")) return 1;
     const int nnz = 6 * F;
     if (F > 0) {
         SOAR_HIP_OK(hipMemsetAsync(b.bad, 0, 4, stream));
         hipLaunchKernelGGL(adj_keys_kernel, dim3((F + 255) / 256), dim3(256), 0, stream, V, F, faces, b.keys, b.bad);
         SOAR_LAUNCH_OK("mesh_adjacency_keys", stream, 0);
-        size_t bytes = b.sort_bytes;
-        SOAR_HIP_OK(rocprim::radix_sort_keys(b.sort_temp, bytes, b.keys, b.keys_sorted, (size_t)nnz, 0u, 64u, stream));
+        SOAR_HIP_OK(sort_keys(b.sort_temp, b.sort_bytes, b.keys, b.keys_sorted, (size_t)nnz, 64u, stream));
         hipLaunchKernelGGL(adj_nbr_kernel, dim3((nnz + 255) / 256), dim3(256), 0, stream, nnz, b.keys_sorted, nbr);
     }
     hipLaunchKernelGGL(adj_rows_kernel, dim3((V + 1 + 255) / 256), dim3(256), 0, stream, V, nnz, b.keys_sorted, row_start, border);
@@ -357,11 +299,11 @@ extern "C" int soar_mesh_smooth(int32_t V, int32_t nnz, const float *verts, cons
     }
     if (!verts || !row_start || !border || !verts_out || (nnz > 0 && !nbr)) { set_error("soar_mesh_smooth: NULL argument"); return 1; }
     if (verts == verts_out) { set_error("soar_mesh_smooth: verts_out must not be verts (a step reads the old positions)"); return 1; }
-    if (!workspace_ok("soar_mesh_smooth", workspace, workspace_bytes, align_up((size_t)V * 12))) return 1;
+    if (!workspace_ok("soar_mesh_smooth", workspace, workspace_bytes, align_up((size_t)V * 12), "soar_mesh_smooth_bytes")) return 1;
     float *other = static_cast<float *>(workspace);
     const dim3 gv((V + 255) / 256), blk(256);
     if (steps == 0) {
-        hipLaunchKernelGGL(copy_floats_kernel, dim3(((size_t)V * 3 + 255) / 256), blk, 0, stream, (size_t)V * 3, verts, verts_out);
+        hipLaunchKernelGGL(copy_floats_kernel<>, dim3(((size_t)V * 3 + 255) / 256), blk, 0, stream, (size_t)V * 3, verts, verts_out);
         SOAR_LAUNCH_OK("mesh_smooth_copy", stream, 0);
         return 0;
     }
@@ -379,7 +321,7 @@ extern "C" int soar_mesh_prune_bytes(int32_t V, int32_t F, size_t *bytes)
 {
     if (!bytes) { set_error("soar_mesh_prune_bytes: NULL result pointer"); return 1; }
     if (!sizes_ok("soar_mesh_prune_bytes", V, F)) return 1;
-    PruneBuf b;
+    CompactBuf b;
     *bytes = carve_prune(b, nullptr, (size_t)V, (size_t)F);
     return 0;
 }
@@ -395,27 +337,10 @@ extern "C" int soar_mesh_prune(int32_t V, int32_t F, const float *verts, const i
         return 1;
     }
     if (thresh != thresh) { set_error("soar_mesh_prune: the threshold is not a number"); return 1; }
-    PruneBuf b;
-    if (!workspace_ok("soar_mesh_prune", workspace, workspace_bytes, carve_prune(b, nullptr, (size_t)V, (size_t)F))) return 1;
-    carve_prune(b, workspace, (size_t)V, (size_t)F);
-    const dim3 gm(((V > F ? V : F) + 255) / 256), blk(256);
+    CompactBuf b;
+    if (!workspace_ok("soar_mesh_prune", workspace, workspace_bytes, carve_prune(b, workspace, (size_t)V, (size_t)F), "soar_mesh_prune_bytes")) return 1;
     SOAR_HIP_OK(hipMemsetAsync(b.totals, 0, 12, stream));
-    hipLaunchKernelGGL(prune_flags_kernel, gm, blk, 0, stream, V, F, faces, quality, thresh, b);
+    hipLaunchKernelGGL(prune_flags_kernel, dim3(((V > F ? V : F) + 255) / 256), dim3(256), 0, stream, V, F, faces, quality, thresh, b);
     SOAR_LAUNCH_OK("mesh_prune_flags", stream, 0);
-    size_t bytes = b.scan_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.vkeep, b.voff, (uint32_t)0, (size_t)V, rocprim::plus<uint32_t>(), stream));
-    if (F > 0) {
-        bytes = b.scan_bytes;
-        SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.fkeep, b.foff, (uint32_t)0, (size_t)F, rocprim::plus<uint32_t>(), stream));
-    }
-    hipLaunchKernelGGL(prune_totals_kernel, dim3(1), dim3(1), 0, stream, V, F, b);
-    hipLaunchKernelGGL(prune_write_kernel, gm, blk, 0, stream, V, F, verts, faces, b, verts_out, faces_out, keep_out);
-    SOAR_LAUNCH_OK("mesh_prune_write", stream, 0);
-    uint32_t tot[3] = {0, 0, 0};
-    SOAR_HIP_OK(hipMemcpyAsync(tot, b.totals, 12, hipMemcpyDeviceToHost, stream));
-    SOAR_HIP_OK(hipStreamSynchronize(stream));
-    if (tot[2]) { set_error("soar_mesh_prune: %u faces name a vertex outside [0, %d)", tot[2], V); return 1; }
-    counts_host[0] = tot[0];
-    counts_host[1] = tot[1];
-    return 0;
+    return compact_mesh("soar_mesh_prune", V, F, verts, faces, b, verts_out, faces_out, keep_out, counts_host, stream);
 }

@@ -28,10 +28,7 @@
 //
 // No float atomics, no host loop over holes or steps, no allocation; one stream synchronisation, for the totals.  Built with
 // -ffp-contract=off like its siblings (the centroid is adds and one divide; nothing here could contract).
-#include "soar_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "mesh_common.h"
 
 namespace soar {
 
@@ -59,22 +56,16 @@ struct HolesBuf {
 size_t carve_holes(HolesBuf &b, void *base, size_t V, size_t F)
 {
     const size_t N = 3 * (F > 0 ? F : 1);
-    b.sort_bytes = b.scan_bytes = 0;
-    (void)rocprim::radix_sort_pairs((void *)nullptr, b.sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, N, 0u, 64u, (hipStream_t)0);
-    (void)rocprim::exclusive_scan((void *)nullptr, b.scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)0, N,
-                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    auto words = [&](size_t n) { return reinterpret_cast<uint32_t *>(take(n * 4)); };
-    b.keys = reinterpret_cast<uint64_t *>(take(N * 8));
-    b.keys_sorted = reinterpret_cast<uint64_t *>(take(N * 8));
+    Carver c(base);
+    auto words = [&](size_t n) { return c.take<uint32_t>(n); };
+    b.keys = c.take<uint64_t>(N);
+    b.keys_sorted = c.take<uint64_t>(N);
     b.ids = words(N);
     b.ids_sorted = words(N);
     b.n_out = words(2 * V);             // n_out and n_in side by side: one memset clears both
-    b.n_in = b.n_out + V;
+    b.n_in = b.n_out ? b.n_out + V : nullptr;
     b.arrive = words(V);
-    b.border = reinterpret_cast<uint8_t *>(take(N));
+    b.border = c.take<uint8_t>(N);
     b.leader = reinterpret_cast<int32_t *>(words(N));
     b.rank = reinterpret_cast<int32_t *>(words(N));
     b.loop_n = words(N);
@@ -85,19 +76,15 @@ size_t carve_holes(HolesBuf &b, void *base, size_t V, size_t F)
     b.off_v = words(N);
     b.off_l = words(N);
     b.totals = words(8);
-    b.sort_temp = take(b.sort_bytes);
-    b.scan_temp = take(b.scan_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    b.sort_bytes = sort_pairs_temp_bytes<uint64_t, uint32_t>(N, 64u);
+    b.scan_bytes = scan_temp_bytes<uint32_t>(N);
+    b.sort_temp = c.take<char>(b.sort_bytes);
+    b.scan_temp = c.take<char>(b.scan_bytes);
+    return c.bytes();
 }
 
 __device__ __forceinline__ int he_from(const int32_t *__restrict__ faces, uint32_t h) { return faces[h]; }
 __device__ __forceinline__ int he_to(const int32_t *__restrict__ faces, uint32_t h) { return faces[h % 3u == 2u ? h - 2u : h + 1u]; }
-
-__global__ void __launch_bounds__(256) holes_copy_kernel(size_t n, const float *__restrict__ src, float *__restrict__ dst)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
 
 __global__ void __launch_bounds__(256) holes_keys_kernel(int V, int F, const int32_t *__restrict__ faces, HolesBuf b,
                                                          int32_t *__restrict__ faces_out)
@@ -248,15 +235,11 @@ extern "C" int soar_mesh_close_holes(int32_t V, int32_t F, const float *verts, c
     }
     if (verts == verts_out || (F > 0 && faces == faces_out)) { set_error("soar_mesh_close_holes: the outputs must not be the inputs"); return 1; }
     HolesBuf b;
-    const size_t need = carve_holes(b, nullptr, (size_t)V, (size_t)F);
-    if (!workspace || ((uintptr_t)workspace & 255)) { set_error("soar_mesh_close_holes: NULL workspace or workspace not 256-byte aligned"); return 1; }
-    if (workspace_bytes < need) {
-        set_error("soar_mesh_close_holes: workspace of %zu bytes, need %zu (ask soar_mesh_close_holes_bytes)", workspace_bytes, need);
+    if (!workspace_ok("soar_mesh_close_holes", workspace, workspace_bytes, carve_holes(b, workspace, (size_t)V, (size_t)F),
+                      "soar_mesh_close_holes_bytes"))
         return 1;
-    }
-    carve_holes(b, workspace, (size_t)V, (size_t)F);
     const dim3 blk(256);
-    hipLaunchKernelGGL(holes_copy_kernel, dim3((unsigned)(((size_t)V * 3 + 255) / 256)), blk, 0, stream, (size_t)V * 3, verts, verts_out);
+    hipLaunchKernelGGL(copy_floats_kernel<>, dim3((unsigned)(((size_t)V * 3 + 255) / 256)), blk, 0, stream, (size_t)V * 3, verts, verts_out);
     SOAR_LAUNCH_OK("mesh_close_holes_copy", stream, 0);
     if (F == 0) {
         counts_host[0] = V;
@@ -269,16 +252,12 @@ extern "C" int soar_mesh_close_holes(int32_t V, int32_t F, const float *verts, c
     SOAR_HIP_OK(hipMemsetAsync(b.n_out, 0, (size_t)V * 8, stream));
     hipLaunchKernelGGL(holes_keys_kernel, dim3((F + 255) / 256), blk, 0, stream, V, F, faces, b, faces_out);
     SOAR_LAUNCH_OK("mesh_close_holes_keys", stream, 0);
-    size_t bytes = b.sort_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_pairs(b.sort_temp, bytes, b.keys, b.keys_sorted, b.ids, b.ids_sorted, (size_t)n3, 0u, 64u, stream));
+    SOAR_HIP_OK(sort_pairs(b.sort_temp, b.sort_bytes, b.keys, b.keys_sorted, b.ids, b.ids_sorted, (size_t)n3, 64u, stream));
     hipLaunchKernelGGL(holes_border_kernel, gh, blk, 0, stream, n3, faces, b);
     hipLaunchKernelGGL(holes_walk_kernel, gh, blk, 0, stream, n3, faces, (int)max_hole_edges, b);
     SOAR_LAUNCH_OK("mesh_close_holes_walk", stream, 0);
     uint32_t *const cnt[3] = {b.cnt_f, b.cnt_v, b.cnt_l}, *const off[3] = {b.off_f, b.off_v, b.off_l};
-    for (int k = 0; k < 3; k++) {
-        bytes = b.scan_bytes;
-        SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, cnt[k], off[k], (uint32_t)0, (size_t)n3, rocprim::plus<uint32_t>(), stream));
-    }
+    for (int k = 0; k < 3; k++) SOAR_HIP_OK(exclusive_scan_sum(b.scan_temp, b.scan_bytes, cnt[k], off[k], (size_t)n3, stream));
     hipLaunchKernelGGL(holes_totals_kernel, dim3(1), dim3(1), 0, stream, n3, b);
     hipLaunchKernelGGL(holes_fill_kernel, gh, blk, 0, stream, V, F, n3, verts, faces, b, verts_out, faces_out, loop_edges_out);
     SOAR_LAUNCH_OK("mesh_close_holes_fill", stream, 0);

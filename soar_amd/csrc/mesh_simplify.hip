@@ -22,13 +22,10 @@
 // Host read-backs (the export path, like soar_mc_count): the bounding box, which sizes the grid, and the totals.
 // Built with -ffp-contract=off: cell indices and float64 sums follow an IEEE evaluation of the expressions as written, which
 // tests/mesh_simplify_ref.py restates.
-#include "soar_common.h"
+#include "mesh_common.h"
 
 #include <climits>
 #include <cmath>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace soar {
 
@@ -65,36 +62,23 @@ struct SimpBuf {
 
 inline size_t simp_temp_bytes(size_t V, size_t F, hipStream_t stream)
 {
-    size_t best = 0, bytes = 0;
     const size_t nv = V > 0 ? V : 1, nf = F > 0 ? F : 1;
-    auto up = [&]() { if (bytes > best) best = bytes; bytes = 0; };
-    (void)rocprim::exclusive_scan((void *)nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)0, nv > nf ? nv : nf,
-                                  rocprim::plus<uint32_t>(), stream);
-    up();
     // the widest bit range.  In this rocPRIM the temporary size grows with the number of digit places; should another one need
     // more for a narrower range, its call is handed the size carved here, checks it and returns an error (never an overrun)
-    (void)rocprim::radix_sort_pairs((void *)nullptr, bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, nv, 0u, 64u, stream);
-    up();
-    (void)rocprim::radix_sort_pairs((void *)nullptr, bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, nf, 0u, 64u, stream);
-    up();
-    (void)rocprim::radix_sort_pairs((void *)nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, nf, 0u, 32u, stream);
-    up();
-    (void)rocprim::radix_sort_pairs((void *)nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, 3 * nf, 0u, 32u, stream);
-    up();
+    const size_t sizes[5] = {scan_temp_bytes<uint32_t>(nv > nf ? nv : nf, stream), sort_pairs_temp_bytes<uint64_t, uint32_t>(nv, 64u, stream),
+                             sort_pairs_temp_bytes<uint64_t, uint32_t>(nf, 64u, stream), sort_pairs_temp_bytes<uint32_t, uint32_t>(nf, 32u, stream),
+                             sort_pairs_temp_bytes<uint32_t, uint32_t>(3 * nf, 32u, stream)};
+    size_t best = 0;
+    for (const size_t n : sizes) best = n > best ? n : best;
     return best;
 }
 
 inline size_t carve_simp(SimpBuf &b, void *base, size_t V, size_t F, hipStream_t stream)
 {
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    auto u32 = [&](size_t n) { return reinterpret_cast<uint32_t *>(take(n * 4)); };
-    auto u64 = [&](size_t n) { return reinterpret_cast<uint64_t *>(take(n * 8)); };
-    b.box = reinterpret_cast<int32_t *>(take(24));
+    Carver c(base);
+    auto u32 = [&](size_t n) { return c.take<uint32_t>(n); };
+    auto u64 = [&](size_t n) { return c.take<uint64_t>(n); };
+    b.box = c.take<int32_t>(6);
     b.totals = u32(4);
     b.vkey = u64(V); b.vkey_s = u64(V);
     b.vidx = u32(V); b.vidx_s = u32(V);
@@ -109,24 +93,8 @@ inline size_t carve_simp(SimpBuf &b, void *base, size_t V, size_t F, hipStream_t
     b.pk = u32(3 * F); b.pk_s = u32(3 * F); b.pv = u32(3 * F); b.pv_s = u32(3 * F);
     b.pbeg = u32(V); b.pend = u32(V);
     b.temp_bytes = simp_temp_bytes(V, F, stream);
-    b.temp = take(b.temp_bytes);
-    return (size_t)(p - static_cast<char *>(base));
-}
-
-// floats as ints whose signed order is the floats' order (a NaN lies beyond the infinity of its sign)
-__host__ __device__ __forceinline__ int simp_ford(float f)
-{
-    int i;
-    __builtin_memcpy(&i, &f, 4);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-
-__host__ __device__ __forceinline__ float simp_fdec(int i)
-{
-    i = i >= 0 ? i : i ^ 0x7fffffff;
-    float f;
-    __builtin_memcpy(&f, &i, 4);
-    return f;
+    b.temp = c.take<char>(b.temp_bytes);
+    return c.bytes();
 }
 
 __global__ void simp_init_kernel(SimpBuf b)
@@ -140,13 +108,9 @@ __global__ void __launch_bounds__(256) simp_bbox_kernel(int V, const float *__re
     const int v = blockIdx.x * 256 + threadIdx.x;
     int lo[3], hi[3];
     for (int k = 0; k < 3; k++) {
-        const int q = v < V ? simp_ford(verts[(size_t)v * 3 + k]) : 0;
-        lo[k] = v < V ? q : INT_MAX;
-        hi[k] = v < V ? q : INT_MIN;
-        for (int m = 32; m >= 1; m >>= 1) {
-            lo[k] = min(lo[k], __shfl_xor(lo[k], m));
-            hi[k] = max(hi[k], __shfl_xor(hi[k], m));
-        }
+        const int q = v < V ? ford(verts[(size_t)v * 3 + k]) : 0;
+        lo[k] = wave_min_i(v < V ? q : INT_MAX);
+        hi[k] = wave_max_i(v < V ? q : INT_MIN);
     }
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < 3; k++) {
@@ -195,14 +159,6 @@ __global__ void __launch_bounds__(256) simp_vassign_kernel(int V, SimpBuf b)
     }
 }
 
-__device__ __forceinline__ bool simp_face_ok(int V, const int32_t *__restrict__ faces, int f, int &a, int &c1, int &c2)
-{
-    a = faces[(size_t)f * 3];
-    c1 = faces[(size_t)f * 3 + 1];
-    c2 = faces[(size_t)f * 3 + 2];
-    return a >= 0 && a < V && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V;
-}
-
 // cb = the bits that hold 0 .. V; the id V marks a face that is dropped (two corners in one cluster, or a bad index)
 __global__ void __launch_bounds__(256) simp_fkey_kernel(int V, int F, const int32_t *__restrict__ faces, int cb, SimpBuf b)
 {
@@ -210,7 +166,7 @@ __global__ void __launch_bounds__(256) simp_fkey_kernel(int V, int F, const int3
     if (f >= F) return;
     int a, c1, c2;
     uint32_t lo = (uint32_t)V, mid = (uint32_t)V, hi = (uint32_t)V;
-    if (!simp_face_ok(V, faces, f, a, c1, c2)) {
+    if (!face_corners(V, faces, f, a, c1, c2)) {
         atomicAdd(b.totals + 3, 1u);
     } else {
         const uint32_t x = b.cid[a], y = b.cid[c1], z = b.cid[c2];
@@ -260,7 +216,7 @@ __global__ void __launch_bounds__(256) simp_pairs_kernel(int V, int F, const int
     if (f >= F) return;
     int a, c1, c2;
     uint32_t k[3] = {(uint32_t)V, (uint32_t)V, (uint32_t)V};
-    if (simp_face_ok(V, faces, f, a, c1, c2)) {
+    if (face_corners(V, faces, f, a, c1, c2)) {
         const uint32_t x = b.cid[a], y = b.cid[c1], z = b.cid[c2];
         if (b.used[x]) k[0] = x;
         if (y != x && b.used[y]) k[1] = y;
@@ -431,16 +387,9 @@ int simp_check(const char *what, int32_t V, int32_t F, const float *verts, const
     if (V < 1 || F < 0) { set_error("%s: need V >= 1 and F >= 0 (V=%d, F=%d)", what, V, F); return 1; }
     if (V > SIMP_MAX_COUNT || F > SIMP_MAX_COUNT) { set_error("%s: at most 2^30 vertices and 2^30 faces (V=%d, F=%d)", what, V, F); return 1; }
     if (!(cell > 0.f) || !std::isfinite(cell)) { set_error("%s: the cell size must be positive and finite (cell=%g)", what, (double)cell); return 1; }
-    if (!verts || (!faces && F > 0) || !workspace || !counts_host || ((uintptr_t)workspace & 255)) {
-        set_error("%s: NULL argument or workspace not 256-byte aligned", what);
-        return 1;
-    }
-    const size_t need = carve_simp(b, workspace, (size_t)V, (size_t)F, stream);      // the one place a call queries the sizes
-    if (workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, need %zu (soar_mesh_simplify_bytes)", what, workspace_bytes, need);
-        return 1;
-    }
-    return 0;
+    if (!verts || (!faces && F > 0) || !counts_host) { set_error("%s: NULL argument", what); return 1; }
+    // (the one place a call queries the sizes)
+    return workspace_ok(what, workspace, workspace_bytes, carve_simp(b, workspace, (size_t)V, (size_t)F, stream), "soar_mesh_simplify_bytes") ? 0 : 1;
 }
 
 int simp_run(const char *what, int32_t V, int32_t F, const float *verts, const int32_t *faces, float cell, const SimpBuf &b,
@@ -457,7 +406,7 @@ int simp_run(const char *what, int32_t V, int32_t F, const float *verts, const i
     g.cell = cell;
     uint64_t cells = 1;
     for (int k = 0; k < 3; k++) {
-        const float lo = simp_fdec(box[k]), hi = simp_fdec(box[3 + k]);
+        const float lo = fdec(box[k]), hi = fdec(box[3 + k]);
         if (!std::isfinite(lo) || !std::isfinite(hi)) { set_error("%s: a vertex coordinate is not finite", what); return 1; }
         const float q = (hi - lo) / cell;
         if (!(q < (float)SIMP_MAX_DIM)) {
@@ -473,28 +422,22 @@ int simp_run(const char *what, int32_t V, int32_t F, const float *verts, const i
     const int cb = bit_width64((uint64_t)V);
 
     hipLaunchKernelGGL(simp_vkey_kernel, gv, blk, 0, stream, V, verts, g, b);
-    size_t bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_pairs(b.temp, bytes, b.vkey, b.vkey_s, b.vidx, b.vidx_s, (size_t)V, 0u, vbits, stream));
+    SOAR_HIP_OK(sort_pairs(b.temp, b.temp_bytes, b.vkey, b.vkey_s, b.vidx, b.vidx_s, (size_t)V, vbits, stream));
     hipLaunchKernelGGL(simp_vhead_kernel, gv, blk, 0, stream, V, b);
-    bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.temp, bytes, b.vflag, b.vscan, (uint32_t)0, (size_t)V, rocprim::plus<uint32_t>(), stream));
+    SOAR_HIP_OK(exclusive_scan_sum(b.temp, b.temp_bytes, b.vflag, b.vscan, (size_t)V, stream));
     hipLaunchKernelGGL(simp_vassign_kernel, gv, blk, 0, stream, V, b);
     SOAR_LAUNCH_OK("mesh_simplify_clusters", stream, 0);
     counts_host[0] = counts_host[1] = 0;
     if (F == 0) return 0;
 
     hipLaunchKernelGGL(simp_fkey_kernel, gf, blk, 0, stream, V, F, faces, cb, b);
-    bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_pairs(b.temp, bytes, b.fk2, b.fk2_s, b.fidx, b.fidx_s, (size_t)F, 0u, (unsigned)(2 * cb), stream));
+    SOAR_HIP_OK(sort_pairs(b.temp, b.temp_bytes, b.fk2, b.fk2_s, b.fidx, b.fidx_s, (size_t)F, (unsigned)(2 * cb), stream));
     hipLaunchKernelGGL(simp_fgather_kernel, gf, blk, 0, stream, F, b);
-    bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_pairs(b.temp, bytes, b.fk1_g, b.fk1_s, b.fidx_s, b.fidx_s2, (size_t)F, 0u, (unsigned)cb, stream));
+    SOAR_HIP_OK(sort_pairs(b.temp, b.temp_bytes, b.fk1_g, b.fk1_s, b.fidx_s, b.fidx_s2, (size_t)F, (unsigned)cb, stream));
     hipLaunchKernelGGL(simp_fhead_kernel, gf, blk, 0, stream, V, F, cb, b);
     SOAR_LAUNCH_OK("mesh_simplify_faces", stream, 0);
-    bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.temp, bytes, b.used, b.voff, (uint32_t)0, (size_t)V, rocprim::plus<uint32_t>(), stream));
-    bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.temp, bytes, b.fkeep, b.foff, (uint32_t)0, (size_t)F, rocprim::plus<uint32_t>(), stream));
+    SOAR_HIP_OK(exclusive_scan_sum(b.temp, b.temp_bytes, b.used, b.voff, (size_t)V, stream));
+    SOAR_HIP_OK(exclusive_scan_sum(b.temp, b.temp_bytes, b.fkeep, b.foff, (size_t)F, stream));
     hipLaunchKernelGGL(simp_totals_kernel, dim3(1), dim3(1), 0, stream, V, F, b);
     SOAR_LAUNCH_OK("mesh_simplify_totals", stream, 0);
     uint32_t tot[4] = {0, 0, 0, 0};
@@ -507,8 +450,7 @@ int simp_run(const char *what, int32_t V, int32_t F, const float *verts, const i
 
     const size_t N = (size_t)F * 3;
     hipLaunchKernelGGL(simp_pairs_kernel, gf, blk, 0, stream, V, F, faces, b);
-    bytes = b.temp_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_pairs(b.temp, bytes, b.pk, b.pk_s, b.pv, b.pv_s, N, 0u, (unsigned)cb, stream));
+    SOAR_HIP_OK(sort_pairs(b.temp, b.temp_bytes, b.pk, b.pk_s, b.pv, b.pv_s, N, (unsigned)cb, stream));
     hipLaunchKernelGGL(simp_pruns_kernel, dim3((unsigned)((N + 255) / 256)), blk, 0, stream, V, N, b);
     hipLaunchKernelGGL(simp_place_kernel, dim3((tot[0] + 3u) / 4u), blk, 0, stream, verts, faces, g, b, verts_out);
     hipLaunchKernelGGL(simp_faces_kernel, gf, blk, 0, stream, F, faces, b, faces_out);

@@ -20,10 +20,7 @@
 //   texture_write_kernel   bytes = floor(255 c + 0.5) at the chunk's addresses, zero for a flagged texel.
 //
 // Integer arithmetic decides every position; no float atomics: two runs give the same bytes.
-#include "soar_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "mesh_common.h"
 
 namespace soar {
 
@@ -57,21 +54,18 @@ struct AtlasBuf {
 size_t carve_atlas(AtlasBuf &b, void *base, size_t F)
 {
     const size_t N = F > 0 ? F : 1;
-    b.sort_bytes = 0;
-    (void)rocprim::radix_sort_pairs((void *)nullptr, b.sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, N, 0u, 4u, (hipStream_t)0);
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.level = reinterpret_cast<int32_t *>(take(N * 4));
-    b.keys = reinterpret_cast<uint32_t *>(take(N * 4));
-    b.keys_sorted = reinterpret_cast<uint32_t *>(take(N * 4));
-    b.vals = reinterpret_cast<uint32_t *>(take(N * 4));
-    b.vals_sorted = reinterpret_cast<uint32_t *>(take(N * 4));
-    b.hist = reinterpret_cast<uint32_t *>(take(TEX_HIST * 4));
-    b.classes = reinterpret_cast<AtlasClasses *>(take(sizeof(AtlasClasses)));
-    b.bad = reinterpret_cast<uint32_t *>(take(4));
-    b.sort_temp = take(b.sort_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    Carver c(base);
+    b.level = c.take<int32_t>(N);
+    b.keys = c.take<uint32_t>(N);
+    b.keys_sorted = c.take<uint32_t>(N);
+    b.vals = c.take<uint32_t>(N);
+    b.vals_sorted = c.take<uint32_t>(N);
+    b.hist = c.take<uint32_t>(TEX_HIST);
+    b.classes = c.take<AtlasClasses>(1);
+    b.bad = c.take<uint32_t>(1);
+    b.sort_bytes = sort_pairs_temp_bytes<uint32_t, uint32_t>(N, 4u);
+    b.sort_temp = c.take<char>(b.sort_bytes);
+    return c.bytes();
 }
 
 __global__ void __launch_bounds__(256) atlas_levels_kernel(int V, int F, const float *__restrict__ verts, const int32_t *__restrict__ faces,
@@ -209,16 +203,13 @@ struct TexelBuf {
 
 size_t carve_texels(TexelBuf &b, void *base, size_t F)
 {
-    b.scan_bytes = 0;
-    (void)rocprim::exclusive_scan((void *)nullptr, b.scan_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, F + 1,
-                                  rocprim::plus<uint64_t>(), (hipStream_t)0);
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.counts = reinterpret_cast<uint64_t *>(take((F + 1) * 8));
-    b.offsets = reinterpret_cast<uint64_t *>(take((F + 1) * 8));
-    b.bad = reinterpret_cast<uint32_t *>(take(8));
-    b.scan_temp = take(b.scan_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    Carver c(base);
+    b.counts = c.take<uint64_t>(F + 1);
+    b.offsets = c.take<uint64_t>(F + 1);
+    b.bad = c.take<uint32_t>(2);
+    b.scan_bytes = scan_temp_bytes<uint64_t>(F + 1);
+    b.scan_temp = c.take<char>(b.scan_bytes);
+    return c.bytes();
 }
 
 __device__ __forceinline__ bool cell_ok(int x0, int y0, int s, int half, int T)
@@ -326,13 +317,6 @@ bool size_ok(const char *what, int32_t T)
     return true;
 }
 
-bool ws_ok(const char *what, const void *workspace, size_t have, size_t need)
-{
-    if (!workspace || ((uintptr_t)workspace & 255)) { set_error("%s: NULL workspace or workspace not 256-byte aligned", what); return false; }
-    if (have < need) { set_error("%s: workspace of %zu bytes, need %zu (ask the call's _bytes query)", what, have, need); return false; }
-    return true;
-}
-
 }  // namespace
 
 }  // namespace soar
@@ -358,8 +342,7 @@ extern "C" int soar_mesh_atlas_levels(int32_t V, int32_t F, const float *verts, 
     if (n_ladder < 1 || n_ladder > TEX_MAX_LADDER) { set_error("soar_mesh_atlas_levels: need 1 <= n_ladder <= %d (n_ladder=%d)", TEX_MAX_LADDER, n_ladder); return 1; }
     if (!verts || !faces || !ladder || !hist_host) { set_error("soar_mesh_atlas_levels: NULL argument"); return 1; }
     AtlasBuf b;
-    if (!ws_ok("soar_mesh_atlas_levels", workspace, workspace_bytes, carve_atlas(b, nullptr, (size_t)F))) return 1;
-    carve_atlas(b, workspace, (size_t)F);
+    if (!workspace_ok("soar_mesh_atlas_levels", workspace, workspace_bytes, carve_atlas(b, workspace, (size_t)F), "soar_mesh_atlas_bytes")) return 1;
     SOAR_HIP_OK(hipMemsetAsync(b.hist, 0, TEX_HIST * 4, stream));
     SOAR_HIP_OK(hipMemsetAsync(b.bad, 0, 4, stream));
     hipLaunchKernelGGL(atlas_levels_kernel, dim3((F + 255) / 256), dim3(256), 0, stream, V, F, verts, faces, ladder, n_ladder, b.level, b.hist, b.bad);
@@ -387,8 +370,7 @@ extern "C" int soar_mesh_atlas_place(int32_t F, int32_t texture_size, int32_t n_
     }
     if (!uv_out || !uv_faces_out || !cell_out) { set_error("soar_mesh_atlas_place: NULL argument"); return 1; }
     AtlasBuf b;
-    if (!ws_ok("soar_mesh_atlas_place", workspace, workspace_bytes, carve_atlas(b, nullptr, (size_t)F))) return 1;
-    carve_atlas(b, workspace, (size_t)F);
+    if (!workspace_ok("soar_mesh_atlas_place", workspace, workspace_bytes, carve_atlas(b, workspace, (size_t)F), "soar_mesh_atlas_bytes")) return 1;
     const dim3 gf((F + 255) / 256), blk(256);
     hipLaunchKernelGGL(atlas_classes_kernel, dim3(1), dim3(64), 0, stream, n_ladder, scale_step, texture_size, b.hist, b.classes);
     SOAR_LAUNCH_OK("mesh_atlas_classes", stream, 0);
@@ -406,8 +388,7 @@ extern "C" int soar_mesh_atlas_place(int32_t F, int32_t texture_size, int32_t n_
     }
     hipLaunchKernelGGL(atlas_keys_kernel, gf, blk, 0, stream, F, scale_step, texture_size, b.level, b.keys, b.vals);
     SOAR_LAUNCH_OK("mesh_atlas_keys", stream, 0);
-    size_t bytes = b.sort_bytes;
-    SOAR_HIP_OK(rocprim::radix_sort_pairs(b.sort_temp, bytes, b.keys, b.keys_sorted, b.vals, b.vals_sorted, (size_t)F, 0u, 4u, stream));
+    SOAR_HIP_OK(sort_pairs(b.sort_temp, b.sort_bytes, b.keys, b.keys_sorted, b.vals, b.vals_sorted, (size_t)F, 4u, stream));
     hipLaunchKernelGGL(atlas_place_kernel, gf, blk, 0, stream, F, texture_size, b.keys_sorted, b.vals_sorted, b.classes, uv_out, uv_faces_out, cell_out);
     SOAR_LAUNCH_OK("mesh_atlas_place", stream, 0);
     return 0;
@@ -432,13 +413,11 @@ extern "C" int soar_mesh_texel_offsets(int32_t V, int32_t F, int32_t texture_siz
     if (!size_ok("soar_mesh_texel_offsets", texture_size)) return 1;
     if (!faces || !cell || !total_host) { set_error("soar_mesh_texel_offsets: NULL argument"); return 1; }
     TexelBuf b;
-    if (!ws_ok("soar_mesh_texel_offsets", workspace, workspace_bytes, carve_texels(b, nullptr, (size_t)F))) return 1;
-    carve_texels(b, workspace, (size_t)F);
+    if (!workspace_ok("soar_mesh_texel_offsets", workspace, workspace_bytes, carve_texels(b, workspace, (size_t)F), "soar_mesh_texels_bytes")) return 1;
     SOAR_HIP_OK(hipMemsetAsync(b.bad, 0, 8, stream));
     hipLaunchKernelGGL(texel_counts_kernel, dim3((F + 1 + 255) / 256), dim3(256), 0, stream, V, F, texture_size, faces, cell, b.counts, b.bad);
     SOAR_LAUNCH_OK("mesh_texel_counts", stream, 0);
-    size_t bytes = b.scan_bytes;
-    SOAR_HIP_OK(rocprim::exclusive_scan(b.scan_temp, bytes, b.counts, b.offsets, (uint64_t)0, (size_t)F + 1, rocprim::plus<uint64_t>(), stream));
+    SOAR_HIP_OK(exclusive_scan_sum(b.scan_temp, b.scan_bytes, b.counts, b.offsets, (size_t)F + 1, stream));
     uint32_t bad[2] = {0, 0};
     uint64_t total = 0;
     SOAR_HIP_OK(hipMemcpyAsync(bad, b.bad, 8, hipMemcpyDeviceToHost, stream));
@@ -468,8 +447,8 @@ extern "C" int soar_mesh_texels(int32_t V, int32_t F, int32_t texture_size, cons
     }
     if (!verts || !faces || !cell || !pos_out || !addr_out) { set_error("soar_mesh_texels: NULL argument"); return 1; }
     TexelBuf b;
-    if (!ws_ok("soar_mesh_texels", workspace, workspace_bytes, carve_texels(b, nullptr, (size_t)F))) return 1;
-    carve_texels(b, const_cast<void *>(workspace), (size_t)F);
+    if (!workspace_ok("soar_mesh_texels", workspace, workspace_bytes, carve_texels(b, const_cast<void *>(workspace), (size_t)F), "soar_mesh_texels_bytes"))
+        return 1;
     hipLaunchKernelGGL(texels_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, V, F, texture_size, verts, faces, cell, b.offsets,
                        (uint64_t)first, count, pos_out, addr_out, owner_img, bary_img, position_img);
     SOAR_LAUNCH_OK("mesh_texels", stream, 0);

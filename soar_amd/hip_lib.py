@@ -521,6 +521,13 @@ def check(rc: int, what: str) -> None:
         raise SoarHipError(f"{what} failed: {last_error()}")
 
 
+def _bytes(fn, name: str, *sizes) -> int:
+    """What the sizing call ``fn`` (named ``name`` in the error) answers for ``sizes``."""
+    nb = C.c_size_t(0)
+    check(fn(*sizes, C.byref(nb)), name)
+    return nb.value
+
+
 def ptr(t) -> Optional[int]:
     """Device/host pointer of a torch tensor (None for an empty / missing tensor, like the reference's nullptr)."""
     if t is None or t.numel() == 0:

@@ -40,7 +40,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, check
 
 TSDF_MAX_VIEWS = 64          # views per soar_tsdf_integrate call
 ZNEAR = 0.2                  # znear of the export cameras: voxels nearer than this to a camera are not observed by it
@@ -127,18 +127,17 @@ def marching_cubes(values: torch.Tensor, level: float = 0.0, valid: Optional[tor
             raise ValueError("valid must have the shape of values")
         m = valid.to(dev, torch.bool).contiguous()
     L = hip_lib.lib()
-    nb = C.c_size_t(0)
-    check(L.soar_mc_workspace_bytes(X, Y, Z, C.byref(nb)), "soar_mc_workspace_bytes")
-    ws = _workspace(nb.value, dev)
+    nb = _bytes(L.soar_mc_workspace_bytes, "soar_mc_workspace_bytes", X, Y, Z)
+    ws = _workspace(nb, dev)
     counts = (C.c_int64 * 2)()
     mp = None if m is None else m.data_ptr()
     with torch.cuda.device(dev):
         st = _stream(dev)
-        check(L.soar_mc_count(X, Y, Z, v.data_ptr(), mp, float(level), ws.data_ptr(), nb.value, counts, st), "soar_mc_count")
+        check(L.soar_mc_count(X, Y, Z, v.data_ptr(), mp, float(level), ws.data_ptr(), nb, counts, st), "soar_mc_count")
         verts = torch.empty(int(counts[0]), 3, device=dev)
         faces = torch.empty(int(counts[1]), 3, dtype=torch.int32, device=dev)
         if counts[0] > 0:
-            check(L.soar_mc_emit(X, Y, Z, v.data_ptr(), mp, float(level), ws.data_ptr(), nb.value, verts.data_ptr(),
+            check(L.soar_mc_emit(X, Y, Z, v.data_ptr(), mp, float(level), ws.data_ptr(), nb, verts.data_ptr(),
                                  faces.data_ptr() if counts[1] > 0 else verts.data_ptr(), st), "soar_mc_emit")
     return verts, faces
 
@@ -155,15 +154,14 @@ def filter_components(verts: torch.Tensor, faces: torch.Tensor, min_faces: int =
     vv = verts.to(torch.float32).contiguous()
     ff = faces.to(dev, torch.int32).contiguous()
     L = hip_lib.lib()
-    nb = C.c_size_t(0)
-    check(L.soar_mesh_filter_bytes(V, F, C.byref(nb)), "soar_mesh_filter_bytes")
-    ws = _workspace(nb.value, dev)
+    nb = _bytes(L.soar_mesh_filter_bytes, "soar_mesh_filter_bytes", V, F)
+    ws = _workspace(nb, dev)
     vo = torch.empty(V, 3, device=dev)
     fo = torch.empty(F, 3, dtype=torch.int32, device=dev)
     counts = (C.c_int64 * 2)()
     with torch.cuda.device(dev):
         check(L.soar_mesh_filter_components(V, F, vv.data_ptr(), ff.data_ptr(), int(min_faces), float(min_diag_frac), ws.data_ptr(),
-                                            nb.value, vo.data_ptr(), fo.data_ptr(), counts, _stream(dev)),
+                                            nb, vo.data_ptr(), fo.data_ptr(), counts, _stream(dev)),
               "soar_mesh_filter_components")
     return vo[:int(counts[0])].clone(), fo[:int(counts[1])].clone()
 
@@ -196,9 +194,7 @@ class _Simplifier:
         self.verts, self.faces = verts, faces
         self.V, self.F = int(verts.shape[0]), int(faces.shape[0])
         self.lib = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(self.lib.soar_mesh_simplify_bytes(self.V, self.F, C.byref(nb)), "soar_mesh_simplify_bytes")
-        self.nb = nb.value
+        self.nb = _bytes(self.lib.soar_mesh_simplify_bytes, "soar_mesh_simplify_bytes", self.V, self.F)
         self.ws = _workspace(self.nb, verts.device)
         self.fptr = faces.data_ptr() if self.F > 0 else verts.data_ptr()
 
@@ -385,12 +381,6 @@ def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.T
 
 ATTR_K, ATTR_MAX_K = 4, 8    # the reference's knn_points(K=4) (utils/general_utils.py:270); the kernel's upper bound
 SMOOTH_STEPS = 3             # apply_coord_laplacian_smoothing(stepsmoothnum=3) (:301)
-
-
-def _bytes(fn, name: str, *sizes) -> int:
-    nb = C.c_size_t(0)
-    check(fn(*sizes, C.byref(nb)), name)
-    return nb.value
 
 
 @torch.no_grad()

@@ -177,6 +177,36 @@ def n_components(n_verts, faces):
     return len({find(int(u)) for u in used})
 
 
+def filter_components(verts, faces, min_faces, min_diag_frac):
+    """soar_mesh_filter_components restated: a component (labelled by its least vertex id, as n_components finds it) stays when
+    it has >= min_faces faces and its bounding-box diagonal is not below min_diag_frac times the diagonal over all vertices
+    that a face uses; kept vertices and faces keep their input order.  The diagonals are float64 here, float32 there."""
+    verts, faces = np.asarray(verts, np.float32), np.asarray(faces, np.int32).reshape(-1, 3)
+    parent = np.arange(len(verts))
+
+    def find(x):
+        while parent[x] != x:
+            x = parent[x]
+        return x
+
+    for a, b, c in faces.tolist():
+        for u, v in ((a, b), (b, c)):
+            ru, rv = find(u), find(v)
+            parent[max(ru, rv)] = min(ru, rv)
+    label = np.array([find(v) for v in range(len(verts))])
+    used = np.zeros(len(verts), bool)
+    used[faces.reshape(-1)] = True
+    diag = lambda p: float(np.linalg.norm(p.max(0).astype(np.float64) - p.min(0).astype(np.float64)))
+    whole = diag(verts[used])
+    keep_v = np.zeros(len(verts), bool)
+    for lab in np.unique(label[used]):
+        mine = used & (label == lab)
+        n_faces = int((label[faces[:, 0]] == lab).sum())
+        keep_v[mine] = n_faces >= min_faces and not diag(verts[mine]) < min_diag_frac * whole
+    new_id = np.cumsum(keep_v) - 1
+    return verts[keep_v], new_id[faces[keep_v[faces[:, 0]]]].astype(np.int32)
+
+
 def tsdf_reference(depth, opac, viewm, projm, prcp, origin, voxel, dims, trunc, znear=0.2, min_opac=0.5, acc=None, eps_px=1e-3):
     """float64 restatement of soar_tsdf_integrate (torch tensors on the CPU) -> (sum, weight, ambiguous) where `ambiguous`
     flags voxels whose projection lies within eps_px of a pixel-rounding boundary (or on another decision boundary) in a view."""

@@ -264,3 +264,47 @@ def test_component_filter_removes_small_clusters(person):
     # a component is kept only when it has >= 64 faces AND a diagonal >= 20 % of the whole mesh's
     fv2, ff2 = mesh.filter_components(big_v, all_f, min_faces=1, min_diag_frac=0.0)
     assert len(fv2) == len(big_v) and len(ff2) == len(all_f)
+
+
+# ---- 7. the component filter at small sizes -----------------------------------------------------------------------------
+
+def _small_filter_mesh(levels, strays, seed):
+    """an icosphere of radius 1, a far-away icosahedron of radius 0.005 and `strays` vertices that no face uses; the vertices
+    interleaved and the faces shuffled by a seeded permutation -> (verts, faces, which input vertices / faces are the sphere's)"""
+    import mesh_attr_ref as A
+    sv, sf = A.icosphere(levels)
+    iv, jf = A.icosahedron()
+    rng = np.random.default_rng(seed)
+    v = np.concatenate([sv, 0.005 * iv + 1.5, rng.uniform(-1.0, 1.0, (strays, 3))]).astype(np.float32)
+    f = np.concatenate([sf, jf + len(sv)])
+    where = rng.permutation(len(v))                     # vertex i goes to row where[i]
+    order = rng.permutation(len(f))
+    verts = np.empty_like(v)
+    verts[where] = v
+    faces = where[f][order].astype(np.int32)
+    sphere_v = np.zeros(len(v), bool)
+    sphere_v[where[:len(sv)]] = True
+    return verts, faces, sphere_v, order < len(sf)
+
+
+# (levels, strays): V = 324 < F = 340 and V = 354 > F = 100; the write kernel runs one grid over max(V, F), two blocks either way
+@pytest.mark.parametrize("levels,strays,V,F", [(2, 150, 324, 340), (1, 300, 354, 100)])
+def test_component_filter_at_small_sizes(levels, strays, V, F):
+    from soar_amd import hip_lib, mesh
+    dev = _dev()
+    verts, faces, sphere_v, sphere_f = _small_filter_mesh(levels, strays, 40 + levels)
+    assert verts.shape == (V, 3) and faces.shape == (F, 3)
+    used = np.zeros(V, bool)
+    used[faces.reshape(-1)] = True
+    # the icosahedron's diagonal is a factor 59 below the threshold of 20 % and the sphere's a factor 4 above it: float32 or
+    # float64 diagonals decide alike
+    for kw, keep_v, keep_f in ((dict(), sphere_v, sphere_f), (dict(min_faces=1, min_diag_frac=0.0), used, np.ones(F, bool))):
+        want_v, want_f = R.filter_components(verts, faces, kw.get("min_faces", mesh.MIN_FACES), kw.get("min_diag_frac", mesh.MIN_DIAG_FRAC))
+        assert np.array_equal(want_v, verts[keep_v]) and len(want_f) == int(keep_f.sum())     # the restatement keeps what it should
+        got_v, got_f = mesh.filter_components(torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev), **kw)
+        assert got_v.dtype == torch.float32 and got_f.dtype == torch.int32
+        assert np.array_equal(_np(got_v), want_v) and np.array_equal(_np(got_f), want_f)
+    bad = faces.copy()
+    bad[F // 2, 1] = V
+    with pytest.raises(hip_lib.SoarHipError, match="outside"):
+        mesh.filter_components(torch.from_numpy(verts).to(dev), torch.from_numpy(bad).to(dev))
