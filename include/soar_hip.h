@@ -1719,6 +1719,49 @@ int soar_fitviz_strip(const SoarFitvizStripArgs *args, void *stream);
 int soar_fitviz_residuals(int32_t N, int32_t K, const float *fit_px, const float *target_px, const float *conf, const uint8_t *kp_mask,
                           float thresh, float *out, void *stream);
 
+/* ---- MJPEG video output: a baseline JPEG encoder (video.hip, soar_amd/video.py) ----
+ * B frames of uint8 pixels -> B complete JPEG files (SOI .. EOI), one after the other in one device buffer, with their byte offsets.
+ * Baseline sequential, 8 bit, components 1, 2, 3 = Y, Cb, Cr, the four Annex K Huffman tables, restart markers.  Current stream, no
+ * synchronisation, no allocation; integer arithmetic only: two calls give the same bytes, and a frame's bytes depend neither on B nor
+ * on its place.  frames, workspace, offsets and out are device memory; args is host memory.
+ *
+ * frames: [B][H][W][channels] uint8, channels 3 (R, G, B) or 4 (the fourth is ignored); every frame contiguous, frame_stride bytes
+ *   from frame to frame (>= H W channels).  1 <= H, W <= 65535, 0 <= B <= 65535.
+ * qtables: [0] for Y, [1] for Cb and Cr; natural (row-major) order, entries 1 .. 255.
+ * subsampling: 444, or 420 (2 x 2 luma blocks per MCU).  restart_interval: MCUs, 1 .. 65535.
+ *
+ * Colour: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ * Padding at 444: the last column and row replicated up to a multiple of 8.  At 420: chroma columns replicated to a multiple of 16,
+ *   the last row to an even height, then (a + b + c + d + bias) >> 2 with bias 1 in even and 2 in odd output columns, then the last
+ *   DOWNSAMPLED row replicated down to the MCU grid.  Luma is replicated inside the ceil(W / 8) x ceil(H / 8) real blocks only; a luma
+ *   block of an MCU beyond them is a dummy: its AC coefficients are 0 and its DC is that of the block coded before it in the MCU.
+ * Forward DCT: libjpeg's jfdctint on samples - 128 (13-bit constants, PASS1_BITS = 2, rows first, DESCALE(x, n) =
+ *   (x + (1 << (n - 1))) >> n, outputs scaled by 8).  Quantisation: q = 8 Q, (|c| + (q >> 1)) / q truncated, the sign restored.
+ * Entropy coding: zigzag order, DC differences per component, (run, size) symbols with ZRL and EOB, a negative value v of size n coded
+ *   as v + 2^n - 1, 0xFF followed by 0x00.  In front of MCU k restart_interval (k >= 1) the bit stream is padded with 1-bits to a
+ *   byte, FF D0+((k - 1) & 7) is written and the three DC predictors are reset; the last interval is padded the same way before EOI.
+ * Header (the same for every frame of a call, 629 bytes): SOI, APP0 (JFIF 1.01, no units, 1:1), DQT 0, DQT 1, SOF0 (sampling 1x1, or
+ *   2x2 1x1 1x1; Tq 0 1 1), DHT DC0 AC0 DC1 AC1, DRI, SOS (Ss 0, Se 63, Ah/Al 0).
+ *
+ * soar_jpeg_workspace_bytes: what both calls need for these B, H, W, subsampling and restart_interval.
+ * soar_jpeg_measure: transform, entropy coding as a count, scan.  offsets [B + 1] int64: frame b will occupy bytes
+ *   offsets[b] .. offsets[b + 1] of the output; offsets[B] is its length.  Leaves the coefficients and the offsets in the workspace.
+ * soar_jpeg_emit: the same args and the workspace soar_jpeg_measure left -> out.  If offsets[B] > capacity NOTHING is written (the
+ *   caller reads the need from offsets); nothing is ever written at or behind out + capacity.
+ * Both refuse bad arguments before any launch. */
+typedef struct SoarJpegArgs {
+    int32_t B, H, W, channels;
+    int32_t subsampling;              /* 444 or 420 */
+    int32_t restart_interval;         /* MCUs */
+    const uint8_t *frames;
+    int64_t frame_stride;             /* bytes */
+    uint8_t qtables[2][64];
+} SoarJpegArgs;
+int soar_jpeg_workspace_bytes(const SoarJpegArgs *args, size_t *bytes);
+int soar_jpeg_measure(const SoarJpegArgs *args, void *workspace, size_t workspace_bytes, int64_t *offsets, void *stream);
+int soar_jpeg_emit(const SoarJpegArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int64_t capacity, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

@@ -13,7 +13,8 @@ Every keypoint is a filled disc, as in the reference (its ``draw_pose`` draws a 
 skeleton is opt-in: pass ``limbs=OPENPOSE_BODY25_LIMBS[0], limb_rgb=OPENPOSE_BODY25_LIMBS[1]``.  The coverage rules are this
 project's own definitions: they are not measured against OpenCV's rasterizer, and the normal renders are those of
 ``prior.render_normal_priors`` (9n), not of the reference's ``render_mesh``.  Where the reference writes an ``.mp4`` per call, a
-folder of PNGs is written: no video encoder is assumed.  HIP only: CPU tensors are refused, there is no CPU fallback.
+folder of PNGs is written and, with ``video=``, a Motion-JPEG ``video.avi`` encoded on the device (soar_amd/video.py).  HIP only: CPU
+tensors are refused, there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -266,10 +267,15 @@ def fit_strips(rig, body, topo: MeshTopology, params: Mapping[str, torch.Tensor]
     return dict(strips=torch.cat(strips, dim=0), residuals=residuals)
 
 
-def save_strips(strips: torch.Tensor, folder: str) -> None:
-    """``<folder>/<frame:05d>.png`` for every strip of ``[N,h,w,3]`` uint8 (a folder of PNGs where the reference writes one ``.mp4``)."""
+def save_strips(strips: torch.Tensor, folder: str, video=None) -> None:
+    """``<folder>/<frame:05d>.png`` for every strip of ``[N,h,w,3]`` uint8.  Where the reference writes one ``.mp4``, ``video=True`` or
+    ``video=dict(fps=..., quality=..., subsampling=...)`` (``video.MjpegWriter``'s keywords) also writes ``<folder>/video.avi``:
+    Motion-JPEG, encoded on the device from the strips (which must then be on a HIP device)."""
     from PIL import Image
     os.makedirs(folder, exist_ok=True)
+    if video is not None and video is not False:
+        from .video import video_options, write_video
+        write_video(os.path.join(folder, "video.avi"), strips.detach(), **video_options(video))
     host = strips.detach().cpu().numpy()
     for n in range(host.shape[0]):
         Image.fromarray(host[n]).save(os.path.join(folder, f"{n:05d}.png"))
@@ -278,15 +284,15 @@ def save_strips(strips: torch.Tensor, folder: str) -> None:
 class FitVisualizer:
     """What ``SMPLify.fit(..., visual=...)`` calls at the reference's moments: ``visual(name, params, Ks, w2c, img_wh, target_kps)``
     runs ``fit_strips``, writes the strips under ``out_dir/name`` and keeps ``residuals[name]`` (a host ``[N,3]`` array).
-    ``debug=True`` asks ``fit`` for every fifth step instead of the stages' last."""
+    ``debug=True`` asks ``fit`` for every fifth step instead of the stages' last; ``video``: what ``save_strips`` takes."""
 
-    def __init__(self, rig, body, topo: MeshTopology, out_dir: str, imgs=None, debug: bool = False, pose_mean=None, **draw):
+    def __init__(self, rig, body, topo: MeshTopology, out_dir: str, imgs=None, debug: bool = False, pose_mean=None, video=None, **draw):
         self.rig, self.body, self.topo, self.out_dir, self.imgs, self.debug = rig, body, topo, out_dir, imgs, bool(debug)
-        self.pose_mean, self.draw = pose_mean, draw
+        self.pose_mean, self.video, self.draw = pose_mean, video, draw
         self.residuals: Dict[str, np.ndarray] = {}
 
     def __call__(self, name: str, params, Ks, w2c, img_wh, target_kps) -> None:
         out = fit_strips(self.rig, self.body, self.topo, params, Ks, w2c, img_wh, target_kps, imgs=self.imgs,
                          pose_mean=self.pose_mean, **self.draw)
-        save_strips(out["strips"], os.path.join(self.out_dir, name))
+        save_strips(out["strips"], os.path.join(self.out_dir, name), video=self.video)
         self.residuals[name] = out["residuals"].cpu().numpy()

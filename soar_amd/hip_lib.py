@@ -266,6 +266,12 @@ class SoarFrameExtraArgs(C.Structure):
                 ("g_occ", _vp)]
 
 
+class SoarJpegArgs(C.Structure):
+    """Mirror of ``struct SoarJpegArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32), ("subsampling", C.c_int32),
+                ("restart_interval", C.c_int32), ("frames", _vp), ("frame_stride", C.c_int64), ("qtables", (C.c_uint8 * 64) * 2)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -480,6 +486,9 @@ SIGNATURES = {
     "soar_fitviz_yaw_views": (C.c_int, [C.c_int32] * 3 + [_vp, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     "soar_fitviz_strip": (C.c_int, [C.POINTER(SoarFitvizStripArgs), _vp]),
     "soar_fitviz_residuals": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp]),
+    "soar_jpeg_workspace_bytes": (C.c_int, [C.POINTER(SoarJpegArgs), C.POINTER(C.c_size_t)]),
+    "soar_jpeg_measure": (C.c_int, [C.POINTER(SoarJpegArgs), _vp, C.c_size_t, _vp, _vp]),
+    "soar_jpeg_emit": (C.c_int, [C.POINTER(SoarJpegArgs), _vp, C.c_size_t, _vp, C.c_int64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

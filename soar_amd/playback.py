@@ -342,12 +342,19 @@ class AvatarPlayer:
         return out
 
     def play(self, poses: Mapping[str, torch.Tensor], camera, out_dir: str, bg: Optional[torch.Tensor] = None, chunk: int = 8,
-             normal_as_rgb: bool = False) -> Dict[str, torch.Tensor]:
+             normal_as_rgb: bool = False, video=None) -> Dict[str, torch.Tensor]:
         """``render``, then ``out_dir/{rgb,normal,occ,mask}/{i:05d}.png``: RGBA PNGs (the image with the mask as alpha, as the reference's
-        ``save_image(torch.cat([image, mask]))`` writes them) and the greyscale mask.  -> what ``render`` returned.  The reference also
-        writes ``video.mp4`` with imageio, which is not a dependency of this package: it is left out."""
+        ``save_image(torch.cat([image, mask]))`` writes them) and the greyscale mask.  -> what ``render`` returned.  Where the reference
+        writes ``video.mp4`` with imageio, ``video=True`` or ``video=dict(fps=25, quality=90, subsampling="420")`` (``video.MjpegWriter``'s
+        keywords) also writes ``out_dir/{rgb,normal,occ}/video.avi``: Motion-JPEG, encoded on the device ``chunk`` frames at a time from
+        the byte images, the alpha channel dropped (``rgb`` is composited over ``bg`` already).  Without ``video`` nothing changes."""
         from PIL import Image
         res = self.render(poses, camera, bg=bg, chunk=chunk, normal_as_rgb=normal_as_rgb)
+        if video is not None and video is not False:
+            from .video import video_options, write_video
+            for k in ("rgb", "normal", "occ"):
+                os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+                write_video(os.path.join(out_dir, k, "video.avi"), res[k], chunk=chunk, **video_options(video))
         for k, t in res.items():
             folder = os.path.join(out_dir, k)
             os.makedirs(folder, exist_ok=True)
