@@ -1762,6 +1762,54 @@ int soar_jpeg_workspace_bytes(const SoarJpegArgs *args, size_t *bytes);
 int soar_jpeg_measure(const SoarJpegArgs *args, void *workspace, size_t workspace_bytes, int64_t *offsets, void *stream);
 int soar_jpeg_emit(const SoarJpegArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int64_t capacity, void *stream);
 
+/* ---- PNG output: filters, run-length deflate, CRC (png.hip, soar_amd/png.py) ----
+ * B images of uint8 pixels -> B complete PNG files (signature, IHDR, IDAT ..., IEND), one after the other in one device buffer, with
+ * their byte offsets.  8 bit, colour type 0, 2 or 6, no interlace, no ancillary chunks.  Current stream, no synchronisation, no
+ * allocation; integer arithmetic and integer atomics only: two calls give the same bytes, and an image's bytes depend neither on B nor
+ * on its place.  images, workspace, offsets and out are device memory; args is host memory.  The host adds nothing to the files.
+ *
+ * images: [B][H][W][channels] uint8, channels 1 (grey, colour type 0), 3 (RGB, type 2) or 4 (RGBA, type 6); every image contiguous,
+ *   image_stride bytes from image to image (>= H W channels).  1 <= H, W <= 65535, 0 <= B <= 65535.
+ * filter: 0 .. 4 forces None, Sub, Up, Average or Paeth (the PNG specification's, bytes beyond the image being 0) on every row; -1
+ *   picks for every row the type with the smallest sum of |residual as int8|, ties to the lowest type.  A row is filtered against the
+ *   RAW row above.  The filtered stream of an image is H rows of 1 + W channels bytes, the type first.
+ * piece_bytes: 32 .. 65535.  The stream is cut into pieces of that many bytes (the last may be shorter); nothing in a piece refers to
+ *   another, and at most B ceil(H (1 + W channels) / piece_bytes) <= 2^30 pieces are in a call.
+ * Tokens: maximal runs of equal bytes inside a piece, from the left.  A run of N bytes is one literal, then with rest = N - 1: while
+ *   rest >= 3 a match of min(rest, 258) at distance 1; then the rest (1 or 2) as literals.  No search, no hash table.
+ * Code: counts over the 286 literal/length symbols, the end-of-block symbol counted once; T their sum, f = 1 + T / 32000, every used
+ *   count raised to at least f, T' the raised counts' sum.  A used symbol's length is the smallest l with (count << l) >= T' (1 .. 15;
+ *   the Kraft sum is at most 1).  Then sweeps: for L = 2 .. 15 in turn, of the symbols of length L the first min(their number,
+ *   D >> (15 - L)) in symbol order are shortened to L - 1, D being 2^15 minus the sum of 2^(15 - length); sweeps repeat until D is 0:
+ *   the code is complete.  Codes are RFC 1951's canonical ones.  The distance alphabet is one code of one bit.
+ * Block: BFINAL 0, BTYPE 2, HLIT 29, HDIST 0, HCLEN 15; the code-length alphabet's lengths are 0 for 16, 17, 18 and 4 for 0 .. 15, so
+ *   each of the 286 + 1 lengths follows as 4 bits of its own (1222 header bits; no run-length coding of the header); the tokens (a
+ *   Huffman code goes most significant bit first, extra bits least significant first); end of block; an empty stored block (000,
+ *   zeros to the byte, 00 00 FF FF), so that a piece ends on a byte.  If that is not smaller than 5 + n bytes the piece is ONE
+ *   STORED BLOCK instead (00, n, ~n, the n bytes).
+ * Framing: 89 'PNG' 0D 0A 1A 0A; IHDR; one IDAT per piece, the first beginning with the zlib header 78 01; an IDAT with the final
+ *   empty fixed block 03 00 and the Adler-32 of the whole filtered stream, big-endian, joined from the pieces' values
+ *   (A = A1 + A2 - 1, B = B1 + B2 + len2 (A1 - 1), modulo 65521); IEND.  Every chunk's CRC-32 is computed on the device.
+ *
+ * soar_png_workspace_bytes: what both calls need for these B, H, W, channels and piece_bytes.
+ * soar_png_measure: filtering, tokens, codes and sizes, scan.  offsets [B + 1] int64: image b will occupy bytes
+ *   offsets[b] .. offsets[b + 1] of the output; offsets[B] is its length.  Leaves the filtered streams, the codes and the offsets in
+ *   the workspace.
+ * soar_png_emit: the same args and the workspace soar_png_measure left -> out.  If offsets[B] > capacity NOTHING is written (the
+ *   caller reads the need from offsets): every wavefront returns before its first store; nothing is ever written at or behind
+ *   out + capacity.
+ * Both refuse bad arguments before any launch. */
+typedef struct SoarPngArgs {
+    int32_t B, H, W, channels;
+    int32_t filter;                   /* 0 .. 4, or -1: adaptive */
+    int32_t piece_bytes;
+    const uint8_t *images;
+    int64_t image_stride;             /* bytes */
+} SoarPngArgs;
+int soar_png_workspace_bytes(const SoarPngArgs *args, size_t *bytes);
+int soar_png_measure(const SoarPngArgs *args, void *workspace, size_t workspace_bytes, int64_t *offsets, void *stream);
+int soar_png_emit(const SoarPngArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int64_t capacity, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

@@ -133,10 +133,11 @@ class TestEvaluator:
             raise RuntimeError("TestEvaluator.finish: no frame was added")
         return self.buffer.cpu().numpy()[:self.count]
 
-    def finish(self, save_dir: Optional[str] = None, step: int = 0) -> Dict[str, Any]:
+    def finish(self, save_dir: Optional[str] = None, step: int = 0, device_png: bool = False) -> Dict[str, Any]:
         """-> ``psnrs``, ``ssims`` (float64 [count]), ``lpips`` (float32 [count]), ``psnr``, ``ssim``, ``lpips_mean`` (their means) and
         ``gt_indices``.  With ``save_dir``: psnrs.txt, ssims.txt, lpips.txt (``np.savetxt``) and average.txt, the reference's files; with
-        ``keep_images`` also ``it{step}-test/{gt_index}.png``."""
+        ``keep_images`` also ``it{step}-test/{gt_index}.png``, made on the device with ``device_png=True`` (``png.write_png_files``:
+        the same names and pixels, and only compressed bytes are copied to the host)."""
         import numpy as np
         host = self._read_back()
         psnrs, ssims = host[:, 0].copy(), host[:, 1].copy()
@@ -154,6 +155,10 @@ class TestEvaluator:
                 from PIL import Image
                 folder = os.path.join(save_dir, f"it{step}-test")
                 os.makedirs(folder, exist_ok=True)
+                if device_png:
+                    from .png import write_png_files
+                    write_png_files([os.path.join(folder, f"{i}.png") for i in self.gt_indices], torch.stack(self.images))
+                    return res
                 for i, img in zip(self.gt_indices, torch.stack(self.images).cpu().numpy()):
                     Image.fromarray(img).save(os.path.join(folder, f"{i}.png"))
         return res

@@ -267,15 +267,20 @@ def fit_strips(rig, body, topo: MeshTopology, params: Mapping[str, torch.Tensor]
     return dict(strips=torch.cat(strips, dim=0), residuals=residuals)
 
 
-def save_strips(strips: torch.Tensor, folder: str, video=None) -> None:
+def save_strips(strips: torch.Tensor, folder: str, video=None, device_png: bool = False) -> None:
     """``<folder>/<frame:05d>.png`` for every strip of ``[N,h,w,3]`` uint8.  Where the reference writes one ``.mp4``, ``video=True`` or
     ``video=dict(fps=..., quality=..., subsampling=...)`` (``video.MjpegWriter``'s keywords) also writes ``<folder>/video.avi``:
-    Motion-JPEG, encoded on the device from the strips (which must then be on a HIP device)."""
+    Motion-JPEG, encoded on the device from the strips (which must then be on a HIP device).  ``device_png=True`` makes the PNG files
+    on the device as well (``png.write_png_files``): the same names and pixels, and only compressed bytes are copied to the host."""
     from PIL import Image
     os.makedirs(folder, exist_ok=True)
     if video is not None and video is not False:
         from .video import video_options, write_video
         write_video(os.path.join(folder, "video.avi"), strips.detach(), **video_options(video))
+    if device_png:
+        from .png import write_png_files
+        write_png_files([os.path.join(folder, f"{n:05d}.png") for n in range(strips.shape[0])], strips.detach())
+        return
     host = strips.detach().cpu().numpy()
     for n in range(host.shape[0]):
         Image.fromarray(host[n]).save(os.path.join(folder, f"{n:05d}.png"))

@@ -272,6 +272,12 @@ class SoarJpegArgs(C.Structure):
                 ("restart_interval", C.c_int32), ("frames", _vp), ("frame_stride", C.c_int64), ("qtables", (C.c_uint8 * 64) * 2)]
 
 
+class SoarPngArgs(C.Structure):
+    """Mirror of ``struct SoarPngArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32),
+                ("piece_bytes", C.c_int32), ("images", _vp), ("image_stride", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -489,6 +495,9 @@ SIGNATURES = {
     "soar_jpeg_workspace_bytes": (C.c_int, [C.POINTER(SoarJpegArgs), C.POINTER(C.c_size_t)]),
     "soar_jpeg_measure": (C.c_int, [C.POINTER(SoarJpegArgs), _vp, C.c_size_t, _vp, _vp]),
     "soar_jpeg_emit": (C.c_int, [C.POINTER(SoarJpegArgs), _vp, C.c_size_t, _vp, C.c_int64, _vp]),
+    "soar_png_workspace_bytes": (C.c_int, [C.POINTER(SoarPngArgs), C.POINTER(C.c_size_t)]),
+    "soar_png_measure": (C.c_int, [C.POINTER(SoarPngArgs), _vp, C.c_size_t, _vp, _vp]),
+    "soar_png_emit": (C.c_int, [C.POINTER(SoarPngArgs), _vp, C.c_size_t, _vp, C.c_int64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

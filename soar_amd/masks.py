@@ -183,9 +183,20 @@ def segment_sequence(predict: Callable, images: Sequence, keypoints, chunk: int 
     return torch.cat(masks), torch.cat(stats)
 
 
-def save_masks(masks, data_dir: str) -> List[str]:
+def save_masks(masks, data_dir: str, device_png: bool = False) -> List[str]:
     """``masks [N,H,W]`` (non-zero is foreground) -> ``data_dir/masks/00000.png`` ..., 8-bit greyscale 0 / 255 (both
-    ``FrameStore.read_dataroot`` and the reference's loader read a mask as ``> 0``).  Returns the paths."""
+    ``FrameStore.read_dataroot`` and the reference's loader read a mask as ``> 0``).  Returns the paths.  ``device_png=True`` makes the
+    files on the device (``png.write_png_files``; ``masks`` must then be a tensor on a HIP device): the same names and pixels, and only
+    compressed bytes are copied to the host."""
+    if device_png:
+        from .png import write_png_files
+        if not isinstance(masks, torch.Tensor) or masks.dim() != 3:
+            raise ValueError("save_masks: with device_png masks must be a [N,H,W] tensor")
+        out_dir = os.path.join(data_dir, "masks")
+        os.makedirs(out_dir, exist_ok=True)
+        paths = [os.path.join(out_dir, f"{i:05d}.png") for i in range(masks.shape[0])]
+        write_png_files(paths, (masks.detach() != 0).to(torch.uint8) * 255)
+        return paths
     from PIL import Image
     m = masks.detach().cpu().numpy() if isinstance(masks, torch.Tensor) else np.asarray(masks)
     if m.ndim != 3:

@@ -304,11 +304,18 @@ def estimate_normals(net: NormalNet, images, masks, Ks, prior_F: torch.Tensor, p
     return out
 
 
-def save_normals(result: Mapping[str, torch.Tensor], data_dir: str) -> None:
-    """Writes ``normal_F/%05d.png`` and ``normal_B/%05d.png`` (RGBA: the normal's bytes and the normal mask) under ``data_dir``, the
-    layout ``FrameStore.read_dataroot`` reads, and, as the reference does, puts ``normal_Ks`` into ``data_dir/smplx/params.pth`` next
-    to ``Ks`` when that file exists (it holds the body's parameters and is not made here; without it ``normal_Ks`` stays with the
-    caller)."""
+def _save_normals_on_device(result: Mapping[str, torch.Tensor], data_dir: str) -> None:
+    from .png import write_png_files
+    mask = result["normal_mask"].detach()
+    for name in ("normal_F", "normal_B"):
+        rgb = result[name].detach()
+        if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[-1] != 3 or mask.shape != rgb.shape[:3] or mask.dtype != torch.uint8:
+            raise ValueError(f"save_normals: {name} must be uint8 [N,H,W,3] and normal_mask uint8 [N,H,W]")
+        os.makedirs(os.path.join(data_dir, name), exist_ok=True)
+        write_png_files([os.path.join(data_dir, name, f"{i:05d}.png") for i in range(rgb.shape[0])], torch.cat([rgb, mask[..., None]], dim=-1))
+
+
+def _save_normals_on_host(result: Mapping[str, torch.Tensor], data_dir: str) -> None:
     from PIL import Image
     import numpy as np
     nM = result["normal_mask"].detach().cpu().numpy()
@@ -319,6 +326,15 @@ def save_normals(result: Mapping[str, torch.Tensor], data_dir: str) -> None:
             raise ValueError(f"save_normals: {name} must be uint8 [N,H,W,3] and normal_mask [N,H,W]")
         for i in range(rgb.shape[0]):
             Image.fromarray(np.concatenate([rgb[i], nM[i][..., None]], axis=-1), "RGBA").save(os.path.join(data_dir, name, f"{i:05d}.png"))
+
+
+def save_normals(result: Mapping[str, torch.Tensor], data_dir: str, device_png: bool = False) -> None:
+    """Writes ``normal_F/%05d.png`` and ``normal_B/%05d.png`` (RGBA: the normal's bytes and the normal mask) under ``data_dir``, the
+    layout ``FrameStore.read_dataroot`` reads, and, as the reference does, puts ``normal_Ks`` into ``data_dir/smplx/params.pth`` next
+    to ``Ks`` when that file exists (it holds the body's parameters and is not made here; without it ``normal_Ks`` stays with the
+    caller).  ``device_png=True`` joins the channels and makes the PNG files on the device (``png.write_png_files``; the maps must then
+    be on a HIP device): the same names and pixels, and only compressed bytes are copied to the host."""
+    (_save_normals_on_device if device_png else _save_normals_on_host)(result, data_dir)
     params = os.path.join(data_dir, "smplx", "params.pth")
     if "normal_Ks" in result and os.path.exists(params):
         body = torch.load(params, map_location="cpu")

@@ -342,12 +342,14 @@ class AvatarPlayer:
         return out
 
     def play(self, poses: Mapping[str, torch.Tensor], camera, out_dir: str, bg: Optional[torch.Tensor] = None, chunk: int = 8,
-             normal_as_rgb: bool = False, video=None) -> Dict[str, torch.Tensor]:
+             normal_as_rgb: bool = False, video=None, device_png: bool = False) -> Dict[str, torch.Tensor]:
         """``render``, then ``out_dir/{rgb,normal,occ,mask}/{i:05d}.png``: RGBA PNGs (the image with the mask as alpha, as the reference's
         ``save_image(torch.cat([image, mask]))`` writes them) and the greyscale mask.  -> what ``render`` returned.  Where the reference
         writes ``video.mp4`` with imageio, ``video=True`` or ``video=dict(fps=25, quality=90, subsampling="420")`` (``video.MjpegWriter``'s
         keywords) also writes ``out_dir/{rgb,normal,occ}/video.avi``: Motion-JPEG, encoded on the device ``chunk`` frames at a time from
-        the byte images, the alpha channel dropped (``rgb`` is composited over ``bg`` already).  Without ``video`` nothing changes."""
+        the byte images, the alpha channel dropped (``rgb`` is composited over ``bg`` already).  Without ``video`` nothing changes.
+        ``device_png=True`` makes the PNG files on the device too (``png.write_png_files``, ``chunk`` images per call): the same names,
+        pixels and modes, other bytes, and only compressed bytes are copied to the host."""
         from PIL import Image
         res = self.render(poses, camera, bg=bg, chunk=chunk, normal_as_rgb=normal_as_rgb)
         if video is not None and video is not False:
@@ -358,6 +360,10 @@ class AvatarPlayer:
         for k, t in res.items():
             folder = os.path.join(out_dir, k)
             os.makedirs(folder, exist_ok=True)
+            if device_png:
+                from .png import write_png_files
+                write_png_files([os.path.join(folder, f"{i:05d}.png") for i in range(t.shape[0])], t, chunk=chunk)
+                continue
             for i, img in enumerate(t.cpu().numpy()):                   # [H,W,4] bytes -> "RGBA", [H,W] -> "L"
                 Image.fromarray(img).save(os.path.join(folder, f"{i:05d}.png"))
         return res

@@ -199,10 +199,11 @@ def bake_texture(mesh, atlas: Atlas, means3D: torch.Tensor, colors: torch.Tensor
     return (texture, debug) if return_debug else texture
 
 
-def save_textured_obj(path: str, mesh, atlas: Atlas, texture: torch.Tensor) -> None:
+def save_textured_obj(path: str, mesh, atlas: Atlas, texture: torch.Tensor, device_png: bool = False) -> None:
     """Three files: the Wavefront OBJ at ``path`` (``mtllib``, ``v x y z`` at float32 round-trip precision, the 3F ``vt u v`` lines,
     ``usemtl``, ``f a/ta b/tb c/tc`` with 1-based indices), ``<stem>.mtl`` next to it with ``map_Kd <stem>.png``, and that PNG
-    (``texture`` [T,T,3] uint8, row 0 at the top).  Works on host copies of the tensors."""
+    (``texture`` [T,T,3] uint8, row 0 at the top).  Works on host copies of the tensors; ``device_png=True`` makes the PNG on the
+    device instead (``png.save_png``; ``texture`` must then be on a HIP device): the same pixels, and only compressed bytes are copied."""
     import numpy as np
     from PIL import Image
     vertices, faces = mesh
@@ -226,4 +227,8 @@ def save_textured_obj(path: str, mesh, atlas: Atlas, texture: torch.Tensor) -> N
         fh.writelines(f"f {a + 1}/{ta + 1} {b + 1}/{tb + 1} {c + 1}/{tc + 1}\n" for (a, b, c), (ta, tb, tc) in zip(f, ft.tolist()))
     with open(os.path.join(folder, stem + ".mtl"), "w") as fh:
         fh.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n")
+    if device_png:
+        from .png import save_png
+        save_png(os.path.join(folder, stem + ".png"), texture.detach())
+        return
     Image.fromarray(np.ascontiguousarray(tex.numpy())).save(os.path.join(folder, stem + ".png"))
