@@ -915,9 +915,11 @@ int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout
  *   [X][Y][Z] (X * Y * Z < 2^31) whose voxel (x, y, z) sits at origin + voxel * (x, y, z).  viewmatrix / projmatrix
  *   [n_views][16]: world_view_transform / full_proj_transform (row-vector convention); prcppoint [n_views][2].  Per voxel and
  *   view: skip when the view-space z <= znear or the nearest pixel floor(pix + 0.5) is outside the image; opac < min_opacity
- *   records s = +1, else skip when depth - z < -trunc, else s = min(1, (depth - z) / trunc); sum += s, weight += 1.  One
- *   thread per voxel, no atomics: deterministic.  sum / weight are read and written in place (zero them before the first
- *   call); calls accumulate.
+ *   records s = +1, else skip when depth - z < -trunc, else s = min(1, (depth - z) / trunc); sum += s, weight += 1.
+ *   Non-finite pixels: a view whose pixel has a NaN opacity, or an opacity >= min_opacity with a NaN depth, is no observation
+ *   of that voxel (sum and weight stay as they were); +-inf follow the arithmetic above (+inf depth: s = 1; -inf depth:
+ *   hidden, skipped; +inf opacity: opaque; -inf opacity: free space).  One thread per voxel, no atomics: deterministic.
+ *   sum / weight are read and written in place (zero them before the first call); calls accumulate.
  * soar_mc_workspace_bytes / soar_mc_count / soar_mc_emit: marching cubes of values [X][Y][Z] at `level` (inside: value <
  *   level), valid [X][Y][Z] bytes or NULL.  An edge carries a vertex when both ends are valid and exactly one is inside; a
  *   cell emits triangles only when its 8 corners are valid.  soar_mc_count reads back counts_host[2] = {vertices, triangles}

@@ -4,7 +4,8 @@
 // stages with deterministic kernels (DESIGN.md section "Mesh export").
 //
 //   tsdf_integrate_kernel  one thread per voxel gathers over the views of a call, no atomics: sum += s, weight += 1 per
-//                          observation (s = +1 in free space, min(1, (depth - z) / trunc) in front of / near the surface)
+//                          observation (s = +1 in free space, min(1, (depth - z) / trunc) in front of / near the surface);
+//                          a NaN opacity, or an opaque pixel with a NaN depth, is no observation
 //   mc_count_kernel        per voxel: the edges it owns (+x, +y, +z) that carry a vertex and the triangle count of its cell,
 //                          packed into one u64 (vertices low, triangles high) and exclusive-scanned (rocPRIM): vertex and
 //                          triangle ids follow (voxel, axis) and (cell, table order) -- a welded mesh, bit-identical per run
@@ -66,9 +67,11 @@ __global__ void __launch_bounds__(256) tsdf_integrate_kernel(int n_views, int H,
         if (!(fi >= 0.f && fi < (float)W && fj >= 0.f && fj < (float)H)) continue;     // (NaN fails too)
         const size_t pix = (size_t)k * plane + (size_t)fj * W + (size_t)fi;
         float s = 1.f;                                                                    // free space
-        if (!(opac[pix] < min_opac)) {
+        const float o = opac[pix];
+        if (o != o) continue;                                                             // NaN opacity: no observation
+        if (!(o < min_opac)) {
             const float eta = depth[pix] - zc;
-            if (eta < -trunc) continue;                                                   // hidden behind the surface
+            if (!(eta >= -trunc)) continue;                                               // hidden behind the surface, or a NaN depth
             s = fminf(1.f, eta / trunc);
         }
         acc += s;

@@ -177,15 +177,34 @@ def n_components(n_verts, faces):
     return len({find(int(u)) for u in used})
 
 
-def filter_components(verts, faces, min_faces, min_diag_frac):
-    """soar_mesh_filter_components restated: a component (labelled by its least vertex id, as n_components finds it) stays when
-    it has >= min_faces faces and its bounding-box diagonal is not below min_diag_frac times the diagonal over all vertices
-    that a face uses; kept vertices and faces keep their input order.  The diagonals are float64 here, float32 there."""
+def table_face_count(values, level=0.0, valid=None):
+    """The number of triangles the case table gives a field: the sum, over the cells with 8 valid corners, of the case's count."""
+    _, tris = table()
+    ntri = np.array([len(t) for t in tris])
+    f = np.asarray(values, np.float32)
+    if min(f.shape) < 2:
+        return 0
+    ok = np.ones(f.shape, bool) if valid is None else np.asarray(valid, bool)
+    inside = f < np.float32(level)
+    case = np.zeros(tuple(d - 1 for d in f.shape), np.int64)
+    whole = np.ones(case.shape, bool)
+    for c in range(8):
+        sl = tuple(slice(o, o + d - 1) for o, d in zip((c & 1, (c >> 1) & 1, (c >> 2) & 1), f.shape))
+        case |= inside[sl].astype(np.int64) << c
+        whole &= ok[sl]
+    return int(ntri[case[whole]].sum())
+
+
+def component_stats(verts, faces):
+    """The components of a mesh over its faces' edges, each labelled by its least vertex id -> (label [V], used [V] bool,
+    labs [C] ascending, n_faces [C], lo [C,3], hi [C,3], glo [3], ghi [3]): the boxes (float32 coordinates, exact) over the
+    vertices that a face uses, per component and of the whole mesh."""
     verts, faces = np.asarray(verts, np.float32), np.asarray(faces, np.int32).reshape(-1, 3)
-    parent = np.arange(len(verts))
+    parent = list(range(len(verts)))
 
     def find(x):
         while parent[x] != x:
+            parent[x] = parent[parent[x]]              # halving: the roots are what they are without it, the walks are short
             x = parent[x]
         return x
 
@@ -193,23 +212,48 @@ def filter_components(verts, faces, min_faces, min_diag_frac):
         for u, v in ((a, b), (b, c)):
             ru, rv = find(u), find(v)
             parent[max(ru, rv)] = min(ru, rv)
-    label = np.array([find(v) for v in range(len(verts))])
+    label = np.array([find(v) for v in range(len(verts))], np.int64)
     used = np.zeros(len(verts), bool)
     used[faces.reshape(-1)] = True
-    diag = lambda p: float(np.linalg.norm(p.max(0).astype(np.float64) - p.min(0).astype(np.float64)))
-    whole = diag(verts[used])
+    labs, inv = np.unique(label[used], return_inverse=True)
+    lo, hi = np.full((len(labs), 3), np.inf, np.float32), np.full((len(labs), 3), -np.inf, np.float32)
+    np.minimum.at(lo, inv, verts[used])
+    np.maximum.at(hi, inv, verts[used])
+    n_faces = np.bincount(np.searchsorted(labs, label[faces[:, 0]]), minlength=len(labs))
+    return label, used, labs, n_faces, lo, hi, verts[used].min(0), verts[used].max(0)
+
+
+def box_diag64(lo, hi):
+    d = np.asarray(hi, np.float64) - np.asarray(lo, np.float64)
+    return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+
+
+def box_diag32(lo, hi):
+    """the kernel's box_diag: float32 differences, squares and sums in the order written, sqrtf"""
+    d = np.asarray(hi, np.float32) - np.asarray(lo, np.float32)
+    return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2], dtype=np.float32)
+
+
+def filter_components(verts, faces, min_faces, min_diag_frac, diag=box_diag64):
+    """soar_mesh_filter_components restated: a component (labelled by its least vertex id, as n_components finds it) stays when
+    it has >= min_faces faces and its bounding-box diagonal is not below min_diag_frac times the diagonal over all vertices
+    that a face uses; kept vertices and faces keep their input order.  The diagonals are float64 here, float32 there
+    (diag=box_diag32 restates those: tests/test_mesh_cases_cpu.py holds the two together on every case)."""
+    verts, faces = np.asarray(verts, np.float32), np.asarray(faces, np.int32).reshape(-1, 3)
+    label, used, labs, n_faces, lo, hi, glo, ghi = component_stats(verts, faces)
+    frac = np.float32(min_diag_frac) if diag is box_diag32 else min_diag_frac
+    keep_c = (n_faces >= min_faces) & ~(diag(lo, hi) < frac * diag(glo, ghi))
     keep_v = np.zeros(len(verts), bool)
-    for lab in np.unique(label[used]):
-        mine = used & (label == lab)
-        n_faces = int((label[faces[:, 0]] == lab).sum())
-        keep_v[mine] = n_faces >= min_faces and not diag(verts[mine]) < min_diag_frac * whole
+    keep_v[used] = keep_c[np.searchsorted(labs, label[used])]
     new_id = np.cumsum(keep_v) - 1
-    return verts[keep_v], new_id[faces[keep_v[faces[:, 0]]]].astype(np.int32)
+    return verts[keep_v], new_id[faces[keep_v[faces[:, 0]]]].astype(np.int32).reshape(-1, 3)
 
 
 def tsdf_reference(depth, opac, viewm, projm, prcp, origin, voxel, dims, trunc, znear=0.2, min_opac=0.5, acc=None, eps_px=1e-3):
     """float64 restatement of soar_tsdf_integrate (torch tensors on the CPU) -> (sum, weight, ambiguous) where `ambiguous`
-    flags voxels whose projection lies within eps_px of a pixel-rounding boundary (or on another decision boundary) in a view."""
+    flags voxels whose projection lies within eps_px of a pixel-rounding boundary (or on another decision boundary) in a view.
+    Non-finite pixels: a NaN opacity, or an opacity >= min_opac with a NaN depth, is no observation; +inf depth gives s = 1,
+    -inf depth is hidden, +inf opacity is opaque, -inf opacity is free space -- the arithmetic as written."""
     import torch
     X, Y, Z = dims
     d = torch.float64
@@ -243,7 +287,8 @@ def tsdf_reference(depth, opac, viewm, projm, prcp, origin, voxel, dims, trunc, 
         free = o < min_opac
         amb |= seen & ((o - min_opac).abs() < 1e-6)
         amb |= seen & ~free & ((eta + trunc).abs() < 1e-5)
-        use = seen & (free | (eta >= -trunc))
+        # a NaN opacity, or an opaque pixel with a NaN depth (eta >= -trunc is false), is no observation
+        use = seen & ~o.isnan() & (free | (eta >= -trunc))
         s = torch.where(free, torch.ones_like(eta), torch.clamp(eta / trunc, max=1.0))
         s_acc += torch.where(use, s, torch.zeros_like(s))
         w_acc += use.to(d)

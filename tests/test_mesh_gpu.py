@@ -1,12 +1,15 @@
 """GPU tests of the mesh export (soar_amd/mesh.py, csrc/mesh.hip): TSDF fusion against a float64 restatement, the depth
 convention of the renderer, marching cubes against the Python table driver, analytic fields, the whole path on the bench's
-person and the component filter."""
+person and the component filter; from section 8 on, the three stages off the cube, at their block edges, ties and thresholds, on
+the cases of tests/mesh_cases.py."""
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import mesh_cases as MC
 import mesh_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -308,3 +311,267 @@ def test_component_filter_at_small_sizes(levels, strays, V, F):
     bad[F // 2, 1] = V
     with pytest.raises(hip_lib.SoarHipError, match="outside"):
         mesh.filter_components(torch.from_numpy(verts).to(dev), torch.from_numpy(bad).to(dev))
+
+
+# ---- 8. fusion off the cube (tests/mesh_cases.py; tests/test_mesh_cases_cpu.py checks the cases themselves) -----------------------
+
+def _bits(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a.view(np.int32) if a.dtype == np.float32 else a
+
+
+def _same_bits(a, b):
+    a, b = _bits(a), _bits(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+
+
+def _fuse(case, views=slice(None), acc=None):
+    from soar_amd import mesh
+    t = lambda a: a[views].to(_dev())
+    return mesh.fuse_depth(t(case.depth), t(case.opac), t(case.viewm), t(case.projm), t(case.prcp), case.origin, case.voxel, case.dims, acc=acc)
+
+
+def _holds_against_the_restatement(case, s, w, ref=None):
+    """the rules of test_fuse_depth_matches_float64_restatement: at most 5 % of the voxels ambiguous, outside them equal weights and
+    sums within 1e-5"""
+    rs, rw, amb = MC.reference(case, R) if ref is None else ref
+    s, w = s.cpu().double(), w.cpu().double()
+    ok = ~amb
+    err = float((s[ok] - rs[ok]).abs().max())
+    print(f"ambiguous {float(amb.float().mean()):.4f}, weights differing {int((w[ok] != rw[ok]).sum())}, largest sum error {err:.2e}")
+    assert amb.float().mean() <= MC.AMBIGUOUS_CAP
+    assert torch.equal(w[ok], rw[ok])
+    assert err <= 1e-5
+
+
+@pytest.mark.parametrize("name", list(MC.FUSION_CASES))
+def test_fuse_depth_off_the_cube(name):
+    case = MC.fusion_case(name)
+    s, w = _fuse(case)
+    assert s.shape == case.dims and w.shape == case.dims
+    _holds_against_the_restatement(case, s, w)
+
+
+@pytest.mark.parametrize("n", [64, 65, 130])
+def test_fuse_depth_chunks_equal_one_call_per_view(n):
+    """fuse_depth hands the kernel 64 views per call; the kernel adds in view order, so one call per view gives the same bits"""
+    case = MC.fusion_case("chunk")
+    s, w = _fuse(case, slice(0, n))
+    acc = None
+    for k in range(n):
+        acc = _fuse(case, slice(k, k + 1), acc)
+    assert _same_bits(s, acc[0]) and _same_bits(w, acc[1])
+    assert float(w.max()) > 0.75 * n                      # voxels that most views observe: more than one call's 64 at n = 130
+
+
+def test_fuse_depth_a_view_of_the_second_chunk_alone():
+    case = MC.fusion_case("chunk")
+    s, w = _fuse(case, slice(MC.CHUNK_VIEW, MC.CHUNK_VIEW + 1))
+    _holds_against_the_restatement(MC.one_view(case, MC.CHUNK_VIEW), s, w)
+
+
+def test_fuse_depth_input_forms():
+    from soar_amd import mesh
+    case, dev = MC.fusion_case("offcube"), _dev()
+    s, w = _fuse(case)
+
+    def strided64(t):                                     # float64, every second element of a buffer twice as wide, NaN between
+        wide = torch.full(t.shape[:-1] + (2 * t.shape[-1],), float("nan"), dtype=torch.float64, device=dev)
+        wide[..., ::2] = t.to(dev)
+        assert not wide[..., ::2].is_contiguous()
+        return wide[..., ::2]
+
+    def transposed(t):                                    # the matrices stored column-major
+        v = t.to(dev).transpose(1, 2).contiguous().transpose(1, 2)
+        assert not v.is_contiguous()
+        return v
+    s2, w2 = mesh.fuse_depth(strided64(case.depth), strided64(case.opac), transposed(case.viewm), strided64(case.projm), strided64(case.prcp),
+                             case.origin, case.voxel, case.dims)
+    assert _same_bits(s, s2) and _same_bits(w, w2)
+    one = torch.tensor([0.45, 0.55], device=dev).expand(case.n, 2)
+    assert one.stride(0) == 0
+    args = [t.to(dev) for t in (case.depth, case.opac, case.viewm, case.projm)]
+    s3, w3 = mesh.fuse_depth(*args, one, case.origin, case.voxel, case.dims)
+    s4, w4 = mesh.fuse_depth(*args, one.contiguous(), case.origin, case.voxel, case.dims)
+    assert _same_bits(s3, s4) and _same_bits(w3, w4) and not _same_bits(s3, s)
+
+
+def test_fuse_depth_nonfinite_pixels():
+    """A NaN opacity, or an opaque pixel with a NaN depth, is no observation; +-inf follow the arithmetic (include/soar_hip.h)."""
+    case = MC.fusion_case("offcube")
+    planted = MC.plant_nonfinite(case)
+    s, w = _fuse(planted)
+    assert bool(torch.isfinite(s).all()) and bool(torch.isfinite(w).all())
+    _holds_against_the_restatement(planted, s, w)
+    clean_w = _fuse(case)[1].cpu().double()
+    _, rw, amb = MC.reference(case, R)
+    for kind in ("depth nan", "opac nan"):
+        only = MC.plant_nonfinite(case, (kind,))
+        _, kw, kamb = MC.reference(only, R)
+        lost = ~(amb | kamb) & (kw < rw)                  # voxels that project to a planted NaN pixel (test_mesh_cases_cpu: there are some)
+        got = _fuse(only)[1].cpu().double()
+        assert lost.any() and bool((got < clean_w)[lost].all()), kind
+
+
+def test_extract_mesh_is_the_same_in_any_grouping():
+    from soar_amd import mesh
+    from soar_amd import synthetic as syn
+    s = syn.make_surfels(4000)
+    args = [t.to(_dev()) for t in (s.xyz, s.rot, s.scales, s.opacity)]
+    a = mesh.extract_mesh(*args, resolution=48, n_views=10, image_size=128, group=4)
+    b = mesh.extract_mesh(*args, resolution=48, n_views=10, image_size=128, group=10)
+    assert a.faces.shape[0] > 500
+    assert _same_bits(a.vertices, b.vertices) and _same_bits(a.faces, b.faces)
+
+
+# ---- 9. marching cubes off the cube --------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _mc_reference(order, masked, level):
+    f, m = MC.mc_field(order)
+    return R.marching_cubes(f, level, m if masked else None)
+
+
+def _mc_equals_the_driver(f, valid=None, level=0.0, ref=None):
+    v, fc = _gpu_mc(f, valid, level)
+    rv, rf = R.marching_cubes(f, level, valid) if ref is None else ref
+    assert v.dtype == np.float32 and fc.dtype == np.int32 and v.shape[1:] == (3,) and fc.shape[1:] == (3,)
+    assert _same_bits(v, rv) and _same_bits(fc, rf)
+    assert len(fc) == R.table_face_count(f, level, valid)
+    return v, fc
+
+
+@pytest.mark.parametrize("level", [0.0, 0.25])
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("order", list(MC.MC_AXES))
+def test_marching_cubes_equals_the_table_driver_off_the_cube(order, masked, level):
+    f, m = MC.mc_field(order)
+    valid = m if masked else None
+    v, fc = _mc_equals_the_driver(f, valid, level, _mc_reference(order, masked, level))
+    assert len(fc) > 5000
+    R.check_vertices_on_crossings(v, f, level, valid)
+    if not masked:
+        R.check_closed_manifold(v, fc, f.shape)
+
+
+@pytest.mark.parametrize("level", [0.0, 0.25])
+@pytest.mark.parametrize("masked", [False, True])
+def test_marching_cubes_does_not_depend_on_the_axis_order(masked, level):
+    """the same field with its axes in another order: the same vertices (as a set, columns permuted back) and as many faces"""
+    base = None
+    for order in MC.MC_AXES:
+        f, m = MC.mc_field(order)
+        v, fc = _gpu_mc(f, m if masked else None, level)
+        got = (MC.sorted_rows(MC.mc_unpermute(v, order)), len(fc))
+        base = base or got
+        assert _same_bits(got[0], base[0]) and got[1] == base[1] > 0, order
+
+
+@pytest.mark.parametrize("shape", MC.MC_SIZE_GRIDS + MC.MC_FLAT_GRIDS, ids=lambda s: "x".join(map(str, s)))
+def test_marching_cubes_at_the_block_edge_and_on_flat_grids(shape):
+    f = MC.mc_random(shape, 320)
+    v, fc = _mc_equals_the_driver(f)
+    assert len(v) > 0
+    R.check_vertices_on_crossings(v, f)
+    if min(shape) == 1:
+        assert fc.shape == (0, 3)                         # vertices but no cell
+    else:
+        assert len(fc) > 0
+        R.check_closed_manifold(v, fc, shape)
+    valid = np.random.default_rng(325).uniform(size=shape) > 0.1
+    _mc_equals_the_driver(f, valid, 0.25)
+
+
+def test_marching_cubes_empty_results():
+    f = np.abs(MC.mc_random((6, 7, 8), 321)) + 0.5        # no crossing
+    one = np.zeros(f.shape, bool)
+    one[2, 3, 4] = True
+    for field, valid in ((f, None), (MC.mc_random(f.shape, 322), np.zeros(f.shape, bool)), (MC.mc_random(f.shape, 322), one)):
+        v, fc = _mc_equals_the_driver(field, valid)
+        assert v.shape == (0, 3) and fc.shape == (0, 3)
+
+
+@pytest.mark.parametrize("negative_zeros", [False, True])
+def test_marching_cubes_ties(negative_zeros):
+    """values equal to the level: t = 0 or 1 exactly and triangles of zero area; the bits and the table's count are the check"""
+    f = MC.mc_ties(negative_zeros)
+    v, fc = _mc_equals_the_driver(f)
+    assert len(fc) > 0 and (v == np.floor(v)).all(1).any()
+    valid = np.random.default_rng(326).uniform(size=f.shape) > 0.1
+    _mc_equals_the_driver(f, valid)
+
+
+def test_marching_cubes_input_forms():
+    from soar_amd import mesh
+    dev = _dev()
+    run = lambda f, valid=None: mesh.marching_cubes(f, 0.25, valid)
+    f64 = torch.from_numpy(np.random.default_rng(327).standard_normal(MC.MC_BASE)).to(dev)
+    valid = torch.from_numpy(MC.mc_field("xyz")[1]).to(dev)
+    for f in (f64, f64.half()):                           # float64 and float16 against their float32 copies
+        assert f.dtype != torch.float32
+        a, b = run(f, valid), run(f.float(), valid)
+        assert len(a[1]) > 5000 and _same_bits(a[0], b[0]) and _same_bits(a[1], b[1])
+    assert not _same_bits(run(f64)[0], run(f64.half())[0])
+    view = f64.float().permute(2, 0, 1)                   # not contiguous
+    mview = valid.permute(2, 0, 1)
+    assert not view.is_contiguous() and not mview.is_contiguous()
+    a, b = run(view, mview), run(view.contiguous(), mview.contiguous())
+    assert _same_bits(a[0], b[0]) and _same_bits(a[1], b[1])
+    bytes_ = valid.to(torch.uint8) * torch.from_numpy(np.random.default_rng(328).integers(1, 256, MC.MC_BASE).astype(np.uint8)).to(dev)
+    assert bytes_.dtype == torch.uint8 and int(bytes_.max()) > 1 and torch.equal(bytes_ != 0, valid)
+    a, b = run(f64.float(), bytes_), run(f64.float(), valid)
+    assert _same_bits(a[0], b[0]) and _same_bits(a[1], b[1])
+
+
+# ---- 10. the component filter at its thresholds ----------------------------------------------------------------------------------
+
+def _gpu_filter(case):
+    from soar_amd import mesh
+    dev = _dev()
+    v, f = mesh.filter_components(torch.from_numpy(case.verts).to(dev), torch.from_numpy(case.faces).to(dev), min_faces=case.min_faces,
+                                  min_diag_frac=case.min_diag_frac)
+    assert v.dtype == torch.float32 and f.dtype == torch.int32 and v.shape[1:] == (3,) and f.shape[1:] == (3,)
+    return _np(v), _np(f)
+
+
+def _filter_equals_the_restatement(case):
+    want_v, want_f = R.filter_components(case.verts, case.faces, case.min_faces, case.min_diag_frac)
+    if hasattr(case, "keep_v"):                           # the restatement keeps what the case is built to keep
+        assert np.array_equal(want_v, case.verts[case.keep_v]) and len(want_f) == int(case.keep_f.sum())
+    got_v, got_f = _gpu_filter(case)
+    assert _same_bits(got_v, want_v) and _same_bits(got_f, want_f)
+    return got_v, got_f
+
+
+@pytest.mark.parametrize("min_faces", MC.FAN_MIN_FACES)
+def test_component_filter_counts_faces_under_mixed_waves(min_faces):
+    v, f = _filter_equals_the_restatement(MC.fans_case(min_faces))
+    assert len(f) == 2 * sum(k for k in range(1, 131) if k >= min_faces)
+
+
+@pytest.mark.parametrize("permute", [False, True])
+def test_component_filter_boxes_at_a_tie_and_unused_vertices(permute):
+    v, f = _filter_equals_the_restatement(MC.tie_case(permute, strays=False))
+    assert len(f) == 103
+    v2, f2 = _filter_equals_the_restatement(MC.tie_case(permute, strays=True))
+    assert _same_bits(v, v2) and _same_bits(f, f2)        # vertices that no face uses, 1000 away, change nothing
+
+
+@pytest.mark.parametrize("shuffled", [False, True])
+def test_component_filter_deep_forests(shuffled):
+    case = MC.strip_case(shuffled)
+    v, f = _filter_equals_the_restatement(case)
+    assert _same_bits(v, case.verts) and _same_bits(f, case.faces)
+
+
+@pytest.mark.parametrize("V,F,seed", MC.SIZED_CASES)
+def test_component_filter_sizes(V, F, seed):
+    case = MC.sized_case(V, F, seed)
+    assert case.verts.shape == (V, 3) and case.faces.shape == (F, 3)
+    _filter_equals_the_restatement(case)
+
+
+def test_component_filter_single_triangle():
+    case = MC.single_triangle()
+    v, f = _filter_equals_the_restatement(case)
+    assert _same_bits(v, case.verts) and np.array_equal(f, case.faces)
