@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from knn_cases import _rows_equal_or_proved_ties
 from oracle import lbs_oracle as lo
 from soar_amd import synthetic as syn
 
@@ -21,25 +22,6 @@ def _setup(P=4000, seed=0, V=syn.SMPLX_NUM_VERTS):
                                  bm.parents, poses["transl"][3:4])
     cano2live = torch.matmul(A_live, torch.linalg.inv(A_cano))[0]
     return s, bm, cano2live
-
-
-def _rows_equal_or_proved_ties(idx, i_ref, queries, verts):
-    """Neighbour index sets are exact except where two candidates tie within fp32 rounding of d2 at the K-th place -- and every row
-    that differs is shown to BE such a tie: the distances of the members only one side picked, recomputed in float64, lie within fp32
-    rounding of the squared-distance expression (a few ulp of the K-th distance) of each other.  -> mask of the identical rows."""
-    same_rows = (np.sort(idx, 1) == np.sort(i_ref, 1)).all(1)
-    q64, v64 = queries.astype(np.float64), verts.astype(np.float64)
-    for row in np.nonzero(~same_rows)[0]:
-        mine, theirs = set(idx[row].tolist()), set(i_ref[row].tolist())
-        only_mine, only_theirs = sorted(mine - theirs), sorted(theirs - mine)
-        assert len(only_mine) == len(only_theirs) and len(mine) == idx.shape[1], (row, only_mine, only_theirs)
-        d2 = lambda ids: ((v64[ids] - q64[row]) ** 2).sum(1)
-        kth = max(d2(sorted(theirs)).max(), d2(sorted(mine)).max())
-        gap = np.abs(np.sort(d2(only_mine)) - np.sort(d2(only_theirs))).max()
-        # fp32 evaluation of |q - v|^2 for coordinates of magnitude c carries ~4 ulp(c^2) of rounding: allow that much, no more
-        c2 = max((q64[row] ** 2).sum(), (v64[sorted(mine | theirs)] ** 2).sum(1).max())
-        assert gap <= 8 * np.finfo(np.float32).eps * max(kth, c2), (row, gap, kth, only_mine, only_theirs)
-    return same_rows
 
 
 def test_knn_blend_weights_match_oracle():
