@@ -1812,6 +1812,46 @@ int soar_png_workspace_bytes(const SoarPngArgs *args, size_t *bytes);
 int soar_png_measure(const SoarPngArgs *args, void *workspace, size_t workspace_bytes, int64_t *offsets, void *stream);
 int soar_png_emit(const SoarPngArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int64_t capacity, void *stream);
 
+/* ---- PNG input: chunk walk, inflate, Adler-32, row filters (png_decode.hip, png_inflate.h, soar_amd/png.py) ----
+ * B PNG files, one after the other in one device buffer -> B images of uint8 pixels, each with a status.  8 bit, colour type 0, 2
+ * or 6, no interlace; ancillary chunks (and a PLTE) are skipped; any number of IDATs of any length; all of RFC 1951 and the zlib
+ * framing of RFC 1950 (method 8, any window, no dictionary).  Current stream, no synchronisation, no allocation; integer arithmetic
+ * and integer atomics only: two calls give the same bytes, and an image's bytes and status depend neither on B nor on its place.
+ * data, offsets, workspace, out, status and segments are device memory; args is host memory.
+ *
+ * data: total_bytes bytes; file b is data[offsets[b], offsets[b + 1]).  offsets [B + 1] int64, ascending inside [0, total_bytes]: if
+ *   they are not, every file of the call gets SOAR_PNG_BAD_STRUCTURE.  Every file must have this H, W and channels (1: colour type 0,
+ *   3: type 2, 4: type 6); H (1 + W channels) < 2^31, a file is shorter than 2^31 bytes, 0 <= B <= 65535.
+ * out: [B][H][W][channels].  status [B]: 0, or the first fault met in this order -- the chunk walk from the file's start (signature;
+ *   a chunk that does not fit the file; IHDR first, its CRC-32, its fields; every IDAT's CRC-32; IEND), the zlib header, the deflate
+ *   blocks, the bytes behind the final block, the output's length, the Adler-32, the rows' filter bytes.  The image of a failed
+ *   file is all zeros.  Nothing is read outside a file's bytes, nothing is written outside its image and its parts of the workspace.
+ * segments [B]: a file whose IDATs provably begin at block boundaries of the deflate stream is inflated segment by segment, a
+ *   wavefront each.  A candidate is byte 2 of the joined IDAT data Z and every later start p of an IDAT's data, p < |Z|, in front of
+ *   which lie 00 00 FF FF or an IDAT that is exactly one stored block that is not final.  A first pass decodes every candidate from
+ *   its byte without a store: it succeeds if a block that is not final ends at bit 8 p' (p' the next candidate) or, for the last,
+ *   the final block ends with four bytes left, and no match reaches before the segment's own first byte.  If all succeed and their
+ *   lengths sum to H (1 + W channels), a second pass writes each at its offset, and segments[b] counts those that gave a byte;
+ *   otherwise the file is ONE segment from byte 2 and its faults are that decode's. */
+#define SOAR_PNG_OK 0
+#define SOAR_PNG_BAD_STRUCTURE 1      /* signature, truncation, chunk order, no IDAT, a width or height of 0, bad offsets */
+#define SOAR_PNG_UNSUPPORTED 2        /* interlace, depth, colour type 3 or 4, unknown critical chunk, FDICT, another H, W or channels */
+#define SOAR_PNG_BAD_CRC 3            /* of IHDR or an IDAT */
+#define SOAR_PNG_CORRUPT 4            /* the deflate stream: block type 3, LEN / NLEN, a bad code, symbol 286 / 287, distance code 30 / 31,
+                                         a distance before the output's start, the input's end inside the stream */
+#define SOAR_PNG_WRONG_LENGTH 5       /* more or fewer than H (1 + W channels) bytes, or other than 4 bytes behind the final block */
+#define SOAR_PNG_BAD_ADLER 6
+#define SOAR_PNG_BAD_FILTER 7         /* a row's filter byte above 4 */
+typedef struct SoarPngDecodeArgs {
+    int32_t B, H, W, channels;
+    const uint8_t *data;
+    const int64_t *offsets;
+    int64_t total_bytes;
+} SoarPngDecodeArgs;
+int soar_png_decode_workspace_bytes(const SoarPngDecodeArgs *args, size_t *bytes);
+int soar_png_decode(const SoarPngDecodeArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int32_t *status, int32_t *segments,
+                    void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

@@ -14,6 +14,7 @@
 //                    polynomial.  The first piece of an image also writes the signature and IHDR, the last the final IDAT and IEND.
 // A piece is one wavefront's serial work (piece_bytes / 64 steps); the number of pieces is the parallelism.
 #include "mesh_common.h"
+#include "png_common.h"
 
 namespace soar {
 namespace {
@@ -25,8 +26,6 @@ constexpr int HEADER_BITS = 3 + 5 + 5 + 4 + 19 * 3 + 287 * 4;
 constexpr int FIRST_BYTES = 8 + 25 + 2;         // in front of an image's first piece: signature, IHDR, and 78 01 inside its IDAT
 constexpr int LAST_BYTES = 18 + 12;             // behind its last: the final IDAT and IEND
 constexpr int FILTER_THREADS = 256;
-constexpr uint32_t ADLER_MOD = 65521u;
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
 
 struct PngDev {
     const uint8_t *images;
@@ -289,57 +288,6 @@ __device__ __forceinline__ void drain(uint32_t *buf, uint32_t &pos, int lane, co
     w += nbytes;
     pos &= 7u;
     __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t crc_bytes(const uint32_t *tab, uint32_t c, const uint8_t *p, int64_t n)
-{
-    for (int64_t i = 0; i < n; i++) c = tab[(c ^ p[i]) & 255u] ^ (c >> 8);
-    return c;
-}
-
-// a b modulo the CRC's polynomial, bit 31 being x^0
-__device__ __forceinline__ uint32_t mulmod(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0u;
-    for (int i = 31; i >= 0; i--) {
-        if ((a >> i) & 1u) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 k)
-__device__ __forceinline__ uint32_t x8n(int64_t k)
-{
-    uint32_t p = 0x80000000u, base = 0x00800000u;
-    for (; k; k >>= 1) {
-        if (k & 1) p = mulmod(p, base);
-        base = mulmod(base, base);
-    }
-    return p;
-}
-
-// the CRC-32 of out[from, to), which this wavefront has written: lane j runs over the j-th stretch (lane 0 from the all-ones start),
-// the stretch's register is multiplied by x^(8 bytes behind it), and the XOR of all is the register at the end
-__device__ __forceinline__ uint32_t crc_written(const uint32_t *tab, const uint8_t *out, int64_t from, int64_t to, int lane)
-{
-    __threadfence_block();
-    __syncthreads();
-    const int64_t m = to - from, q = (m + WAVE - 1) / WAVE;
-    const int64_t s = min(m, lane * q), e = min(m, s + q);
-    uint32_t c = crc_bytes(tab, lane == 0 ? 0xFFFFFFFFu : 0u, out + from + s, e - s);
-    c = mulmod(c, x8n(m - e));
-    for (int k = 32; k >= 1; k >>= 1) c ^= (uint32_t)__shfl_xor((int)c, k);
-    return ~c;
-}
-
-// two Adler-32 values and the second's length -> the value of the two stretches one after the other
-__device__ __forceinline__ uint32_t adler_join(uint32_t x, uint32_t y, uint32_t len2_mod)
-{
-    const uint32_t A1 = x & 0xFFFFu, B1 = x >> 16, A2 = y & 0xFFFFu, B2 = y >> 16;
-    const uint32_t A = (A1 + A2 + ADLER_MOD - 1u) % ADLER_MOD;
-    const uint32_t B = (uint32_t)((B1 + B2 + (unsigned long long)len2_mod * (A1 + ADLER_MOD - 1u)) % ADLER_MOD);
-    return B << 16 | A;
 }
 
 __global__ void __launch_bounds__(WAVE) emit_kernel(PngDev a)

@@ -111,10 +111,59 @@ class FrameStore:
         return self
 
     @classmethod
-    def from_dataroot(cls, path: str, smpl_type: str = "smplx", device="cuda") -> "FrameStore":
-        """The reference's directory layout (:114-244): ``read_dataroot`` on the host, then ``from_arrays``."""
-        _need_cuda(device, "FrameStore")
+    def from_dataroot(cls, path: str, smpl_type: str = "smplx", device="cuda", device_png: bool = False) -> "FrameStore":
+        """The reference's directory layout (:114-244): ``read_dataroot`` on the host, then ``from_arrays``.  With ``device_png`` the
+        four folders of PNG files are decoded on the device (soar_amd.png.read_png_files: only the files' bytes are uploaded) and
+        ``read_dataroot``'s rules are applied there; the store is the same bit for bit.  That path reads 8-bit grey, RGB and RGBA
+        files only, and every folder's files must agree in size and colour type."""
+        dev = _need_cuda(device, "FrameStore")
+        if device_png:
+            return cls.from_arrays(**cls._read_dataroot_device(path, smpl_type, dev), device=device)
         return cls.from_arrays(**cls.read_dataroot(path, smpl_type), device=device)
+
+    @staticmethod
+    def _read_dataroot_device(path: str, smpl_type: str, dev: torch.device) -> Dict[str, Any]:
+        """``read_dataroot`` with the PNG files decoded on the device: the same lists, rules and messages, on tensors that stay there
+        (``from_arrays`` takes device tensors as they are).  Cameras and body parameters are read on the host as there."""
+        import numpy as np
+        from glob import glob
+        from .png import read_png_files
+        base = os.path.join(path, "train") if smpl_type == "smpl" else path
+        img_list = sorted(glob(os.path.join(base, "images", "*.png")))
+        mask_list = sorted(glob(os.path.join(base, "masks", "*.png")))
+        nf_list = sorted(glob(os.path.join(path, "normal_F", "*.png")))
+        nb_list = sorted(glob(os.path.join(path, "normal_B", "*.png")))
+        if not img_list or not (len(img_list) == len(nf_list) == len(nb_list)):
+            raise ValueError(f"{path}: {len(img_list)} images, {len(nf_list)} normal_F, {len(nb_list)} normal_B: the numbers must agree")
+        img = read_png_files(img_list, dev)
+        if img.shape[-1] == 4:
+            mask, img = img[..., 3], img[..., :3]
+        else:
+            if len(mask_list) != len(img_list):
+                raise ValueError(f"{path}: {len(img_list)} images without alpha but {len(mask_list)} masks")
+            mask = read_png_files(mask_list, dev)[..., 0]
+        if img.shape[-1] == 1:
+            img = img.expand(-1, -1, -1, 3)
+        f = read_png_files(nf_list, dev)
+        if f.shape[-1] != 4:
+            raise ValueError(f"{nf_list[0]}: normal_F needs an alpha channel (the normal mask)")
+        nB = read_png_files(nb_list, dev)[..., :3]
+        if smpl_type == "smpl":
+            cam = np.load(os.path.join(path, "cameras.npz"))
+            Ks, w2c = torch.from_numpy(np.array(cam["intrinsic"])).float(), torch.from_numpy(np.array(cam["extrinsic"])).float()
+            if "normal_intrinsic" not in cam:
+                raise ValueError(f"{path}/cameras.npz has no normal_intrinsic: the crops' rays need the normal maps' intrinsics")
+            normal_Ks = torch.from_numpy(np.array(cam["normal_intrinsic"])).float()
+            sp = dict(np.load(os.path.join(path, "poses_optimized.npz")))
+        else:
+            body = torch.load(os.path.join(path, "smplx", "params.pth"), map_location="cpu")
+            w2c, Ks, normal_Ks, sp = body["w2c"].clone().float(), body["Ks"], body["normal_Ks"], dict(body)
+        if "thetas" in sp:
+            sp["body_pose"], sp["global_orient"] = sp["thetas"][..., 3:], sp["thetas"][..., :3]
+        w2c[1:3] *= -1
+        smpl = {k: torch.as_tensor(sp[k]).float() for k in ("betas", "body_pose", "global_orient", "transl")}
+        return dict(images=img, masks=(mask > 0).to(torch.uint8), normal_F=f[..., :3], normal_B=nB, normal_mask=f[..., 3], Ks=Ks,
+                    normal_Ks=normal_Ks, w2c=w2c, smpl_parms=smpl)
 
     @staticmethod
     def read_dataroot(path: str, smpl_type: str = "smplx") -> Dict[str, Any]:

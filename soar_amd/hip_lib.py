@@ -278,6 +278,12 @@ class SoarPngArgs(C.Structure):
                 ("piece_bytes", C.c_int32), ("images", _vp), ("image_stride", C.c_int64)]
 
 
+class SoarPngDecodeArgs(C.Structure):
+    """Mirror of ``struct SoarPngDecodeArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32), ("data", _vp), ("offsets", _vp),
+                ("total_bytes", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -498,6 +504,8 @@ SIGNATURES = {
     "soar_png_workspace_bytes": (C.c_int, [C.POINTER(SoarPngArgs), C.POINTER(C.c_size_t)]),
     "soar_png_measure": (C.c_int, [C.POINTER(SoarPngArgs), _vp, C.c_size_t, _vp, _vp]),
     "soar_png_emit": (C.c_int, [C.POINTER(SoarPngArgs), _vp, C.c_size_t, _vp, C.c_int64, _vp]),
+    "soar_png_decode_workspace_bytes": (C.c_int, [C.POINTER(SoarPngDecodeArgs), C.POINTER(C.c_size_t)]),
+    "soar_png_decode": (C.c_int, [C.POINTER(SoarPngDecodeArgs), _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

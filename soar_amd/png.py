@@ -1,4 +1,4 @@
-"""PNG output: complete PNG files made on the device (csrc/png.hip), so that only compressed bytes cross to the host.
+"""PNG output and input on the device (csrc/png.hip, csrc/png_decode.hip), so that only compressed bytes cross the bus.
 
 Every stage that ends in a folder of PNGs -- playback, fit inspection, normal maps, masks, evaluation, texture export -- has its uint8
 images on the device already.  PNG is what the reference writes (``save_image``) and what ``FrameStore.read_dataroot`` reads back, so
@@ -13,11 +13,19 @@ the files.
 The deflate stream is cut into independent pieces of ``piece_bytes``, each with a Huffman code of its own over literals and
 run-length matches (distance 1 only); include/soar_hip.h and DESIGN.md 9s state every rule, tests/png_ref.py restates them byte for
 byte.  Any decoder gives the pixels back exactly.  HIP only: CPU tensors are refused, there is no CPU fallback.  Out of scope:
-matches at other distances, 16-bit and palette images, interlacing, ancillary chunks, decoding.
+matches at other distances, 16-bit and palette images, interlacing, ancillary chunks.
+
+Reading: the host reads the files' bytes and uploads them; the chunk walk, the CRCs, inflate, the Adler-32 and the row
+filters run on the device and every file gets a status.
+
+* ``png_info(data)`` -> ``(H, W, C)`` from a file's first bytes, on the host: what sizes the output.
+* ``decode_png(data, offsets, H, W, C, ...)`` -> uint8 ``[B,H,W,C]`` on the device.
+* ``read_png_files(paths, device, chunk=32)`` -> uint8 ``[N,H,W,C]`` on the device.
 """
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
@@ -32,6 +40,7 @@ FILTERS = {"adaptive": -1, 0: 0, 1: 1, 2: 2, 3: 3, 4: 4}
 # files are what is kept, and a millisecond per 8 frames is little next to writing them: the largest piece.
 DEFAULT_PIECE_BYTES = 65535
 _COLOUR_CHANNELS = (1, 3, 4)
+_byref = C.byref                                                   # (decode_png has a parameter C, as png_bound has)
 
 
 def png_bound(H: int, W: int, C: int, piece_bytes: Optional[int] = None) -> int:
@@ -130,3 +139,125 @@ def write_png_files(paths: Sequence[str], images: torch.Tensor, chunk: int = 8) 
             with open(paths[i + b], "wb") as f:
                 f.write(host[off[b]:off[b + 1]])
     return copied
+
+
+# ---- reading --------------------------------------------------------------------------------------------------------------------------
+# a file's status (SOAR_PNG_* of include/soar_hip.h)
+PNG_OK, PNG_BAD_STRUCTURE, PNG_UNSUPPORTED, PNG_BAD_CRC, PNG_CORRUPT, PNG_WRONG_LENGTH, PNG_BAD_ADLER, PNG_BAD_FILTER = range(8)
+PNG_STATUS = {
+    PNG_OK: "ok",
+    PNG_BAD_STRUCTURE: "bad signature or chunk structure (truncated, no IDAT, IHDR not first, a width or height of 0, or bad offsets)",
+    PNG_UNSUPPORTED: "unsupported (interlace, a depth other than 8, colour type 3 or 4, FDICT, or another height, width or colour type "
+                     "than the call's)",
+    PNG_BAD_CRC: "chunk CRC mismatch",
+    PNG_CORRUPT: "corrupt deflate stream",
+    PNG_WRONG_LENGTH: "the stream does not inflate to H (1 + W C) bytes, or bytes follow its final block other than the Adler-32",
+    PNG_BAD_ADLER: "Adler-32 mismatch",
+    PNG_BAD_FILTER: "filter byte above 4",
+}
+_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_CHANNELS_OF_TYPE = {0: 1, 2: 3, 6: 4}
+
+
+def png_info(data: bytes) -> Tuple[int, int, int]:
+    """``(H, W, C)`` of a PNG file from its first 26 bytes, on the host; ``ValueError`` for anything that is not the header of an 8-bit
+    grey, RGB or RGBA file.  (The device checks the same fields again, and the rest of the file.)"""
+    data = bytes(data[:26])
+    if len(data) < 26 or data[:8] != _SIGNATURE or data[12:16] != b"IHDR":
+        raise ValueError("png_info: not the beginning of a PNG file")
+    w, h, depth, colour = struct.unpack(">IIBB", data[16:26])
+    if depth != 8 or colour not in _CHANNELS_OF_TYPE or w < 1 or h < 1:
+        raise ValueError(f"png_info: {w} x {h}, bit depth {depth}, colour type {colour}: only 8-bit colour types 0, 2 and 6 are read")
+    return h, w, _CHANNELS_OF_TYPE[colour]
+
+
+def decode_png(data: torch.Tensor, offsets: torch.Tensor, H: int, W: int, C: int, strict: bool = True, out: Optional[torch.Tensor] = None,
+               return_info: bool = False):
+    """``data``: uint8 1-D on the device, B PNG files one after the other; ``offsets``: int64 ``[B+1]`` on the device, file b being
+    ``data[offsets[b]:offsets[b+1]]``; every file ``H`` x ``W`` with ``C`` = 1 (grey), 3 (RGB) or 4 (RGBA) channels of 8 bits
+    -> uint8 ``[B,H,W,C]`` on the device (``out`` if given).
+
+    Every file gets a status (``PNG_STATUS``); the image of a failed file is zeros.  With ``strict`` the statuses are read back -- the
+    call's one synchronisation -- and a ``ValueError`` names the first failed index and its reason.  With ``strict=False`` nothing is
+    read back and ``(images, status)`` is returned, status int32 ``[B]`` on the device.  ``return_info`` adds ``segments`` (int32
+    ``[B]``: the pieces the file's deflate stream was proven to consist of and was decoded in, 1 for a serial stream)."""
+    for name, t, dt in (("data", data, torch.uint8), ("offsets", offsets, torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+            raise RuntimeError(f"{name} is on '{where}': soar_amd.png runs on HIP devices only; there is no CPU fallback")
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"decode_png: {name} must be a contiguous 1-D {dt} tensor (got {t.dtype} {tuple(t.shape)})")
+    dev = data.device
+    if offsets.device != dev or offsets.numel() < 1:
+        raise ValueError(f"decode_png: offsets must be B + 1 values on {dev}")
+    H, W, ch = int(H), int(W), int(C)
+    if H < 1 or W < 1 or ch not in _COLOUR_CHANNELS:
+        raise ValueError(f"decode_png: need H, W >= 1 and C = 1, 3 or 4 (got {H}, {W}, {C})")
+    B = offsets.numel() - 1
+    if out is None:
+        out = torch.empty((B, H, W, ch), dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, ch) or
+          not out.is_contiguous()):
+        raise ValueError(f"decode_png: out must be a contiguous uint8 [{B},{H},{W},{ch}] tensor on {dev}")
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    segments = torch.empty(B, dtype=torch.int32, device=dev)
+    if B:
+        a = hip_lib.SoarPngDecodeArgs()
+        a.B, a.H, a.W, a.channels, a.total_bytes = B, H, W, ch, data.numel()
+        a.data, a.offsets = hip_lib.ptr(data), offsets.data_ptr()
+        lib = hip_lib.lib()
+        ws = torch.empty(hip_lib._bytes(lib.soar_png_decode_workspace_bytes, "soar_png_decode_workspace_bytes", _byref(a)), dtype=torch.uint8,
+                         device=dev)
+        with torch.cuda.device(dev):
+            if data.numel() == 0:
+                a.data = ws.data_ptr()                            # (no byte of it is read: every file is empty)
+            check(lib.soar_png_decode(_byref(a), ws.data_ptr(), ws.numel(), out.data_ptr(), status.data_ptr(), segments.data_ptr(),
+                                      torch.cuda.current_stream(dev).cuda_stream), "soar_png_decode")
+    if strict:
+        bad = torch.nonzero(status.cpu()).reshape(-1).tolist() if B else []
+        if bad:
+            code = int(status[bad[0]])
+            raise ValueError(f"decode_png: file {bad[0]} of {B}: {PNG_STATUS.get(code, code)} (status {code}); failed files: {bad}")
+        return (out, segments) if return_info else out
+    return (out, status, segments) if return_info else (out, status)
+
+
+def read_png_files(paths: Sequence[str], device="cuda", chunk: int = 32) -> torch.Tensor:
+    """The PNG files ``paths`` (all of one size and colour type) -> uint8 ``[N,H,W,C]`` on the device.  The host reads the files and
+    uploads their bytes, ``chunk`` files per decoder call; nothing is decoded on the host.  Raises with the file's name on any status."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"device is '{dev}': soar_amd.png runs on HIP devices only; there is no CPU fallback")
+    paths = list(paths)
+    if not paths:
+        raise ValueError("read_png_files: no files")
+    blobs, info = [], None
+    for p in paths:
+        with open(p, "rb") as f:
+            blobs.append(f.read())
+        try:
+            here = png_info(blobs[-1])
+        except ValueError as e:
+            raise ValueError(f"{p}: {e}") from None
+        if info is None:
+            info = here
+        elif here != info:
+            raise ValueError(f"{p}: {here[0]} x {here[1]} with {here[2]} channels, but {paths[0]} has {info[0]} x {info[1]} with {info[2]}")
+    H, W, ch = info
+    out = torch.empty((len(paths), H, W, ch), dtype=torch.uint8, device=dev)
+    step, pending = max(1, int(chunk)), []
+    for i in range(0, len(paths), step):
+        part = blobs[i:i + step]
+        off = [0]
+        for b in part:
+            off.append(off[-1] + len(b))
+        data = torch.frombuffer(bytearray(b"".join(part)), dtype=torch.uint8).to(dev, non_blocking=True)
+        offsets = torch.tensor(off, dtype=torch.int64).to(dev, non_blocking=True)
+        _, status = decode_png(data, offsets, H, W, ch, strict=False, out=out[i:i + len(part)])
+        pending.append((i, status))
+    for i, status in pending:                                     # the statuses of all calls, read once they all are queued
+        bad = torch.nonzero(status.cpu()).reshape(-1).tolist()
+        if bad:
+            code = int(status[bad[0]])
+            raise ValueError(f"{paths[i + bad[0]]}: {PNG_STATUS.get(code, code)} (status {code})")
+    return out
