@@ -1852,6 +1852,62 @@ int soar_png_decode_workspace_bytes(const SoarPngDecodeArgs *args, size_t *bytes
 int soar_png_decode(const SoarPngDecodeArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int32_t *status, int32_t *segments,
                     void *stream);
 
+/* ---- JPEG input: marker walk, restart scan, Huffman decode, inverse DCT, upsampling, colour (jpeg_decode.hip, jpeg_entropy.h,
+ *      soar_amd/jpeg.py) ----
+ * B baseline JPEG files, one after the other in one device buffer -> B images of uint8 pixels, each with a status.  SOF0, 8 bit,
+ * Huffman; one component (channels 1), or three (channels 3: YCbCr, luma sampled 1x1, 2x1 or 2x2, chroma 1x1); one interleaved scan;
+ * any DQT (8-bit entries) and DHT tables, any restart interval; APPn, COM and fill bytes skipped, bytes after EOI ignored; a file
+ * without any DHT gets Annex K's four tables (an MJPG chunk of an AVI).  The pixels are libjpeg's, exact in integers: dequantisation,
+ * the slow-but-accurate inverse DCT (jidctint) with clamping to 0 .. 255, "fancy" triangle-filter upsampling with the true
+ * downsampled size as the edge (plain replication where the downsampled width is 2 or less), and the fixed-point YCbCr -> RGB
+ * tables.  Current stream, no synchronisation, no allocation; integer arithmetic only: two calls give the same bytes, and an image's
+ * bytes and status depend neither on B nor on its place.  data, offsets, workspace, out, status and intervals are device memory;
+ * args is host memory.
+ *
+ * data: total_bytes bytes; file b is data[offsets[b], offsets[b + 1]).  offsets [B + 1] int64, ascending inside [0, total_bytes]: if
+ *   they are not, every file of the call gets SOAR_JPEG_BAD_STRUCTURE.  Every file must have this H, W and component count;
+ *   1 <= H, W <= 65535, a file is shorter than 2^31 bytes, 0 <= B <= 65535.
+ * out: [B][H][W][channels].  status [B]: 0, or the first fault of the walk from SOI to the end of SOS; then of the restart scan (inside
+ *   the entropy-coded segment an FF followed by anything but 00 or FF is a marker; the first that is no RSTn ends the segment; the
+ *   RSTn in front of it must number ceil(MCUs / Ri) - 1 and count 0 .. 7 cyclically); then of the intervals: CORRUPT if any interval
+ *   is, else TRUNCATED.  The image of a failed file is all zeros.  Nothing is read outside a file's bytes, nothing is written outside
+ *   its image and its parts of the workspace.
+ * intervals [B]: the restart intervals the file's scan was decoded in, one lane each (1: no restart markers, one lane's serial work);
+ *   0 for a file that failed before its scan was decoded. */
+#define SOAR_JPEG_OK 0
+#define SOAR_JPEG_BAD_STRUCTURE 1     /* no SOI, a segment running past the end, SOS before SOF, a width or height of 0, table ids or
+                                         Huffman counts that are no code, bad offsets */
+#define SOAR_JPEG_UNSUPPORTED 2       /* progressive, extended, lossless, arithmetic; 12 bit; 16-bit quantisers; other component counts or
+                                         sampling factors; several scans; DNL; another H, W or channels than the call's */
+#define SOAR_JPEG_MISSING_TABLE 3     /* the frame or the scan names a table that was never defined */
+#define SOAR_JPEG_CORRUPT 4           /* an invalid Huffman code, a run past coefficient 63, a wrong, missing or misplaced restart marker */
+#define SOAR_JPEG_TRUNCATED 5         /* the data ends before the last MCU */
+typedef struct SoarJpegDecodeArgs {
+    int32_t B, H, W, channels;
+    const uint8_t *data;
+    const int64_t *offsets;
+    int64_t total_bytes;
+} SoarJpegDecodeArgs;
+int soar_jpeg_decode_workspace_bytes(const SoarJpegDecodeArgs *args, size_t *bytes);
+int soar_jpeg_decode(const SoarJpegDecodeArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int32_t *status, int32_t *intervals,
+                     void *stream);
+
+/* ---- resize of 8-bit images by Pillow's rule (image_resize.hip, soar_amd/jpeg.py resize_images) ----
+ * images [B][H][W][channels] uint8 -> out [B][out_h][out_w][channels]: a horizontal pass into temp [B][H][out_w][channels], then a
+ * vertical one.  Per output position of a pass the tables give the first input sample and the count (bounds [n][2] int32) and the
+ * coefficients (coef [n][ksize] int32, 22-bit fixed point); an output is clamp((2^21 + sum sample * coefficient) >> 22, 0, 255).
+ * The tables are the caller's (soar_amd/jpeg.py builds Pillow's bicubic ones: support widened by the scale when shrinking,
+ * normalised in double); bounds that do not fit the axis or ksize give 0.  Everything but args is device memory; current stream,
+ * no synchronisation, no allocation. */
+typedef struct SoarResizeArgs {
+    int32_t B, H, W, channels, out_h, out_w, ksize_h, ksize_v;
+    const uint8_t *images;
+    uint8_t *temp;
+    const int32_t *bounds_h, *coef_h;     /* [out_w][2], [out_w][ksize_h] */
+    const int32_t *bounds_v, *coef_v;     /* [out_h][2], [out_h][ksize_v] */
+} SoarResizeArgs;
+int soar_resize_u8(const SoarResizeArgs *args, uint8_t *out, void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

@@ -284,6 +284,19 @@ class SoarPngDecodeArgs(C.Structure):
                 ("total_bytes", C.c_int64)]
 
 
+class SoarJpegDecodeArgs(C.Structure):
+    """Mirror of ``struct SoarJpegDecodeArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32), ("data", _vp), ("offsets", _vp),
+                ("total_bytes", C.c_int64)]
+
+
+class SoarResizeArgs(C.Structure):
+    """Mirror of ``struct SoarResizeArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("ksize_h", C.c_int32), ("ksize_v", C.c_int32), ("images", _vp), ("temp", _vp), ("bounds_h", _vp), ("coef_h", _vp),
+                ("bounds_v", _vp), ("coef_v", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -506,6 +519,9 @@ SIGNATURES = {
     "soar_png_emit": (C.c_int, [C.POINTER(SoarPngArgs), _vp, C.c_size_t, _vp, C.c_int64, _vp]),
     "soar_png_decode_workspace_bytes": (C.c_int, [C.POINTER(SoarPngDecodeArgs), C.POINTER(C.c_size_t)]),
     "soar_png_decode": (C.c_int, [C.POINTER(SoarPngDecodeArgs), _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "soar_jpeg_decode_workspace_bytes": (C.c_int, [C.POINTER(SoarJpegDecodeArgs), C.POINTER(C.c_size_t)]),
+    "soar_jpeg_decode": (C.c_int, [C.POINTER(SoarJpegDecodeArgs), _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "soar_resize_u8": (C.c_int, [C.POINTER(SoarResizeArgs), _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

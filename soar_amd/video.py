@@ -9,6 +9,8 @@ compressed bytes cross to the host, and the result is one file every player open
 * ``save_jpeg(path, image, ...)``: a still image.
 * ``MjpegWriter``: a context manager; ``write(frames)`` encodes a chunk and appends it to the AVI file.
 * ``read_mjpeg_avi(path)``: the frames' JPEG bytes back, from the file's index, on the host.
+* ``MjpegReader(path)``: ``height``, ``width``, ``fps``, ``frames`` from the headers; ``read(start, stop, step, device)`` yields decoded
+  chunks on the device (``soar_amd.jpeg.decode_jpeg``); ``read_video(path, device)`` is the whole file.
 
 The encoder's rules are libjpeg's, exact in integers (include/soar_hip.h and DESIGN.md 9r state them): with the same tables,
 subsampling and restart interval the entropy-coded bytes are those libjpeg-turbo (Pillow) writes.  HIP only: CPU tensors are refused,
@@ -238,6 +240,92 @@ def read_mjpeg_avi(path: str) -> List[bytes]:
             raise ValueError(f"read_mjpeg_avi: index entry {len(out)} of '{path}' does not point at a '00dc' chunk of its length")
         out.append(d[at + 8:at + 8 + n])
     return out
+
+
+class MjpegReader:
+    """An MJPEG AVI file read back.  ``height``, ``width`` and ``fps`` come from the ``avih`` and ``strh`` headers,
+    ``frames`` from the ``idx1`` index ``read_mjpeg_avi`` walks.  Index entries other than ``00dc`` (audio, a second stream) and
+    zero-length entries (dropped frames) are skipped, so frame numbers count the pictures that are there.  The frames' bytes are
+    uploaded as they are and decoded on the device (``soar_amd.jpeg``): baseline JPEG, grey or 4:4:4 / 4:2:2 / 4:2:0, with or without
+    Huffman tables of their own.  OpenDML files (more than one RIFF chunk) are not read."""
+
+    def __init__(self, path: str):
+        from . import jpeg
+        self.path = path
+        with open(path, "rb") as f:
+            d = f.read()
+        if len(d) < 12 or d[:4] != b"RIFF" or d[8:12] != b"AVI ":
+            raise ValueError(f"MjpegReader: '{path}' is not a RIFF AVI file")
+        self._data = d
+        movi = idx = avih = strh = None
+
+        def walk(p, end):
+            nonlocal movi, idx, avih, strh
+            while p + 8 <= end:
+                cc, n = d[p:p + 4], struct.unpack_from("<I", d, p + 4)[0]
+                if cc == b"LIST" and d[p + 8:p + 12] == b"movi":
+                    movi = p + 8
+                elif cc == b"LIST" and d[p + 8:p + 12] in (b"hdrl", b"strl"):
+                    walk(p + 12, min(end, p + 8 + n))
+                elif cc == b"avih" and avih is None:
+                    avih = p + 8
+                elif cc == b"strh" and strh is None and d[p + 8:p + 12] == b"vids":
+                    strh = p + 8
+                elif cc == b"idx1":
+                    idx = (p + 8, min(n, len(d) - p - 8))
+                p += 8 + n + (n & 1)
+
+        walk(12, len(d))
+        if movi is None or idx is None or avih is None or avih + 40 > len(d):
+            raise ValueError(f"MjpegReader: '{path}' has no 'avih' header, no 'movi' list or no 'idx1' index")
+        usec, self.width, self.height = struct.unpack_from("<I", d, avih)[0], *struct.unpack_from("<II", d, avih + 32)
+        self.fps = 1e6 / usec if usec else 25.0
+        if strh is not None and strh + 28 <= len(d):
+            scale, rate = struct.unpack_from("<II", d, strh + 20)
+            if scale and rate:
+                self.fps = rate / scale
+        self._index: List[Tuple[int, int]] = []                  # (first byte, length) of every picture
+        for e in range(idx[0], idx[0] + idx[1] - 15, 16):
+            cc, _, off, n = struct.unpack_from("<4sIII", d, e)
+            at = movi + off
+            if cc[2:] not in (b"dc", b"db") or cc[:2] != b"00" or n == 0:
+                continue
+            if at + 8 + n > len(d) or struct.unpack_from("<I", d, at + 4)[0] != n:
+                raise ValueError(f"MjpegReader: an index entry of '{path}' does not point at a chunk of its length")
+            self._index.append((at + 8, n))
+        self.frames = len(self._index)
+        self.channels = jpeg.jpeg_info(self.frame_bytes(0))[2] if self.frames else 3
+
+    def frame_bytes(self, i: int) -> bytes:
+        """frame i as the JPEG file it is, on the host"""
+        at, n = self._index[i]
+        return self._data[at:at + n]
+
+    def read(self, start: int = 0, stop: Optional[int] = None, step: int = 1, device="cuda", chunk: int = 8):
+        """yields uint8 ``[n,height,width,C]`` on the device, n <= ``chunk``: the frames ``range(start, stop, step)``"""
+        from . import jpeg
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"device is '{dev}': soar_amd.video runs on HIP devices only; there is no CPU fallback")
+        if int(step) < 1 or int(start) < 0:
+            raise ValueError(f"MjpegReader.read: need start >= 0 and step >= 1 (got {start}, {step})")
+        which = list(range(int(start), self.frames if stop is None else min(int(stop), self.frames), int(step)))
+        for i in range(0, len(which), max(1, int(chunk))):
+            part = which[i:i + max(1, int(chunk))]
+            images, status = jpeg.decode_blobs([self.frame_bytes(k) for k in part], self.height, self.width, self.channels, dev)
+            bad = torch.nonzero(status.cpu()).reshape(-1).tolist()
+            if bad:
+                code = int(status[bad[0]])
+                raise ValueError(f"{self.path}: frame {part[bad[0]]}: {jpeg.JPEG_STATUS.get(code, code)} (status {code})")
+            yield images
+
+
+def read_video(path: str, device="cuda", chunk: int = 8) -> torch.Tensor:
+    """An MJPEG AVI file -> uint8 ``[F,H,W,C]`` on the device"""
+    r = MjpegReader(path)
+    if not r.frames:
+        raise ValueError(f"read_video: '{path}' has no frames")
+    return torch.cat(list(r.read(device=device, chunk=chunk)), dim=0)
 
 
 def write_video(path: str, frames: torch.Tensor, chunk: int = 8, **options) -> MjpegWriter:
