@@ -27,7 +27,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "scripts")]
 
 from playback_time import events  # noqa: E402
 from png_decode_time import synthetic, wall  # noqa: E402
-from soar_amd import jpeg  # noqa: E402
+from soar_amd import codec_io, jpeg  # noqa: E402
 from soar_amd.frames import extract_frames  # noqa: E402
 from soar_amd.video import MjpegWriter, encode_jpeg  # noqa: E402
 
@@ -61,7 +61,7 @@ def main():
 
     for name, blobs in files.items():
         r = res[name] = {"compressed_bytes": sum(len(b) for b in blobs), "raw_bytes": N * H * W * 3}
-        d, o = jpeg._upload(blobs, dev)
+        d, o = codec_io.upload(blobs, dev)
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
         _, status, intervals = jpeg.decode_jpeg(d, o, H, W, 3, strict=False, out=out, return_info=True)
         med, low = events(lambda: jpeg.decode_jpeg(d, o, H, W, 3, strict=False, out=out), 5, warmup=1)
@@ -69,7 +69,7 @@ def main():
                             "intervals_per_file": sorted(set(intervals.tolist())), "all_ok": bool((status == 0).all()),
                             "equal_to_pillow": bool(torch.equal(out, pillow_path(blobs)))}
         one = torch.empty((1, H, W, 3), dtype=torch.uint8, device=dev)
-        d1, o1 = jpeg._upload(blobs[:1], dev)
+        d1, o1 = codec_io.upload(blobs[:1], dev)
         med, low = events(lambda: jpeg.decode_jpeg(d1, o1, H, W, 3, strict=False, out=one), 5, warmup=1)
         r["decode_jpeg_one_file"] = {"ms": med, "min_ms": low}
         cross = r["by_n"] = {}

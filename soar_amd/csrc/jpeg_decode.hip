@@ -16,7 +16,7 @@
 // Bounds hold by construction: a file's bytes are read through jpeg_entropy.h against the file's range, which itself is clamped to
 // the buffer; the marker table has a slot per 8 x 8 block of the image, more than a file of that size can have intervals, and a
 // write to it is checked; a block index is checked against the record's count, which parse() derives from the call's own H and W.
-#include "mesh_common.h"
+#include "codec_common.h"
 #include "jpeg_entropy.h"
 
 namespace soar {
@@ -312,11 +312,7 @@ extern "C" {
 
 int soar_jpeg_decode_workspace_bytes(const SoarJpegDecodeArgs *args, size_t *bytes)
 {
-    Plan p;
-    if (!bytes) { set_error("soar_jpeg_decode_workspace_bytes: NULL bytes"); return 1; }
-    if (!plan_of("soar_jpeg_decode_workspace_bytes", args, nullptr, p)) return 1;
-    *bytes = p.bytes > 0 ? p.bytes : ALIGN;
-    return 0;
+    return workspace_bytes_of("soar_jpeg_decode_workspace_bytes", plan_of, args, bytes);
 }
 
 int soar_jpeg_decode(const SoarJpegDecodeArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int32_t *status, int32_t *intervals,
@@ -327,11 +323,7 @@ int soar_jpeg_decode(const SoarJpegDecodeArgs *args, void *workspace, size_t wor
     if (!plan_of(me, args, workspace, p)) return 1;
     const SoarJpegDecodeArgs &a = *args;
     if (a.B == 0) return 0;
-    if (!a.data || !a.offsets || !out || !status || !intervals) {
-        set_error("%s: NULL data, offsets, out, status or intervals", me);
-        return 1;
-    }
-    if (!workspace_ok(me, workspace, workspace_bytes, p.bytes, "soar_jpeg_decode_workspace_bytes")) return 1;
+    if (!decode_ok(me, a, out, status, intervals, "intervals", workspace, workspace_bytes, p.bytes, "soar_jpeg_decode_workspace_bytes")) return 1;
     p.d.out = out; p.d.status = status; p.d.intervals = intervals;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const unsigned B = (unsigned)a.B;

@@ -13,7 +13,7 @@
 //                    CRC-32 over what was written, 64 stretches in parallel, joined by multiplying with powers of x modulo the CRC's
 //                    polynomial.  The first piece of an image also writes the signature and IHDR, the last the final IDAT and IEND.
 // A piece is one wavefront's serial work (piece_bytes / 64 steps); the number of pieces is the parallelism.
-#include "mesh_common.h"
+#include "codec_common.h"
 #include "png_common.h"
 
 namespace soar {
@@ -246,12 +246,6 @@ __global__ void __launch_bounds__(WAVE) measure_kernel(PngDev a)
     }
 }
 
-__global__ void __launch_bounds__(256) image_offsets_kernel(int32_t B, int64_t np, const int64_t *__restrict__ offs, int64_t *__restrict__ out)
-{
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b <= B) out[b] = offs[(int64_t)b * np];
-}
-
 // ---- emitting -----------------------------------------------------------------------------------------------------------------------
 // where a piece's wavefront may write: [lo, hi) of out
 struct Sink {
@@ -457,8 +451,8 @@ __global__ void __launch_bounds__(WAVE) emit_kernel(PngDev a)
 // ---- the host side ------------------------------------------------------------------------------------------------------------------
 struct Plan {
     PngDev d;
-    void *scan_temp;
-    size_t scan_bytes, bytes;
+    SizeScan scan;
+    size_t bytes;
 };
 
 bool plan_of(const char *me, const SoarPngArgs *args, void *workspace, Plan &p)
@@ -485,11 +479,8 @@ bool plan_of(const char *me, const SoarPngArgs *args, void *workspace, Plan &p)
     d.lens = c.take<uint8_t>((size_t)d.n * LEN_STRIDE);
     d.adler = c.take<uint32_t>(cnt);
     d.payload = c.take<int32_t>(cnt);
-    d.sizes = c.take<int64_t>(cnt);
-    int64_t *offs = c.take<int64_t>(cnt);
-    d.offs = offs;
-    p.scan_bytes = scan_temp_bytes<int64_t>(cnt);
-    p.scan_temp = c.take<char>(p.scan_bytes);
+    carve_size_scan(c, p.scan, cnt);
+    d.sizes = p.scan.sizes; d.offs = p.scan.offs;
     p.bytes = c.bytes();
     d.out = nullptr; d.capacity = 0;
     return true;
@@ -504,11 +495,7 @@ extern "C" {
 
 int soar_png_workspace_bytes(const SoarPngArgs *args, size_t *bytes)
 {
-    Plan p;
-    if (!bytes) { set_error("soar_png_workspace_bytes: NULL bytes"); return 1; }
-    if (!plan_of("soar_png_workspace_bytes", args, nullptr, p)) return 1;
-    *bytes = p.bytes;
-    return 0;
+    return workspace_bytes_of("soar_png_workspace_bytes", plan_of, args, bytes);
 }
 
 int soar_png_measure(const SoarPngArgs *args, void *workspace, size_t workspace_bytes, int64_t *offsets, void *stream_)
@@ -519,24 +506,14 @@ int soar_png_measure(const SoarPngArgs *args, void *workspace, size_t workspace_
     const SoarPngArgs &a = *args;
     if (!offsets) { set_error("%s: NULL offsets", me); return 1; }
     if (!workspace_ok(me, workspace, workspace_bytes, p.bytes, "soar_png_workspace_bytes")) return 1;
-    const int64_t image_bytes = (int64_t)a.H * a.W * a.channels;
-    if (a.B > 0 && (!a.images || (a.B > 1 && a.image_stride < image_bytes))) {
-        set_error("%s: NULL images, or an image stride of %lld bytes shorter than an image of %lld", me, (long long)a.image_stride, (long long)image_bytes);
-        return 1;
-    }
+    if (!batch_ok(me, a.B, a.images, a.image_stride, (int64_t)a.H * a.W * a.channels, "images", "an image")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (a.B == 0) {
-        SOAR_HIP_OK(hipMemsetAsync(offsets, 0, sizeof(int64_t), stream));
-        return 0;
-    }
+    if (a.B == 0) return no_item_offsets(offsets, stream);
     hipLaunchKernelGGL(filter_kernel, dim3((unsigned)a.H, (unsigned)a.B), dim3(FILTER_THREADS), 0, stream, p.d);
     SOAR_LAUNCH_OK("png_filter", stream, 0);
     hipLaunchKernelGGL(measure_kernel, dim3((unsigned)p.d.n), dim3(WAVE), 0, stream, p.d);
     SOAR_LAUNCH_OK("png_measure", stream, 0);
-    SOAR_HIP_OK(exclusive_scan_sum(p.scan_temp, p.scan_bytes, p.d.sizes, const_cast<int64_t *>(p.d.offs), (size_t)p.d.n + 1, stream));
-    hipLaunchKernelGGL(image_offsets_kernel, dim3((unsigned)(a.B + 256) / 256), dim3(256), 0, stream, a.B, (int64_t)p.d.np, p.d.offs, offsets);
-    SOAR_LAUNCH_OK("png_image_offsets", stream, 0);
-    return 0;
+    return item_offsets("png_image_offsets", p.scan, a.B, p.d.np, offsets, stream);
 }
 
 int soar_png_emit(const SoarPngArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int64_t capacity, void *stream_)
@@ -544,7 +521,7 @@ int soar_png_emit(const SoarPngArgs *args, void *workspace, size_t workspace_byt
     const char *me = "soar_png_emit";
     Plan p;
     if (!plan_of(me, args, workspace, p)) return 1;
-    if (capacity < 0 || (capacity > 0 && !out)) { set_error("%s: bad arguments (capacity=%lld with out %s)", me, (long long)capacity, out ? "given" : "NULL"); return 1; }
+    if (!emit_out_ok(me, out, capacity)) return 1;
     if (!workspace_ok(me, workspace, workspace_bytes, p.bytes, "soar_png_workspace_bytes")) return 1;
     if (args->B == 0) return 0;
     p.d.out = out; p.d.capacity = capacity;

@@ -22,7 +22,7 @@
 // Bounds hold by construction: a file's bytes are read through rd() against the file's range, which itself is clamped to the buffer;
 // Z is written inside the file's slot (as long as the file) and read through png_inflate.h's checked reader; every sink checks a store
 // against the segment's stretch of the filtered stream, and every stretch against the stream.
-#include "mesh_common.h"
+#include "codec_common.h"
 #include "png_common.h"
 #include "png_inflate.h"
 
@@ -505,11 +505,7 @@ extern "C" {
 
 int soar_png_decode_workspace_bytes(const SoarPngDecodeArgs *args, size_t *bytes)
 {
-    Plan p;
-    if (!bytes) { set_error("soar_png_decode_workspace_bytes: NULL bytes"); return 1; }
-    if (!plan_of("soar_png_decode_workspace_bytes", args, nullptr, p)) return 1;
-    *bytes = p.bytes > 0 ? p.bytes : ALIGN;
-    return 0;
+    return workspace_bytes_of("soar_png_decode_workspace_bytes", plan_of, args, bytes);
 }
 
 int soar_png_decode(const SoarPngDecodeArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int32_t *status, int32_t *segments,
@@ -520,11 +516,7 @@ int soar_png_decode(const SoarPngDecodeArgs *args, void *workspace, size_t works
     if (!plan_of(me, args, workspace, p)) return 1;
     const SoarPngDecodeArgs &a = *args;
     if (a.B == 0) return 0;
-    if (!a.data || !a.offsets || !out || !status || !segments) {
-        set_error("%s: NULL data, offsets, out, status or segments", me);
-        return 1;
-    }
-    if (!workspace_ok(me, workspace, workspace_bytes, p.bytes, "soar_png_decode_workspace_bytes")) return 1;
+    if (!decode_ok(me, a, out, status, segments, "segments", workspace, workspace_bytes, p.bytes, "soar_png_decode_workspace_bytes")) return 1;
     p.d.out = out; p.d.status = status; p.d.segments = segments;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const unsigned strided = (unsigned)std::min<int64_t>(p.d.E, MAX_BLOCKS);

@@ -12,7 +12,7 @@
 //                      go through a scan), once writing at the final offsets (soar_jpeg_emit).  Coding twice was chosen over a buffer of
 //                      unstuffed bits, which would have to hold the worst case (208 bytes a block) and be written and read back.
 // An interval is one wavefront's serial work: a large restart_interval is correct and slow (one wavefront per frame at the extreme).
-#include "mesh_common.h"
+#include "codec_common.h"
 
 namespace soar {
 namespace {
@@ -359,20 +359,13 @@ __global__ void __launch_bounds__(WAVE) entropy_kernel(EntropyDev a)
     }
 }
 
-__global__ void __launch_bounds__(256) frame_offsets_kernel(int32_t B, int64_t n_int, const int64_t *__restrict__ offs, int64_t *__restrict__ out)
-{
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b <= B) out[b] = offs[(int64_t)b * n_int];
-}
-
 // ---- the host side ------------------------------------------------------------------------------------------------------------------
 struct Plan {
     int hs, bpm, mcux, mcuy;
     int64_t nmcu, n_int, n;
     int16_t *coef;
-    int64_t *sizes, *offs;
-    void *scan_temp;
-    size_t scan_bytes, bytes;
+    SizeScan scan;
+    size_t bytes;
 };
 
 bool plan_of(const char *me, const SoarJpegArgs *args, void *workspace, Plan &p)
@@ -399,10 +392,7 @@ bool plan_of(const char *me, const SoarJpegArgs *args, void *workspace, Plan &p)
     const size_t cnt = (size_t)p.n + 1;
     Carver c(workspace);
     p.coef = c.take<int16_t>((size_t)a.B * (size_t)p.nmcu * p.bpm * 64 + 64);
-    p.sizes = c.take<int64_t>(cnt);
-    p.offs = c.take<int64_t>(cnt);
-    p.scan_bytes = scan_temp_bytes<int64_t>(cnt);
-    p.scan_temp = c.take<char>(p.scan_bytes);
+    carve_size_scan(c, p.scan, cnt);
     p.bytes = c.bytes();
     return true;
 }
@@ -445,7 +435,7 @@ int build_header(const SoarJpegArgs &a, uint8_t *out)
 
 void entropy_args(const SoarJpegArgs &a, const Plan &p, EntropyDev &d)
 {
-    d.coef = p.coef; d.sizes = p.sizes; d.offs = p.offs; d.out = nullptr; d.capacity = 0;
+    d.coef = p.coef; d.sizes = p.scan.sizes; d.offs = p.scan.offs; d.out = nullptr; d.capacity = 0;
     d.n_int = p.n_int; d.nmcu = p.nmcu; d.n = p.n; d.ri = a.restart_interval; d.bpm = p.bpm;
 }
 
@@ -458,11 +448,7 @@ extern "C" {
 
 int soar_jpeg_workspace_bytes(const SoarJpegArgs *args, size_t *bytes)
 {
-    Plan p;
-    if (!bytes) { set_error("soar_jpeg_workspace_bytes: NULL bytes"); return 1; }
-    if (!plan_of("soar_jpeg_workspace_bytes", args, nullptr, p)) return 1;
-    *bytes = p.bytes;
-    return 0;
+    return workspace_bytes_of("soar_jpeg_workspace_bytes", plan_of, args, bytes);
 }
 
 int soar_jpeg_measure(const SoarJpegArgs *args, void *workspace, size_t workspace_bytes, int64_t *offsets, void *stream_)
@@ -473,16 +459,9 @@ int soar_jpeg_measure(const SoarJpegArgs *args, void *workspace, size_t workspac
     const SoarJpegArgs &a = *args;
     if (!offsets) { set_error("%s: NULL offsets", me); return 1; }
     if (!workspace_ok(me, workspace, workspace_bytes, p.bytes, "soar_jpeg_workspace_bytes")) return 1;
-    const int64_t frame_bytes = (int64_t)a.H * a.W * a.channels;
-    if (a.B > 0 && (!a.frames || (a.B > 1 && a.frame_stride < frame_bytes))) {
-        set_error("%s: NULL frames, or a frame stride of %lld bytes shorter than a frame of %lld", me, (long long)a.frame_stride, (long long)frame_bytes);
-        return 1;
-    }
+    if (!batch_ok(me, a.B, a.frames, a.frame_stride, (int64_t)a.H * a.W * a.channels, "frames", "a frame")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (a.B == 0) {
-        SOAR_HIP_OK(hipMemsetAsync(offsets, 0, sizeof(int64_t), stream));
-        return 0;
-    }
+    if (a.B == 0) return no_item_offsets(offsets, stream);
     TransformDev t;
     t.frames = a.frames; t.stride = a.frame_stride; t.H = a.H; t.W = a.W; t.C = a.channels;
     t.wide = a.channels == 4 && ((uintptr_t)a.frames & 3) == 0 && (a.frame_stride & 3) == 0;
@@ -499,10 +478,7 @@ int soar_jpeg_measure(const SoarJpegArgs *args, void *workspace, size_t workspac
     entropy_args(a, p, d);
     hipLaunchKernelGGL(entropy_kernel<false>, dim3((unsigned)p.n), dim3(WAVE), 0, stream, d);
     SOAR_LAUNCH_OK("jpeg_measure", stream, 0);
-    SOAR_HIP_OK(exclusive_scan_sum(p.scan_temp, p.scan_bytes, p.sizes, p.offs, (size_t)p.n + 1, stream));
-    hipLaunchKernelGGL(frame_offsets_kernel, dim3((unsigned)(a.B + 256) / 256), dim3(256), 0, stream, a.B, p.n_int, p.offs, offsets);
-    SOAR_LAUNCH_OK("jpeg_frame_offsets", stream, 0);
-    return 0;
+    return item_offsets("jpeg_frame_offsets", p.scan, a.B, p.n_int, offsets, stream);
 }
 
 int soar_jpeg_emit(const SoarJpegArgs *args, void *workspace, size_t workspace_bytes, uint8_t *out, int64_t capacity, void *stream_)
@@ -511,7 +487,7 @@ int soar_jpeg_emit(const SoarJpegArgs *args, void *workspace, size_t workspace_b
     Plan p;
     if (!plan_of(me, args, workspace, p)) return 1;
     const SoarJpegArgs &a = *args;
-    if (capacity < 0 || (capacity > 0 && !out)) { set_error("%s: bad arguments (capacity=%lld with out %s)", me, (long long)capacity, out ? "given" : "NULL"); return 1; }
+    if (!emit_out_ok(me, out, capacity)) return 1;
     if (!workspace_ok(me, workspace, workspace_bytes, p.bytes, "soar_jpeg_workspace_bytes")) return 1;
     if (a.B == 0) return 0;
     EntropyDev d;

@@ -15,10 +15,12 @@ rules, tests/jpeg_decode_ref.py restates them.  The resize is Pillow's ``Image.r
 A file's restart intervals are decoded in parallel, one lane each; a file without restart markers is one lane's serial work, correct
 and slow.  HIP only: CPU tensors are refused, there is no CPU fallback.  Out of scope: progressive, extended, lossless and arithmetic
 files, 12 bit, four components, other sampling factors, several scans, EXIF orientation.
+
+The plumbing around the kernels that PNG needs as well (guards, upload, the decoder's call, statuses, file lists) is in ``codec_io.py``.
 """
 from __future__ import annotations
 
-import ctypes as C
+import ctypes
 import functools
 import math
 from typing import Optional, Sequence, Tuple
@@ -26,7 +28,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip_lib
+from . import codec_io, hip_lib
 from .hip_lib import check
 
 # a file's status (SOAR_JPEG_* of include/soar_hip.h)
@@ -41,7 +43,6 @@ JPEG_STATUS = {
     JPEG_TRUNCATED: "truncated: the data ends before the last MCU",
 }
 _SUBSAMPLING = {(1, 1): "444", (2, 1): "422", (2, 2): "420"}
-_byref = C.byref                                                   # (decode_jpeg has a parameter C)
 
 
 def jpeg_info(data: bytes) -> Tuple[int, int, int, str]:
@@ -91,97 +92,21 @@ def decode_jpeg(data: torch.Tensor, offsets: torch.Tensor, H: int, W: int, C: in
     call's one synchronisation -- and a ``ValueError`` names the first failed index and its reason.  With ``strict=False`` nothing is
     read back and ``(images, status)`` is returned, status int32 ``[B]`` on the device.  ``return_info`` adds ``intervals`` (int32
     ``[B]``: the restart intervals the file was decoded in, in parallel; 1 for a file without restart markers)."""
-    for name, t, dt in (("data", data, torch.uint8), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-            raise RuntimeError(f"{name} is on '{where}': soar_amd.jpeg runs on HIP devices only; there is no CPU fallback")
-        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"decode_jpeg: {name} must be a contiguous 1-D {dt} tensor (got {t.dtype} {tuple(t.shape)})")
-    dev = data.device
-    if offsets.device != dev or offsets.numel() < 2:
-        raise ValueError(f"decode_jpeg: offsets must be B + 1 values on {dev}, B >= 1")
-    H, W, ch = int(H), int(W), int(C)
-    if not (1 <= H <= 65535 and 1 <= W <= 65535) or ch not in (1, 3):
-        raise ValueError(f"decode_jpeg: need 1 <= H, W <= 65535 and C = 1 or 3 (got {H}, {W}, {C})")
-    B = offsets.numel() - 1
-    if B > 65535:
-        raise ValueError(f"decode_jpeg: at most 65535 files per call (got {B})")
-    if out is None:
-        out = torch.empty((B, H, W, ch), dtype=torch.uint8, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, ch) or
-          not out.is_contiguous()):
-        raise ValueError(f"decode_jpeg: out must be a contiguous uint8 [{B},{H},{W},{ch}] tensor on {dev}")
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    intervals = torch.empty(B, dtype=torch.int32, device=dev)
-    a = hip_lib.SoarJpegDecodeArgs()
-    a.B, a.H, a.W, a.channels, a.total_bytes = B, H, W, ch, data.numel()
-    a.data, a.offsets = hip_lib.ptr(data), offsets.data_ptr()
-    lib = hip_lib.lib()
-    ws = torch.empty(hip_lib._bytes(lib.soar_jpeg_decode_workspace_bytes, "soar_jpeg_decode_workspace_bytes", _byref(a)), dtype=torch.uint8,
-                     device=dev)
-    with torch.cuda.device(dev):
-        if data.numel() == 0:
-            a.data = ws.data_ptr()                                # (no byte of it is read: every file is empty)
-        check(lib.soar_jpeg_decode(_byref(a), ws.data_ptr(), ws.numel(), out.data_ptr(), status.data_ptr(), intervals.data_ptr(),
-                                   torch.cuda.current_stream(dev).cuda_stream), "soar_jpeg_decode")
-    if strict:
-        bad = torch.nonzero(status.cpu()).reshape(-1).tolist()
-        if bad:
-            code = int(status[bad[0]])
-            raise ValueError(f"decode_jpeg: file {bad[0]} of {B}: {JPEG_STATUS.get(code, code)} (status {code}); failed files: {bad}")
-        return (out, intervals) if return_info else out
-    return (out, status, intervals) if return_info else (out, status)
-
-
-def _upload(blobs, dev):
-    off = [0]
-    for b in blobs:
-        off.append(off[-1] + len(b))
-    data = torch.frombuffer(bytearray(b"".join(blobs) or b"\x00"), dtype=torch.uint8)[:off[-1]].to(dev, non_blocking=True)
-    return data, torch.tensor(off, dtype=torch.int64).to(dev, non_blocking=True)
+    return codec_io.decode("decode_jpeg", "jpeg", hip_lib.SoarJpegDecodeArgs(), ("soar_jpeg_decode_workspace_bytes", "soar_jpeg_decode"), JPEG_STATUS,
+                           data, offsets, H, W, C, strict, out, return_info, channels=(1, 3), sizes_capped=True, empty_ok=False, files_capped=True)
 
 
 def decode_blobs(blobs: Sequence[bytes], H: int, W: int, C: int, device, out: Optional[torch.Tensor] = None):
     """JPEG files as host bytes -> ``(images, status)`` on the device, nothing read back (``decode_jpeg`` with ``strict=False``)"""
-    data, offsets = _upload(blobs, torch.device(device))
-    return decode_jpeg(data, offsets, H, W, C, strict=False, out=out)
+    return decode_jpeg(*codec_io.upload(blobs, torch.device(device)), H, W, C, strict=False, out=out)
 
 
 def read_jpeg_files(paths: Sequence[str], device="cuda", chunk: int = 32) -> torch.Tensor:
     """The JPEG files ``paths`` (all of one size and component count; the subsampling may differ) -> uint8 ``[N,H,W,C]`` on the device.
     The host reads the files and uploads their bytes, ``chunk`` files per decoder call; nothing is decoded on the host.  Raises with
     the file's name on any status."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"device is '{dev}': soar_amd.jpeg runs on HIP devices only; there is no CPU fallback")
-    paths = list(paths)
-    if not paths:
-        raise ValueError("read_jpeg_files: no files")
-    blobs, info = [], None
-    for p in paths:
-        with open(p, "rb") as f:
-            blobs.append(f.read())
-        try:
-            here = jpeg_info(blobs[-1])[:3]
-        except ValueError as e:
-            raise ValueError(f"{p}: {e}") from None
-        if info is None:
-            info = here
-        elif here != info:
-            raise ValueError(f"{p}: {here[0]} x {here[1]} with {here[2]} components, but {paths[0]} has {info[0]} x {info[1]} with {info[2]}")
-    H, W, ch = info
-    out = torch.empty((len(paths), H, W, ch), dtype=torch.uint8, device=dev)
-    step, pending = max(1, int(chunk)), []
-    for i in range(0, len(paths), step):
-        part = blobs[i:i + step]
-        _, status = decode_blobs(part, H, W, ch, dev, out=out[i:i + len(part)])
-        pending.append((i, status))
-    for i, status in pending:                                     # the statuses of all calls, read once they all are queued
-        bad = torch.nonzero(status.cpu()).reshape(-1).tolist()
-        if bad:
-            code = int(status[bad[0]])
-            raise ValueError(f"{paths[i + bad[0]]}: {JPEG_STATUS.get(code, code)} (status {code})")
-    return out
+    return codec_io.read_files("read_jpeg_files", "jpeg", paths, device, chunk, lambda blob: jpeg_info(blob)[:3], "components", decode_jpeg,
+                               JPEG_STATUS)
 
 
 # ---- resize -------------------------------------------------------------------------------------------------------------------------
@@ -231,9 +156,7 @@ def resize_images(images: torch.Tensor, height: int, width: Optional[int] = None
     """``images``: uint8 ``[B,H,W,C]`` on the device, C = 1 .. 4 -> uint8 ``[B,height,width,C]``: Pillow's
     ``Image.resize((width, height), Image.BICUBIC)``, bit for bit (a horizontal pass into 8 bits, then a vertical one).  ``width``:
     ``round(W * height / H)`` when not given, at least 1.  No synchronisation."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda:
-        where = images.device if isinstance(images, torch.Tensor) else type(images).__name__
-        raise RuntimeError(f"images is on '{where}': soar_amd.jpeg runs on HIP devices only; there is no CPU fallback")
+    codec_io.need_hip_tensor("images", images, "jpeg")
     if images.dim() != 4 or images.dtype != torch.uint8 or not 1 <= images.shape[3] <= 4 or images.shape[1] < 1 or images.shape[2] < 1:
         raise ValueError(f"resize_images: images must be uint8 [B,H,W,C] with C = 1 .. 4 (got {images.dtype} {tuple(images.shape)})")
     B, H, W, ch = images.shape
@@ -255,5 +178,5 @@ def resize_images(images: torch.Tensor, height: int, width: Optional[int] = None
     a.images, a.temp = images.data_ptr(), temp.data_ptr()
     a.bounds_h, a.coef_h, a.bounds_v, a.coef_v = (t.data_ptr() for t in tables)
     with torch.cuda.device(dev):
-        check(hip_lib.lib().soar_resize_u8(_byref(a), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "soar_resize_u8")
+        check(hip_lib.lib().soar_resize_u8(ctypes.byref(a), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "soar_resize_u8")
     return out

@@ -21,17 +21,17 @@ filters run on the device and every file gets a status.
 * ``png_info(data)`` -> ``(H, W, C)`` from a file's first bytes, on the host: what sizes the output.
 * ``decode_png(data, offsets, H, W, C, ...)`` -> uint8 ``[B,H,W,C]`` on the device.
 * ``read_png_files(paths, device, chunk=32)`` -> uint8 ``[N,H,W,C]`` on the device.
+
+The plumbing around the kernels that JPEG needs as well (guards, measure and emit, statuses, file lists) is in ``codec_io.py``.
 """
 from __future__ import annotations
 
-import ctypes as C
 import struct
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import hip_lib
-from .hip_lib import check
+from . import codec_io, hip_lib
 
 FILTERS = {"adaptive": -1, 0: 0, 1: 1, 2: 2, 3: 3, 4: 4}
 # A piece is one wavefront's serial work and pays 153 bytes of block header.  Measured on 8 RGBA frames of 1080 x 1920 of the playback
@@ -40,7 +40,6 @@ FILTERS = {"adaptive": -1, 0: 0, 1: 1, 2: 2, 3: 3, 4: 4}
 # files are what is kept, and a millisecond per 8 frames is little next to writing them: the largest piece.
 DEFAULT_PIECE_BYTES = 65535
 _COLOUR_CHANNELS = (1, 3, 4)
-_byref = C.byref                                                   # (decode_png has a parameter C, as png_bound has)
 
 
 def png_bound(H: int, W: int, C: int, piece_bytes: Optional[int] = None) -> int:
@@ -54,10 +53,8 @@ def png_bound(H: int, W: int, C: int, piece_bytes: Optional[int] = None) -> int:
     return 8 + 25 + 2 + ((S + P - 1) // P) * 17 + S + 18 + 12
 
 
-def _args_of(images: torch.Tensor, filters, piece_bytes: Optional[int]):
-    if not isinstance(images, torch.Tensor) or not images.is_cuda:
-        where = images.device if isinstance(images, torch.Tensor) else type(images).__name__
-        raise RuntimeError(f"images is on '{where}': soar_amd.png runs on HIP devices only; there is no CPU fallback")
+def _encode(images, filters, piece_bytes, out):
+    codec_io.need_hip_tensor("images", images, "png")
     if images.dim() != 4 or images.dtype != torch.uint8 or images.shape[3] not in _COLOUR_CHANNELS:
         raise ValueError(f"encode_png: images must be uint8 [B,H,W,1], [B,H,W,3] or [B,H,W,4] (got {images.dtype} {tuple(images.shape)})")
     if isinstance(filters, bool) or filters not in FILTERS:
@@ -65,38 +62,10 @@ def _args_of(images: torch.Tensor, filters, piece_bytes: Optional[int]):
     P = DEFAULT_PIECE_BYTES if piece_bytes is None else int(piece_bytes)
     if not 32 <= P <= 65535:
         raise ValueError(f"encode_png: piece_bytes must be 32 .. 65535 (got {piece_bytes})")
-    B, H, W, ch = images.shape
-    if not (1 <= H <= 65535 and 1 <= W <= 65535 and B <= 65535):
-        raise ValueError(f"encode_png: need 1 <= H, W <= 65535 and B <= 65535 (got {tuple(images.shape)})")
-    images = images.detach()
-    # every image contiguous; the step from image to image is free
-    if B and not (images[0].is_contiguous() and (B < 2 or images.stride(0) >= H * W * ch)):
-        images = images.contiguous()
     a = hip_lib.SoarPngArgs()
-    a.B, a.H, a.W, a.channels, a.filter, a.piece_bytes = B, H, W, ch, FILTERS[filters], P
-    a.images = images.data_ptr() if B else None
-    a.image_stride = images.stride(0) if B > 1 else H * W * ch
-    return a, images
-
-
-def _encode(images, filters, piece_bytes, out):
-    a, images = _args_of(images, filters, piece_bytes)
-    dev = images.device
-    if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.dim() != 1 or
-                            not out.is_contiguous()):
-        raise ValueError(f"encode_png: out must be a contiguous 1-D uint8 tensor on {dev}")
-    lib = hip_lib.lib()
-    ws = torch.empty(hip_lib._bytes(lib.soar_png_workspace_bytes, "soar_png_workspace_bytes", C.byref(a)), dtype=torch.uint8, device=dev)
-    offsets = torch.empty(a.B + 1, dtype=torch.int64, device=dev)
-    host = None
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        check(lib.soar_png_measure(C.byref(a), ws.data_ptr(), ws.numel(), offsets.data_ptr(), stream), "soar_png_measure")
-        if out is None:
-            host = offsets.cpu()                                  # the one read-back: B + 1 offsets
-            out = torch.empty(int(host[-1]), dtype=torch.uint8, device=dev)
-        check(lib.soar_png_emit(C.byref(a), ws.data_ptr(), ws.numel(), hip_lib.ptr(out), out.numel(), stream), "soar_png_emit")
-    return out, offsets, host
+    a.B, a.H, a.W, a.channels, a.filter, a.piece_bytes = *images.shape, FILTERS[filters], P
+    images, a.images, a.image_stride = codec_io.batch_view("encode_png", images)
+    return codec_io.measure_and_emit("encode_png", a, ("soar_png_workspace_bytes", "soar_png_measure", "soar_png_emit"), a.B, images.device, out)
 
 
 def encode_png(images: torch.Tensor, filters: Union[str, int] = "adaptive", piece_bytes: Optional[int] = None,
@@ -132,12 +101,11 @@ def write_png_files(paths: Sequence[str], images: torch.Tensor, chunk: int = 8) 
     step, copied = max(1, int(chunk)), 0
     for i in range(0, len(paths), step):
         data, _, offsets = _encode(images[i:i + step] if isinstance(images, torch.Tensor) else images, "adaptive", None, None)
-        host = data.cpu().numpy().tobytes()
-        copied += len(host)
-        off = offsets.tolist()                                    # (the host copy of the offsets that sized data)
-        for b in range(len(off) - 1):
-            with open(paths[i + b], "wb") as f:
-                f.write(host[off[b]:off[b + 1]])
+        files, n = codec_io.host_items(data, offsets)
+        copied += n
+        for path, file in zip(paths[i:], files):
+            with open(path, "wb") as f:
+                f.write(file)
     return copied
 
 
@@ -181,83 +149,12 @@ def decode_png(data: torch.Tensor, offsets: torch.Tensor, H: int, W: int, C: int
     call's one synchronisation -- and a ``ValueError`` names the first failed index and its reason.  With ``strict=False`` nothing is
     read back and ``(images, status)`` is returned, status int32 ``[B]`` on the device.  ``return_info`` adds ``segments`` (int32
     ``[B]``: the pieces the file's deflate stream was proven to consist of and was decoded in, 1 for a serial stream)."""
-    for name, t, dt in (("data", data, torch.uint8), ("offsets", offsets, torch.int64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-            raise RuntimeError(f"{name} is on '{where}': soar_amd.png runs on HIP devices only; there is no CPU fallback")
-        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"decode_png: {name} must be a contiguous 1-D {dt} tensor (got {t.dtype} {tuple(t.shape)})")
-    dev = data.device
-    if offsets.device != dev or offsets.numel() < 1:
-        raise ValueError(f"decode_png: offsets must be B + 1 values on {dev}")
-    H, W, ch = int(H), int(W), int(C)
-    if H < 1 or W < 1 or ch not in _COLOUR_CHANNELS:
-        raise ValueError(f"decode_png: need H, W >= 1 and C = 1, 3 or 4 (got {H}, {W}, {C})")
-    B = offsets.numel() - 1
-    if out is None:
-        out = torch.empty((B, H, W, ch), dtype=torch.uint8, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, ch) or
-          not out.is_contiguous()):
-        raise ValueError(f"decode_png: out must be a contiguous uint8 [{B},{H},{W},{ch}] tensor on {dev}")
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    segments = torch.empty(B, dtype=torch.int32, device=dev)
-    if B:
-        a = hip_lib.SoarPngDecodeArgs()
-        a.B, a.H, a.W, a.channels, a.total_bytes = B, H, W, ch, data.numel()
-        a.data, a.offsets = hip_lib.ptr(data), offsets.data_ptr()
-        lib = hip_lib.lib()
-        ws = torch.empty(hip_lib._bytes(lib.soar_png_decode_workspace_bytes, "soar_png_decode_workspace_bytes", _byref(a)), dtype=torch.uint8,
-                         device=dev)
-        with torch.cuda.device(dev):
-            if data.numel() == 0:
-                a.data = ws.data_ptr()                            # (no byte of it is read: every file is empty)
-            check(lib.soar_png_decode(_byref(a), ws.data_ptr(), ws.numel(), out.data_ptr(), status.data_ptr(), segments.data_ptr(),
-                                      torch.cuda.current_stream(dev).cuda_stream), "soar_png_decode")
-    if strict:
-        bad = torch.nonzero(status.cpu()).reshape(-1).tolist() if B else []
-        if bad:
-            code = int(status[bad[0]])
-            raise ValueError(f"decode_png: file {bad[0]} of {B}: {PNG_STATUS.get(code, code)} (status {code}); failed files: {bad}")
-        return (out, segments) if return_info else out
-    return (out, status, segments) if return_info else (out, status)
+    return codec_io.decode("decode_png", "png", hip_lib.SoarPngDecodeArgs(), ("soar_png_decode_workspace_bytes", "soar_png_decode"), PNG_STATUS,
+                           data, offsets, H, W, C, strict, out, return_info, channels=_COLOUR_CHANNELS, sizes_capped=False, empty_ok=True,
+                           files_capped=False)
 
 
 def read_png_files(paths: Sequence[str], device="cuda", chunk: int = 32) -> torch.Tensor:
     """The PNG files ``paths`` (all of one size and colour type) -> uint8 ``[N,H,W,C]`` on the device.  The host reads the files and
     uploads their bytes, ``chunk`` files per decoder call; nothing is decoded on the host.  Raises with the file's name on any status."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"device is '{dev}': soar_amd.png runs on HIP devices only; there is no CPU fallback")
-    paths = list(paths)
-    if not paths:
-        raise ValueError("read_png_files: no files")
-    blobs, info = [], None
-    for p in paths:
-        with open(p, "rb") as f:
-            blobs.append(f.read())
-        try:
-            here = png_info(blobs[-1])
-        except ValueError as e:
-            raise ValueError(f"{p}: {e}") from None
-        if info is None:
-            info = here
-        elif here != info:
-            raise ValueError(f"{p}: {here[0]} x {here[1]} with {here[2]} channels, but {paths[0]} has {info[0]} x {info[1]} with {info[2]}")
-    H, W, ch = info
-    out = torch.empty((len(paths), H, W, ch), dtype=torch.uint8, device=dev)
-    step, pending = max(1, int(chunk)), []
-    for i in range(0, len(paths), step):
-        part = blobs[i:i + step]
-        off = [0]
-        for b in part:
-            off.append(off[-1] + len(b))
-        data = torch.frombuffer(bytearray(b"".join(part)), dtype=torch.uint8).to(dev, non_blocking=True)
-        offsets = torch.tensor(off, dtype=torch.int64).to(dev, non_blocking=True)
-        _, status = decode_png(data, offsets, H, W, ch, strict=False, out=out[i:i + len(part)])
-        pending.append((i, status))
-    for i, status in pending:                                     # the statuses of all calls, read once they all are queued
-        bad = torch.nonzero(status.cpu()).reshape(-1).tolist()
-        if bad:
-            code = int(status[bad[0]])
-            raise ValueError(f"{paths[i + bad[0]]}: {PNG_STATUS.get(code, code)} (status {code})")
-    return out
+    return codec_io.read_files("read_png_files", "png", paths, device, chunk, png_info, "channels", decode_png, PNG_STATUS)

@@ -12,6 +12,8 @@ compressed bytes cross to the host, and the result is one file every player open
 * ``MjpegReader(path)``: ``height``, ``width``, ``fps``, ``frames`` from the headers; ``read(start, stop, step, device)`` yields decoded
   chunks on the device (``soar_amd.jpeg.decode_jpeg``); ``read_video(path, device)`` is the whole file.
 
+The plumbing around the kernels that PNG needs as well (guards, measure and emit, statuses, bytes to the host) is in ``codec_io.py``.
+
 The encoder's rules are libjpeg's, exact in integers (include/soar_hip.h and DESIGN.md 9r state them): with the same tables,
 subsampling and restart interval the entropy-coded bytes are those libjpeg-turbo (Pillow) writes.  HIP only: CPU tensors are refused,
 there is no CPU fallback.  Out of scope: H.264 / MP4, progressive or optimised-Huffman JPEG, 4:2:2, audio, OpenDML AVI (files of
@@ -19,15 +21,14 @@ there is no CPU fallback.  Out of scope: H.264 / MP4, progressive or optimised-H
 """
 from __future__ import annotations
 
-import ctypes as C
+import ctypes
 import struct
 from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import hip_lib
-from .hip_lib import check
+from . import codec_io, hip_lib
 
 # Annex K's example tables, natural (row-major) order
 _BASE_LUM = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -55,10 +56,8 @@ def jpeg_tables(quality: int) -> np.ndarray:
     return np.clip((base * scale + 50) // 100, 1, 255).astype(np.uint8)
 
 
-def _args_of(frames: torch.Tensor, quality: int, subsampling: str, restart_interval: Optional[int]):
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        where = frames.device if isinstance(frames, torch.Tensor) else type(frames).__name__
-        raise RuntimeError(f"frames is on '{where}': soar_amd.video runs on HIP devices only; there is no CPU fallback")
+def _encode(frames, quality, subsampling, restart_interval, out):
+    codec_io.need_hip_tensor("frames", frames, "video")
     if frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[3] not in (3, 4):
         raise ValueError(f"encode_jpeg: frames must be uint8 [B,H,W,3] or [B,H,W,4] (got {frames.dtype} {tuple(frames.shape)})")
     if subsampling not in SUBSAMPLINGS:
@@ -66,39 +65,11 @@ def _args_of(frames: torch.Tensor, quality: int, subsampling: str, restart_inter
     ri = DEFAULT_RESTART_INTERVAL[subsampling] if restart_interval is None else int(restart_interval)
     if not 1 <= ri <= 65535:
         raise ValueError(f"encode_jpeg: restart_interval must be 1 .. 65535 MCUs (got {restart_interval})")
-    B, H, W, ch = frames.shape
-    if not (1 <= H <= 65535 and 1 <= W <= 65535 and B <= 65535):
-        raise ValueError(f"encode_jpeg: need 1 <= H, W <= 65535 and B <= 65535 (got {tuple(frames.shape)})")
-    frames = frames.detach()
-    # every frame contiguous; the step from frame to frame is free
-    if B and not (frames[0].is_contiguous() and (B < 2 or frames.stride(0) >= H * W * ch)):
-        frames = frames.contiguous()
     a = hip_lib.SoarJpegArgs()
-    a.B, a.H, a.W, a.channels, a.subsampling, a.restart_interval = B, H, W, ch, SUBSAMPLINGS[subsampling], ri
-    a.frames = frames.data_ptr() if B else None
-    a.frame_stride = frames.stride(0) if B > 1 else H * W * ch
-    C.memmove(a.qtables, jpeg_tables(quality).tobytes(), 128)
-    return a, frames
-
-
-def _encode(frames, quality, subsampling, restart_interval, out):
-    a, frames = _args_of(frames, quality, subsampling, restart_interval)
-    dev = frames.device
-    if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.dim() != 1 or
-                            not out.is_contiguous()):
-        raise ValueError(f"encode_jpeg: out must be a contiguous 1-D uint8 tensor on {dev}")
-    lib = hip_lib.lib()
-    ws = torch.empty(hip_lib._bytes(lib.soar_jpeg_workspace_bytes, "soar_jpeg_workspace_bytes", C.byref(a)), dtype=torch.uint8, device=dev)
-    offsets = torch.empty(a.B + 1, dtype=torch.int64, device=dev)
-    host = None
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        check(lib.soar_jpeg_measure(C.byref(a), ws.data_ptr(), ws.numel(), offsets.data_ptr(), stream), "soar_jpeg_measure")
-        if out is None:
-            host = offsets.cpu()                                  # the one read-back: B + 1 offsets
-            out = torch.empty(int(host[-1]), dtype=torch.uint8, device=dev)
-        check(lib.soar_jpeg_emit(C.byref(a), ws.data_ptr(), ws.numel(), hip_lib.ptr(out), out.numel(), stream), "soar_jpeg_emit")
-    return out, offsets, host
+    a.B, a.H, a.W, a.channels, a.subsampling, a.restart_interval = *frames.shape, SUBSAMPLINGS[subsampling], ri
+    frames, a.frames, a.frame_stride = codec_io.batch_view("encode_jpeg", frames)
+    ctypes.memmove(a.qtables, jpeg_tables(quality).tobytes(), 128)
+    return codec_io.measure_and_emit("encode_jpeg", a, ("soar_jpeg_workspace_bytes", "soar_jpeg_measure", "soar_jpeg_emit"), a.B, frames.device, out)
 
 
 def encode_jpeg(frames: torch.Tensor, quality: int = 90, subsampling: str = "444", restart_interval: Optional[int] = None,
@@ -120,9 +91,9 @@ def save_jpeg(path: str, image: torch.Tensor, quality: int = 90, subsampling: st
     """``image``: uint8 ``[H,W,3]`` or ``[H,W,4]`` on the device -> a baseline JPEG file at ``path``."""
     if isinstance(image, torch.Tensor) and image.dim() != 3:
         raise ValueError(f"save_jpeg: image must be uint8 [H,W,3] or [H,W,4] (got {tuple(image.shape)})")
-    data, _, _ = _encode(image[None] if isinstance(image, torch.Tensor) else image, quality, subsampling, restart_interval, None)
+    data, _, offsets = _encode(image[None] if isinstance(image, torch.Tensor) else image, quality, subsampling, restart_interval, None)
     with open(path, "wb") as f:
-        f.write(data.cpu().numpy().tobytes())
+        f.write(codec_io.host_items(data, offsets)[0][0])
 
 
 # ---- the container ------------------------------------------------------------------------------------------------------------------
@@ -196,11 +167,10 @@ class MjpegWriter:
         if isinstance(frames, torch.Tensor) and frames.dim() == 4 and tuple(frames.shape[1:3]) != (self.height, self.width):
             raise ValueError(f"MjpegWriter: frames of {self.height} x {self.width} expected (got {tuple(frames.shape)})")
         data, _, offsets = _encode(frames, self.quality, self.subsampling, self.restart_interval, None)
-        host = data.cpu().numpy().tobytes()
-        self.bytes_to_host += len(host)
-        off = offsets.tolist()
-        for b in range(len(off) - 1):
-            self.append_jpeg(host[off[b]:off[b + 1]])
+        jpegs, n = codec_io.host_items(data, offsets)
+        self.bytes_to_host += n
+        for blob in jpegs:
+            self.append_jpeg(blob)
 
     def close(self) -> None:
         if self._file is None:
@@ -304,19 +274,14 @@ class MjpegReader:
     def read(self, start: int = 0, stop: Optional[int] = None, step: int = 1, device="cuda", chunk: int = 8):
         """yields uint8 ``[n,height,width,C]`` on the device, n <= ``chunk``: the frames ``range(start, stop, step)``"""
         from . import jpeg
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"device is '{dev}': soar_amd.video runs on HIP devices only; there is no CPU fallback")
+        dev = codec_io.hip_device(device, "video")
         if int(step) < 1 or int(start) < 0:
             raise ValueError(f"MjpegReader.read: need start >= 0 and step >= 1 (got {start}, {step})")
         which = list(range(int(start), self.frames if stop is None else min(int(stop), self.frames), int(step)))
         for i in range(0, len(which), max(1, int(chunk))):
             part = which[i:i + max(1, int(chunk))]
             images, status = jpeg.decode_blobs([self.frame_bytes(k) for k in part], self.height, self.width, self.channels, dev)
-            bad = torch.nonzero(status.cpu()).reshape(-1).tolist()
-            if bad:
-                code = int(status[bad[0]])
-                raise ValueError(f"{self.path}: frame {part[bad[0]]}: {jpeg.JPEG_STATUS.get(code, code)} (status {code})")
+            codec_io.raise_on_status(status, jpeg.JPEG_STATUS, lambda k: f"{self.path}: frame {part[k]}")
             yield images
 
 

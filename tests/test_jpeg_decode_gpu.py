@@ -5,6 +5,7 @@ Pillow; MjpegReader, read_video and read_jpeg_files; and extract_frames from an 
 opened by FrameStore.from_dataroot(device_png=True)."""
 import io
 import os
+import re
 
 import numpy as np
 import pytest
@@ -165,6 +166,33 @@ def test_calls_streams_positions_and_arguments():
     wrong[3] = data.numel() + 5
     out, status = decode_jpeg(data, wrong, *shape, strict=False)
     assert bool((status == D.BAD_STRUCTURE).all()) and not bool(out.any())
+
+
+def test_two_files_in_a_buffer_of_no_bytes():
+    """offsets [0, 0, 0] over empty data: the decoder is called (with a pointer that is never read) and both files are refused"""
+    from soar_amd.jpeg import decode_jpeg
+    data, offsets = torch.empty(0, dtype=torch.uint8, device=DEV), torch.zeros(3, dtype=torch.int64, device=DEV)
+    want = D.decode(b"", 8, 8, 3)
+    assert want.status == D.BAD_STRUCTURE
+    out, status = decode_jpeg(data, offsets, 8, 8, 3, strict=False)
+    assert status.tolist() == [want.status] * 2 and out.shape == (2, 8, 8, 3) and np.array_equal(out[1].cpu().numpy(), want.image)
+    with pytest.raises(ValueError, match=r"decode_jpeg: file 0 of 2: bad structure.*\[0, 1\]"):
+        decode_jpeg(data, offsets, 8, 8, 3)
+
+
+def test_a_bad_file_behind_a_chunk_boundary_is_named_by_its_path(tmp_path):
+    from soar_amd.jpeg import JPEG_STATUS, read_jpeg_files
+    files = [T.pillow_file(17, 13, "420", quality=q) for q in (50, 75, 90)]
+    paths = [str(tmp_path / f"{i}.jpg") for i in range(3)]
+    for p, f in zip(paths, files):
+        open(p, "wb").write(f)
+    got = read_jpeg_files(paths, DEV, chunk=2)                      # two calls: two files, then one
+    assert np.array_equal(got.cpu().numpy(), np.stack([D.decode(f, 17, 13, 3).image for f in files]))
+    cut = files[2][:-10]
+    open(paths[2], "wb").write(cut)
+    reason = JPEG_STATUS[D.decode(cut, 17, 13, 3).status]
+    with pytest.raises(ValueError, match=re.escape(f"{paths[2]}: {reason}")):
+        read_jpeg_files(paths, DEV, chunk=2)
 
 
 @pytest.mark.parametrize("subsampling", ["444", "420"])

@@ -5,6 +5,7 @@ else); batches, streams and positions; the round trip through encode_png; read_p
 against the host path."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -156,6 +157,34 @@ def test_empty_batches_callers_buffers_strictness_and_refusals():
             decode_png(data, o, 17, 23, 4)
         out, status = decode_png(data, o, 17, 23, 4, strict=False)
         assert status.tolist() == [D.BAD_STRUCTURE] * 2 and not out.any()
+
+
+def test_two_files_in_a_buffer_of_no_bytes():
+    """offsets [0, 0, 0] over empty data: the decoder is called (with a pointer that is never read) and both files are refused"""
+    from soar_amd.png import decode_png
+    data, offsets = torch.empty(0, dtype=torch.uint8, device=DEV), torch.zeros(3, dtype=torch.int64, device=DEV)
+    want = D.decode(b"", want=(8, 8, 3), report=False)
+    assert want.status == D.BAD_STRUCTURE
+    out, status = decode_png(data, offsets, 8, 8, 3, strict=False)
+    assert status.tolist() == [want.status] * 2 and out.shape == (2, 8, 8, 3) and np.array_equal(out[1].cpu().numpy(), want.image)
+    with pytest.raises(ValueError, match=r"decode_png: file 0 of 2: bad signature or chunk structure.*\[0, 1\]"):
+        decode_png(data, offsets, 8, 8, 3)
+
+
+def test_a_bad_file_behind_a_chunk_boundary_is_named_by_its_path(tmp_path):
+    from soar_amd.png import PNG_STATUS, read_png_files
+    imgs = [TE.make_image(kind, 17, 13, 3, seed=i) for i, kind in enumerate(("noise", "blob", "ramp"))]
+    files = [T.pillow_file(im) for im in imgs]
+    paths = [str(tmp_path / f"{i}.png") for i in range(3)]
+    for p, f in zip(paths, files):
+        open(p, "wb").write(f)
+    got = read_png_files(paths, DEV, chunk=2)                       # two calls: two files, then one
+    assert np.array_equal(got.cpu().numpy(), np.stack([D.decode(f).image for f in files]))
+    cut = files[2][:-20]
+    open(paths[2], "wb").write(cut)
+    reason = PNG_STATUS[D.decode(cut, want=(17, 13, 3), report=False).status]
+    with pytest.raises(ValueError, match=re.escape(f"{paths[2]}: {reason}")):
+        read_png_files(paths, DEV, chunk=2)
 
 
 @pytest.mark.parametrize("c", TE.CHANNELS)

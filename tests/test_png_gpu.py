@@ -111,6 +111,25 @@ def test_a_strided_batch_into_a_guarded_buffer_equals_the_single_calls(c, slack)
         assert files_of(one, off) == [want[i]]
 
 
+def test_a_batch_cut_out_of_a_taller_buffer_is_encoded_where_it_lies():
+    """big[:, :H]: every image contiguous, the step from image to image wider than an image; no copy is made of it"""
+    from soar_amd import codec_io
+    from soar_amd.png import encode_png
+    H, W, B = 17, 13, 3
+    imgs = [T.make_image(k, H, W, 3, seed=i) for i, k in enumerate(("noise", "blob", "ramp"))]
+    big = torch.full((B, H + 5, W, 3), 7, dtype=torch.uint8, device=DEV)
+    images = big[:, :H]
+    images.copy_(torch.from_numpy(np.stack(imgs)).to(DEV))
+    assert not images.is_contiguous()
+    _, pointer, stride = codec_io.batch_view("encode_png", images)
+    assert pointer == big.data_ptr() and stride == (H + 5) * W * 3
+    want = [ref_file(im, "adaptive", 256) for im in imgs]
+    assert files_of(*encode_png(images, piece_bytes=256)) == want
+    for i in range(B):
+        assert files_of(*encode_png(images[i:i + 1], piece_bytes=256)) == [want[i]]
+    assert bool((big[:, H:] == 7).all())
+
+
 def test_an_image_stride_past_2_to_the_31_bytes():
     """two small images 2^31 + 4096 bytes apart in one (untouched) allocation: the image's address is 64-bit arithmetic"""
     from soar_amd.png import encode_png

@@ -77,6 +77,31 @@ def test_a_strided_rgba_batch_into_a_guarded_buffer_equals_the_single_calls(subs
         assert files_of(one, off) == [want[i]]
 
 
+def test_a_batch_cut_out_of_a_taller_buffer_is_encoded_where_it_lies():
+    """big[:, :H]: every frame contiguous, the step from frame to frame wider than a frame; no copy is made of it"""
+    from soar_amd import codec_io
+    from soar_amd.video import encode_jpeg
+    H, W, B = 17, 13, 3
+    imgs = [make_image(k, H, W, seed=i) for i, k in enumerate(("noise", "blob", "ramp"))]
+    big = torch.full((B, H + 5, W, 3), 7, dtype=torch.uint8, device=DEV)
+    frames = big[:, :H]
+    frames.copy_(torch.from_numpy(np.stack(imgs)).to(DEV))
+    assert not frames.is_contiguous()
+    _, pointer, stride = codec_io.batch_view("encode_jpeg", frames)
+    assert pointer == big.data_ptr() and stride == (H + 5) * W * 3
+    want = [ref_file(im, 90, "420", 3) for im in imgs]
+    assert files_of(*encode_jpeg(frames, quality=90, subsampling="420", restart_interval=3)) == want
+    for i in range(B):
+        assert files_of(*encode_jpeg(frames[i:i + 1], quality=90, subsampling="420", restart_interval=3)) == [want[i]]
+    assert bool((big[:, H:] == 7).all())
+
+
+def test_an_empty_batch_gives_the_offsets_of_nothing():
+    from soar_amd.video import encode_jpeg
+    data, offsets = encode_jpeg(torch.empty((0, 8, 8, 3), dtype=torch.uint8, device=DEV))
+    assert data.numel() == 0 and offsets.dtype == torch.int64 and offsets.cpu().tolist() == [0]
+
+
 def test_a_frame_stride_past_2_to_the_31_bytes():
     """two small frames 2^31 + 4096 bytes apart in one (untouched) allocation: the frame's address is 64-bit arithmetic"""
     from soar_amd.video import encode_jpeg
