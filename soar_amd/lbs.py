@@ -26,7 +26,10 @@ def _need_hip(t: torch.Tensor, name: str):
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().float().contiguous()
+    t = t.detach().float().contiguous()
+    # the warp kernels read and write quaternion rows, per-point matrices and weight rows as float4: a contiguous view that starts
+    # at a storage offset off the 16-byte grid goes in as a copy (a fresh allocation, aligned)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
 def _stream(device):

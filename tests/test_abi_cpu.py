@@ -67,6 +67,16 @@ def test_bad_arguments_fail_loudly_without_touching_the_gpu(lib):
     assert lib.soar_lbs_knn_query(0x1000, 100, 0x1000, 55, 0x1000, 10, 30, 0x1000, None, None, 0, None) != 0
     assert "workspace" in hip_lib.last_error()
     assert lib.soar_lbs_warp_forward(None, None, None, None, None, None, 5, 100, None, None, None, None) != 0
+    # with blend weights the warp serves 1 .. 64 joints: every entry point refuses 65 and 0 before it looks at a pointer
+    p = 0x1000
+    for J in (65, 0, -1):
+        for call in (lambda: lib.soar_lbs_warp_forward(p, p, p, p, None, None, 5, J, p, p, None, None),
+                     lambda: lib.soar_lbs_warp_backward(p, p, p, p, None, 5, J, p, p, p, p, None),
+                     lambda: lib.soar_lbs_warp_forward_batch(p, p, p, p, 2, 5, J, p, p, None),
+                     lambda: lib.soar_lbs_warp_backward_sum(p, p, p, p, 2, 5, J, p, p, p, p, 0, None, None, None, None),
+                     lambda: lib.soar_lbs_warp_backward_views(p, p, p, p, None, 2, 5, J, p, p, p, p, 0, None, None, None, None)):
+            assert lib.soar_rast_image_bytes(0, 10, None) != 0 and "bad sizes" not in hip_lib.last_error()      # (another message in between)
+            assert call() != 0 and f"bad sizes P=5 J={J} (max J 64)" in hip_lib.last_error()
 
 
 def test_batch_control_calls_check_their_arguments(lib):
