@@ -59,7 +59,9 @@ extern "C" {
  * _bytes: normal-map preprocessing.  soar_selftest_conv_gemm / _conv_pack (+ SoarConvGemmArgs, SoarConvGemmTaps): the shared
  * implicit-GEMM convolution and its weight packer by themselves, for the tests.  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
  * normal priors (a triangle-mesh rasterizer).  soar_rast_backward_plan_loss (+ SoarBackwardLoss),
- * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch. */
+ * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch.  soar_sam_weights_bytes /
+ * _pack_weights / _workspace_bytes / _preprocess / _encode / _decode / _postprocess / _attention (+ SoarSamConfig, SoarSamEncodeArgs,
+ * SoarSamDecodeArgs): SAM point-prompt segmentation. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1907,6 +1909,66 @@ typedef struct SoarResizeArgs {
     const int32_t *bounds_v, *coef_v;     /* [out_h][2], [out_h][ksize_v] */
 } SoarResizeArgs;
 int soar_resize_u8(const SoarResizeArgs *args, uint8_t *out, void *stream);
+
+/* ---- SAM point-prompt segmentation, forward only, float32 (sam.hip, soar_amd/sam.py) ----
+ * The sizes of a model (what soar_amd/sam.py reads from a state dict).  window[b] = 0: block b attends over the whole grid.
+ * Every width that feeds a matrix product (embed, mlp, out_chans, dec_mlp, out_chans / dec_down, iou_hidden, 3 patch patch) is a
+ * multiple of 8, head_dim a multiple of 4 up to 96, a window or a global grid at most 64 tokens a side. */
+#define SOAR_SAM_MAX_DEPTH 32
+typedef struct SoarSamConfig {
+    int32_t image_size, patch, grid;           /* grid = image_size / patch tokens a side */
+    int32_t embed, depth, heads, head_dim, mlp;/* encoder: width, blocks, heads x head_dim = embed, MLP width */
+    int32_t out_chans;                         /* neck / prompt / decoder width */
+    int32_t window[SOAR_SAM_MAX_DEPTH];
+    int32_t dec_layers, dec_heads, dec_down, dec_mlp, mask_tokens, hyper_depth, iou_depth, iou_hidden;
+} SoarSamConfig;
+/* The packed weights: `count` contiguous float32 device tensors in the order of soar_amd.sam.tensor_keys (segment_anything's
+ * layouts), copied, with the 3 x 3 neck convolution and the two transposed convolutions re-laid for the kernels and the dense
+ * positional encoding of the token grid computed behind them.  packed: soar_sam_weights_bytes bytes, 256-byte aligned. */
+int soar_sam_weights_bytes(const SoarSamConfig *cfg, size_t *bytes, int32_t *count);
+int soar_sam_pack_weights(const SoarSamConfig *cfg, const float *const *tensors, int32_t count, void *packed, size_t packed_bytes,
+                          void *stream);
+/* one workspace for encode and decode of B frames with up to max_points points each */
+int soar_sam_workspace_bytes(const SoarSamConfig *cfg, int32_t B, int32_t max_points, size_t *bytes);
+/* resized [B][nh][nw][3] uint8 (the longer side = image_size) -> patches [B][grid grid][3 patch patch] float32: (x - mean) / std,
+ * zeros below and right of the frame, one row per token in the patch convolution's (channel, y, x) order */
+int soar_sam_preprocess(const SoarSamConfig *cfg, int32_t B, int32_t nh, int32_t nw, const uint8_t *resized, float *patches, void *stream);
+/* The image encoder, or a part of it.  patches != NULL: patch embedding + pos_embed first; else tokens_in [B][grid grid][embed] is
+ * the input.  Blocks block_begin .. block_end - 1 run on it; tokens_out (or NULL) receives the tokens after them; embeddings (or
+ * NULL: no neck) [B][grid][grid][out_chans] the neck's output. */
+typedef struct SoarSamEncodeArgs {
+    int32_t B, block_begin, block_end;
+    const float *patches, *tokens_in;
+    float *tokens_out, *embeddings;
+} SoarSamEncodeArgs;
+int soar_sam_encode(const SoarSamConfig *cfg, const void *packed, const SoarSamEncodeArgs *args, void *workspace, size_t workspace_bytes,
+                    void *stream);
+/* Prompt encoder and mask decoder.  points [B][max_points][2] (x, y) in pixels of the original frame, scaled here by scale_x,
+ * scale_y; labels [B][max_points] int32 (1 / 0); counts [B] int32 in [0, max_points]: frame b has counts[b] points and one padding
+ * point behind them, and slots past that take part in nothing.  low_res [B][mask_tokens - 1][4 grid][4 grid], iou
+ * [B][mask_tokens - 1]: masks 1 .. (multimask output).  prompt_tokens / tokens_out (or NULL) [B][1 + mask_tokens + max_points + 1]
+ * [out_chans]: the decoder's tokens before and after the two-way transformer (a frame's first 2 + mask_tokens + counts[b]; what lies
+ * behind them is unspecified). */
+typedef struct SoarSamDecodeArgs {
+    int32_t B, max_points;
+    float scale_x, scale_y;
+    const float *embeddings, *points;
+    const int32_t *labels, *counts;
+    float *low_res, *iou, *prompt_tokens, *tokens_out;
+} SoarSamDecodeArgs;
+int soar_sam_decode(const SoarSamConfig *cfg, const void *packed, const SoarSamDecodeArgs *args, void *workspace, size_t workspace_bytes,
+                    void *stream);
+/* low_res [B][K][L][L] -> bilinear (align_corners = false) to image_size squared, cropped to nh x nw, bilinear to H x W:
+ * logits [B][K][H][W] float32 and / or masks (logit > 0) uint8, either may be NULL */
+int soar_sam_postprocess(int32_t B, int32_t K, int32_t L, int32_t image_size, int32_t nh, int32_t nw, int32_t H, int32_t W,
+                         const float *low_res, float *logits, uint8_t *masks, void *stream);
+/* Multi-head attention with the decomposed relative-position bias by itself: qkv [B][gh gw][3 heads hd] (q | k | v, head-major) ->
+ * out [B][gh gw][heads hd].  window = 0: every token attends to the gh x gw grid; else inside window x window windows of the grid
+ * zero-padded to a multiple of the window, where a padded key is bias's k and v ([3 heads hd]) and padded queries are dropped.
+ * logit = (scale q) . k + q . rel_h[qy - ky + Sh - 1] + q . rel_w[qx - kx + Sw - 1]; rel_h [(2 Sh - 1)][hd], rel_w [(2 Sw - 1)][hd]
+ * for the sequence Sh x Sw (the window or the grid), or both NULL. */
+int soar_sam_attention(const float *qkv, const float *bias, const float *rel_h, const float *rel_w, float *out, int32_t B, int32_t gh,
+                       int32_t gw, int32_t heads, int32_t hd, int32_t window, float scale, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

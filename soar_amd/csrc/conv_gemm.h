@@ -21,7 +21,9 @@ inline void square_taps(ConvTaps &p, const float *w, int64_t ldw, int side, int 
     for (int t = 0; t < side * side; t++) { p.dy[t] = (signed char)(t / side + off); p.dx[t] = (signed char)(t % side + off); }
 }
 
-// y = alpha * (A B^T) + bias + res.  A row is one grid position's (tap, cin) window of x, gathered on load; nothing padded or
+enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
+
+// y = act(alpha * (A B^T) + bias) + res.  A row is one grid position's (tap, cin) window of x, gathered on load; nothing padded or
 // zero-dilated is ever materialised.
 struct ConvGemm {
     const float *x;                // A: image n's pixel (iy, ix) at x + (n xim + iy Win + ix) ldx, Cin floats (a multiple of 8, 16-byte aligned)
@@ -43,9 +45,10 @@ struct ConvGemm {
     int nph;                       // tap tables in use: gridDim.y picks one (the phases of a transposed convolution)
     ConvTaps ph[4];
     int tiles_n, tiles_img;        // (the launcher's)
+    int act;                       // ACT_NONE (0: what a zero-initialised descriptor asks for), ACT_GELU (exact, erf) or ACT_RELU
 };
 // Refuses (set_error, 1, nothing launched) a descriptor the kernel cannot run: more than 2^30 rows; Cin no multiple of 8; nph outside
-// 1 .. 4; wbat without per_image; dil not 1 or 2, or 2 with reflect; stride, os, Cout, Hin or Win below 1; x, y or a table's w NULL; x
+// 1 .. 4; act outside 0 .. 2; wbat without per_image; dil not 1 or 2, or 2 with reflect; stride, os, Cout, Hin or Win below 1; x, y or a table's w NULL; x
 // or w off 16 bytes, or ldx, ldw, wbat no multiple of 4 (the loads are float4); a table with ntaps outside 1 .. 9 or py, px outside
 // [0, os); with reflect, a coordinate gy stride + dy outside [-(Hin - 1), 2 (Hin - 1)] (mirror() reflects once), likewise along x.
 int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream);
@@ -66,6 +69,7 @@ constexpr int LDSK = BK + 4;       // LDS row pitch in floats: rows 16 B apart i
 __device__ __forceinline__ float comp(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 // C / D of the 32 x 32 MFMA: lane l holds column l & 31; its register e is row (e & 3) + 8 (e >> 2) + 4 h with h = l >> 5
 __device__ __forceinline__ int mfma_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 __device__ __forceinline__ int mirror(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 #endif
 

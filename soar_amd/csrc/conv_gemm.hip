@@ -5,8 +5,8 @@
 //                          [Cin][tap][ldb] (data gradient): both directions are then the same implicit GEMM
 //   conv_gemm_kernel       an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32 products): M = grid positions, N = output
 //                          channels, K = (tap, cin), tiles staged through LDS.  The A loader does strides, padding (zero or mirrored)
-//                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = alpha acc + bias + res, scattered
-//                          to the tap table's output parity
+//                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = act(alpha acc + bias) + res,
+//                          scattered to the tap table's output parity (act: none, exact GELU or ReLU)
 //
 // The launcher refuses the descriptors the kernel cannot run (conv_gemm.h); soar_selftest_conv_gemm / _conv_pack at the end of the
 // file reach the launcher and the packer by themselves (tests/test_conv_gemm_*.py).
@@ -181,6 +181,7 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(ConvGemm k)
                 if (!cv[c]) continue;
                 const size_t idx = base + (c0 + wc + c * 32 + i);
                 float v = acc[r][c][e] * k.alpha + bias[c];
+                if (k.act) v = k.act == ACT_GELU ? gelu_erf(v) : fmaxf(v, 0.f);     // (act = 0: the arithmetic of every call before it)
                 if (k.res) v += k.res[idx];
                 k.y[idx] = v;
             }
@@ -201,6 +202,7 @@ bool check_desc(const ConvGemm &k, int64_t M)
         set_error("conv_gemm: dil must be 1, or 2 with zero padding (dil=%d, reflect=%d)", k.dil, k.reflect);
         return false;
     }
+    if (k.act < 0 || k.act > ACT_RELU) { set_error("conv_gemm: act must be 0 (none), 1 (GELU) or 2 (ReLU) (got %d)", k.act); return false; }
     if (k.stride < 1 || k.os < 1 || k.Cout < 1 || k.Hin < 1 || k.Win < 1) {
         set_error("conv_gemm: stride, os, Cout, Hin and Win must be at least 1 (stride=%d, os=%d, Cout=%d, Hin=%d, Win=%d)", k.stride, k.os,
                   k.Cout, k.Hin, k.Win);

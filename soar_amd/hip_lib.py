@@ -297,6 +297,28 @@ class SoarResizeArgs(C.Structure):
                 ("bounds_v", _vp), ("coef_v", _vp)]
 
 
+SAM_MAX_DEPTH = 32
+
+
+class SoarSamConfig(C.Structure):
+    """Mirror of ``struct SoarSamConfig`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("image_size", "patch", "grid", "embed", "depth", "heads", "head_dim", "mlp", "out_chans")] + \
+               [("window", C.c_int32 * SAM_MAX_DEPTH)] + \
+               [(n, C.c_int32) for n in ("dec_layers", "dec_heads", "dec_down", "dec_mlp", "mask_tokens", "hyper_depth", "iou_depth", "iou_hidden")]
+
+
+class SoarSamEncodeArgs(C.Structure):
+    """Mirror of ``struct SoarSamEncodeArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("block_begin", C.c_int32), ("block_end", C.c_int32), ("patches", _vp), ("tokens_in", _vp),
+                ("tokens_out", _vp), ("embeddings", _vp)]
+
+
+class SoarSamDecodeArgs(C.Structure):
+    """Mirror of ``struct SoarSamDecodeArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("max_points", C.c_int32), ("scale_x", C.c_float), ("scale_y", C.c_float), ("embeddings", _vp),
+                ("points", _vp), ("labels", _vp), ("counts", _vp), ("low_res", _vp), ("iou", _vp), ("prompt_tokens", _vp), ("tokens_out", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -522,6 +544,14 @@ SIGNATURES = {
     "soar_jpeg_decode_workspace_bytes": (C.c_int, [C.POINTER(SoarJpegDecodeArgs), C.POINTER(C.c_size_t)]),
     "soar_jpeg_decode": (C.c_int, [C.POINTER(SoarJpegDecodeArgs), _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "soar_resize_u8": (C.c_int, [C.POINTER(SoarResizeArgs), _vp, _vp]),
+    "soar_sam_weights_bytes": (C.c_int, [C.POINTER(SoarSamConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "soar_sam_pack_weights": (C.c_int, [C.POINTER(SoarSamConfig), C.POINTER(_vp), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_sam_workspace_bytes": (C.c_int, [C.POINTER(SoarSamConfig), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_sam_preprocess": (C.c_int, [C.POINTER(SoarSamConfig), C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "soar_sam_encode": (C.c_int, [C.POINTER(SoarSamConfig), _vp, C.POINTER(SoarSamEncodeArgs), _vp, C.c_size_t, _vp]),
+    "soar_sam_decode": (C.c_int, [C.POINTER(SoarSamConfig), _vp, C.POINTER(SoarSamDecodeArgs), _vp, C.c_size_t, _vp]),
+    "soar_sam_postprocess": (C.c_int, [C.c_int32] * 8 + [_vp, _vp, _vp, _vp]),
+    "soar_sam_attention": (C.c_int, [_vp] * 5 + [C.c_int32] * 6 + [C.c_float, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

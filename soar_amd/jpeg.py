@@ -123,16 +123,32 @@ def _bicubic(x: float) -> float:
     return 0.0
 
 
-@functools.lru_cache(maxsize=16)
+def _triangle(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+# filter name -> (function, support): Pillow's BICUBIC and BILINEAR (Resample.c: bicubic_filter, bilinear_filter)
+_FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_triangle, 1.0)}
+
+
 def bicubic_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray, int]:
+    """``resize_tables(in_size, out_size, "bicubic")``."""
+    return resize_tables(in_size, out_size, "bicubic")
+
+
+@functools.lru_cache(maxsize=32)
+def resize_tables(in_size: int, out_size: int, filter: str = "bicubic") -> Tuple[np.ndarray, np.ndarray, int]:
     """Pillow's ``precompute_coeffs`` and ``normalize_coeffs_8bpc`` (Resample.c) for one axis, in the same double arithmetic:
     -> ``(bounds int32 [out,2]`` (first input sample, count), ``coefficients int32 [out,ksize]`` (22-bit fixed point), ``ksize)``.
-    The support of the filter (2) is widened by the scale factor when shrinking; the coefficients of an output are normalised to sum 1.
+    The support of the filter (2 for bicubic, 1 for bilinear: the triangle) is widened by the scale factor when shrinking; the
+    coefficients of an output are normalised to sum 1.
     (Kept for the sizes last asked for: the arrays are shared and must not be written.)"""
+    _kernel, _support = _FILTERS[filter]
     scale = filterscale = float(in_size) / out_size
     if filterscale < 1.0:
         filterscale = 1.0
-    support = 2.0 * filterscale
+    support = _support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     kk = np.zeros((out_size, ksize), np.int32)
@@ -141,7 +157,7 @@ def bicubic_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray,
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        k = [_kernel((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for w in k:
             ww += w
@@ -152,10 +168,13 @@ def bicubic_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray,
     return bounds, kk, ksize
 
 
-def resize_images(images: torch.Tensor, height: int, width: Optional[int] = None) -> torch.Tensor:
+def resize_images(images: torch.Tensor, height: int, width: Optional[int] = None, filter: str = "bicubic") -> torch.Tensor:
     """``images``: uint8 ``[B,H,W,C]`` on the device, C = 1 .. 4 -> uint8 ``[B,height,width,C]``: Pillow's
-    ``Image.resize((width, height), Image.BICUBIC)``, bit for bit (a horizontal pass into 8 bits, then a vertical one).  ``width``:
-    ``round(W * height / H)`` when not given, at least 1.  No synchronisation."""
+    ``Image.resize((width, height), Image.BICUBIC)`` (or ``Image.BILINEAR`` with ``filter="bilinear"``), bit for bit (a horizontal pass
+    into 8 bits, then a vertical one).  ``width``: ``round(W * height / H)``
+    when not given, at least 1.  No synchronisation."""
+    if filter not in _FILTERS:
+        raise ValueError(f"resize_images: filter must be one of {sorted(_FILTERS)} (got {filter!r})")
     codec_io.need_hip_tensor("images", images, "jpeg")
     if images.dim() != 4 or images.dtype != torch.uint8 or not 1 <= images.shape[3] <= 4 or images.shape[1] < 1 or images.shape[2] < 1:
         raise ValueError(f"resize_images: images must be uint8 [B,H,W,C] with C = 1 .. 4 (got {images.dtype} {tuple(images.shape)})")
@@ -169,8 +188,8 @@ def resize_images(images: torch.Tensor, height: int, width: Optional[int] = None
     out = torch.empty((B, h, w, ch), dtype=torch.uint8, device=dev)
     if B == 0:
         return out
-    bh, kh, nh = bicubic_tables(W, w)
-    bv, kv, nv = bicubic_tables(H, h)
+    bh, kh, nh = resize_tables(W, w, filter)
+    bv, kv, nv = resize_tables(H, h, filter)
     tables = [torch.from_numpy(t).to(dev, non_blocking=True) for t in (bh, kh, bv, kv)]
     temp = torch.empty((B, H, w, ch), dtype=torch.uint8, device=dev)
     a = hip_lib.SoarResizeArgs()

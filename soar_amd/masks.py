@@ -3,13 +3,14 @@
 
 The reference does this per frame on the host (preproc/compute_kp_and_mask.py:61-79): the union of SAM's three candidates,
 ``cv2.morphologyEx`` OPEN then CLOSE with a 5 x 5 kernel, ``cv2.connectedComponentsWithStats(connectivity=8)``, the largest
-component, a PNG.  The segmenter stays the caller's; everything behind it runs here, on bit-planes, for N frames per call.
+component, a PNG.  The segmenter is ``sam.SamSegmenter`` or the caller's; everything behind it runs here, on bit-planes, for N
+frames per call.
 
 * ``open_close(mask)``: union over K (if given), OPEN, CLOSE -> uint8 ``[N,H,W]``.
 * ``largest_component(mask)``: the largest 8-connected component of every frame.
 * ``clean_masks(candidates)``: the pipeline, in chunks of frames under a workspace cap.
 * ``keypoint_prompts`` / ``segment_sequence`` / ``save_masks``: the prompts from the OpenPose keypoints, the loop over the caller's
-  predictor, and the PNGs ``FrameStore.read_dataroot`` reads.
+  predictor (or the batched path of ``sam.SamSegmenter``), and the PNGs ``FrameStore.read_dataroot`` reads.
 
 **Border rule.**  An erosion treats pixels outside the image as set, a dilation as unset, and each of the four operations applies
 this to its own input: OpenCV's documented default (``morphologyDefaultBorderValue``), identical to
@@ -158,6 +159,9 @@ def segment_sequence(predict: Callable, images: Sequence, keypoints, chunk: int 
     tensor or an array, logits or booleans) is called once per frame with the prompts of ``keypoint_prompts``; a chunk of frames is
     stacked on the device and cleaned.  Returns ``(masks [N,H,W] uint8, stats [N,4] int32)``.
 
+    With a ``sam.SamSegmenter`` as ``predict`` a chunk is uploaded once, segmented in one batch (``SamSegmenter.logits``) and cleaned
+    without leaving the device; any other callable goes through the loop.
+
     ``reverse_channels=True`` hands the image over as ``image[..., ::-1]`` because the reference does
     (compute_kp_and_mask.py:61: the RGB file reaches SAM with its channels reversed)."""
     if chunk < 1:
@@ -165,6 +169,9 @@ def segment_sequence(predict: Callable, images: Sequence, keypoints, chunk: int 
     prompts = keypoint_prompts(keypoints)
     if len(prompts) != len(images):
         raise ValueError(f"segment_sequence: {len(images)} images but keypoints of {len(prompts)} frames")
+    from .sam import SamSegmenter
+    if isinstance(predict, SamSegmenter):
+        return _segment_sequence_sam(predict, images, prompts, chunk, reverse_channels, device, threshold)
     dev = _need_cuda(torch.device("cuda" if device is None else device), "segment_sequence")
     masks, stats = [], []
     for i in range(0, len(images), chunk):
@@ -180,6 +187,39 @@ def segment_sequence(predict: Callable, images: Sequence, keypoints, chunk: int 
         stats.append(s)
     if not masks:
         return torch.empty((0, 0, 0), dtype=torch.uint8, device=dev), torch.empty((0, 4), dtype=torch.int32, device=dev)
+    return torch.cat(masks), torch.cat(stats)
+
+
+def _segment_sequence_sam(sam, images: Sequence, prompts, chunk: int, reverse_channels: bool, device, threshold: float):
+    """``segment_sequence`` with this project's segmenter (``sam.SamSegmenter``): a chunk of frames is uploaded once, segmented in
+    one batch and cleaned, and nothing comes back to the host in between.  Frames of one chunk that differ in size go in runs of
+    equal size.  The prompts' labels count as 1 where non-zero."""
+    dev = _need_cuda(sam.weights.device if device is None else torch.device(device), "segment_sequence")
+    masks, stats = [], []
+    for i in range(0, len(images), chunk):
+        frames = [np.asarray(im.detach().cpu() if isinstance(im, torch.Tensor) else im) for im in images[i:i + chunk]]
+        j = 0
+        while j < len(frames):
+            k = j + 1
+            while k < len(frames) and frames[k].shape == frames[j].shape:
+                k += 1
+            run = np.stack(frames[j:k])
+            batch = torch.from_numpy(np.ascontiguousarray(run[..., ::-1] if reverse_channels else run)).to(dev, non_blocking=True)
+            pr = prompts[i + j:i + k]
+            M = max(1, max(len(c) for c, _ in pr))
+            pts, lab = np.zeros((k - j, M, 2), np.float32), np.zeros((k - j, M), np.int32)
+            for b, (c, l) in enumerate(pr):
+                pts[b, :len(c)], lab[b, :len(c)] = c, np.asarray(l) != 0
+            counts = torch.tensor([len(c) for c, _ in pr], dtype=torch.int32).to(dev, non_blocking=True)
+            cand = sam.logits(batch, torch.from_numpy(pts).to(dev, non_blocking=True), counts, torch.from_numpy(lab).to(dev, non_blocking=True))
+            m, s = clean_masks(cand, threshold=threshold, return_stats=True)
+            masks.append(m)
+            stats.append(s)
+            j = k
+    if not masks:
+        return torch.empty((0, 0, 0), dtype=torch.uint8, device=dev), torch.empty((0, 4), dtype=torch.int32, device=dev)
+    if any(m.shape[1:] != masks[0].shape[1:] for m in masks):
+        raise ValueError("segment_sequence: the frames differ in size: their masks cannot be stacked")
     return torch.cat(masks), torch.cat(stats)
 
 
