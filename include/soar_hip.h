@@ -1387,7 +1387,7 @@ int soar_data_step_batch(const SoarDataStepArgs *args, void *stream);
  *   metrics[n] = {psnr, ssim, mse};  pred2 = pred * 2 - 1, gt2 = gt_white * 2 - 1 (the LPIPS inputs);
  *   grid (NULL = skip) [N][H][2 W][3] = pred | gt_white as bytes: clamp(v, 0, 1) * 255, truncated.
  * pred, gt_rgb [N][H][W][3] and gt_mask [N][H][W] are read at their element strides; gt_white, pred2, gt2 are contiguous [N][H][W][3].
- * No float atomics: every workgroup writes four float64 partial sums into `scratch` (soar_eval_scratch_bytes bytes, 8-byte aligned),
+ * No float atomics: every workgroup writes four float64 partial sums into `scratch` (soar_eval_scratch_bytes bytes, 256-byte aligned),
  * a second kernel of the same call adds them in a fixed order: two calls give the same bits.  No host synchronisation, no allocation.
  * Refused before any launch: H < 7 or W < 7 (no window fits; skimage raises too), N < 1, N > 65535, N H W > 2^30, a NULL pointer other
  * than grid, a short scratch. */

@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 from .renderer import registry
 from .renderer.cameras import device_constant
 
@@ -112,7 +112,7 @@ class _EnvmapFn(torch.autograd.Function):
         a = _args(B, H, W, n_comp, color, dirs, renders, masks, (w1, w2, w3))
         a.bg, a.comp = hip_lib.ptr(bg), hip_lib.ptr(comp)
         with torch.cuda.device(dev):
-            check(hip_lib.lib().soar_envmap_forward(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "soar_envmap_forward")
+            check(hip_lib.lib().soar_envmap_forward(C.byref(a), _stream(dev)), "soar_envmap_forward")
         ctx.n_comp = n_comp
         ctx.save_for_backward(color, dirs, renders, masks, w1, w2, w3)
         ctx.set_materialize_grads(False)
@@ -148,12 +148,9 @@ class _EnvmapFn(torch.autograd.Function):
             d_w = [torch.empty_like(w1), torch.empty_like(w2), torch.empty_like(w3)]
             a.d_w1, a.d_w2, a.d_w3 = (t.data_ptr() for t in d_w)
         L = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(L.soar_envmap_workspace_bytes(B, H, W, C.byref(nb)), "soar_envmap_workspace_bytes")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = _workspace(_bytes(L.soar_envmap_workspace_bytes, "soar_envmap_workspace_bytes", B, H, W), dev)
         with torch.cuda.device(dev):
-            check(L.soar_envmap_backward(C.byref(a), ws.data_ptr(), nb.value, torch.cuda.current_stream(dev).cuda_stream),
-                  "soar_envmap_backward")
+            check(L.soar_envmap_backward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(dev)), "soar_envmap_backward")
         g_render = g_comp if need[3] else None
         dw = [d_w[k] if d_w is not None and need[5 + k] else None for k in range(3)]
         return (None, None, None, g_render, g_mask, *dw)

@@ -22,7 +22,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import hip_lib
-from .hip_lib import _bytes, check, ptr
+from .hip_lib import _bytes, _stream, _workspace, check, ptr
 
 WEIGHTINGS = {"angle": 0, "area": 1, "uniform": 2}       # SOAR_NORMALS_*
 
@@ -38,16 +38,9 @@ def _hip(t: torch.Tensor, name: str) -> None:
         raise RuntimeError(f"{name} is on '{where}': soar_amd.body runs on HIP devices only; there is no CPU fallback")
 
 
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _workspace(F: int, device: torch.device) -> Tuple[torch.Tensor, int]:
+def _mesh_workspace(F: int, device: torch.device) -> Tuple[torch.Tensor, int]:
     nb = _bytes(hip_lib.lib().soar_mesh_workspace_bytes, "soar_mesh_workspace_bytes", int(F))
-    buf = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
-    if buf.data_ptr() % 256:
-        raise RuntimeError("device allocation is not 256-byte aligned")
-    return buf, nb
+    return _workspace(nb, device), nb
 
 
 def _mesh_args(verts: torch.Tensor, faces: torch.Tensor):
@@ -127,7 +120,7 @@ def subdivide(verts: torch.Tensor, faces: torch.Tensor, levels: int = 1) -> Tupl
         V, F = int(v.shape[0]), int(f.shape[0])
         if F == 0:
             break
-        ws, nb = _workspace(F, dev)
+        ws, nb = _mesh_workspace(F, dev)
         E = C.c_int64(0)
         with torch.cuda.device(dev):
             st = _stream(dev)
@@ -157,7 +150,7 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, weighting: str = "a
     if V == 0 or F == 0:
         return torch.zeros(V, 3, dtype=torch.float32, device=dev)
     out = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    ws, nb = _workspace(F, dev)
+    ws, nb = _mesh_workspace(F, dev)
     with torch.cuda.device(dev):
         check(hip_lib.lib().soar_mesh_vertex_normals(V, F, v.data_ptr(), f.data_ptr(), WEIGHTINGS[weighting], ws.data_ptr(), nb,
                                                      out.data_ptr(), _stream(dev)), "soar_mesh_vertex_normals")

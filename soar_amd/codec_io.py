@@ -10,7 +10,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 
 def need_hip_tensor(name: str, t, module: str) -> None:
@@ -38,10 +38,6 @@ def batch_view(who: str, images: torch.Tensor) -> Tuple[torch.Tensor, Optional[i
     return images, images.data_ptr() if B else None, images.stride(0) if B > 1 else H * W * ch
 
 
-def _workspace(lib, sizing: str, a, dev) -> torch.Tensor:
-    return torch.empty(hip_lib._bytes(getattr(lib, sizing), sizing, ctypes.byref(a)), dtype=torch.uint8, device=dev)
-
-
 def measure_and_emit(who: str, a, entry_points: Tuple[str, str, str], B: int, dev, out: Optional[torch.Tensor]):
     """``a``: an encoder's args; ``entry_points``: its sizing, measure and emit calls -> ``(data, offsets, host)``: ``host`` is the
     host copy of the offsets that sized ``data``, None with a caller's ``out``."""
@@ -50,11 +46,11 @@ def measure_and_emit(who: str, a, entry_points: Tuple[str, str, str], B: int, de
         raise ValueError(f"{who}: out must be a contiguous 1-D uint8 tensor on {dev}")
     sizing, measure, emit = entry_points
     lib = hip_lib.lib()
-    ws = _workspace(lib, sizing, a, dev)
+    ws = _workspace(_bytes(getattr(lib, sizing), sizing, ctypes.byref(a)), dev)
     offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
     host = None
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         check(getattr(lib, measure)(ctypes.byref(a), ws.data_ptr(), ws.numel(), offsets.data_ptr(), stream), measure)
         if out is None:
             host = offsets.cpu()                                  # the one read-back: B + 1 offsets
@@ -121,12 +117,12 @@ def decode(who: str, module: str, a, entry_points: Tuple[str, str], table: Dict[
         a.B, a.H, a.W, a.channels, a.total_bytes = B, H, W, ch, data.numel()
         a.data, a.offsets = hip_lib.ptr(data), offsets.data_ptr()
         lib = hip_lib.lib()
-        ws = _workspace(lib, sizing, a, dev)
+        ws = _workspace(_bytes(getattr(lib, sizing), sizing, ctypes.byref(a)), dev)
         with torch.cuda.device(dev):
             if data.numel() == 0:
                 a.data = ws.data_ptr()                            # (no byte of it is read: every file is empty)
             check(getattr(lib, decoder)(ctypes.byref(a), ws.data_ptr(), ws.numel(), out.data_ptr(), status.data_ptr(), info.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream), decoder)
+                                        _stream(dev)), decoder)
     if strict:
         raise_on_status(status, table, lambda i: f"{who}: file {i} of {B}", list_failed=True)
         return (out, info) if return_info else out

@@ -1,10 +1,12 @@
 // codec_common.h -- the host-side plumbing that the image codecs share (png.hip, video.hip, png_decode.hip, jpeg_decode.hip): the
 // encoders' sizes -> offsets step (a scan over the pieces, then one offset per item) with its workspace blocks, and the argument
 // checks the entry points have in common.  The kernels and the workspace layouts stay in the codecs' own files; the checksums of PNG
-// are in png_common.h.  As in mesh_common.h, what launches or scans is a template so that it exists only in the files that use it.
+// are in png_common.h.  The carver and the workspace check come from workspace.h, the scans from scan_sort.h.  What launches or scans
+// is a template so that it exists only in the files that use it.
 #pragma once
 
-#include "mesh_common.h"
+#include "scan_sort.h"
+#include "workspace.h"
 
 namespace soar {
 namespace {

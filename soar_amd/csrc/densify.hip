@@ -13,7 +13,7 @@
 // The state machine is deterministic given the accumulators and the normal samples, so ranks of a frame-data-parallel job
 // that all-reduce the accumulators and share the noise generator stay identical (soar_amd/densify.py).
 // Built with -ffp-contract=off: thresholds decide integer layout.
-#include "soar_common.h"
+#include "workspace.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -45,15 +45,14 @@ inline size_t plan_scan_bytes(int P)
 
 inline size_t carve_plan(PlanBuf &b, void *base, int P)
 {
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t n) { char *q = p; p += (n + 255) & ~(size_t)255; return q; };
-    b.flags = reinterpret_cast<uint8_t *>(take((size_t)P));
-    b.packed = reinterpret_cast<uint64_t *>(take((size_t)P * 8));
-    b.offs = reinterpret_cast<uint64_t *>(take((size_t)P * 8));
-    b.totals = reinterpret_cast<uint64_t *>(take(8));
+    Carver c(base);
+    b.flags = c.take<uint8_t>((size_t)P);
+    b.packed = c.take<uint64_t>((size_t)P);
+    b.offs = c.take<uint64_t>((size_t)P);
+    b.totals = c.take<uint64_t>(1);
     b.scan_bytes = plan_scan_bytes(P);
-    b.scan_temp = take(b.scan_bytes);
-    return (size_t)(p - static_cast<char *>(base));
+    b.scan_temp = c.take<char>(b.scan_bytes);
+    return c.bytes();
 }
 
 __global__ void __launch_bounds__(256) densify_stats_kernel(int P, const int *__restrict__ radii, const float *__restrict__ grad2d,

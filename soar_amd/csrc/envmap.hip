@@ -14,7 +14,7 @@
 //
 // The whole file is compiled without contraction (build.py): comp is then rounded as torch's three separate operations, and
 // the backward's recomputed bg is the forward's bg.  No host synchronisation, no allocation.
-#include "soar_common.h"
+#include "workspace.h"
 
 namespace soar {
 
@@ -293,10 +293,11 @@ int blocks_of(int64_t npix)
     const int64_t chunks = (npix + CHUNK - 1) / CHUNK;
     return (int)(chunks < MAX_G ? chunks : MAX_G);
 }
+// one block: the backward's partial rows.  Never 0 bytes
 size_t ws_bytes(int64_t npix)
 {
     const size_t b = (size_t)blocks_of(npix) * NW * sizeof(double);
-    return b == 0 ? ALIGN : (b + ALIGN - 1) / ALIGN * ALIGN;
+    return b == 0 ? ALIGN : align_up(b);
 }
 
 bool check_sizes(const char *what, int32_t B, int32_t H, int32_t W)
@@ -373,12 +374,8 @@ extern "C" int soar_envmap_forward(const SoarEnvmapArgs *args, void *stream_)
 extern "C" int soar_envmap_backward(const SoarEnvmapArgs *args, void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (!check_args("soar_envmap_backward", args)) return 1;
-    size_t need = 0;
-    soar_envmap_workspace_bytes(args->B, args->H, args->W, &need);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & (ALIGN - 1))) {
-        set_error("soar_envmap_backward: workspace must be %zu bytes, 256-byte aligned (got %zu)", need, workspace_bytes);
-        return 1;
-    }
+    const size_t need = ws_bytes((int64_t)args->B * args->H * args->W);
+    if (!workspace_ok("soar_envmap_backward", workspace, workspace_bytes, need, "soar_envmap_workspace_bytes")) return 1;
     const bool want_w = args->d_w1 || args->d_w2 || args->d_w3;
     if (want_w && !(args->d_w1 && args->d_w2 && args->d_w3)) {
         set_error("soar_envmap_backward: d_w1, d_w2 and d_w3 are wanted together or not at all");

@@ -9,7 +9,7 @@
 // the last 7 of them kept in registers, their sum is the window's.  No float atomics: a workgroup leaves four float64 partial sums
 // in the caller's scratch, a second small kernel adds them per image in a fixed order.
 // Compiled with -ffp-contract=off: the values are pinned on a NumPy restatement (tests/eval_ref.py).
-#include "soar_common.h"
+#include "workspace.h"
 
 namespace soar {
 namespace {
@@ -200,10 +200,7 @@ int soar_eval_image_metrics(const SoarEvalArgs *args, void *scratch, size_t scra
     if (!a.gt_white || !a.pred2 || !a.gt2 || !a.metrics) { set_error("%s: NULL gt_white / pred2 / gt2 / metrics", me); return 1; }
     size_t need = 0;
     if (soar_eval_scratch_bytes(a.N, a.H, a.W, &need)) return 1;
-    if (!scratch || scratch_bytes < need) {
-        set_error("%s: scratch of %zu bytes, %zu needed (soar_eval_scratch_bytes)", me, scratch ? scratch_bytes : (size_t)0, need);
-        return 1;
-    }
+    if (!workspace_ok(me, scratch, scratch_bytes, need, "soar_eval_scratch_bytes")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     EvalDev d;
     d.H = a.H; d.W = a.W;

@@ -15,7 +15,7 @@
 //
 // The table gradients are the only atomics: their last bits depend on arrival order.  Everything else is bit-identical
 // from run to run.  No host synchronisation, no allocation.
-#include "soar_common.h"
+#include "workspace.h"
 
 namespace soar {
 
@@ -561,8 +561,6 @@ size_t partial_floats(int N)
     for (int k = 0; k < NHEAD; k++) s += (size_t)blocks_of(N) * head_floats(k);
     return s;
 }
-size_t ws_round(size_t b) { return (b + ALIGN - 1) / ALIGN * ALIGN; }
-
 bool check_args(const char *what, const SoarFieldArgs *a)
 {
     if (!a) { set_error("%s: NULL args", what); return false; }
@@ -604,6 +602,16 @@ FieldK make_k(const SoarFieldArgs *a)
     return k;
 }
 
+// the backward's workspace: dL/de of every head, then the blocks' partial sums.  Never 0 bytes
+size_t carve(int N, void *workspace, FieldK *k)
+{
+    Carver c(workspace);
+    float *de = c.take<float>(de_floats(N));
+    float *partial = c.take<float>(partial_floats(N));
+    if (k) { k->de = de; k->partial = partial; }
+    return c.bytes() ? c.bytes() : ALIGN;
+}
+
 }  // namespace
 }  // namespace soar
 
@@ -612,8 +620,7 @@ using namespace soar;
 extern "C" int soar_field_workspace_bytes(int32_t N, size_t *bytes)
 {
     if (!bytes || N < 0 || N > MAX_N) { set_error("soar_field_workspace_bytes: bad arguments (N=%d)", N); return 1; }
-    *bytes = ws_round(de_floats(N) * sizeof(float)) + ws_round(partial_floats(N) * sizeof(float));
-    if (*bytes == 0) *bytes = ALIGN;
+    *bytes = carve(N, nullptr, nullptr);
     return 0;
 }
 
@@ -633,12 +640,7 @@ extern "C" int soar_field_forward(const SoarFieldArgs *args, void *stream_)
 extern "C" int soar_field_backward(const SoarFieldArgs *args, void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (!check_args("soar_field_backward", args)) return 1;
-    size_t need = 0;
-    soar_field_workspace_bytes(args->N, &need);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & (ALIGN - 1))) {
-        set_error("soar_field_backward: workspace must be %zu bytes, 256-byte aligned (got %zu)", need, workspace_bytes);
-        return 1;
-    }
+    if (!workspace_ok("soar_field_backward", workspace, workspace_bytes, carve(args->N, nullptr, nullptr), "soar_field_workspace_bytes")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const size_t rows = (size_t)LEVELS << args->log2_T;
     if (args->d_table) SOAR_HIP_OK(hipMemsetAsync(args->d_table, 0, rows * 2 * sizeof(float), stream));
@@ -650,8 +652,7 @@ extern "C" int soar_field_backward(const SoarFieldArgs *args, void *workspace, s
         return 0;
     }
     FieldK k = make_k(args);
-    k.de = static_cast<float *>(workspace);
-    k.partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + ws_round(de_floats(args->N) * sizeof(float)));
+    carve(args->N, workspace, &k);
     bool any = false;
     for (int h = 0; h < NHEAD; h++) {
         if (args->g_out[h]) any = true;

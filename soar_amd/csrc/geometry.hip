@@ -8,7 +8,7 @@
 //    partial sums in double that a second, one-workgroup launch adds in a fixed order (bitwise reproducible, no float atomics).
 //
 // Both are memory-bound streams of about 100 bytes per surfel: one thread per surfel, wave64, no LDS beyond the block reduction.
-#include "soar_common.h"
+#include "workspace.h"
 
 #include <cmath>
 #include <cstdint>
@@ -259,8 +259,7 @@ extern "C" int soar_surfel_regularizers_workspace_bytes(int32_t P, size_t *bytes
         set_error("soar_surfel_regularizers_workspace_bytes: bad arguments (P=%d >= 0, bytes must be given)", P);
         return 1;
     }
-    const size_t n = (size_t)reg_blocks(P) * REG_TERMS * sizeof(double);
-    *bytes = (n + ALIGN - 1) / ALIGN * ALIGN;
+    *bytes = align_up((size_t)reg_blocks(P) * REG_TERMS * sizeof(double));
     return 0;
 }
 
@@ -277,10 +276,8 @@ extern "C" int soar_surfel_regularizers(int32_t P, int32_t S, int32_t K, const f
     if (P == 0) return 0;
     size_t need = 0;
     soar_surfel_regularizers_workspace_bytes(P, &need);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7u)) {
-        set_error("soar_surfel_regularizers: workspace of %zu bytes (8-byte aligned) needed, %zu given", need, workspace_bytes);
-        return 1;
-    }
+    // one block of doubles: 8-byte alignment is all it needs
+    if (!workspace_ok("soar_surfel_regularizers", workspace, workspace_bytes, need, "soar_surfel_regularizers_workspace_bytes", 8)) return 1;
     RegArgs a = {};
     a.P = P; a.S = S; a.K = K;
     a.xyz = xyz; a.original_pos = original_pos; a.scaling = scaling; a.opacity = opacity; a.scales = scales;

@@ -16,7 +16,7 @@
 //           the K-th place in list order until K are reached), then lanes = joints blend their skinning rows, so row
 //           reads and the 220-byte result row are coalesced.
 // A generic one-thread-per-query kernel (any K <= 32, any J) is kept for non-default K / J.
-#include "soar_common.h"
+#include "workspace.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -1211,20 +1211,18 @@ int carve_knn_grid(void *base, int32_t V, KnnGrid *g, hipStream_t stream)
     size_t sort_bytes = 0;
     (void)rocprim::radix_sort_pairs((void *)nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                     (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)V, 0u, 18u, stream);     // size query only
-    char *b = static_cast<char *>(base);
-    size_t off = 0;
-    auto carve = [&](size_t n) { size_t o = off; off = align_up(off + n); return b + o; };
-    g->meta = reinterpret_cast<GridMeta *>(carve(sizeof(GridMeta)));
-    g->cell_range = reinterpret_cast<uint2 *>(carve(sizeof(uint2) * (size_t)GRID_CELLS));
-    g->sorted_verts = reinterpret_cast<float4 *>(carve(sizeof(float4) * (size_t)V));
-    g->rows = reinterpret_cast<float *>(carve(sizeof(float) * (size_t)V * KNN_JMAX));
-    g->k0 = reinterpret_cast<uint32_t *>(carve(4 * (size_t)V));
-    g->k1 = reinterpret_cast<uint32_t *>(carve(4 * (size_t)V));
-    g->v0 = reinterpret_cast<uint32_t *>(carve(4 * (size_t)V));
-    g->v1 = reinterpret_cast<uint32_t *>(carve(4 * (size_t)V));
-    g->sort_tmp = carve(sort_bytes);
+    Carver c(base);
+    g->meta = c.take<GridMeta>(1);
+    g->cell_range = c.take<uint2>((size_t)GRID_CELLS);
+    g->sorted_verts = c.take<float4>((size_t)V);
+    g->rows = c.take<float>((size_t)V * KNN_JMAX);
+    g->k0 = c.take<uint32_t>((size_t)V);
+    g->k1 = c.take<uint32_t>((size_t)V);
+    g->v0 = c.take<uint32_t>((size_t)V);
+    g->v1 = c.take<uint32_t>((size_t)V);
+    g->sort_tmp = c.take<char>(sort_bytes);
     g->sort_bytes = sort_bytes;
-    g->total = off + ALIGN;
+    g->total = c.bytes() + ALIGN;
     return 0;
 }
 
@@ -1248,6 +1246,7 @@ int knn_build(const float *verts, int32_t V, const float *vert_weights, int32_t 
 // and the order is stored; resort == 0: the stored order is reused and only the cell keys are recomputed.
 struct QueryWs {
     size_t sort_bytes, total;
+    void *sort_tmp;
     uint32_t *qk0, *qk1, *qv0, *qv1;
     uint32_t *item_cost, *item_order; // [KNN_SLOTS * ceil(P / 64) (+ 1)] cost and heaviest-first order of the (chunk, slot) work items
                                       // (kept between re-sorts)
@@ -1260,18 +1259,14 @@ int carve_query_ws(void *base, int32_t P, QueryWs *out, hipStream_t stream)
     // without a GPU, where the sizing entry points are part of the CPU test suite)
     (void)rocprim::radix_sort_pairs((void *)nullptr, qsort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                     (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)(P > 0 ? P : 1), 0u, 18u, stream);
-    size_t off = 0;
-    auto carve = [&](size_t n) { size_t o = off; off = align_up(off + n); return o; };
-    const size_t o_tmp = carve(qsort_bytes), o_qk0 = carve(4 * (size_t)P), o_qk1 = carve(4 * (size_t)P),
-                 o_qv0 = carve(4 * (size_t)P), o_qv1 = carve(4 * (size_t)P), o_cost = carve(4 * KNN_SLOTS * (((size_t)P + WAVE - 1) / WAVE)),
-                 o_ord = carve(4 * (KNN_SLOTS * (((size_t)P + WAVE - 1) / WAVE) + 1));
-    (void)o_tmp;
-    char *b = static_cast<char *>(base);
+    const size_t items = KNN_SLOTS * (((size_t)P + WAVE - 1) / WAVE);
+    Carver c(base);
     out->sort_bytes = qsort_bytes;
-    out->total = off;
-    out->qk0 = reinterpret_cast<uint32_t *>(b + o_qk0); out->qk1 = reinterpret_cast<uint32_t *>(b + o_qk1);
-    out->qv0 = reinterpret_cast<uint32_t *>(b + o_qv0); out->qv1 = reinterpret_cast<uint32_t *>(b + o_qv1);
-    out->item_cost = reinterpret_cast<uint32_t *>(b + o_cost); out->item_order = reinterpret_cast<uint32_t *>(b + o_ord);
+    out->sort_tmp = c.take<char>(qsort_bytes);
+    out->qk0 = c.take<uint32_t>((size_t)P); out->qk1 = c.take<uint32_t>((size_t)P);
+    out->qv0 = c.take<uint32_t>((size_t)P); out->qv1 = c.take<uint32_t>((size_t)P);
+    out->item_cost = c.take<uint32_t>(items); out->item_order = c.take<uint32_t>(items + 1);
+    out->total = c.bytes();
     return 0;
 }
 
@@ -1279,17 +1274,15 @@ int carve_query_ws(void *base, int32_t P, QueryWs *out, hipStream_t stream)
 struct KnnState { KnnStatePtrs p; size_t total; };
 int carve_knn_state(void *base, int32_t P, KnnState *out)
 {
-    char *b = static_cast<char *>(base);
     const size_t n = (size_t)(P > 0 ? P : 1);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return b + o; };
-    out->p.nbr = reinterpret_cast<uint32_t *>(carve(sizeof(uint32_t) * KNN_STATE_STRIDE * n));
-    out->p.ref30 = reinterpret_cast<float4 *>(carve(sizeof(float4) * n));
-    out->p.ref32 = reinterpret_cast<float4 *>(carve(sizeof(float4) * n));
-    out->p.in30 = reinterpret_cast<uint32_t *>(carve(sizeof(uint32_t) * n));
-    out->p.work = reinterpret_cast<uint32_t *>(carve(sizeof(uint32_t) * knn_work_words(P)));
-    out->p.d2 = reinterpret_cast<float *>(carve(sizeof(float) * KNN_STATE_STRIDE * n));
-    out->total = off;
+    Carver c(base);
+    out->p.nbr = c.take<uint32_t>(KNN_STATE_STRIDE * n);
+    out->p.ref30 = c.take<float4>(n);
+    out->p.ref32 = c.take<float4>(n);
+    out->p.in30 = c.take<uint32_t>(n);
+    out->p.work = c.take<uint32_t>(knn_work_words(P));
+    out->p.d2 = c.take<float>(KNN_STATE_STRIDE * n);
+    out->total = c.bytes();
     return 0;
 }
 
@@ -1310,20 +1303,15 @@ int knn_query(const KnnGrid &g, int32_t V, const float *vert_weights, int32_t J,
     // query-side workspace (keys / ids of the cell sort): caller-owned, carved here
     QueryWs ws;
     if (carve_query_ws(query_ws, P, &ws, stream)) return 1;
-    if (ws.total > query_ws_bytes) {
-        set_error("soar_lbs_knn_query: query workspace too small (%zu bytes, need %zu for P=%d)", query_ws_bytes, ws.total, P);
-        return 1;
-    }
+    if (!workspace_ok("soar_lbs_knn_query", query_ws, query_ws_bytes, ws.total, "soar_lbs_knn_query_bytes")) return 1;
     size_t qsort_bytes = ws.sort_bytes;
-    char *b = static_cast<char *>(query_ws);
-    const size_t o_tmp = 0;
     uint32_t *qk0 = ws.qk0, *qk1 = ws.qk1, *qv0 = ws.qv0, *qv1 = ws.qv1;
     if (order && !resort) {
         hipLaunchKernelGGL(query_cells_ordered_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, xyz, P, g.meta, order, qk1);
         qv1 = order;
     } else {
         hipLaunchKernelGGL(query_cells_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, xyz, P, g.meta, qk0, qv0);
-        SOAR_HIP_OK(rocprim::radix_sort_pairs(b + o_tmp, qsort_bytes, qk0, qk1, qv0, order ? order : qv1, (size_t)P, 0u, 18u,
+        SOAR_HIP_OK(rocprim::radix_sort_pairs(ws.sort_tmp, qsort_bytes, qk0, qk1, qv0, order ? order : qv1, (size_t)P, 0u, 18u,
                                               stream));
         if (order) qv1 = order;
         // the item order is rebuilt with every sort and reused by the calls that keep the stored query order
@@ -1379,13 +1367,9 @@ extern "C" int soar_lbs_knn_query_bytes(int32_t P, size_t *bytes)
     return 0;
 }
 
-static int check_ws(const char *who, const void *ws, size_t have)
-{
-    if (!ws) { set_error("%s: NULL workspace (caller-owned, see the *_bytes query)", who); return 1; }
-    if (reinterpret_cast<uintptr_t>(ws) % ALIGN) { set_error("%s: workspace is not %zu-byte aligned", who, ALIGN); return 1; }
-    (void)have;
-    return 0;
-}
+// a caller-owned buffer at the head of the argument checks: the query path judges its size once it knows that it needs it, and the
+// ABI does not pass the state buffer's
+static int check_ws(const char *who, const void *ws) { return workspace_ok(who, ws, 0, 0, "") ? 0 : 1; }
 
 extern "C" int soar_lbs_knn_query(const void *grid_buffer, int32_t V, const float *vert_weights, int32_t J, const float *xyz,
                                   int32_t P, int32_t K, float *weights_out, int32_t *knn_idx_out, void *query_workspace,
@@ -1395,7 +1379,7 @@ extern "C" int soar_lbs_knn_query(const void *grid_buffer, int32_t V, const floa
     if (check_knn_sizes(P, V, J, K)) return 1;
     if (P == 0) return 0;
     if (!grid_buffer || !xyz || !vert_weights || !weights_out) { set_error("soar_lbs_knn_query: NULL pointer"); return 1; }
-    if (check_ws("soar_lbs_knn_query", query_workspace, query_workspace_bytes)) return 1;
+    if (check_ws("soar_lbs_knn_query", query_workspace)) return 1;
     KnnGrid g;
     if (carve_knn_grid(const_cast<void *>(grid_buffer), V, &g, stream)) return 1;
     StageTimer timer(ST_LBS_KNN, stream);
@@ -1411,7 +1395,7 @@ extern "C" int soar_lbs_knn_query_ordered(const void *grid_buffer, int32_t V, co
     if (check_knn_sizes(P, V, J, K)) return 1;
     if (P == 0) return 0;
     if (!grid_buffer || !xyz || !vert_weights || !weights_out || !order) { set_error("soar_lbs_knn_query_ordered: NULL pointer"); return 1; }
-    if (check_ws("soar_lbs_knn_query_ordered", query_workspace, query_workspace_bytes)) return 1;
+    if (check_ws("soar_lbs_knn_query_ordered", query_workspace)) return 1;
     KnnGrid g;
     if (carve_knn_grid(const_cast<void *>(grid_buffer), V, &g, stream)) return 1;
     StageTimer timer(ST_LBS_KNN, stream);
@@ -1437,7 +1421,7 @@ extern "C" int soar_lbs_knn_query_state(const void *grid_buffer, int32_t V, cons
     if (V < KNN_STATE_STRIDE) { set_error("soar_lbs_knn_query_state: the neighbour state keeps %d vertices per query, V=%d", KNN_STATE_STRIDE, V); return 1; }
     if (P == 0) return 0;
     if (!grid_buffer || !xyz || !vert_weights || !weights_out || !order || !state_buffer) { set_error("soar_lbs_knn_query_state: NULL pointer"); return 1; }
-    if (check_ws("soar_lbs_knn_query_state", query_workspace, query_workspace_bytes) || check_ws("soar_lbs_knn_query_state", state_buffer, 0)) return 1;
+    if (check_ws("soar_lbs_knn_query_state", query_workspace) || check_ws("soar_lbs_knn_query_state", state_buffer)) return 1;
     KnnGrid g;
     if (carve_knn_grid(const_cast<void *>(grid_buffer), V, &g, stream)) return 1;
     if (V <= KNN_KEEP) { set_error("soar_lbs_knn_query_state: the neighbour state keeps %d vertices per query, V = %d", KNN_KEEP, V); return 1; }
@@ -1458,7 +1442,7 @@ extern "C" int soar_lbs_knn_refresh(const void *grid_buffer, int32_t V, int32_t 
     if (V < KNN_STATE_STRIDE) { set_error("soar_lbs_knn_refresh: the neighbour state keeps %d vertices per query, V=%d", KNN_STATE_STRIDE, V); return 1; }
     if (P == 0) return 0;
     if (!grid_buffer || !xyz || !weights_out || !state_buffer || !order) { set_error("soar_lbs_knn_refresh: NULL pointer"); return 1; }
-    if (check_ws("soar_lbs_knn_refresh", state_buffer, 0)) return 1;
+    if (check_ws("soar_lbs_knn_refresh", state_buffer)) return 1;
     KnnGrid g;
     if (carve_knn_grid(const_cast<void *>(grid_buffer), V, &g, stream)) return 1;
     KnnState st;
@@ -1494,16 +1478,12 @@ extern "C" int soar_lbs_knn_weights(const float *xyz, int32_t P, const float *ve
     if (check_knn_sizes(P, V, J, K)) return 1;
     if (P == 0) return 0;
     if (!xyz || !verts || !vert_weights || !weights_out) { set_error("soar_lbs_knn_weights: NULL pointer"); return 1; }
-    if (check_ws("soar_lbs_knn_weights", workspace, workspace_bytes)) return 1;
     KnnGrid g;
     if (carve_knn_grid(workspace, V, &g, stream)) return 1;
     QueryWs ws;
     if (carve_query_ws(nullptr, P, &ws, stream)) return 1;
     const size_t grid_part = align_up(g.total);
-    if (workspace_bytes < grid_part + ws.total) {
-        set_error("soar_lbs_knn_weights: workspace too small (%zu bytes, need %zu)", workspace_bytes, grid_part + ws.total);
-        return 1;
-    }
+    if (!workspace_ok("soar_lbs_knn_weights", workspace, workspace_bytes, grid_part + ws.total, "soar_lbs_knn_weights_bytes")) return 1;
     StageTimer timer(ST_LBS_KNN, stream);
     if (knn_build(verts, V, vert_weights, J, g, stream)) return 1;
     return knn_query(g, V, vert_weights, J, xyz, P, K, weights_out, knn_idx_out, nullptr, 1,

@@ -18,6 +18,7 @@
 // No atomics: every value and gradient has one fixed order of summation (bitwise reproducible).  No host synchronisation, no
 // allocation.
 #include "conv_gemm.h"
+#include "workspace.h"
 
 namespace soar {
 
@@ -49,17 +50,16 @@ struct WLayout {
 WLayout wlayout()
 {
     WLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t floats) { const size_t o = off; off += (floats + 63) / 64 * 64; return o; };
+    Carver pk;
     for (int i = 0; i < NL; i++) {
-        L.fwd[i] = take((size_t)COUT[i] * 9 * CIN[i]);         // conv1_1: the torch layout [64][3][3][3]
-        L.bwd[i] = i == 0 ? 0 : take((size_t)COUT[i] * 9 * CIN[i]);
-        L.bias[i] = take(COUT[i]);
+        L.fwd[i] = pk.float_offset((size_t)COUT[i] * 9 * CIN[i]);         // conv1_1: the torch layout [64][3][3][3]
+        L.bwd[i] = i == 0 ? 0 : pk.float_offset((size_t)COUT[i] * 9 * CIN[i]);
+        L.bias[i] = pk.float_offset(COUT[i]);
     }
-    for (int k = 0; k < NT; k++) L.lin[k] = take(TAP_C[k]);
-    L.shift = take(3);
-    L.scale = take(3);
-    L.total = off;
+    for (int k = 0; k < NT; k++) L.lin[k] = pk.float_offset(TAP_C[k]);
+    L.shift = pk.float_offset(3);
+    L.scale = pk.float_offset(3);
+    L.total = pk.bytes() / sizeof(float);
     return L;
 }
 
@@ -88,25 +88,24 @@ struct WsLayout {
 WsLayout ws_layout(const Dims &d, int grads)
 {
     WsLayout L{};
-    size_t off = 0;
-    auto take = [&](int64_t floats) { const size_t o = off; off += align_up((size_t)floats * sizeof(float)); return o; };
+    Carver ws;
     const int64_t widest = d.pix(0) * 64;                      // level 0 at 64 channels holds the most of any level
     for (int b = 0; b < 2; b++) {
         if (grads & (1 << b)) {
-            for (int i = 0; i < NL; i++) L.act[b][i] = take(d.pix(LEVEL[i]) * COUT[i]);
-            for (int k = 0; k < NT; k++) L.gtap[b][k] = take(d.pix(LEVEL[TAP_LAYER[k]]) * TAP_C[k]);
+            for (int i = 0; i < NL; i++) L.act[b][i] = ws.offset<float>(d.pix(LEVEL[i]) * COUT[i]);
+            for (int k = 0; k < NT; k++) L.gtap[b][k] = ws.offset<float>(d.pix(LEVEL[TAP_LAYER[k]]) * TAP_C[k]);
         } else {
-            L.ping[b][0] = take(widest);
-            L.ping[b][1] = take(widest);
+            L.ping[b][0] = ws.offset<float>(widest);
+            L.ping[b][1] = ws.offset<float>(widest);
         }
     }
-    L.pool = take(d.pix(1) * 64);
-    for (int k = 0; k < NT; k++) L.s[k] = take(d.pix(LEVEL[TAP_LAYER[k]]));
+    L.pool = ws.offset<float>(d.pix(1) * 64);
+    for (int k = 0; k < NT; k++) L.s[k] = ws.offset<float>(d.pix(LEVEL[TAP_LAYER[k]]));
     if (grads) {
-        L.gbuf[0] = take(widest);
-        L.gbuf[1] = take(widest);
+        L.gbuf[0] = ws.offset<float>(widest);
+        L.gbuf[1] = ws.offset<float>(widest);
     }
-    L.total = off == 0 ? ALIGN : off;
+    L.total = ws.bytes() == 0 ? ALIGN : ws.bytes();
     return L;
 }
 
@@ -515,12 +514,7 @@ bool check_args(const char *what, const SoarLpipsArgs *a, const void *ws, size_t
     if (a->N == 0) return true;
     if (!a->in0 || !a->in1 || !a->weights) { set_error("%s: NULL in0 / in1 / weights", what); return false; }
     if ((uintptr_t)a->weights & (ALIGN - 1)) { set_error("%s: the packed weights must be 256-byte aligned", what); return false; }
-    const size_t need = ws_layout(dims_of(a->N, a->H, a->W), a->grads).total;
-    if (!ws || ws_bytes < need || ((uintptr_t)ws & (ALIGN - 1))) {
-        set_error("%s: workspace must be %zu bytes, 256-byte aligned (got %zu)", what, need, ws_bytes);
-        return false;
-    }
-    return true;
+    return workspace_ok(what, ws, ws_bytes, ws_layout(dims_of(a->N, a->H, a->W), a->grads).total, "soar_lpips_workspace_bytes");
 }
 
 }  // namespace

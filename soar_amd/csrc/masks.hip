@@ -25,7 +25,7 @@
 //
 // Everything is integer arithmetic; the sums are integer atomics, so outputs and statistics are the same bits in every run.  The
 // number of launches does not depend on the images, nothing is read back, nothing is allocated.
-#include "soar_common.h"
+#include "workspace.h"
 
 namespace soar {
 
@@ -428,25 +428,13 @@ bool masks_shape(const char *what, int N, int K, int H, int W)
 Layout masks_layout(int N, int H, int W)
 {
     Layout l;
+    Carver c;
     l.WPR = (W + 31) / 32;
-    l.key = 0;
-    l.plane = align_up((size_t)N * sizeof(unsigned long long));
-    l.parent = l.plane + align_up((size_t)N * H * l.WPR * sizeof(uint32_t));
-    l.total = l.parent + align_up((size_t)N * H * W * sizeof(int32_t));
+    l.key = c.offset<unsigned long long>((size_t)N);
+    l.plane = c.offset<uint32_t>((size_t)N * H * l.WPR);
+    l.parent = c.offset<int32_t>((size_t)N * H * W);
+    l.total = c.bytes();
     return l;
-}
-
-bool masks_workspace(const char *what, const Layout &l, const void *workspace, size_t workspace_bytes)
-{
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) % ALIGN)) {
-        set_error("%s: NULL workspace or workspace not 256-byte aligned", what);
-        return false;
-    }
-    if (workspace_bytes < l.total) {
-        set_error("%s: workspace of %zu bytes, need %zu (soar_masks_workspace_bytes)", what, workspace_bytes, l.total);
-        return false;
-    }
-    return true;
 }
 
 int launch_pack(int N, int K, int H, int W, const void *cand, int dtype, float thr, int morph, const Layout &l, void *workspace,
@@ -496,7 +484,7 @@ int masks_run(const char *what, int N, int K, int H, int W, const void *cand, in
     if (!cand || !out || !stats) { set_error("%s: NULL argument", what); return 1; }
     if (dtype != DT_U8 && dtype != DT_F32) { set_error("%s: unknown dtype code %d (0: uint8 / bool, 1: float32)", what, dtype); return 1; }
     const Layout l = masks_layout(N, H, W);
-    if (!masks_workspace(what, l, workspace, workspace_bytes)) return 1;
+    if (!workspace_ok(what, workspace, workspace_bytes, l.total, "soar_masks_workspace_bytes")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (launch_pack(N, K, H, W, cand, dtype, thr, morph, l, workspace, stats, stream)) return 1;
     return launch_emit(N, H, W, select, l, workspace, out, stats, stream);

@@ -1,86 +1,18 @@
 // mesh_common.h -- what the mesh-export files (mesh.hip, mesh_simplify.hip, mesh_attr.hip, mesh_holes.hip, mesh_texture.hip and the
-// subdivision / normals half of body.hip) share: carving a caller's workspace into blocks, rocPRIM's temporary-size queries and
-// runs, the workspace check, a few device helpers and the compaction of a mesh under keep flags.  Only the export path includes it;
-// the files that run in a training step carve their workspaces themselves.
+// subdivision / normals half of body.hip) share: a few device helpers and the compaction of a mesh under keep flags.  It brings
+// along the workspace carver and check (workspace.h) and the rocPRIM wrappers (scan_sort.h), which every one of these files uses.
 //
 // The kernels here and compact_mesh are templates on a parameter that never varies: hipcc emits every __global__ function a file
 // defines, used or not, and instantiates rocPRIM's kernels behind every function it parses.  As templates they, and the uint32 scan
 // behind compact_mesh, exist only in the files that use them.
 #pragma once
 
-#include "soar_common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "scan_sort.h"
+#include "workspace.h"
 
 namespace soar {
 
 namespace {
-
-// ---- workspace ---------------------------------------------------------------------------------------------------------------
-
-// Blocks of a workspace, one after the other, each rounded up to 256 bytes.  With a NULL base (a _bytes query) every block is NULL
-// and only the offset advances: a NULL pointer takes no part in pointer arithmetic.
-struct Carver {
-    char *base;
-    size_t off = 0;
-    explicit Carver(void *workspace) : base(static_cast<char *>(workspace)) {}
-    template <class T> T *take(size_t count)
-    {
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += align_up(count * sizeof(T));
-        return p;
-    }
-    size_t bytes() const { return off; }
-};
-
-inline bool workspace_ok(const char *what, const void *workspace, size_t have, size_t need, const char *sizing_call)
-{
-    if (!workspace || ((uintptr_t)workspace & 255)) { set_error("%s: NULL workspace or workspace not 256-byte aligned", what); return false; }
-    if (have < need) { set_error("%s: workspace of %zu bytes, need %zu (%s)", what, have, need, sizing_call); return false; }
-    return true;
-}
-
-// ---- rocPRIM: temporary sizes (nothing runs, nothing is read) and runs.  A run takes the carved size by value and checks it -------
-
-template <class T> inline size_t scan_temp_bytes(size_t n, hipStream_t stream = 0)
-{
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan((void *)nullptr, bytes, (T *)nullptr, (T *)nullptr, (T)0, n, rocprim::plus<T>(), stream);
-    return bytes;
-}
-
-template <class K> inline size_t sort_keys_temp_bytes(size_t n, unsigned end_bit, hipStream_t stream = 0)
-{
-    size_t bytes = 0;
-    (void)rocprim::radix_sort_keys((void *)nullptr, bytes, (K *)nullptr, (K *)nullptr, n, 0u, end_bit, stream);
-    return bytes;
-}
-
-template <class K, class V> inline size_t sort_pairs_temp_bytes(size_t n, unsigned end_bit, hipStream_t stream = 0)
-{
-    size_t bytes = 0;
-    (void)rocprim::radix_sort_pairs((void *)nullptr, bytes, (K *)nullptr, (K *)nullptr, (V *)nullptr, (V *)nullptr, n, 0u, end_bit, stream);
-    return bytes;
-}
-
-template <class T> inline hipError_t exclusive_scan_sum(void *temp, size_t temp_bytes, T *in, T *out, size_t n, hipStream_t stream)
-{
-    return rocprim::exclusive_scan(temp, temp_bytes, in, out, (T)0, n, rocprim::plus<T>(), stream);
-}
-
-// stable, ascending, on the bits [0, end_bit)
-template <class K> inline hipError_t sort_keys(void *temp, size_t temp_bytes, K *in, K *out, size_t n, unsigned end_bit, hipStream_t stream)
-{
-    return rocprim::radix_sort_keys(temp, temp_bytes, in, out, n, 0u, end_bit, stream);
-}
-
-template <class K, class V>
-inline hipError_t sort_pairs(void *temp, size_t temp_bytes, K *keys, K *keys_out, V *vals, V *vals_out, size_t n, unsigned end_bit,
-                             hipStream_t stream)
-{
-    return rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_out, vals, vals_out, n, 0u, end_bit, stream);
-}
 
 // ---- device helpers ----------------------------------------------------------------------------------------------------------
 

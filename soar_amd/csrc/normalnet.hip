@@ -17,6 +17,7 @@
 // No atomics: every output has one fixed order of summation, the same whatever the tile and the batch (a batch of N is bit-equal to
 // N single calls).  No host synchronisation, no allocation.
 #include "conv_gemm.h"
+#include "workspace.h"
 
 namespace soar {
 
@@ -77,21 +78,19 @@ inline int phase_taps(int ph) { return ((ph >> 1) + 1) * ((ph & 1) + 1); }     /
 WLayout wlayout(const Cfg &c)
 {
     WLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t floats) { const size_t o = off; off += (floats + 63) / 64 * 64; return o; };
-    L.first = take((size_t)c.ngf * 49 * CIN0);
-    for (int i = 0; i < c.n_down; i++) L.down[i] = take((size_t)(c.ngf << (i + 1)) * 9 * (c.ngf << i));
+    Carver pk;
+    L.first = pk.float_offset((size_t)c.ngf * 49 * CIN0);
+    for (int i = 0; i < c.n_down; i++) L.down[i] = pk.float_offset((size_t)(c.ngf << (i + 1)) * 9 * (c.ngf << i));
     const size_t ct = (size_t)c.ctrunk();
-    L.block0 = off;
-    L.block_stride = (ct * 9 * ct + 63) / 64 * 64;
-    off += L.block_stride * 2 * (size_t)c.n_blocks;
+    L.block_stride = align_up(ct * 9 * ct * sizeof(float)) / sizeof(float);
+    L.block0 = pk.float_offset(L.block_stride * 2 * (size_t)c.n_blocks);
     for (int i = 0; i < c.n_down; i++) {
         const size_t cin = (size_t)c.ngf << (c.n_down - i), cout = cin / 2;
-        for (int ph = 0; ph < 4; ph++) L.up[i][ph] = take(cout * phase_taps(ph) * cin);
+        for (int ph = 0; ph < 4; ph++) L.up[i][ph] = pk.float_offset(cout * phase_taps(ph) * cin);
     }
-    L.last = take((size_t)3 * 49 * c.ngf);
-    L.last_bias = take(3);
-    L.total = off;
+    L.last = pk.float_offset((size_t)3 * 49 * c.ngf);
+    L.last_bias = pk.float_offset(3);
+    L.total = pk.bytes() / sizeof(float);
     return L;
 }
 inline int n_tensors(const Cfg &c) { return 1 + c.n_down + 2 * c.n_blocks + c.n_down + 2; }
@@ -106,19 +105,17 @@ struct WsLayout {
 WsLayout ws_layout(const Cfg &c, int N, int H, int W)
 {
     WsLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
-    const size_t widest = (size_t)N * H * W * c.ngf * sizeof(float);
-    for (int b = 0; b < 3; b++) L.buf[b] = take(widest);
+    Carver ws;
+    for (int b = 0; b < 3; b++) L.buf[b] = ws.offset<float>((size_t)N * H * W * c.ngf);
     size_t part = 0;
     for (int l = 0; l <= c.n_down; l++) {
         const size_t hw = (size_t)(H >> l) * (W >> l), ch = (size_t)c.ngf << l;
         const size_t v = (size_t)N * in_chunks((int64_t)hw) * ch * 2 * sizeof(double);
         part = v > part ? v : part;
     }
-    L.part = take(part);
-    L.stats = take((size_t)N * c.ctrunk() * 2 * sizeof(float));
-    L.total = off == 0 ? ALIGN : off;
+    L.part = ws.offset<char>(part);
+    L.stats = ws.offset<float>((size_t)N * c.ctrunk() * 2);
+    L.total = ws.bytes() == 0 ? ALIGN : ws.bytes();
     return L;
 }
 
@@ -490,10 +487,7 @@ extern "C" int soar_normalnet_forward(const SoarNormalNetArgs *a, void *workspac
     }
     if (((uintptr_t)a->weights_F | (uintptr_t)a->weights_B) & (ALIGN - 1)) { set_error("%s: the packed weights must be 256-byte aligned", what); return 1; }
     const WsLayout L = ws_layout(c, a->N, a->H, a->W);
-    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & (ALIGN - 1))) {
-        set_error("%s: workspace must be %zu bytes, 256-byte aligned (got %zu)", what, L.total, workspace ? workspace_bytes : (size_t)0);
-        return 1;
-    }
+    if (!workspace_ok(what, workspace, workspace_bytes, L.total, "soar_normalnet_workspace_bytes")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     char *ws = static_cast<char *>(workspace);
     if (run_generator(c, a, a->prior_F, a->prior_F_stride, static_cast<const float *>(a->weights_F), a->normal_F, ws, L, stream)) return 1;

@@ -1,5 +1,5 @@
 // png_common.h -- the checksums that the PNG encoder (png.hip) and decoder (png_decode.hip) share: CRC-32 over a stretch of bytes by the
-// 64 lanes of a wavefront, and the joining of Adler-32 values.
+// 64 lanes of a wavefront, and the joining of Adler-32 values; and the integer sum over a wavefront that both count with.
 #pragma once
 
 #include "soar_common.h"
@@ -9,6 +9,13 @@ namespace {
 
 constexpr uint32_t ADLER_MOD = 65521u;
 constexpr uint32_t CRC_POLY = 0xEDB88320u;
+
+// over the 64 lanes of a wavefront; every lane gets the result
+__device__ __forceinline__ int wave_sum_i(int x)
+{
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
+    return x;
+}
 
 // tab[256] in LDS, by one wavefront
 __device__ __forceinline__ void crc_table(uint32_t *tab, int lane)

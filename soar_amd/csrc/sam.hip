@@ -9,6 +9,7 @@
 // Every matrix product (linear layers, patch embedding, the neck's convolutions) is launch_conv_gemm (conv_gemm.h).
 // No atomics; no sum's order depends on the batch: a frame's result does not depend on its neighbours or its place among them.
 #include "conv_gemm.h"
+#include "workspace.h"
 
 #include <vector>
 
@@ -513,36 +514,31 @@ __global__ void __launch_bounds__(256) postprocess_kernel(const float *__restric
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------
-struct Carver {
-    char *base;
-    size_t used = 0;
-    float *take(size_t floats) { float *p = reinterpret_cast<float *>(base + used); used += align_up(floats * sizeof(float)); return p; }
-};
 struct EncWs { float *x, *t, *qkv, *h, *n1, *n2; };
 struct DecWs { float *q, *q0, *qpe, *keys, *kpe, *qp, *kp, *vp, *ao, *hid, *up1, *up2, *hy1, *hy2, *hin, *io1, *io2; };
 size_t carve_enc(const SoarSamConfig &c, int B, void *base, EncWs *w)
 {
-    Carver cv{static_cast<char *>(base)};
+    Carver cv(base);
     const size_t M = (size_t)B * c.grid * c.grid;
     EncWs e;
-    e.x = cv.take(M * c.embed); e.t = cv.take(M * c.embed); e.qkv = cv.take(M * 3 * c.embed); e.h = cv.take(M * c.mlp);
-    e.n1 = cv.take(M * c.out_chans); e.n2 = cv.take(M * c.out_chans);
+    e.x = cv.take<float>(M * c.embed); e.t = cv.take<float>(M * c.embed); e.qkv = cv.take<float>(M * 3 * c.embed); e.h = cv.take<float>(M * c.mlp);
+    e.n1 = cv.take<float>(M * c.out_chans); e.n2 = cv.take<float>(M * c.out_chans);
     if (w) *w = e;
-    return cv.used;
+    return cv.bytes();
 }
 size_t carve_dec(const SoarSamConfig &c, int B, int T, void *base, DecWs *w)
 {
-    Carver cv{static_cast<char *>(base)};
+    Carver cv(base);
     const size_t P = c.out_chans, HW = (size_t)c.grid * c.grid, R = HW > (size_t)T ? HW : (size_t)T, BT = (size_t)B * T;
     DecWs d;
-    d.q = cv.take(BT * P); d.q0 = cv.take(BT * P); d.qpe = cv.take(BT * P); d.keys = cv.take(B * HW * P); d.kpe = cv.take(B * HW * P);
-    d.qp = cv.take(B * R * P); d.kp = cv.take(B * R * P); d.vp = cv.take(B * R * P); d.ao = cv.take(B * R * P); d.hid = cv.take(BT * c.dec_mlp);
-    d.up1 = cv.take(B * HW * 4 * (P / 4)); d.up2 = cv.take(B * HW * 16 * (P / 8));
-    d.hy1 = cv.take((size_t)B * c.mask_tokens * P); d.hy2 = cv.take((size_t)B * c.mask_tokens * P); d.hin = cv.take((size_t)B * c.mask_tokens * (P / 8));
+    d.q = cv.take<float>(BT * P); d.q0 = cv.take<float>(BT * P); d.qpe = cv.take<float>(BT * P); d.keys = cv.take<float>(B * HW * P); d.kpe = cv.take<float>(B * HW * P);
+    d.qp = cv.take<float>(B * R * P); d.kp = cv.take<float>(B * R * P); d.vp = cv.take<float>(B * R * P); d.ao = cv.take<float>(B * R * P); d.hid = cv.take<float>(BT * c.dec_mlp);
+    d.up1 = cv.take<float>(B * HW * 4 * (P / 4)); d.up2 = cv.take<float>(B * HW * 16 * (P / 8));
+    d.hy1 = cv.take<float>((size_t)B * c.mask_tokens * P); d.hy2 = cv.take<float>((size_t)B * c.mask_tokens * P); d.hin = cv.take<float>((size_t)B * c.mask_tokens * (P / 8));
     const size_t iw = (size_t)(c.iou_hidden > c.mask_tokens ? c.iou_hidden : c.mask_tokens);
-    d.io1 = cv.take(B * iw); d.io2 = cv.take(B * iw);
+    d.io1 = cv.take<float>(B * iw); d.io2 = cv.take<float>(B * iw);
     if (w) *w = d;
-    return cv.used;
+    return cv.bytes();
 }
 
 }  // namespace
@@ -644,11 +640,7 @@ int soar_sam_encode(const SoarSamConfig *cfg, const void *packed, const SoarSamE
         set_error("%s: need packed weights, exactly one of patches and tokens_in, and tokens_out or embeddings", me);
         return 1;
     }
-    const size_t need = carve_enc(c, a.B, nullptr, nullptr);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) {
-        set_error("%s: the workspace is too small or not 256-byte aligned (%zu bytes, need %zu)", me, workspace_bytes, need);
-        return 1;
-    }
+    if (!workspace_ok(me, workspace, workspace_bytes, carve_enc(c, a.B, nullptr, nullptr), "soar_sam_workspace_bytes")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const Layout L = make_layout(c);
     const float *base = static_cast<const float *>(packed);
@@ -707,11 +699,7 @@ int soar_sam_decode(const SoarSamConfig *cfg, const void *packed, const SoarSamD
         set_error("%s: NULL packed weights, embeddings, counts, points, labels, low_res or iou", me);
         return 1;
     }
-    const size_t need = carve_dec(c, a.B, T, nullptr, nullptr);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) {
-        set_error("%s: the workspace is too small or not 256-byte aligned (%zu bytes, need %zu)", me, workspace_bytes, need);
-        return 1;
-    }
+    if (!workspace_ok(me, workspace, workspace_bytes, carve_dec(c, a.B, T, nullptr, nullptr), "soar_sam_workspace_bytes")) return 1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const Layout L = make_layout(c);
     const float *base = static_cast<const float *>(packed);

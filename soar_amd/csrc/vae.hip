@@ -31,6 +31,7 @@
 // No atomics: every value and gradient has one fixed order of summation, independent of N (bitwise reproducible, N = 4 equals four
 // N = 1 calls).  No host synchronisation, no allocation.  Offsets are size_t.
 #include "conv_gemm.h"
+#include "workspace.h"
 
 namespace soar {
 
@@ -94,22 +95,22 @@ Layout layout()
     L.qc_w = raw((size_t)2 * ZC * 2 * ZC); L.qc_b = raw(2 * ZC);
     L.raw_total = off;
     // packed regions, every one 256-byte aligned
-    off = (off + 63) / 64 * 64;
-    auto take = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+    Carver pk;
+    pk.float_offset(L.raw_total);       // behind the raw copy
     auto rb_pack = [&](RB &b) {
-        b.c1f = take((size_t)b.cout * b.cin * 9); b.c1r = take((size_t)b.cout * b.cin * 9);
-        b.c2f = take((size_t)b.cout * b.cout * 9); b.c2r = take((size_t)b.cout * b.cout * 9);
-        if (b.cin != b.cout) { b.ninf = take((size_t)b.cout * b.cin); b.ninr = take((size_t)b.cout * b.cin); }
+        b.c1f = pk.float_offset((size_t)b.cout * b.cin * 9); b.c1r = pk.float_offset((size_t)b.cout * b.cin * 9);
+        b.c2f = pk.float_offset((size_t)b.cout * b.cout * 9); b.c2r = pk.float_offset((size_t)b.cout * b.cout * 9);
+        if (b.cin != b.cout) { b.ninf = pk.float_offset((size_t)b.cout * b.cin); b.ninr = pk.float_offset((size_t)b.cout * b.cin); }
     };
     for (int l = 0; l < NLEV; l++) {
         for (int j = 0; j < 2; j++) rb_pack(L.rb[l][j]);
-        if (l < 3) { L.df[l] = take((size_t)LEVC[l] * LEVC[l] * 9); L.dr[l] = take((size_t)LEVC[l] * LEVC[l] * 9); }
+        if (l < 3) { L.df[l] = pk.float_offset((size_t)LEVC[l] * LEVC[l] * 9); L.dr[l] = pk.float_offset((size_t)LEVC[l] * LEVC[l] * 9); }
     }
     rb_pack(L.mid1);
     rb_pack(L.mid2);
-    L.qkv_f = take((size_t)3 * CMID * CMID); L.qkv_b = take(3 * CMID); L.qkv_r = take((size_t)3 * CMID * CMID);
-    L.p_f = take((size_t)CMID * CMID); L.p_r = take((size_t)CMID * CMID);
-    L.total = off;
+    L.qkv_f = pk.float_offset((size_t)3 * CMID * CMID); L.qkv_b = pk.float_offset(3 * CMID); L.qkv_r = pk.float_offset((size_t)3 * CMID * CMID);
+    L.p_f = pk.float_offset((size_t)CMID * CMID); L.p_r = pk.float_offset((size_t)CMID * CMID);
+    L.total = pk.bytes() / sizeof(float);
     return L;
 }
 
@@ -144,49 +145,48 @@ struct WsLayout {
 WsLayout ws_layout(const Dims &d)
 {
     WsLayout L{};
-    size_t off = 0;
-    auto take = [&](int64_t floats) { const size_t o = off; off += align_up((size_t)floats * sizeof(float)); return o; };
+    Carver ws;
     const int64_t st = (int64_t)d.N * GROUPS * 2;
     int c = CH;
-    L.t_in = take(d.pix(0) * CH);
+    L.t_in = ws.offset<float>(d.pix(0) * CH);
     for (int l = 0; l < NLEV; l++) {
         for (int j = 0; j < 2; j++) {
-            L.rb[l][j].h1 = take(d.pix(l) * LEVC[l]);
-            L.rb[l][j].st1 = take(st);
-            L.rb[l][j].st2 = take(st);
-            L.rb_out[l][j] = take(d.pix(l) * LEVC[l]);
+            L.rb[l][j].h1 = ws.offset<float>(d.pix(l) * LEVC[l]);
+            L.rb[l][j].st1 = ws.offset<float>(st);
+            L.rb[l][j].st2 = ws.offset<float>(st);
+            L.rb_out[l][j] = ws.offset<float>(d.pix(l) * LEVC[l]);
             c = LEVC[l];
         }
-        if (l < 3) L.down[l] = take(d.pix(l + 1) * c);
+        if (l < 3) L.down[l] = ws.offset<float>(d.pix(l + 1) * c);
     }
     for (RBws *b : {&L.mid1, &L.mid2}) {
-        b->h1 = take(d.pix(3) * CMID);
-        b->st1 = take(st);
-        b->st2 = take(st);
+        b->h1 = ws.offset<float>(d.pix(3) * CMID);
+        b->st1 = ws.offset<float>(st);
+        b->st2 = ws.offset<float>(st);
     }
-    L.mid1_out = take(d.pix(3) * CMID);
-    L.an_st = take(st);
+    L.mid1_out = ws.offset<float>(d.pix(3) * CMID);
+    L.an_st = ws.offset<float>(st);
     const int64_t NT = (int64_t)d.N * d.Tp;
-    L.qkv = take(NT * 3 * CMID);
-    L.P = take(NT * d.Tp);
-    L.vT = take(NT * CMID);
-    L.O = take(NT * CMID);
-    L.attn_out = take(d.pix(3) * CMID);
-    L.mid2_out = take(d.pix(3) * CMID);
-    L.no_st = take(st);
-    L.m8 = take(d.pix(3) * 2 * ZC);
-    L.dlv = take(d.pix(3) * ZC);
-    L.tmp = take(d.pix(0) * CH);
+    L.qkv = ws.offset<float>(NT * 3 * CMID);
+    L.P = ws.offset<float>(NT * d.Tp);
+    L.vT = ws.offset<float>(NT * CMID);
+    L.O = ws.offset<float>(NT * CMID);
+    L.attn_out = ws.offset<float>(d.pix(3) * CMID);
+    L.mid2_out = ws.offset<float>(d.pix(3) * CMID);
+    L.no_st = ws.offset<float>(st);
+    L.m8 = ws.offset<float>(d.pix(3) * 2 * ZC);
+    L.dlv = ws.offset<float>(d.pix(3) * ZC);
+    L.tmp = ws.offset<float>(d.pix(0) * CH);
     const int64_t nchunk = (int64_t)(d.S[0] * d.S[0] + CHUNK - 1) / CHUNK;
-    L.part = take((int64_t)d.N * nchunk * GROUPS * 2 * 2 + (int64_t)d.N * GROUPS * 2);   // the doubles, then the backward's two means
-    for (int i = 0; i < 3; i++) L.g[i] = take(d.pix(0) * CH);
-    L.dO = take(NT * CMID);
-    L.dOT = take(NT * CMID);
-    L.dP = take(NT * d.Tp);
-    L.XT = take(NT * d.Tp);
-    L.dqkv = take(NT * 3 * CMID);
-    L.g8 = take(d.pix(3) * 2 * ZC);
-    L.gxr = take(d.pix(0) * 4);
+    L.part = ws.offset<float>((int64_t)d.N * nchunk * GROUPS * 2 * 2 + (int64_t)d.N * GROUPS * 2);   // the doubles, then the backward's two means
+    for (int i = 0; i < 3; i++) L.g[i] = ws.offset<float>(d.pix(0) * CH);
+    L.dO = ws.offset<float>(NT * CMID);
+    L.dOT = ws.offset<float>(NT * CMID);
+    L.dP = ws.offset<float>(NT * d.Tp);
+    L.XT = ws.offset<float>(NT * d.Tp);
+    L.dqkv = ws.offset<float>(NT * 3 * CMID);
+    L.g8 = ws.offset<float>(d.pix(3) * 2 * ZC);
+    L.gxr = ws.offset<float>(d.pix(0) * 4);
     // the blocks' inputs are the outputs in front of them
     L.rb[0][0].x = L.t_in;
     L.rb[0][1].x = L.rb_out[0][0];
@@ -196,7 +196,7 @@ WsLayout ws_layout(const Dims &d)
     }
     L.mid1.x = L.rb_out[3][1];
     L.mid2.x = L.attn_out;
-    L.total = off == 0 ? ALIGN : off;
+    L.total = ws.bytes() == 0 ? ALIGN : ws.bytes();
     return L;
 }
 
@@ -1016,12 +1016,7 @@ bool check_args(const char *what, const SoarVaeArgs *a, const void *ws, size_t w
     if (a->N == 0) return true;
     if (!a->weights) { set_error("%s: NULL weights", what); return false; }
     if ((uintptr_t)a->weights & (ALIGN - 1)) { set_error("%s: the packed weights must be 256-byte aligned", what); return false; }
-    const size_t need = ws_layout(dims_of(a->N, a->image_size)).total;
-    if (!ws || ws_bytes < need || ((uintptr_t)ws & (ALIGN - 1))) {
-        set_error("%s: workspace must be %zu bytes, 256-byte aligned (got %zu)", what, need, ws_bytes);
-        return false;
-    }
-    return true;
+    return workspace_ok(what, ws, ws_bytes, ws_layout(dims_of(a->N, a->image_size)).total, "soar_vae_workspace_bytes");
 }
 
 }  // namespace

@@ -13,7 +13,7 @@
 // bit for bit (tests/test_plugin_gpu.py).  Front views (render_front = True in the plugin's sense: main pass sorted front to back, the
 // occlusion image a subsequence of it, fused into its blend) and back views (main pass sorted back to front -- the tile binning
 // orders the flipped depth keys --, the occlusion image a rasterization of its own) are both served; back views one after the other.
-#include "soar_common.h"
+#include "workspace.h"
 
 #include <cstdint>
 
@@ -154,24 +154,23 @@ int carve_view(void *base, int32_t P, int32_t W, int32_t H, int64_t capacity, in
     if (soar_rast_geometry_bytes(P, 0, &gb) || soar_rast_image_bytes(W, H, &ib) || soar_rast_binning_bytes(capacity, &bb) ||
         soar_rast_backward_workspace_bytes(P, &wb))
         return 1;
-    char *p = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { char *q = p; p += align_up(bytes); return q; };
-    out->geom = take(gb);
-    out->img = take(ib);
-    out->binning = take(bb);
-    out->work = take(wb);
+    Carver c(base);
+    out->geom = c.take<char>(gb);
+    out->img = c.take<char>(ib);
+    out->binning = c.take<char>(bb);
+    out->work = c.take<char>(wb);
     out->work_bytes = wb;
-    out->g_nd = reinterpret_cast<float *>(take(sizeof(float) * 4 * (size_t)W * H));
-    out->zero4 = reinterpret_cast<float *>(take(sizeof(float) * 4 * (size_t)W * H));
+    out->g_nd = c.take<float>(4 * (size_t)W * H);
+    out->zero4 = c.take<float>(4 * (size_t)W * H);
     out->geom_o = out->img_o = out->binning_o = nullptr; out->scratch7 = nullptr; out->radii_o = nullptr;
     if (back) {
-        out->geom_o = take(gb);
-        out->img_o = take(ib);
-        out->binning_o = take(bb);
-        out->scratch7 = reinterpret_cast<float *>(take(sizeof(float) * 7 * (size_t)W * H));
-        out->radii_o = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * (size_t)(P > 0 ? P : 1)));
+        out->geom_o = c.take<char>(gb);
+        out->img_o = c.take<char>(ib);
+        out->binning_o = c.take<char>(bb);
+        out->scratch7 = c.take<float>(7 * (size_t)W * H);
+        out->radii_o = c.take<int32_t>((size_t)(P > 0 ? P : 1));
     }
-    out->total = (size_t)(p - static_cast<char *>(base)) + ALIGN;
+    out->total = c.bytes() + ALIGN;
     return 0;
 }
 

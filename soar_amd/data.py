@@ -23,14 +23,11 @@ import torch
 import torch.nn.functional as F
 
 from . import hip_lib
+from .hip_lib import _stream
 from .renderer import registry
 
 CROP = hip_lib.DATA_CROP
 RING_DEPTH = 4
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _need_cuda(dev: torch.device, what: str) -> torch.device:

@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import SoarDensifyRow, check, ptr
+from .hip_lib import SoarDensifyRow, _bytes, _stream, _workspace, check, ptr
 
 PARAMS = ("xyz", "f_dc", "f_rest", "color", "opacity", "scaling", "rotation")
 _MODE = {"xyz": 2, "scaling": 3}
@@ -105,9 +105,6 @@ class SurfelDensifier:
     opac_gradient_accum = property(lambda s: s.accum[3][:, None])
     denom = property(lambda s: s.accum[4][:, None])
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def add_densification_stats(self, radii: torch.Tensor, viewspace_grad: torch.Tensor, scaling_grad: Optional[torch.Tensor] = None):
         """One view of ``update_states`` (:1208-1216): max_radii2D and the five accumulators, filter = radii > 0."""
         P = self.num_points
@@ -123,7 +120,7 @@ class SurfelDensifier:
         op = self.params["opacity"].detach().reshape(-1).contiguous()
         with torch.cuda.device(self.device):
             check(hip_lib.lib().soar_densify_stats(P, ptr(r), ptr(g), g.shape[1], ptr(sg), ptr(rot), ptr(op), ptr(self.accum),
-                                                   ptr(self.max_radii2D), self._stream()), "soar_densify_stats")
+                                                   ptr(self.max_radii2D), _stream(self.device)), "soar_densify_stats")
 
     def sync_stats(self, group=None):
         """Frame-DP: every rank saw other frames; sum the accumulators and max the radii so that all ranks plan alike."""
@@ -169,15 +166,13 @@ class SurfelDensifier:
         scaling = self.params["scaling"].detach().contiguous()
         rotation = self.params["rotation"].detach().contiguous()
         opacity = self.params["opacity"].detach().reshape(-1).contiguous()
-        nbytes = C.c_size_t(0)
-        check(L.soar_densify_plan_bytes(P, C.byref(nbytes)), "soar_densify_plan_bytes")
-        plan = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        plan = _workspace(_bytes(L.soar_densify_plan_bytes, "soar_densify_plan_bytes", P), self.device)
         counts = (C.c_int64 * 3)()
         with torch.cuda.device(self.device):
             # thresholds as the reference forms them: python doubles, compared against float32 tensors
             check(L.soar_densify_plan(P, ptr(self.accum), ptr(scaling), ptr(opacity), int(do_prune), int(do_densify),
                                       float(min_opacity), float(0.5 * extent), float(1e-8 * extent ** 2), float(max_grad),
-                                      float(self.percent_dense * extent), ptr(plan), counts, self._stream()), "soar_densify_plan")
+                                      float(self.percent_dense * extent), ptr(plan), counts, _stream(self.device)), "soar_densify_plan")
         kept, cloned, split = int(counts[0]), int(counts[1]), int(counts[2])
         P_new = kept + cloned + N * split
         if split and noise is None:
@@ -208,7 +203,7 @@ class SurfelDensifier:
         if P_new > 0:
             with torch.cuda.device(self.device):
                 check(L.soar_densify_apply(P, N, ptr(plan), len(rows), arr, ptr(scaling), ptr(rotation), ptr(noise), int(self.surface),
-                                           self._stream()), "soar_densify_apply")
+                                           _stream(self.device)), "soar_densify_apply")
         if self.spatial_order and P_new > 1:
             perm = spatial_permutation(news["xyz"])
             for k in PARAMS:
@@ -236,16 +231,14 @@ class SurfelDensifier:
         """The per-point decision byte (1 pruned, 2 clone, 4 split) without applying it (diagnostics / tests)."""
         L = hip_lib.lib()
         P = self.num_points
-        nbytes = C.c_size_t(0)
-        check(L.soar_densify_plan_bytes(P, C.byref(nbytes)), "soar_densify_plan_bytes")
-        plan = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        plan = _workspace(_bytes(L.soar_densify_plan_bytes, "soar_densify_plan_bytes", P), self.device)
         out = torch.empty(P, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             check(L.soar_densify_plan(P, ptr(self.accum), ptr(self.params["scaling"].detach().contiguous()),
                                       ptr(self.params["opacity"].detach().reshape(-1).contiguous()), int(do_prune), int(do_densify),
                                       float(min_opacity), float(0.5 * extent), float(1e-8 * extent ** 2), float(max_grad),
-                                      float(self.percent_dense * extent), ptr(plan), None, self._stream()), "soar_densify_plan")
-            check(L.soar_densify_flags(P, ptr(plan), ptr(out), self._stream()), "soar_densify_flags")
+                                      float(self.percent_dense * extent), ptr(plan), None, _stream(self.device)), "soar_densify_plan")
+            check(L.soar_densify_flags(P, ptr(plan), ptr(out), _stream(self.device)), "soar_densify_flags")
         return out
 
     # ---- optimizer surgery (cat_tensors_to_optimizer / _prune_optimizer, :862-950) ------------------------------------------------

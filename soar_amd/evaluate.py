@@ -18,7 +18,7 @@ from typing import Any, Callable, Dict, List, Optional
 import torch
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 from .lpips import LPIPSVGG
 
 WINDOW = 7          # skimage's default win_size
@@ -63,9 +63,7 @@ def image_metrics(pred: torch.Tensor, gt_rgb: torch.Tensor, gt_mask: torch.Tenso
     dev = pred.device
     N, H, W = gt_mask.shape
     L = hip_lib.lib()
-    nb = C.c_size_t(0)
-    check(L.soar_eval_scratch_bytes(N, H, W, C.byref(nb)), "soar_eval_scratch_bytes")
-    scratch = torch.empty(nb.value // 8, dtype=torch.float64, device=dev)
+    scratch = _workspace(_bytes(L.soar_eval_scratch_bytes, "soar_eval_scratch_bytes", N, H, W), dev)
     out = torch.empty((3, N, H, W, 3), dtype=torch.float32, device=dev)        # gt_white, pred2, gt2
     metrics = torch.empty((N, 3), dtype=torch.float64, device=dev)
     grid_t = torch.empty((N, H, 2 * W, 3), dtype=torch.uint8, device=dev) if grid else None
@@ -80,8 +78,7 @@ def image_metrics(pred: torch.Tensor, gt_rgb: torch.Tensor, gt_mask: torch.Tenso
     a.grid = None if grid_t is None else grid_t.data_ptr()
     a.metrics = metrics.data_ptr()
     with torch.cuda.device(dev):
-        check(L.soar_eval_image_metrics(C.byref(a), scratch.data_ptr(), nb.value, torch.cuda.current_stream(dev).cuda_stream),
-              "soar_eval_image_metrics")
+        check(L.soar_eval_image_metrics(C.byref(a), scratch.data_ptr(), scratch.numel(), _stream(dev)), "soar_eval_image_metrics")
     lp = None
     if lpips is not None:
         with torch.no_grad():

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 HEADS = ("shs", "scales", "quats", "offsets", "opacities")     # the C ABI's head order
 HEAD_OUT = {"shs": 3, "scales": 1, "quats": 4, "offsets": 3, "opacities": 1}
@@ -76,7 +76,7 @@ class _FieldFn(torch.autograd.Function):
         for k in range(5):
             a.out[k] = outs[k].data_ptr()
         with torch.cuda.device(dev):
-            check(hip_lib.lib().soar_field_forward(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "soar_field_forward")
+            check(hip_lib.lib().soar_field_forward(C.byref(a), _stream(dev)), "soar_field_forward")
         ctx.field_cfg = field_cfg
         ctx.save_for_backward(xyz, z, table, qtable, enc, qenc, *weights)
         ctx.set_materialize_grads(False)
@@ -113,12 +113,9 @@ class _FieldFn(torch.autograd.Function):
             if t is not None:
                 setattr(a, name, t.data_ptr())
         L = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(L.soar_field_workspace_bytes(N, C.byref(nb)), "soar_field_workspace_bytes")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = _workspace(_bytes(L.soar_field_workspace_bytes, "soar_field_workspace_bytes", N), dev)
         with torch.cuda.device(dev):
-            check(L.soar_field_backward(C.byref(a), ws.data_ptr(), nb.value, torch.cuda.current_stream(dev).cuda_stream),
-                  "soar_field_backward")
+            check(L.soar_field_backward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(dev)), "soar_field_backward")
         w_grads: List[Optional[torch.Tensor]] = []
         for k, h in enumerate(HEADS):
             in_dim, out = 34 if h == "offsets" else 32, HEAD_OUT[h]

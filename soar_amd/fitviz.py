@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import hip_lib
-from .hip_lib import check, ptr
+from .hip_lib import _stream, check, ptr
 from .prior import MeshTopology, full_pose, render_normal_priors
 
 MAX_KEYPOINTS = MAX_LIMBS = 512          # soar_fitviz_strip
@@ -47,10 +47,6 @@ def _hip(t, name: str) -> None:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
         raise RuntimeError(f"{name} is on '{where}': soar_amd.fitviz runs on HIP devices only; there is no CPU fallback")
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def yaw_matrices(w2c, n_views: int = 3) -> np.ndarray:

@@ -36,7 +36,6 @@ Where this departs from the reference, on purpose:
 """
 from __future__ import annotations
 
-import ctypes as C
 import dataclasses
 import math
 import os
@@ -49,7 +48,7 @@ from torch import nn
 
 from . import hip_lib
 from .field import HashMLPField
-from .hip_lib import check, ptr
+from .hip_lib import _bytes, _stream, _workspace, check, ptr
 from .renderer import registry
 
 C0 = 0.28209479177387814                      # TS/utils/sh_utils.py
@@ -99,10 +98,6 @@ def quaternion2rotmat(q: torch.Tensor) -> torch.Tensor:
 def _need_hip(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(f"{what} is on '{t.device}': soar_amd.geometry computes on HIP devices only; there is no CPU fallback")
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 # ---- the two autograd nodes ----------------------------------------------------------------------------------------------------
@@ -155,9 +150,7 @@ class _Regularizers(torch.autograd.Function):
         g_op = torch.empty_like(opacity) if need[3] else None
         g_sc = torch.empty_like(scales) if need[4] else None
         L = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(L.soar_surfel_regularizers_workspace_bytes(P, C.byref(nb)), "soar_surfel_regularizers_workspace_bytes")
-        ws = torch.empty(max(int(nb.value), 8), dtype=torch.uint8, device=dev)
+        ws = _workspace(_bytes(L.soar_surfel_regularizers_workspace_bytes, "soar_surfel_regularizers_workspace_bytes", P), dev)
         with torch.cuda.device(dev):
             check(L.soar_surfel_regularizers(P, S, K, ptr(xyz), ptr(original_pos), ptr(scaling), ptr(opacity), ptr(scales), ptr(coef),
                                              ptr(upstream), ptr(terms), ptr(g_xyz), ptr(g_op), ptr(g_sc), ptr(ws), ws.numel(),

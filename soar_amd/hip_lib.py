@@ -8,6 +8,8 @@ import ctypes as C
 import os
 from typing import Optional
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SOAR_HIP_LIB: another build of the same library (development A/B runs: scripts/variant.py); still no fallback of any kind
 LIB_PATH = os.environ.get("SOAR_HIP_LIB") or os.path.join(_HERE, "_lib", "libsoar_hip.so")
@@ -565,9 +567,8 @@ def lib() -> C.CDLL:
     """Load libsoar_hip.so (once).  Raises if it has not been built -- there is no fallback path."""
     global _lib
     if _lib is None:
-        # PyTorch-ROCm ships its own HIP runtime: it must be the one this process uses, so torch is loaded first
-        # (loading libsoar_hip.so first would pull a second libamdhip64 from /opt/rocm into the process)
-        import torch  # noqa: F401
+        # PyTorch-ROCm ships its own HIP runtime: it must be the one this process uses, so torch is loaded first (this module imports
+        # it; loading libsoar_hip.so first would pull a second libamdhip64 from /opt/rocm into the process)
         if not os.path.exists(LIB_PATH):
             raise SoarHipError(
                 f"{LIB_PATH} not found: the HIP extension is not built. Run `python -m soar_amd.build` "
@@ -598,6 +599,36 @@ def _bytes(fn, name: str, *sizes) -> int:
     nb = C.c_size_t(0)
     check(fn(*sizes, C.byref(nb)), name)
     return nb.value
+
+
+def _workspace(nbytes: int, device):
+    """A caller-owned workspace of ``nbytes`` on ``device``, as every entry point that takes one wants it."""
+    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    if buf.data_ptr() % 256:
+        raise RuntimeError("device allocation is not 256-byte aligned")
+    return buf
+
+
+def _stream(device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+class PackedWeights:
+    """The packed form of a net's weights, kept until a weight moves or is written in place."""
+
+    def __init__(self):
+        self._key = self.packed = None
+
+    def get(self, tensors, device, wrong_device: str, pack):
+        """``tensors``: the module's weights; ``wrong_device``: the module's error text for weights that are not on ``device``;
+        ``pack()`` packs them into fresh buffers and returns those.  -> what ``pack()`` returned, now or for the same weights."""
+        if any(w.device != device for w in tensors):
+            raise RuntimeError(wrong_device)
+        key = (device, tuple(w.data_ptr() for w in tensors), tuple(w._version for w in tensors))
+        if key != self._key:
+            self.packed = pack()
+            self._key = key
+        return self.packed
 
 
 def ptr(t) -> Optional[int]:

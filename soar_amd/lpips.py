@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 # (Cin, Cout) of the 13 convolutions of VGG16 features[0:30] and their indices in torchvision's ``features``
 CONV_CH: List[Tuple[int, int]] = [(3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512),
@@ -67,15 +67,12 @@ class _LpipsFn(torch.autograd.Function):
         N, _, H, W = in0.shape
         dev = in0.device
         L = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(L.soar_lpips_workspace_bytes(N, H, W, grads, C.byref(nb)), "soar_lpips_workspace_bytes")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = _workspace(_bytes(L.soar_lpips_workspace_bytes, "soar_lpips_workspace_bytes", N, H, W, grads), dev)
         out = torch.empty(N, device=dev)
         a = module._args(in0, in1, grads)
         a.out = hip_lib.ptr(out)
         with torch.cuda.device(dev):
-            check(L.soar_lpips_forward(C.byref(a), ws.data_ptr(), nb.value, torch.cuda.current_stream(dev).cuda_stream),
-                  "soar_lpips_forward")
+            check(L.soar_lpips_forward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(dev)), "soar_lpips_forward")
         ctx.module, ctx.grads, ctx.ws = module, grads, ws
         ctx.save_for_backward(in0, in1)
         return out
@@ -98,8 +95,7 @@ class _LpipsFn(torch.autograd.Function):
                 for i, s in enumerate(g[b].stride()):
                     st[i] = s
         with torch.cuda.device(dev):
-            check(hip_lib.lib().soar_lpips_backward(C.byref(a), ctx.ws.data_ptr(), ctx.ws.numel(),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "soar_lpips_backward")
+            check(hip_lib.lib().soar_lpips_backward(C.byref(a), ctx.ws.data_ptr(), ctx.ws.numel(), _stream(dev)), "soar_lpips_backward")
         return None, None, g[0], g[1]
 
 
@@ -124,7 +120,7 @@ class LPIPSVGG(nn.Module):
             self.register_buffer(f"lin{k}", _take(sd, f"lin{k}.model.1.weight", (1, c, 1, 1)).reshape(c))
         self.register_buffer("shift", _constant(sd, "scaling_layer.shift", SHIFT))
         self.register_buffer("scale", _constant(sd, "scaling_layer.scale", SCALE))
-        self._pack = None
+        self._pack = hip_lib.PackedWeights()
         self.eval()
 
     def _weights(self) -> List[torch.Tensor]:
@@ -133,14 +129,10 @@ class LPIPSVGG(nn.Module):
 
     def _packed(self, dev) -> torch.Tensor:
         ws = self._weights()
-        if any(w.device != dev for w in ws):
-            raise RuntimeError(f"LPIPSVGG: weights are not on {dev}: move the module with .to('{dev}')")
-        key = (dev, tuple(w.data_ptr() for w in ws), tuple(w._version for w in ws))
-        if self._pack is None or self._pack[0] != key:
+
+        def pack():
             L = hip_lib.lib()
-            nb = C.c_size_t(0)
-            check(L.soar_lpips_weights_bytes(C.byref(nb)), "soar_lpips_weights_bytes")
-            packed = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            packed = _workspace(_bytes(L.soar_lpips_weights_bytes, "soar_lpips_weights_bytes"), dev)
             w = hip_lib.SoarLpipsWeights()
             for i in range(13):
                 w.conv_w[i], w.conv_b[i] = ws[i].data_ptr(), ws[13 + i].data_ptr()
@@ -148,10 +140,10 @@ class LPIPSVGG(nn.Module):
                 w.lin[k] = ws[26 + k].data_ptr()
             w.shift, w.scale = self.shift.data_ptr(), self.scale.data_ptr()
             with torch.cuda.device(dev):
-                check(L.soar_lpips_pack_weights(C.byref(w), packed.data_ptr(), nb.value, torch.cuda.current_stream(dev).cuda_stream),
-                      "soar_lpips_pack_weights")
-            self._pack = (key, packed)
-        return self._pack[1]
+                check(L.soar_lpips_pack_weights(C.byref(w), packed.data_ptr(), packed.numel(), _stream(dev)), "soar_lpips_pack_weights")
+            return packed
+
+        return self._pack.get(ws, dev, f"LPIPSVGG: weights are not on {dev}: move the module with .to('{dev}')", pack)
 
     def _args(self, in0, in1, grads) -> hip_lib.SoarLpipsArgs:
         a = hip_lib.SoarLpipsArgs()
@@ -160,7 +152,7 @@ class LPIPSVGG(nn.Module):
         a.in0, a.in1 = hip_lib.ptr(in0), hip_lib.ptr(in1)
         for i in range(4):
             a.in0_stride[i], a.in1_stride[i] = in0.stride(i), in1.stride(i)
-        a.weights = self._pack[1].data_ptr()
+        a.weights = self._pack.packed.data_ptr()
         return a
 
     @staticmethod

@@ -27,7 +27,6 @@ chunked and an unchunked run, give the same bits.  HIP only: CPU tensors are ref
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Callable, List, Sequence, Tuple
 
@@ -36,21 +35,15 @@ import torch
 
 from . import hip_lib
 from .data import _need_cuda
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 DT_U8, DT_F32 = 0, 1               # dtype codes of soar_masks_open_close / soar_masks_clean
 MAX_FRAMES = 65535                 # per call of the library
 STATS = ("union_area", "cleaned_area", "n_components", "kept_area")
 
 
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def workspace_bytes(N: int, H: int, W: int) -> int:
-    n = C.c_size_t(0)
-    check(hip_lib.lib().soar_masks_workspace_bytes(N, H, W, C.byref(n)), "soar_masks_workspace_bytes")
-    return int(n.value)
+    return _bytes(hip_lib.lib().soar_masks_workspace_bytes, "soar_masks_workspace_bytes", N, H, W)
 
 
 def _candidates(x, what: str, allow_float: bool = True):
@@ -100,7 +93,7 @@ def _chunked(entry: str, cand: torch.Tensor, code: int, threshold: float, dev: t
     chunk = max(1, min(N, MAX_FRAMES, int(max_workspace_bytes) // per))
     while chunk > 1 and workspace_bytes(chunk, H, W) > max_workspace_bytes:
         chunk -= 1
-    workspace = torch.empty((workspace_bytes(chunk, H, W),), dtype=torch.uint8, device=dev)
+    workspace = _workspace(workspace_bytes(chunk, H, W), dev)
     for i in range(0, N, chunk):          # one stream: a chunk's launches are done with the workspace before the next one's start
         j = min(i + chunk, N)
         _run(entry, cand[i:j], code, threshold, dev, out[i:j], stats[i:j], workspace)

@@ -40,7 +40,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import hip_lib
-from .hip_lib import _bytes, check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 TSDF_MAX_VIEWS = 64          # views per soar_tsdf_integrate call
 ZNEAR = 0.2                  # znear of the export cameras: voxels nearer than this to a camera are not observed by it
@@ -57,17 +57,6 @@ class Mesh(NamedTuple):
 def _hip(t: torch.Tensor, name: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(f"{name} is on '{t.device}': soar_amd.mesh runs on HIP devices only; there is no CPU fallback")
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _workspace(nbytes: int, device: torch.device) -> torch.Tensor:
-    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    if buf.data_ptr() % 256:
-        raise RuntimeError("device allocation is not 256-byte aligned")
-    return buf
 
 
 def fuse_depth(depth: torch.Tensor, opac: torch.Tensor, viewmatrix: torch.Tensor, projmatrix: torch.Tensor, prcppoint: torch.Tensor,

@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 CROP = hip_lib.DATA_CROP
 CIN = 6
@@ -110,32 +110,29 @@ class NormalNet(nn.Module):
                 self.register_buffer(f"{net}_w{i}", take(f"{net}.model.{key}.weight"))
             self.register_buffer(f"{net}_bias", take(f"{net}.model.{layers[-1][0]}.bias"))
         self._n_layers = len(layers)
-        self._pack = None
+        self._pack = hip_lib.PackedWeights()
         self.eval()
 
     def _tensors(self, net: str) -> List[torch.Tensor]:
         return [getattr(self, f"{net}_w{i}") for i in range(self._n_layers)] + [getattr(self, f"{net}_bias")]
 
     def _packed(self, dev) -> Tuple[torch.Tensor, torch.Tensor]:
-        ws = self._tensors("netF") + self._tensors("netB")
-        if any(w.device != dev for w in ws):
-            raise RuntimeError(f"NormalNet: weights are not on {dev}: move the module with .to('{dev}')")
-        key = (dev, tuple(w.data_ptr() for w in ws), tuple(w._version for w in ws))
-        if self._pack is None or self._pack[0] != key:
+        def pack():
             L = hip_lib.lib()
-            nb = C.c_size_t(0)
-            check(L.soar_normalnet_weights_bytes(self.ngf, self.n_down, self.n_blocks, C.byref(nb)), "soar_normalnet_weights_bytes")
+            nb = _bytes(L.soar_normalnet_weights_bytes, "soar_normalnet_weights_bytes", self.ngf, self.n_down, self.n_blocks)
             packed = []
             for net in ("netF", "netB"):
                 ts = self._tensors(net)
                 arr = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-                p = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+                p = _workspace(nb, dev)
                 with torch.cuda.device(dev):
-                    check(L.soar_normalnet_pack_weights(self.ngf, self.n_down, self.n_blocks, arr, len(ts), p.data_ptr(), nb.value,
-                                                        torch.cuda.current_stream(dev).cuda_stream), "soar_normalnet_pack_weights")
+                    check(L.soar_normalnet_pack_weights(self.ngf, self.n_down, self.n_blocks, arr, len(ts), p.data_ptr(), nb, _stream(dev)),
+                          "soar_normalnet_pack_weights")
                 packed.append(p)
-            self._pack = (key, packed[0], packed[1])
-        return self._pack[1], self._pack[2]
+            return packed[0], packed[1]
+
+        return self._pack.get(self._tensors("netF") + self._tensors("netB"), dev,
+                              f"NormalNet: weights are not on {dev}: move the module with .to('{dev}')", pack)
 
     def _check(self, image, prior_F, prior_B):
         for name, t in (("image", image), ("prior_F", prior_F), ("prior_B", prior_B)):
@@ -168,9 +165,7 @@ class NormalNet(nn.Module):
             return nF, nB
         wF, wB = self._packed(dev)
         L = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(L.soar_normalnet_workspace_bytes(N, H, W, self.ngf, self.n_down, self.n_blocks, C.byref(nb)), "soar_normalnet_workspace_bytes")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = _workspace(_bytes(L.soar_normalnet_workspace_bytes, "soar_normalnet_workspace_bytes", N, H, W, self.ngf, self.n_down, self.n_blocks), dev)
         a = hip_lib.SoarNormalNetArgs()
         a.N, a.H, a.W, a.ngf, a.n_down, a.n_blocks = N, H, W, self.ngf, self.n_down, self.n_blocks
         a.image, a.prior_F, a.prior_B = image.data_ptr(), prior_F.data_ptr(), prior_B.data_ptr()
@@ -179,8 +174,7 @@ class NormalNet(nn.Module):
         a.weights_F, a.weights_B = wF.data_ptr(), wB.data_ptr()
         a.normal_F, a.normal_B = nF.data_ptr(), nB.data_ptr()
         with torch.cuda.device(dev):
-            check(L.soar_normalnet_forward(C.byref(a), ws.data_ptr(), nb.value, torch.cuda.current_stream(dev).cuda_stream),
-                  "soar_normalnet_forward")
+            check(L.soar_normalnet_forward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(dev)), "soar_normalnet_forward")
         return nF, nB
 
 
@@ -223,7 +217,7 @@ def _crop_launch(images, masks, Ks):
     if N:
         L = hip_lib.lib()
         with torch.cuda.device(dev):
-            s = torch.cuda.current_stream(dev).cuda_stream
+            s = _stream(dev)
             check(L.soar_normal_crop_boxes(N, H, W, CROP, masks.data_ptr(), _strides(masks), Ks.data_ptr(), boxes.data_ptr(), nKs.data_ptr(),
                                            status.data_ptr(), s), "soar_normal_crop_boxes")
             check(L.soar_normal_crop_sample(N, H, W, CROP, images.data_ptr(), _strides(images), masks.data_ptr(), _strides(masks),
@@ -269,7 +263,7 @@ def normal_bytes(normal_F: torch.Tensor, normal_B: torch.Tensor, mask: torch.Ten
     if N:
         with torch.cuda.device(dev):
             check(hip_lib.lib().soar_normal_crop_bytes(N, H, W, normal_F.data_ptr(), normal_B.data_ptr(), mask.data_ptr(), oF.data_ptr(),
-                                                       oB.data_ptr(), oM.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                                                       oB.data_ptr(), oM.data_ptr(), _stream(dev)),
                   "soar_normal_crop_bytes")
     return oF, oB, oM
 

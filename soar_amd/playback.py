@@ -26,7 +26,7 @@ from typing import Any, Dict, Mapping, Optional, Sequence, Union
 import torch
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _stream, check
 
 JOINTS = 55
 POSE_KEYS = ("global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")
@@ -151,7 +151,7 @@ def motion_resample(key_pose: torch.Tensor, key_transl: torch.Tensor, key_expr: 
     with torch.cuda.device(dev):
         check(hip_lib.lib().soar_motion_resample(K, F, E, hip_lib.ptr(kp), hip_lib.ptr(kt), hip_lib.ptr(ke), hip_lib.ptr(tm),
                                                  hip_lib.ptr(yw), hip_lib.ptr(pose), hip_lib.ptr(transl), hip_lib.ptr(expr),
-                                                 torch.cuda.current_stream(dev).cuda_stream), "soar_motion_resample")
+                                                 _stream(dev)), "soar_motion_resample")
     return pose, transl, expr
 
 
@@ -191,7 +191,7 @@ def playback_finish(render: torch.Tensor, normal: torch.Tensor, mask: torch.Tens
     a.occ_out = out["occ"].data_ptr() if occ is not None else None
     if B:
         with torch.cuda.device(dev):
-            check(hip_lib.lib().soar_playback_finish(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "soar_playback_finish")
+            check(hip_lib.lib().soar_playback_finish(C.byref(a), _stream(dev)), "soar_playback_finish")
     return {"rgb": out["rgb"], "normal": out["normal"], "occ": out["occ"] if occ is not None else None, "mask": out["mask"]}
 
 

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import hip_lib
-from .hip_lib import check, ptr
+from .hip_lib import _stream, check, ptr
 
 SPACES = {"opencv": 0, "opengl": 1}
 MAX_SIDE = 4096                      # soar_prior_raster
@@ -39,10 +39,6 @@ def _hip(t, name: str) -> None:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
         raise RuntimeError(f"{name} is on '{where}': soar_amd.prior runs on HIP devices only; there is no CPU fallback")
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class MeshTopology:

@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 MAX_TOKENS = 64                    # decoder tokens per frame in the kernels: 1 + mask_tokens + points + 1
 
@@ -178,7 +178,7 @@ class SamSegmenter(nn.Module):
         self.max_points = MAX_TOKENS - 2 - cfg["mask_tokens"]
         self._sizes = [int(np.prod(shape)) for _, shape in keys]
         self.register_buffer("weights", torch.cat([sd[k].detach().to(torch.float32).reshape(-1) for k, _ in keys]).contiguous())
-        self._pack = None
+        self._pack = hip_lib.PackedWeights()
         self.eval()
 
     # ---- plumbing ----
@@ -192,23 +192,20 @@ class SamSegmenter(nn.Module):
 
     def _packed(self, dev) -> torch.Tensor:
         w = self.weights
-        if w.device != dev:
-            raise RuntimeError(f"SamSegmenter: weights are on {w.device}, the input on {dev}: move the module with .to('{dev}')")
-        key = (dev, w.data_ptr(), w._version)
-        if self._pack is None or self._pack[0] != key:
+
+        def pack():
             offs = np.concatenate([[0], np.cumsum(self._sizes)[:-1]])
             arr = (C.c_void_p * len(offs))(*[w.data_ptr() + 4 * int(o) for o in offs])
-            packed = torch.empty(self._packed_bytes, dtype=torch.uint8, device=dev)
+            packed = _workspace(self._packed_bytes, dev)
             with torch.cuda.device(dev):
-                check(hip_lib.lib().soar_sam_pack_weights(C.byref(self._c), arr, len(offs), packed.data_ptr(), self._packed_bytes,
-                                                          torch.cuda.current_stream(dev).cuda_stream), "soar_sam_pack_weights")
-            self._pack = (key, packed)
-        return self._pack[1]
+                check(hip_lib.lib().soar_sam_pack_weights(C.byref(self._c), arr, len(offs), packed.data_ptr(), self._packed_bytes, _stream(dev)),
+                      "soar_sam_pack_weights")
+            return packed
 
-    def _workspace(self, dev, B: int, max_points: int) -> torch.Tensor:
-        nb = C.c_size_t(0)
-        check(hip_lib.lib().soar_sam_workspace_bytes(C.byref(self._c), B, max_points, C.byref(nb)), "soar_sam_workspace_bytes")
-        return torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        return self._pack.get([w], dev, f"SamSegmenter: weights are on {w.device}, the input on {dev}: move the module with .to('{dev}')", pack)
+
+    def _scratch(self, dev, B: int, max_points: int) -> torch.Tensor:
+        return _workspace(_bytes(hip_lib.lib().soar_sam_workspace_bytes, "soar_sam_workspace_bytes", C.byref(self._c), B, max_points), dev)
 
     @staticmethod
     def _need_hip(name: str, t) -> None:
@@ -239,7 +236,7 @@ class SamSegmenter(nn.Module):
         out = torch.empty((B, g * g, 3 * p * p), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             check(hip_lib.lib().soar_sam_preprocess(C.byref(self._c), B, nh, nw, resized.data_ptr(), out.data_ptr(),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "soar_sam_preprocess")
+                                                    _stream(dev)), "soar_sam_preprocess")
         return out, (nh, nw)
 
     def preprocessed(self, images: torch.Tensor) -> torch.Tensor:
@@ -276,10 +273,10 @@ class SamSegmenter(nn.Module):
         if B == 0:
             return out.permute(0, 3, 1, 2) if neck else out
         packed = self._packed(dev)
-        ws = self._workspace(dev, B, 0) if workspace is None else workspace
+        ws = self._scratch(dev, B, 0) if workspace is None else workspace
         with torch.cuda.device(dev):
             check(hip_lib.lib().soar_sam_encode(C.byref(self._c), packed.data_ptr(), C.byref(a), ws.data_ptr(), ws.numel(),
-                                                torch.cuda.current_stream(dev).cuda_stream), "soar_sam_encode")
+                                                _stream(dev)), "soar_sam_encode")
         return out.permute(0, 3, 1, 2) if neck else out
 
     def embed(self, images: torch.Tensor) -> torch.Tensor:
@@ -338,10 +335,10 @@ class SamSegmenter(nn.Module):
             if return_tokens:
                 a.prompt_tokens, a.tokens_out = tok[0].data_ptr(), tok[1].data_ptr()
             packed = self._packed(dev)
-            ws = self._workspace(dev, B, M) if workspace is None else workspace
+            ws = self._scratch(dev, B, M) if workspace is None else workspace
             with torch.cuda.device(dev):
                 check(hip_lib.lib().soar_sam_decode(C.byref(self._c), packed.data_ptr(), C.byref(a), ws.data_ptr(), ws.numel(),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "soar_sam_decode")
+                                                    _stream(dev)), "soar_sam_decode")
         return (low, iou, tok[0], tok[1]) if return_tokens else (low, iou)
 
     @torch.no_grad()
@@ -356,7 +353,7 @@ class SamSegmenter(nn.Module):
         out = torch.empty((B, K, H, W), dtype=torch.uint8 if binary else torch.float32, device=dev)
         with torch.cuda.device(dev):
             check(hip_lib.lib().soar_sam_postprocess(B, K, L, self.image_size, nh, nw, H, W, low_res.data_ptr(), None if binary else out.data_ptr(),
-                                                     out.data_ptr() if binary else None, torch.cuda.current_stream(dev).cuda_stream), "soar_sam_postprocess")
+                                                     out.data_ptr() if binary else None, _stream(dev)), "soar_sam_postprocess")
         return out.view(torch.bool) if binary else out
 
     def _run(self, images, points, counts, labels, binary: bool) -> torch.Tensor:

@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _bytes, _stream, _workspace, check
 
 CH, CH_MULT, Z = 128, (1, 2, 4, 4), 4
 SCALE_FACTOR = 0.18215
@@ -76,10 +76,6 @@ def schedule_tables(alphas_cumprod: torch.Tensor) -> torch.Tensor:
 def _strides(dst, t: torch.Tensor) -> None:
     for i, s in enumerate(t.stride()):
         dst[i] = s
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _check_image(t: torch.Tensor, what: str) -> None:
@@ -146,26 +142,23 @@ class LatentEncoder(nn.Module):
             parts.append(t.detach().to(torch.float32).reshape(-1))
         self.register_buffer("weights", torch.cat(parts).contiguous())
         self.scale_factor = float(scale_factor)
-        self._pack = None
+        self._pack = hip_lib.PackedWeights()
         self.eval()
 
     def _packed(self, dev) -> torch.Tensor:
         w = self.weights
-        if w.device != dev:
-            raise RuntimeError(f"LatentEncoder: weights are not on {dev}: move the module with .to('{dev}')")
-        key = (dev, w.data_ptr(), w._version)
-        if self._pack is None or self._pack[0] != key:
+
+        def pack():
             L = hip_lib.lib()
-            nf, nb = C.c_size_t(0), C.c_size_t(0)
-            check(L.soar_vae_weights_floats(C.byref(nf)), "soar_vae_weights_floats")
-            if nf.value != w.numel():
-                raise RuntimeError(f"LatentEncoder: the library expects {nf.value} weight floats, the module holds {w.numel()}")
-            check(L.soar_vae_weights_bytes(C.byref(nb)), "soar_vae_weights_bytes")
-            packed = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            nf = _bytes(L.soar_vae_weights_floats, "soar_vae_weights_floats")
+            if nf != w.numel():
+                raise RuntimeError(f"LatentEncoder: the library expects {nf} weight floats, the module holds {w.numel()}")
+            packed = _workspace(_bytes(L.soar_vae_weights_bytes, "soar_vae_weights_bytes"), dev)
             with torch.cuda.device(dev):
-                check(L.soar_vae_pack_weights(w.data_ptr(), w.numel(), packed.data_ptr(), nb.value, _stream(dev)), "soar_vae_pack_weights")
-            self._pack = (key, packed)
-        return self._pack[1]
+                check(L.soar_vae_pack_weights(w.data_ptr(), w.numel(), packed.data_ptr(), packed.numel(), _stream(dev)), "soar_vae_pack_weights")
+            return packed
+
+        return self._pack.get([w], dev, f"LatentEncoder: weights are not on {dev}: move the module with .to('{dev}')", pack)
 
     def _args(self, x: torch.Tensor, image_size: int) -> hip_lib.SoarVaeArgs:
         a = hip_lib.SoarVaeArgs()
@@ -173,7 +166,7 @@ class LatentEncoder(nn.Module):
         a.image_size = image_size
         a.x = hip_lib.ptr(x)
         _strides(a.x_stride, x)
-        a.weights = self._pack[1].data_ptr()
+        a.weights = self._pack.packed.data_ptr()
         a.scale_factor = self.scale_factor
         return a
 
@@ -182,9 +175,7 @@ class LatentEncoder(nn.Module):
         N, dev = x.shape[0], x.device
         h = image_size // 8
         L = hip_lib.lib()
-        nb = C.c_size_t(0)
-        check(L.soar_vae_workspace_bytes(N, x.shape[2], x.shape[3], image_size, C.byref(nb)), "soar_vae_workspace_bytes")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = _workspace(_bytes(L.soar_vae_workspace_bytes, "soar_vae_workspace_bytes", N, x.shape[2], x.shape[3], image_size), dev)
         a = self._args(x, image_size)
         outs = {}
         if want_latents:
@@ -194,7 +185,7 @@ class LatentEncoder(nn.Module):
             outs["mean"], outs["logvar"] = torch.empty(N, Z, h, h, device=dev), torch.empty(N, Z, h, h, device=dev)
             a.mean, a.logvar = hip_lib.ptr(outs["mean"]), hip_lib.ptr(outs["logvar"])
         with torch.cuda.device(dev):
-            check(L.soar_vae_forward(C.byref(a), ws.data_ptr(), nb.value, _stream(dev)), "soar_vae_forward")
+            check(L.soar_vae_forward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(dev)), "soar_vae_forward")
         res = outs["latents"] if want_latents else (outs["mean"], outs["logvar"])
         return res, ws
 

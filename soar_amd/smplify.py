@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import hip_lib
-from .hip_lib import check
+from .hip_lib import _stream, check
 
 N_KEYPOINTS = 137
 N_JOINTS = 55
@@ -58,10 +58,6 @@ def _hip(t, name: str) -> None:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
         raise RuntimeError(f"{name} is on '{where}': soar_amd.smplify runs on HIP devices only; there is no CPU fallback")
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _ints(x, name: str) -> torch.Tensor:

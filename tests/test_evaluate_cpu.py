@@ -126,8 +126,9 @@ def test_image_metrics_refuses_bad_arguments_before_any_launch(lib):
         assert "NULL" in hip_lib.last_error() and name in hip_lib.last_error()
     n = C.c_size_t(0)
     assert lib.soar_eval_scratch_bytes(1, 16, 16, C.byref(n)) == 0
-    assert lib.soar_eval_image_metrics(C.byref(args()), None, n.value, None) != 0 and "scratch" in hip_lib.last_error()
-    assert lib.soar_eval_image_metrics(C.byref(args()), p, n.value - 1, None) != 0 and "scratch" in hip_lib.last_error()
+    assert lib.soar_eval_image_metrics(C.byref(args()), None, n.value, None) != 0 and "NULL workspace" in hip_lib.last_error()
+    assert lib.soar_eval_image_metrics(C.byref(args()), 0x1000, n.value - 1, None) != 0
+    assert f"workspace of {n.value - 1} bytes, need {n.value} (soar_eval_scratch_bytes)" in hip_lib.last_error()
 
 
 def test_python_surface_refuses_cpu_tensors_dtypes_and_shapes():

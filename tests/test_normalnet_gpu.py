@@ -129,6 +129,29 @@ def test_zero_prior_and_empty_batch(dev):
     assert nF.shape == nB.shape == (0, 3, 32, 32) and nF.dtype == torch.float32 and nF.is_cuda
 
 
+def test_packed_weights_are_kept_repacked_and_refused(dev):
+    """hip_lib.PackedWeights, which the four nets share, on the smallest net: the packed buffers are kept from call to call, a weight
+    written in place is packed again and changes the output, and weights left on another device raise the module's own error."""
+    sd = ref.random_state_dict(8, 1, 0, seed=31, device=dev)
+    net = normals.NormalNet(sd, 8, 1, 0).to(dev)
+    image, pF, pB = (t.to(dev) for t in ref.make_inputs(1, 16, 16, 131))
+    first = net(image, pF, pB)
+    assert first[0].abs().sum().item() > 0 and first[1].abs().sum().item() > 0
+    packed = net._packed(dev)
+    again = net._packed(dev)
+    assert again[0] is packed[0] and again[1] is packed[1]
+    kept = net(image, pF, pB)
+    assert torch.equal(kept[0], first[0]) and torch.equal(kept[1], first[1])
+    net.netF_w0[0].neg_()                                       # one output channel of the front net's first convolution
+    fresh = net._packed(dev)
+    assert fresh[0] is not packed[0] and fresh[1] is not packed[1]
+    after = net(image, pF, pB)
+    assert not torch.equal(after[0], first[0]) and torch.equal(after[1], first[1])
+    net.cpu()
+    with pytest.raises(RuntimeError, match=r"NormalNet: weights are not on cuda:\d+: move the module with \.to"):
+        net(image, pF, pB)
+
+
 @pytest.fixture(scope="module")
 def frames(dev):
     images, masks, Ks = (t.to(dev) for t in ref.make_frames())

@@ -333,9 +333,9 @@ def test_refusals_come_before_any_launch():
         sam.SamSegmenter(bad, decoder_heads=2)
     patches, _ = seg.patches(img)
     small = torch.empty(256, dtype=torch.uint8, device=DEV)
-    with pytest.raises(hip_lib.SoarHipError, match="workspace is too small"):
+    with pytest.raises(hip_lib.SoarHipError, match=r"workspace of 256 bytes, need [1-9]\d{3,} \(soar_sam_workspace_bytes\)"):
         seg.encode(patches=patches, workspace=small)
-    with pytest.raises(hip_lib.SoarHipError, match="workspace is too small"):
+    with pytest.raises(hip_lib.SoarHipError, match=r"workspace of 256 bytes, need [1-9]\d{3,} \(soar_sam_workspace_bytes\)"):
         seg.decode(seg.embed(img), pts, None, (90, 160), lab, workspace=small)
     # the library's own checks: a head dimension or a sequence the attention kernel cannot run
     p = C.c_void_p(patches.data_ptr())
