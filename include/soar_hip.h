@@ -61,7 +61,8 @@ extern "C" {
  * normal priors (a triangle-mesh rasterizer).  soar_rast_backward_plan_loss (+ SoarBackwardLoss),
  * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch.  soar_sam_weights_bytes /
  * _pack_weights / _workspace_bytes / _preprocess / _encode / _decode / _postprocess / _attention (+ SoarSamConfig, SoarSamEncodeArgs,
- * SoarSamDecodeArgs): SAM point-prompt segmentation. */
+ * SoarSamDecodeArgs): SAM point-prompt segmentation.  soar_unet_weights_bytes / _pack_weights / _workspace_bytes / _forward / _attention
+ * (+ SoarUnetConfig, SoarUnetArgs, SoarUnetAttnArgs): the SDS guidance's multi-view diffusion UNet. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1969,6 +1970,64 @@ int soar_sam_postprocess(int32_t B, int32_t K, int32_t L, int32_t image_size, in
  * for the sequence Sh x Sw (the window or the grid), or both NULL. */
 int soar_sam_attention(const float *qkv, const float *bias, const float *rel_h, const float *rel_w, float *out, int32_t B, int32_t gh,
                        int32_t gw, int32_t heads, int32_t hd, int32_t window, float scale, void *stream);
+
+/* ---- The multi-view diffusion UNet of the SDS guidance, forward only, float32 (unet.hip, attention.h, soar_amd/unet.py) ----
+ * ldm's openaimodel.UNetModel with MVDream's / ImageDream's additions (camera embedding, self-attention over the views of a group,
+ * image-token cross-attention), transformer depth 1, linear proj_in / proj_out.  The sizes are what soar_amd/unet.py reads from a
+ * state dict.  model_channels times every multiplier is a multiple of 32 (GroupNorm) and of head_channels; context_dim, camera_dim
+ * multiples of 8; head_channels a multiple of 4 up to 64.  attention[l] != 0: level l's blocks carry a transformer (the middle
+ * block always does).  camera_dim = 0: no camera embedding.  with_ip: attn2 has to_k_ip / to_v_ip. */
+#define SOAR_UNET_MAX_LEVELS 8
+#define SOAR_UNET_MAX_PROBES 16
+typedef struct SoarUnetConfig {
+    int32_t in_channels, out_channels, model_channels, levels, num_res_blocks;
+    int32_t channel_mult[SOAR_UNET_MAX_LEVELS], attention[SOAR_UNET_MAX_LEVELS];
+    int32_t context_dim, camera_dim, with_ip, head_channels, n_view;
+} SoarUnetConfig;
+/* The packed weights: `count` contiguous float32 device tensors of sizes[i] floats in the order of soar_amd.unet.tensor_keys (ldm's
+ * layouts; a size that is not the layout's is refused, naming the index), copied, the 3 x 3 convolutions re-laid as [Cout][tap][Cin]
+ * (the first one's Cin padded to 8 with zeros).  floats (or NULL): the sum of the sizes.  packed: 256-byte aligned. */
+int soar_unet_weights_bytes(const SoarUnetConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
+int soar_unet_pack_weights(const SoarUnetConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
+                           size_t packed_bytes, void *stream);
+/* N latents of H x W with T context tokens and ip_tokens image tokens (0: none).  Refuses an H or W that is odd at a level that is
+ * down-sampled, naming the level. */
+int soar_unet_workspace_bytes(const SoarUnetConfig *cfg, int32_t N, int32_t H, int32_t W, int32_t T, int32_t ip_tokens, size_t *bytes);
+/* eps = UNet(x, t, context, camera, ip_tokens).  x [N][in_channels][H][W] with any strides (floats); t [N] float32, read on the device;
+ * context [N][T][context_dim]; camera [N][camera_dim] or NULL; ip_tokens [N][n_ip][context_dim] or NULL (n_ip = 0): the second key set
+ * of every cross-attention, its result added times ip_weight.  N is a multiple of n_view: self-attention runs over the n_view latents
+ * of a group, and a group's result does not depend on the other groups, bit for bit.  eps [N][H][W][out_channels] (channels last).
+ * Probes: after the stage probe_code[i] names, that stage's channels-last activation is copied to probe_dst[i].  Code = 8 block +
+ * stage; block = the index in input_blocks, then the middle block, then output_blocks; stage 0: the ResBlock's (or the block's
+ * convolution's) output, 1 / 2 / 3: the transformer's tokens after attn1 / attn2 / ff, 4: the transformer's output, 5: the up-sampling
+ * convolution's output, 6: the concatenated input of an output block; SOAR_UNET_PROBE_EMB: emb [N][4 model_channels].
+ * No atomics, no host synchronisation, no allocation: two calls give the same bits. */
+#define SOAR_UNET_PROBE_EMB 1000000
+typedef struct SoarUnetArgs {
+    int32_t N, H, W, T, n_ip;
+    float ip_weight;
+    const float *x;
+    int64_t x_stride[4];
+    const float *t, *context, *camera, *ip_tokens;
+    float *eps;
+    int32_t n_probes;
+    int32_t probe_code[SOAR_UNET_MAX_PROBES];
+    float *probe_dst[SOAR_UNET_MAX_PROBES];
+} SoarUnetArgs;
+int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarUnetArgs *args, void *workspace, size_t workspace_bytes,
+                      void *stream);
+/* Multi-head attention by itself: out [B][Lq][.] = softmax(scale q k^T) v per head, q [B][Lq][.], k, v [B][Lk][.] from their own
+ * pointers with their own row pitches (ld*, floats, multiples of 4, at least heads hd); head j is channels j hd .. + hd of a row.
+ * Lk is any count from 1; hd a multiple of 4 up to 64.  k2 / v2 [B][Lk2][.] (or both NULL): a second key / value set, whose
+ * normalised result is added times w2 in the same launch. */
+typedef struct SoarUnetAttnArgs {
+    const float *q, *k, *v, *k2, *v2;
+    float *out;
+    int64_t ldq, ldk, ldv, ldk2, ldv2, ldo;
+    int32_t B, Lq, Lk, Lk2, heads, hd;
+    float scale, w2;
+} SoarUnetAttnArgs;
+int soar_unet_attention(const SoarUnetAttnArgs *args, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

@@ -3,12 +3,13 @@
 //   sam_attn_kernel        multi-head attention with the decomposed relative-position bias, windows and whole grids alike: an
 //                          online softmax over tiles of 32 keys, q k^T and p v on v_mfma_f32_32x32x2_f32, nothing of the score
 //                          matrix in memory.  Window partition, its zero padding and the un-partition are index arithmetic
-//   ln_rows_kernel         LayerNorm over the last axis (tokens, and the channels of an NHWC map), optionally GELU behind it
+//   ln_rows_kernel         (layer_norm.h) LayerNorm over the last axis (tokens, and the channels of an NHWC map), optionally GELU behind it
 //   the rest               pre- and post-processing, Fourier features, the decoder's small attentions, the transposed convolutions
 //                          and the hyper-network product: plain VALU kernels
 // Every matrix product (linear layers, patch embedding, the neck's convolutions) is launch_conv_gemm (conv_gemm.h).
 // No atomics; no sum's order depends on the batch: a frame's result does not depend on its neighbours or its place among them.
 #include "conv_gemm.h"
+#include "layer_norm.h"
 #include "workspace.h"
 
 #include <vector>
@@ -283,36 +284,6 @@ int launch_attention(const float *qkv, const float *bias, const float *rel_h, co
     else if (hd <= 64) hipLaunchKernelGGL(sam_attn_kernel<64>, grid, dim3(128), 0, stream, a);
     else hipLaunchKernelGGL(sam_attn_kernel<96>, grid, dim3(128), 0, stream, a);
     SOAR_LAUNCH_OK("sam_attn", stream, 0);
-    return 0;
-}
-
-// ---- LayerNorm over rows of C floats, a wave a row; act = ACT_GELU: GELU behind it.  y may be x: a lane rewrites what it read. -------
-__global__ void __launch_bounds__(256) ln_rows_kernel(const float *x, const float *__restrict__ w, const float *__restrict__ bb,
-                                                      float *y, int64_t rows, int C, float eps, int act)
-{
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const float *xr = x + row * C;
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += xr[c];
-    for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d);
-    const float mean = s / (float)C;
-    float v = 0.f;
-    for (int c = lane; c < C; c += 64) { const float t = xr[c] - mean; v += t * t; }
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    const float rstd = 1.f / sqrtf(v / (float)C + eps);
-    for (int c = lane; c < C; c += 64) {
-        float t = (xr[c] - mean) * rstd * w[c] + bb[c];
-        if (act == ACT_GELU) t = gelu_erf(t);
-        y[row * C + c] = t;
-    }
-}
-int layer_norm(const float *x, const float *w, const float *b, float *y, int64_t rows, int C, float eps, int act, hipStream_t stream)
-{
-    if (rows == 0) return 0;
-    hipLaunchKernelGGL(ln_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, w, b, y, rows, C, eps, act);
-    SOAR_LAUNCH_OK("sam_layer_norm", stream, 0);
     return 0;
 }
 

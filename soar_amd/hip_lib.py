@@ -321,6 +321,31 @@ class SoarSamDecodeArgs(C.Structure):
                 ("points", _vp), ("labels", _vp), ("counts", _vp), ("low_res", _vp), ("iou", _vp), ("prompt_tokens", _vp), ("tokens_out", _vp)]
 
 
+UNET_MAX_LEVELS = 8
+UNET_MAX_PROBES = 16
+UNET_PROBE_EMB = 1000000
+
+
+class SoarUnetConfig(C.Structure):
+    """Mirror of ``struct SoarUnetConfig`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("in_channels", "out_channels", "model_channels", "levels", "num_res_blocks")] + \
+               [("channel_mult", C.c_int32 * UNET_MAX_LEVELS), ("attention", C.c_int32 * UNET_MAX_LEVELS)] + \
+               [(n, C.c_int32) for n in ("context_dim", "camera_dim", "with_ip", "head_channels", "n_view")]
+
+
+class SoarUnetArgs(C.Structure):
+    """Mirror of ``struct SoarUnetArgs`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "T", "n_ip")] + [("ip_weight", C.c_float), ("x", _vp), ("x_stride", C.c_int64 * 4),
+                ("t", _vp), ("context", _vp), ("camera", _vp), ("ip_tokens", _vp), ("eps", _vp), ("n_probes", C.c_int32),
+                ("probe_code", C.c_int32 * UNET_MAX_PROBES), ("probe_dst", _vp * UNET_MAX_PROBES)]
+
+
+class SoarUnetAttnArgs(C.Structure):
+    """Mirror of ``struct SoarUnetAttnArgs`` (include/soar_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("q", "k", "v", "k2", "v2", "out")] + [(n, C.c_int64) for n in ("ldq", "ldk", "ldv", "ldk2", "ldv2", "ldo")] + \
+               [(n, C.c_int32) for n in ("B", "Lq", "Lk", "Lk2", "heads", "hd")] + [("scale", C.c_float), ("w2", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -554,6 +579,11 @@ SIGNATURES = {
     "soar_sam_decode": (C.c_int, [C.POINTER(SoarSamConfig), _vp, C.POINTER(SoarSamDecodeArgs), _vp, C.c_size_t, _vp]),
     "soar_sam_postprocess": (C.c_int, [C.c_int32] * 8 + [_vp, _vp, _vp, _vp]),
     "soar_sam_attention": (C.c_int, [_vp] * 5 + [C.c_int32] * 6 + [C.c_float, _vp]),
+    "soar_unet_weights_bytes": (C.c_int, [C.POINTER(SoarUnetConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "soar_unet_pack_weights": (C.c_int, [C.POINTER(SoarUnetConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_unet_workspace_bytes": (C.c_int, [C.POINTER(SoarUnetConfig)] + [C.c_int32] * 5 + [C.POINTER(C.c_size_t)]),
+    "soar_unet_forward": (C.c_int, [C.POINTER(SoarUnetConfig), _vp, C.POINTER(SoarUnetArgs), _vp, C.c_size_t, _vp]),
+    "soar_unet_attention": (C.c_int, [C.POINTER(SoarUnetAttnArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

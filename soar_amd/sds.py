@@ -11,6 +11,9 @@ the caller's UNet.
 * ``MultiviewSDS(encoder, ...)`` is the guidance's ``forward`` with the UNet left to the caller: ``eps_fn(latent_model_input [2B, 4,
   h, w], t_expand [2B]) -> [2B, 4, h, w]`` in the order (text, uncond), a closure over ``model.apply_model`` and its context.
 
+* ``MultiviewGuidance(encoder, unet, text_embeddings, image_tokens=None, ...)`` is the whole guidance: ``MultiviewSDS`` with
+  ``soar_amd.unet.MultiviewUNet`` as its ``eps_fn``, the callable ``soar_amd.system`` takes as ``guidance``.
+
 HIP only: CPU tensors are refused.  Inputs may have any strides (``comp_rgb.permute(0, 3, 1, 2)`` goes in without a copy; its
 gradient comes back in the same layout).  DESIGN.md 9f states the computation in full.
 """
@@ -330,3 +333,55 @@ class MultiviewSDS(nn.Module):
             return {"loss_sds": z, "grad_norm": z.detach()}
         loss, gn = _SdsFn.apply(self, x, eps_fn, t.reshape(1).contiguous(), noise, post, gs, self.image_size)
         return {"loss_sds": loss, "grad_norm": gn}
+
+
+class MultiviewGuidance(nn.Module):
+    """The guidance's ``forward`` (TS/guidance/imagedream_guidance.py:156-300, without ``ip_mode == "pixel"``'s extra view) with the
+    UNet in this library: ``guidance(rgb, grad_scale=..., c2w=..., ref_rgb=..., **batch) -> {"loss_sds", "grad_norm"}``.
+
+    ``text_embeddings [2, T, ctx]``: the prompt's and the unconditional prompt's CLIP text tokens (the caller's encoder); a row is
+    repeated for every view of its half.  ``image_tokens(ref_rgb) -> (cond [ip_dim, ctx], uncond [ip_dim, ctx])``: the caller's CLIP
+    image encoder and ``Resampler``; None: no image tokens are used, whatever ``ref_rgb`` is.  The cameras ``c2w [B, 4, 4]`` are
+    normalised (``soar_amd.unet.normalize_camera``) and repeated for both halves.  Further arguments are ``MultiviewSDS``'s."""
+
+    def __init__(self, encoder: LatentEncoder, unet, text_embeddings: torch.Tensor, image_tokens: Optional[Callable] = None, **sds_args):
+        super().__init__()
+        if not isinstance(text_embeddings, torch.Tensor) or text_embeddings.dim() != 3 or text_embeddings.shape[0] != 2 or \
+                text_embeddings.shape[2] != unet.cfg["context_dim"]:
+            raise ValueError(f"MultiviewGuidance: text_embeddings must be [2, T, {unet.cfg['context_dim']}] (text, uncond) "
+                             f"(got {list(getattr(text_embeddings, 'shape', ()))})")
+        self.sds = MultiviewSDS(encoder, **sds_args)
+        self.unet, self.image_tokens = unet, image_tokens
+        self.register_buffer("text_embeddings", text_embeddings.detach().to(torch.float32).contiguous())
+
+    def set_step_range(self, min_step_percent: float, max_step_percent: float) -> None:
+        self.sds.set_step_range(min_step_percent, max_step_percent)
+
+    def context(self, B: int, c2w: Optional[torch.Tensor], ref_rgb=None):
+        """-> (context [2B, T, ctx], camera [2B, 16] or None, ip_tokens [2B, ip_dim, ctx] or None) in the order (text, uncond)"""
+        from .unet import normalize_camera
+        ctx = self.text_embeddings.repeat_interleave(B, dim=0)
+        camera = None
+        if self.unet.cfg["camera_dim"]:
+            if c2w is None or tuple(c2w.shape) != (B, 4, 4):
+                raise ValueError(f"MultiviewGuidance: c2w must be [{B}, 4, 4] (got {list(getattr(c2w, 'shape', ()))})")
+            camera = normalize_camera(c2w.to(torch.float32)).repeat(2, 1)
+        ip = None
+        if self.image_tokens is not None and ref_rgb is not None:
+            cond, uncond = self.image_tokens(ref_rgb)
+            ip = torch.cat([cond[None].expand(B, -1, -1), uncond[None].expand(B, -1, -1)]).to(ctx)
+        return ctx, camera, ip
+
+    def forward(self, rgb: torch.Tensor, grad_scale: Optional[torch.Tensor] = None, c2w: Optional[torch.Tensor] = None, ref_rgb=None,
+                t: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, posterior_noise: Optional[torch.Tensor] = None,
+                **ignored) -> Dict[str, torch.Tensor]:
+        if not isinstance(rgb, torch.Tensor) or rgb.dim() != 4 or rgb.shape[3] != 3:
+            raise ValueError(f"MultiviewGuidance: rgb must be a [B, H, W, 3] tensor (got {tuple(getattr(rgb, 'shape', ()))})")
+        if not rgb.is_cuda:
+            raise RuntimeError(f"MultiviewGuidance: rgb is on '{rgb.device}': soar_amd.sds runs on HIP devices only; there is no CPU fallback")
+        ctx, camera, ip = self.context(rgb.shape[0], c2w, ref_rgb)
+
+        def eps_fn(x_in, t_expand):
+            return self.unet(x_in, t_expand, ctx, camera=camera, ip_tokens=ip)
+
+        return self.sds(rgb, eps_fn, t=t, noise=noise, posterior_noise=posterior_noise, grad_scale=grad_scale)
