@@ -62,7 +62,10 @@ extern "C" {
  * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch.  soar_sam_weights_bytes /
  * _pack_weights / _workspace_bytes / _preprocess / _encode / _decode / _postprocess / _attention (+ SoarSamConfig, SoarSamEncodeArgs,
  * SoarSamDecodeArgs): SAM point-prompt segmentation.  soar_unet_weights_bytes / _pack_weights / _workspace_bytes / _forward / _attention
- * (+ SoarUnetConfig, SoarUnetArgs, SoarUnetAttnArgs): the SDS guidance's multi-view diffusion UNet. */
+ * (+ SoarUnetConfig, SoarUnetArgs, SoarUnetAttnArgs): the SDS guidance's multi-view diffusion UNet.  soar_clip_weights_bytes /
+ * _pack_weights / _workspace_bytes / _preprocess / _forward / _attention and soar_resampler_weights_bytes / _pack_weights /
+ * _workspace_bytes / _forward (+ SoarClipConfig, SoarClipArgs, SoarClipAttnArgs, SoarResamplerConfig, SoarResamplerArgs): the
+ * guidance's conditioning, CLIP's two encoders and the image-token Resampler. */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -2028,6 +2031,84 @@ typedef struct SoarUnetAttnArgs {
     float scale, w2;
 } SoarUnetAttnArgs;
 int soar_unet_attention(const SoarUnetAttnArgs *args, void *stream);
+
+/* ---- The SDS guidance's conditioning, forward only, float32 (clip.hip, attention.h, soar_amd/clip.py) ----
+ * One pre-LN transformer tower serves CLIP's text encoder (causal mask; token + position embedding in front) and its ViT image
+ * encoder (patch product, class token, position embedding and ln_pre in front): x += out_proj(attn(ln_1 x)); x += c_proj(gelu_erf(
+ * c_fc(ln_2 x))), LayerNorm eps 1e-5, scale head_dim^-0.5.  width and mlp are multiples of 8, head_dim = width / heads a multiple of
+ * 4 up to 96.  tokens: the text context length, or 1 + grid^2.  A sizing call refuses what the kernels cannot run, naming the number. */
+#define SOAR_CLIP_TEXT 0
+#define SOAR_CLIP_VISION 1
+#define SOAR_CLIP_MAX_LAYERS 64
+#define SOAR_CLIP_MAX_PROBES 16
+typedef struct SoarClipConfig {
+    int32_t kind;                      /* SOAR_CLIP_TEXT or SOAR_CLIP_VISION */
+    int32_t width, heads, layers, mlp, tokens;
+    int32_t vocab;                     /* text */
+    int32_t patch, grid;               /* vision: the image is grid patch pixels a side */
+} SoarClipConfig;
+/* The packed weights: `count` contiguous float32 device tensors of sizes[i] floats in the order of soar_amd.clip.tower_keys (open_clip's
+ * layouts: q | k | v as one in_proj), copied; the patch convolution's rows are padded from 3 patch^2 to a multiple of 8 with zeros.
+ * floats (or NULL): the sum of the sizes.  packed: 256-byte aligned. */
+int soar_clip_weights_bytes(const SoarClipConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
+int soar_clip_pack_weights(const SoarClipConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
+                           size_t packed_bytes, void *stream);
+/* B sequences of L tokens (text: 1 <= L <= tokens; vision: L = tokens) */
+int soar_clip_workspace_bytes(const SoarClipConfig *cfg, int32_t B, int32_t L, size_t *bytes);
+/* images [B][grid patch][grid patch][3] uint8 -> rows [B][grid^2][Kp] float32, Kp = 3 patch^2 rounded up to 8: element
+ * (channel patch + y) patch + x of a token is its pixel's (byte / 255 - mean) / std with CLIP's constants; elements from 3 patch^2 zeros */
+int soar_clip_preprocess(const SoarClipConfig *cfg, int32_t B, const uint8_t *images, float *rows, void *stream);
+/* out [B][L][width]: the tokens after run_layers blocks (0 .. layers), through ln_final / ln_post when final_norm != 0.  Text: ids
+ * [B][L] int32, each in [0, vocab) (the kernel clamps); vision: patches = soar_clip_preprocess's rows.  Probes: the tokens [B][L][width]
+ * after the stage probe_code[i] names are copied to probe_dst[i]; 2 block: after the block's attention, 2 block + 1: after the block;
+ * SOAR_CLIP_PROBE_EMBED: the embedding (vision: patch product, class row and positions), SOAR_CLIP_PROBE_PRE: after ln_pre (vision).
+ * No atomics, no host synchronisation, no allocation; a sequence's result is the same bits alone and in any batch. */
+#define SOAR_CLIP_PROBE_EMBED 1000000
+#define SOAR_CLIP_PROBE_PRE 1000001
+typedef struct SoarClipArgs {
+    int32_t B, L, run_layers, final_norm;
+    const int32_t *ids;
+    const float *patches;
+    float *out;
+    int32_t n_probes;
+    int32_t probe_code[SOAR_CLIP_MAX_PROBES];
+    float *probe_dst[SOAR_CLIP_MAX_PROBES];
+} SoarClipArgs;
+int soar_clip_forward(const SoarClipConfig *cfg, const void *packed, const SoarClipArgs *args, void *workspace, size_t workspace_bytes,
+                      void *stream);
+/* The towers' attention by itself: soar_unet_attention's kernel with one key set, hd a multiple of 4 up to 96, and causal != 0:
+ * key j counts for query i when j <= i (needs Lq = Lk). */
+typedef struct SoarClipAttnArgs {
+    const float *q, *k, *v;
+    float *out;
+    int64_t ldq, ldk, ldv, ldo;
+    int32_t B, Lq, Lk, heads, hd, causal;
+    float scale;
+} SoarClipAttnArgs;
+int soar_clip_attention(const SoarClipAttnArgs *args, void *stream);
+
+/* IP-Adapter's Resampler: `queries` learned latents attend over proj_in(x) and themselves (one softmax over n + queries keys), `depth`
+ * times, each followed by a bias-free feed-forward of width ff; then proj_out and norm_out.  dim, emb, ff and heads dim_head are
+ * multiples of 8, dim_head a multiple of 4 up to 96.  Tensors in the order of soar_amd.clip.resampler_keys. */
+typedef struct SoarResamplerConfig {
+    int32_t dim, depth, heads, dim_head, queries, emb, out, ff;
+} SoarResamplerConfig;
+int soar_resampler_weights_bytes(const SoarResamplerConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
+int soar_resampler_pack_weights(const SoarResamplerConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
+                                size_t packed_bytes, void *stream);
+int soar_resampler_workspace_bytes(const SoarResamplerConfig *cfg, int32_t B, int32_t n, size_t *bytes);
+/* x [B][n][emb] -> out [B][queries][out].  Probes [B][queries][dim]: 2 layer: the latents after the layer's attention, 2 layer + 1:
+ * after its feed-forward. */
+typedef struct SoarResamplerArgs {
+    int32_t B, n;
+    const float *x;
+    float *out;
+    int32_t n_probes;
+    int32_t probe_code[SOAR_CLIP_MAX_PROBES];
+    float *probe_dst[SOAR_CLIP_MAX_PROBES];
+} SoarResamplerArgs;
+int soar_resampler_forward(const SoarResamplerConfig *cfg, const void *packed, const SoarResamplerArgs *args, void *workspace,
+                           size_t workspace_bytes, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

@@ -1,9 +1,12 @@
-// attention.h -- multi-head attention with separate query, key and value sources and any number of keys (unet.hip).
+// attention.h -- multi-head attention with separate query, key and value sources and any number of keys (unet.hip, clip.hip).
 //
 //   kv_attn_kernel         out = softmax(q k^T scale) v  (+ w2 softmax(q k2^T scale) v2: a second key / value set in the same launch,
 //                          the query read once).  An online softmax over tiles of 32 keys, both products on
 //                          v_mfma_f32_32x32x2_f32, nothing of the score matrix in memory.  The last tile's missing keys are masked, not
-//                          padded in memory; the head dimension is padded to 32 or 64 in LDS only
+//                          padded in memory; the head dimension is padded to 32, 64 or 96 in LDS only.  CAUSAL (clip.hip; one key
+//                          set, Lq = Lk): key j counts for query i when j <= i -- masked inside a tile, and the key tiles wholly
+//                          behind the workgroup's last query are not visited.  Key 0 is visible to every query, so a row's running
+//                          maximum is finite from the first tile on and a tile without a visible key adds exp(-inf) = 0
 // The scheme is sam_attn_kernel's (sam.hip): transposed products, a lane owns one query, p stays in its registers.
 // No atomics; a (batch, head, query tile)'s sums do not depend on the rest of the launch.
 #pragma once
@@ -16,7 +19,7 @@ namespace {
 constexpr int KVA_Q = 128;             // queries per workgroup: four waves of 32
 constexpr int KVA_K = 32;              // keys per tile
 
-template <int HDP>
+template <int HDP, bool CAUSAL>
 __global__ void __launch_bounds__(256) kv_attn_kernel(SoarUnetAttnArgs a)
 {
     constexpr int PITCH = HDP + 4, NC = HDP / 32;
@@ -53,7 +56,11 @@ __global__ void __launch_bounds__(256) kv_attn_kernel(SoarUnetAttnArgs a)
         for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int e = 0; e < 16; e++) o[c][e] = 0.f;
-        const int ntiles = (nk + KVA_K - 1) / KVA_K;
+        int ntiles = (nk + KVA_K - 1) / KVA_K;
+        if (CAUSAL) {                                            // the workgroup's last query sees keys 0 .. itself
+            const int last = min(a.Lq, ((int)blockIdx.x + 1) * KVA_Q) - 1;
+            ntiles = min(ntiles, last / KVA_K + 1);
+        }
         for (int kt = 0; kt < ntiles; kt++) {
             // K and V of 32 keys, eight threads a key; rows past the last key and channels past hd are zeros
             {
@@ -85,11 +92,11 @@ __global__ void __launch_bounds__(256) kv_attn_kernel(SoarUnetAttnArgs a)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
                 const int j = kt * KVA_K + mfma_row(e, h);
-                s[e] = j < nk ? s[e] : -INFINITY;                // the tail of the last tile
+                s[e] = j < nk && (!CAUSAL || j <= qi) ? s[e] : -INFINITY;    // the tail of the last tile; the keys behind the query
                 mx = fmaxf(mx, s[e]);
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float mn = fmaxf(m, mx);                       // finite: every tile has its first key
+            const float mn = fmaxf(m, mx);                       // finite: every tile has its first key, and a causal row has key 0
             const float corr = expf(m - mn);                     // (0 at the first tile)
             float sum = 0.f;
 #pragma unroll
@@ -126,13 +133,15 @@ __global__ void __launch_bounds__(256) kv_attn_kernel(SoarUnetAttnArgs a)
         }
 }
 
-int launch_kv_attention(const SoarUnetAttnArgs &a, hipStream_t stream)
+// TOWER (clip.hip's calls): also the causal mask and head dimensions up to 96; the UNet's calls keep their two instantiations
+template <bool TOWER = false>
+int launch_kv_attention(const SoarUnetAttnArgs &a, hipStream_t stream, bool causal = false, const char *me = "unet attention")
 {
-    const char *me = "unet attention";
+    constexpr int hd_max = TOWER ? 96 : 64;
     const int64_t C = (int64_t)a.heads * a.hd;
-    if (a.B < 0 || a.B > 65535 || a.Lq < 1 || a.Lk < 1 || a.heads < 1 || a.heads > 65535 || a.hd < 4 || a.hd > 64 || a.hd % 4 ||
+    if (a.B < 0 || a.B > 65535 || a.Lq < 1 || a.Lk < 1 || a.heads < 1 || a.heads > 65535 || a.hd < 4 || a.hd > hd_max || a.hd % 4 ||
         (int64_t)a.B * a.Lq > (int64_t(1) << 30) || (int64_t)a.B * a.Lk > (int64_t(1) << 30)) {
-        set_error("%s: bad sizes (B=%d <= 65535, Lq=%d, Lk=%d from 1, heads=%d, hd=%d: a multiple of 4 up to 64)", me, a.B, a.Lq, a.Lk, a.heads, a.hd);
+        set_error("%s: bad sizes (B=%d <= 65535, Lq=%d, Lk=%d from 1, heads=%d, hd=%d: a multiple of 4 up to %d)", me, a.B, a.Lq, a.Lk, a.heads, a.hd, hd_max);
         return 1;
     }
     if (a.B == 0) return 0;
@@ -147,9 +156,24 @@ int launch_kv_attention(const SoarUnetAttnArgs &a, hipStream_t stream)
         set_error("%s: pointers must be 16-byte aligned", me);
         return 1;
     }
+    if (causal && (!TOWER || a.k2 || a.Lq != a.Lk)) { set_error("%s: a causal mask needs one key set and Lq = Lk (Lq=%d, Lk=%d)", me, a.Lq, a.Lk); return 1; }
     const dim3 grid((unsigned)((a.Lq + KVA_Q - 1) / KVA_Q), (unsigned)a.heads, (unsigned)a.B);
-    if (a.hd <= 32) hipLaunchKernelGGL(kv_attn_kernel<32>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(kv_attn_kernel<64>, grid, dim3(256), 0, stream, a);
+    if constexpr (TOWER) {
+        if (causal) {
+            if (a.hd <= 32) hipLaunchKernelGGL((kv_attn_kernel<32, true>), grid, dim3(256), 0, stream, a);
+            else if (a.hd <= 64) hipLaunchKernelGGL((kv_attn_kernel<64, true>), grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((kv_attn_kernel<96, true>), grid, dim3(256), 0, stream, a);
+            SOAR_LAUNCH_OK("kv_attn", stream, 0);
+            return 0;
+        }
+        if (a.hd > 64) {
+            hipLaunchKernelGGL((kv_attn_kernel<96, false>), grid, dim3(256), 0, stream, a);
+            SOAR_LAUNCH_OK("kv_attn", stream, 0);
+            return 0;
+        }
+    }
+    if (a.hd <= 32) hipLaunchKernelGGL((kv_attn_kernel<32, false>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((kv_attn_kernel<64, false>), grid, dim3(256), 0, stream, a);
     SOAR_LAUNCH_OK("kv_attn", stream, 0);
     return 0;
 }

@@ -346,6 +346,40 @@ class SoarUnetAttnArgs(C.Structure):
                [(n, C.c_int32) for n in ("B", "Lq", "Lk", "Lk2", "heads", "hd")] + [("scale", C.c_float), ("w2", C.c_float)]
 
 
+CLIP_TEXT, CLIP_VISION = 0, 1        # SOAR_CLIP_TEXT, SOAR_CLIP_VISION
+CLIP_MAX_LAYERS = 64
+CLIP_MAX_PROBES = 16
+CLIP_PROBE_EMBED, CLIP_PROBE_PRE = 1000000, 1000001
+
+
+class SoarClipConfig(C.Structure):
+    """Mirror of ``struct SoarClipConfig`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "width", "heads", "layers", "mlp", "tokens", "vocab", "patch", "grid")]
+
+
+class SoarClipArgs(C.Structure):
+    """Mirror of ``struct SoarClipArgs`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "run_layers", "final_norm")] + [("ids", _vp), ("patches", _vp), ("out", _vp),
+                ("n_probes", C.c_int32), ("probe_code", C.c_int32 * CLIP_MAX_PROBES), ("probe_dst", _vp * CLIP_MAX_PROBES)]
+
+
+class SoarClipAttnArgs(C.Structure):
+    """Mirror of ``struct SoarClipAttnArgs`` (include/soar_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("q", "k", "v", "out")] + [(n, C.c_int64) for n in ("ldq", "ldk", "ldv", "ldo")] + \
+               [(n, C.c_int32) for n in ("B", "Lq", "Lk", "heads", "hd", "causal")] + [("scale", C.c_float)]
+
+
+class SoarResamplerConfig(C.Structure):
+    """Mirror of ``struct SoarResamplerConfig`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "heads", "dim_head", "queries", "emb", "out", "ff")]
+
+
+class SoarResamplerArgs(C.Structure):
+    """Mirror of ``struct SoarResamplerArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("n", C.c_int32), ("x", _vp), ("out", _vp), ("n_probes", C.c_int32),
+                ("probe_code", C.c_int32 * CLIP_MAX_PROBES), ("probe_dst", _vp * CLIP_MAX_PROBES)]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -584,6 +618,16 @@ SIGNATURES = {
     "soar_unet_workspace_bytes": (C.c_int, [C.POINTER(SoarUnetConfig)] + [C.c_int32] * 5 + [C.POINTER(C.c_size_t)]),
     "soar_unet_forward": (C.c_int, [C.POINTER(SoarUnetConfig), _vp, C.POINTER(SoarUnetArgs), _vp, C.c_size_t, _vp]),
     "soar_unet_attention": (C.c_int, [C.POINTER(SoarUnetAttnArgs), _vp]),
+    "soar_clip_weights_bytes": (C.c_int, [C.POINTER(SoarClipConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "soar_clip_pack_weights": (C.c_int, [C.POINTER(SoarClipConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_clip_workspace_bytes": (C.c_int, [C.POINTER(SoarClipConfig), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_clip_preprocess": (C.c_int, [C.POINTER(SoarClipConfig), C.c_int32, _vp, _vp, _vp]),
+    "soar_clip_forward": (C.c_int, [C.POINTER(SoarClipConfig), _vp, C.POINTER(SoarClipArgs), _vp, C.c_size_t, _vp]),
+    "soar_clip_attention": (C.c_int, [C.POINTER(SoarClipAttnArgs), _vp]),
+    "soar_resampler_weights_bytes": (C.c_int, [C.POINTER(SoarResamplerConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "soar_resampler_pack_weights": (C.c_int, [C.POINTER(SoarResamplerConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_resampler_workspace_bytes": (C.c_int, [C.POINTER(SoarResamplerConfig), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_resampler_forward": (C.c_int, [C.POINTER(SoarResamplerConfig), _vp, C.POINTER(SoarResamplerArgs), _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
