@@ -57,7 +57,8 @@ extern "C" {
  * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation).
  * soar_normalnet_weights_bytes / _pack_weights / _workspace_bytes / _forward (+ SoarNormalNetArgs), soar_normal_crop_boxes / _sample /
  * _bytes: normal-map preprocessing.  soar_selftest_conv_gemm / _conv_pack (+ SoarConvGemmArgs, SoarConvGemmTaps): the shared
- * implicit-GEMM convolution and its weight packer by themselves, for the tests.  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
+ * implicit-GEMM convolution and its weight packer by themselves, for the tests; soar_selftest_conv_gemm16 / _conv_pack16 /
+ * _conv_gemm_act: the same with bf16 / f16 operands (SoarUnetConfig.precision uses them).  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
  * normal priors (a triangle-mesh rasterizer).  soar_rast_backward_plan_loss (+ SoarBackwardLoss),
  * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch.  soar_sam_weights_bytes /
  * _pack_weights / _workspace_bytes / _preprocess / _encode / _decode / _postprocess / _attention (+ SoarSamConfig, SoarSamEncodeArgs,
@@ -915,6 +916,16 @@ typedef struct SoarConvGemmArgs {
 } SoarConvGemmArgs;
 int soar_selftest_conv_gemm(const SoarConvGemmArgs *args, int32_t *tile_out, void *stream);
 int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb, void *stream);
+/* The same with 16-bit operands: wtype 1 bf16, 2 f16.  soar_selftest_conv_gemm16 reads the taps' w as 16-bit values
+ * (ldw and wbat still count elements), rounds A to the type (nearest even) as it is loaded and accumulates in float32; x, bias, res
+ * and y stay float32.  It refuses, besides the above: a wtype outside 1 .. 2; an ldw or wbat that is no multiple of 8.
+ * soar_selftest_conv_pack16: torch [Cout][Cin][kk] float32 -> fwd [Cout][kk][Cinp] of the type, rounded to nearest even, channels
+ * Cin .. Cinp - 1 zeros (Cinp >= Cin); kk = 1 converts a linear layer's matrix.  Forward only. */
+int soar_selftest_conv_gemm16(const SoarConvGemmArgs *args, int32_t wtype, int32_t *tile_out, void *stream);
+int soar_selftest_conv_pack16(const float *w, void *fwd, int32_t Cout, int32_t Cin, int32_t Cinp, int32_t kk, int32_t wtype, void *stream);
+/* SoarConvGemmArgs carries no activation: the descriptor at either operand type (wtype 0 .. 2) with the epilogue's act (0 none, 1 exact
+ * GELU, 2 ReLU): y = act(alpha (A B^T) + bias) + res */
+int soar_selftest_conv_gemm_act(const SoarConvGemmArgs *args, int32_t wtype, int32_t act, int32_t *tile_out, void *stream);
 
 /* ---- mesh export (mesh.hip, soar_amd/mesh.py; DESIGN.md "Mesh export").  Not part of the training step.
  * soar_tsdf_integrate: fuses n_views (1..64) rendered depth / opacity planes [n_views][H][W] into the TSDF of a dense grid
@@ -1986,10 +1997,16 @@ typedef struct SoarUnetConfig {
     int32_t in_channels, out_channels, model_channels, levels, num_res_blocks;
     int32_t channel_mult[SOAR_UNET_MAX_LEVELS], attention[SOAR_UNET_MAX_LEVELS];
     int32_t context_dim, camera_dim, with_ip, head_channels, n_view;
+    int32_t precision;             /* of the products' operands: 0 float32 (what a zero-initialised struct asks for), 1 bf16, 2 f16 */
 } SoarUnetConfig;
 /* The packed weights: `count` contiguous float32 device tensors of sizes[i] floats in the order of soar_amd.unet.tensor_keys (ldm's
  * layouts; a size that is not the layout's is refused, naming the index), copied, the 3 x 3 convolutions re-laid as [Cout][tap][Cin]
- * (the first one's Cin padded to 8 with zeros).  floats (or NULL): the sum of the sizes.  packed: 256-byte aligned. */
+ * (the first one's Cin padded to 8 with zeros).  floats (or NULL): the sum of the sizes.  packed: 256-byte aligned.
+ * precision != 0: every tensor that is a product's B operand (the convolutions' and linear layers' weights) is laid as bf16 / f16,
+ * rounded to nearest even, its start still 16-byte aligned; biases, norm gains and the rest stay float32.  The sources are the same
+ * float32 tensors; `bytes` shrinks, `count` and `floats` do not change.  soar_unet_forward then runs every product on the 16-bit
+ * matrix core with float32 accumulation, its activations rounded as they are loaded; activations in memory, GroupNorm, LayerNorm,
+ * attention, inputs, outputs and probes stay float32, and the bit-exact promises below hold for each precision. */
 int soar_unet_weights_bytes(const SoarUnetConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
 int soar_unet_pack_weights(const SoarUnetConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
                            size_t packed_bytes, void *stream);

@@ -1,5 +1,6 @@
 // conv_gemm.h -- the implicit-GEMM convolution and the weight packer that the convolutional networks share (lpips.hip, vae.hip,
-// normalnet.hip), and the small pieces every kernel on v_mfma_f32_32x32x2_f32 needs.
+// normalnet.hip), its form with 16-bit operands (bf16 / f16), and the small pieces every kernel on
+// v_mfma_f32_32x32x2_f32 needs.
 #pragma once
 
 #include "soar_common.h"
@@ -9,7 +10,8 @@ namespace soar {
 // One tap table: output (gy os + py, gx os + px) of grid row (n, gy, gx) sums, tap by tap, input (gy stride + dy, gx stride + dx)
 // times w[co][tap][ci].  A 1 x 1 convolution and a plain matrix product are a table of one entry.
 struct ConvTaps {
-    const float *w;                // B: row co at w + image wbat + co ldw, k = tap Cin + ci
+    const float *w;                // B: row co at w + image wbat + co ldw, k = tap Cin + ci (wtype != 0: 16-bit values behind this
+                                   //   pointer, ldw and wbat counted in elements all the same)
     int64_t ldw;
     int ntaps, py, px;
     signed char dy[9], dx[9];
@@ -22,6 +24,8 @@ inline void square_taps(ConvTaps &p, const float *w, int64_t ldw, int side, int 
 }
 
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
+// what B holds, and what A is rounded to (nearest even) on its way into LDS; the sums and the epilogue are float32 either way
+enum { WT_F32 = 0, WT_BF16 = 1, WT_F16 = 2 };
 
 // y = act(alpha * (A B^T) + bias) + res.  A row is one grid position's (tap, cin) window of x, gathered on load; nothing padded or
 // zero-dilated is ever materialised.
@@ -46,11 +50,13 @@ struct ConvGemm {
     ConvTaps ph[4];
     int tiles_n, tiles_img;        // (the launcher's)
     int act;                       // ACT_NONE (0: what a zero-initialised descriptor asks for), ACT_GELU (exact, erf) or ACT_RELU
+    int wtype;                     // WT_F32 (0: what a zero-initialised descriptor asks for), WT_BF16 or WT_F16: conv_gemm16_kernel
 };
 // Refuses (set_error, 1, nothing launched) a descriptor the kernel cannot run: more than 2^30 rows; Cin no multiple of 8; nph outside
 // 1 .. 4; act outside 0 .. 2; wbat without per_image; dil not 1 or 2, or 2 with reflect; stride, os, Cout, Hin or Win below 1; x, y or a table's w NULL; x
 // or w off 16 bytes, or ldx, ldw, wbat no multiple of 4 (the loads are float4); a table with ntaps outside 1 .. 9 or py, px outside
-// [0, os); with reflect, a coordinate gy stride + dy outside [-(Hin - 1), 2 (Hin - 1)] (mirror() reflects once), likewise along x.
+// [0, os); with reflect, a coordinate gy stride + dy outside [-(Hin - 1), 2 (Hin - 1)] (mirror() reflects once), likewise along x;
+// a wtype outside 0 .. 2; with wtype != 0, ldw or wbat no multiple of 8 (B's loads are 8 elements of 16 bits).
 int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream);
 // the side of the tile launch_conv_gemm picks for desc: 128 or 64
 int conv_gemm_tile(const ConvGemm &desc);
@@ -58,6 +64,10 @@ int conv_gemm_tile(const ConvGemm &desc);
 // torch [Cout][Cin][kk] -> fwd [Cout][kk][Cin] and, unless bwd is NULL, the data gradient's form, spatially flipped and transposed:
 // bwd[(ci kk + kk - 1 - t) ldb + co]
 int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, int kk, int64_t ldb, hipStream_t stream);
+
+// torch [Cout][Cin][kk] float32 -> fwd [Cout][kk][Cinp] of wtype's 16-bit type, rounded to nearest even, channels Cin .. Cinp - 1
+// zeros; kk = 1 converts a linear layer's matrix.  Forward only: there is no data-gradient form.
+int launch_conv_pack16(const float *w, void *fwd, int Cout, int Cin, int Cinp, int kk, int wtype, hipStream_t stream);
 
 inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
 

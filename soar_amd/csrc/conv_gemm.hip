@@ -7,9 +7,12 @@
 //                          channels, K = (tap, cin), tiles staged through LDS.  The A loader does strides, padding (zero or mirrored)
 //                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = act(alpha acc + bias) + res,
 //                          scattered to the tap table's output parity (act: none, exact GELU or ReLU)
+//   conv_pack16_kernel     torch [Cout][Cin][kk] float32 -> [Cout][tap][Cinp] bf16 / f16, rounded to nearest even (forward only)
+//   conv_gemm16_kernel     the same implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16}: B read as 16-bit values, A rounded to the type
+//                          on its way into LDS, float32 accumulators and the same epilogue (ConvGemm::wtype)
 //
-// The launcher refuses the descriptors the kernel cannot run (conv_gemm.h); soar_selftest_conv_gemm / _conv_pack at the end of the
-// file reach the launcher and the packer by themselves (tests/test_conv_gemm_*.py).
+// The launcher refuses the descriptors the kernel cannot run (conv_gemm.h); soar_selftest_conv_gemm / _conv_gemm16 / _conv_pack /
+// _conv_pack16 at the end of the file reach the launcher and the packers by themselves (tests/test_conv_gemm_*.py).
 // No atomics: every output has one fixed order of summation, the same whatever the tile and the batch.
 #include "conv_gemm.h"
 
@@ -30,6 +33,54 @@ __global__ void __launch_bounds__(256) conv_pack_kernel(const float *__restrict_
     fwd[((size_t)co * kk + t) * Cin + ci] = v;
     // the data gradient is the convolution of the output gradient with W'[ci][co][kk - 1 - t]
     if (bwd) bwd[((size_t)ci * kk + (kk - 1 - t)) * ldb + co] = v;
+}
+
+// torch [Cout][Cin][kk] float32 -> [Cout][kk][Cinp] of T, rounded to nearest even, channels Cin .. Cinp - 1 zeros
+template <typename T>
+__global__ void __launch_bounds__(256) conv_pack16_kernel(const float *__restrict__ w, T *__restrict__ out, int Cout, int Cin, int Cinp, int kk)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)Cout * kk * Cinp) return;
+    // e walks the packed layout [co][t][ci]
+    const int ci = (int)(e % Cinp);
+    const int64_t r = e / Cinp;
+    const int t = (int)(r % kk), co = (int)(r / kk);
+    out[e] = ci < Cin ? (T)w[((size_t)co * Cin + ci) * kk + t] : (T)0.f;
+}
+
+// The epilogue of both kernels: y = act(alpha acc + bias) + res of a wave's WM x WN accumulator blocks (C / D layout: mfma_row),
+// scattered to the tap table's output parity.  Lane (i, h); the wave's blocks start at row r0 + wr, column c0 + wc of the product.
+template <int WM, int WN>
+__device__ __forceinline__ void conv_gemm_epilogue(const ConvGemm &k, const ConvTaps &ph, const f32x16 (&acc)[WM][WN], int img0, int rows,
+                                                   int hwg, int r0, int c0, int wr, int wc, int i, int h)
+{
+    bool cv[WN];
+    float bias[WN];
+#pragma unroll
+    for (int c = 0; c < WN; c++) {
+        const int co = c0 + wc + c * 32 + i;
+        cv[c] = co < k.Cout;
+        bias[c] = k.bias && cv[c] ? k.bias[co] : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < WM; r++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const int row = r0 + wr + r * 32 + mfma_row(e, h);
+            if (row >= rows) continue;
+            const int n = row / hwg;
+            const int q = row - n * hwg, y = q / k.Wg, x = q - y * k.Wg;
+            const size_t base = ((size_t)(img0 + n) * k.yim + (size_t)(y * k.os + ph.py) * k.Wout + (size_t)(x * k.os + ph.px)) * k.ldy;
+#pragma unroll
+            for (int c = 0; c < WN; c++) {
+                if (!cv[c]) continue;
+                const size_t idx = base + (c0 + wc + c * 32 + i);
+                float v = acc[r][c][e] * k.alpha + bias[c];
+                if (k.act) v = k.act == ACT_GELU ? gelu_erf(v) : fmaxf(v, 0.f);     // (act = 0: the arithmetic of every call before it)
+                if (k.res) v += k.res[idx];
+                k.y[idx] = v;
+            }
+        }
 }
 
 // Block tile 64 WM x 64 WN, waves 2 x 2, each 32 WM x 32 WN as WM x WN MFMA blocks.  K runs flat over (tap, cin) in chunks of 32; a
@@ -159,33 +210,162 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(ConvGemm k)
         }
         lds_barrier();
     }
-    bool cv[WN];
-    float bias[WN];
+    conv_gemm_epilogue<WM, WN>(k, ph, acc, img0, rows, hwg, r0, c0, wr, wc, i, h);
+}
+
+// ---- 16-bit operands ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// float -> T is the compiler's conversion, which rounds to nearest even (v_cvt_pk_bf16_f32, v_cvt_f16_f32)
+template <typename T> struct Op16;
+template <> struct Op16<__bf16> {
+    typedef bf16x8 v8;
+    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct Op16<_Float16> {
+    typedef f16x8 v8;
+    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+template <typename T> __device__ __forceinline__ typename Op16<T>::v8 round8(const float4 &a, const float4 &b)
+{
+    typename Op16<T>::v8 v;
+    v[0] = (T)a.x; v[1] = (T)a.y; v[2] = (T)a.z; v[3] = (T)a.w;
+    v[4] = (T)b.x; v[5] = (T)b.y; v[6] = (T)b.z; v[7] = (T)b.w;
+    return v;
+}
+
+constexpr int BK16 = 64;           // k per chunk
+// LDS row pitch in 16-bit elements: 144 bytes, nine 16-byte slots.  A fragment read is one ds_read_b128 per lane: lane (i, h) reads
+// slot 9 (row0 + i) + 2 s + h.  That instruction is served in groups of 16 lanes of one h whose i cover every residue modulo 16
+// ({0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}), and a bank row is 16 slots wide: since 9 is odd, i -> 9 i mod 16 is one-to-one, the
+// 16 lanes of a group hit 16 different slots and the read is conflict-free.  A staging write (ds_write_b128, groups of 8 consecutive
+// lanes over a 128-byte bank row) stores one row's eight slots side by side: conflict-free as well.
+constexpr int LDSK16 = BK16 + 8;
+
+// conv_gemm_kernel with B read as 16-bit values T and A rounded to T (nearest even) on its way into LDS: the same tiles, waves, tap
+// tables, padding and epilogue; the accumulators are float32.  K runs flat over (tap, cin) in chunks of 64; a staging thread moves
+// groups of 8 elements (two float4 of A, one 16-byte load of B; rows tid >> 3 (+ 32 j), elements (tid & 7) * 8 .. + 8 of the chunk),
+// which never straddle a tap; groups behind K, rows behind M and columns behind Cout are zeros.  One LDS buffer, as above.
+// Lane (i, h): row / column i of a 32 x 32 block, k half h.  Step s = 0 .. 3 of a chunk is one v_mfma_f32_32x32x16, which adds the
+// sixteen products k = 16 s .. 16 s + 15 of the chunk to the accumulator (lane half h supplies k = 16 s + 8 h + j, j = 0 .. 7); how
+// the instruction orders those sixteen is the hardware's, and the same for every output.  So every output's sum runs chunk by chunk
+// and inside a chunk step by step, whatever WM, WN, its place in the tile and the batch.
+template <typename T, int WM, int WN>
+__global__ void __launch_bounds__(256) conv_gemm16_kernel(ConvGemm k)
+{
+    typedef typename Op16<T>::v8 v8;
+    constexpr int BM = 64 * WM, BN = 64 * WN;
+    __shared__ __attribute__((aligned(16))) T As[BM][LDSK16], Bs[BN][LDSK16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const ConvTaps &ph = k.ph[blockIdx.y];
+    // Workgroups go to the chip's eight XCDs in turn, each with an L2 of its own.  The tiles are dealt so that an XCD gets a
+    // contiguous run of them: the column tiles of a row tile, which read the same A, and the row tiles next to it, which share its
+    // halo, then find A in their L2 instead of each fetching it from the Infinity Cache (measured: DESIGN.md 9y).  XCD x's run
+    // starts at x q + min(x, r) for 8 q + r tiles: one-to-one.  Which workgroup computes a tile changes no sum.
+    const unsigned ntile = gridDim.x, xcd = blockIdx.x % 8, rem = ntile % 8;
+    const unsigned tile = xcd * (ntile / 8) + (xcd < rem ? xcd : rem) + blockIdx.x / 8;
+    const int tn = (int)(tile % (unsigned)k.tiles_n);
+    int tm = (int)(tile / (unsigned)k.tiles_n);
+    const int hwg = k.Hg * k.Wg;
+    int img0 = 0, rows = k.N * hwg;
+    if (k.per_image) { img0 = tm / k.tiles_img; tm -= img0 * k.tiles_img; rows = hwg; }
+    const int r0 = tm * BM, c0 = tn * BN;
+    const int Kp = ph.ntaps * k.Cin, nch = (Kp + BK16 - 1) / BK16;
+    const int dm = k.dil - 1;
+
+    const int srow = tid >> 3, sk = (tid & 7) * 8;
+    bool av[2 * WM];
+    int gy[2 * WM], gx[2 * WM];
+    size_t abase[2 * WM];
 #pragma unroll
-    for (int c = 0; c < WN; c++) {
-        const int co = c0 + wc + c * 32 + i;
-        cv[c] = co < k.Cout;
-        bias[c] = k.bias && cv[c] ? k.bias[co] : 0.f;
+    for (int j = 0; j < 2 * WM; j++) {
+        const int r = r0 + srow + 32 * j;
+        av[j] = r < rows;
+        const int n = av[j] ? r / hwg : 0;
+        const int q = av[j] ? r - n * hwg : 0;
+        gy[j] = q / k.Wg;
+        gx[j] = q - gy[j] * k.Wg;
+        abase[j] = (size_t)(img0 + n) * k.xim;
     }
+    const T *wrow[2 * WN];
+    bool bv[2 * WN];
+#pragma unroll
+    for (int j = 0; j < 2 * WN; j++) {
+        const int co = c0 + srow + 32 * j;
+        bv[j] = co < k.Cout;
+        wrow[j] = reinterpret_cast<const T *>(ph.w) + (size_t)img0 * k.wbat + (size_t)(bv[j] ? co : 0) * ph.ldw;
+    }
+
+    float4 na[2 * WM][2];
+    v8 nb[2 * WN];
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto fetch = [&](int ch) {
+        const int kk = ch * BK16 + sk;
+        const bool kv = kk < Kp;
+        const int t = kv ? kk / k.Cin : 0;
+        const int ci = kk - t * k.Cin;
+        const int dy = ph.dy[t], dx = ph.dx[t];
+#pragma unroll
+        for (int j = 0; j < 2 * WM; j++) {
+            int iy = gy[j] * k.stride + dy, ix = gx[j] * k.stride + dx;
+            bool ok = kv && av[j];
+            ok = ok && !((iy | ix) & dm);
+            iy >>= dm; ix >>= dm;
+            if (k.reflect) { iy = mirror(iy, k.Hin); ix = mirror(ix, k.Win); }
+            else ok = ok && iy >= 0 && iy < k.Hin && ix >= 0 && ix < k.Win;
+            if (ok) {
+                const float4 *s = reinterpret_cast<const float4 *>(k.x + (abase[j] + (size_t)iy * k.Win + ix) * k.ldx + ci);
+                na[j][0] = s[0];
+                na[j][1] = s[1];
+            } else {
+                na[j][0] = na[j][1] = zero4;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2 * WN; j++) {
+            if (kv && bv[j]) nb[j] = *reinterpret_cast<const v8 *>(wrow[j] + kk);
+            else
+#pragma unroll
+                for (int e = 0; e < 8; e++) nb[j][e] = (T)0.f;
+        }
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int j = 0; j < 2 * WM; j++) *reinterpret_cast<v8 *>(&As[srow + 32 * j][sk]) = round8<T>(na[j][0], na[j][1]);
+#pragma unroll
+        for (int j = 0; j < 2 * WN; j++) *reinterpret_cast<v8 *>(&Bs[srow + 32 * j][sk]) = nb[j];
+    };
+
+    const int i = lane & 31, h = lane >> 5;
+    const int wr = (wave >> 1) * 32 * WM, wc = (wave & 1) * 32 * WN;
+    f32x16 acc[WM][WN];
 #pragma unroll
     for (int r = 0; r < WM; r++)
 #pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int row = r0 + wr + r * 32 + mfma_row(e, h);
-            if (row >= rows) continue;
-            const int n = row / hwg;
-            const int q = row - n * hwg, y = q / k.Wg, x = q - y * k.Wg;
-            const size_t base = ((size_t)(img0 + n) * k.yim + (size_t)(y * k.os + ph.py) * k.Wout + (size_t)(x * k.os + ph.px)) * k.ldy;
+        for (int c = 0; c < WN; c++)
 #pragma unroll
-            for (int c = 0; c < WN; c++) {
-                if (!cv[c]) continue;
-                const size_t idx = base + (c0 + wc + c * 32 + i);
-                float v = acc[r][c][e] * k.alpha + bias[c];
-                if (k.act) v = k.act == ACT_GELU ? gelu_erf(v) : fmaxf(v, 0.f);     // (act = 0: the arithmetic of every call before it)
-                if (k.res) v += k.res[idx];
-                k.y[idx] = v;
-            }
+            for (int e = 0; e < 16; e++) acc[r][c][e] = 0.f;
+
+    fetch(0);
+    for (int ch = 0; ch < nch; ch++) {
+        stage();
+        lds_barrier();
+        if (ch + 1 < nch) fetch(ch + 1);            // in flight while the MFMAs of this chunk run
+#pragma unroll
+        for (int s = 0; s < BK16 / 16; s++) {
+            v8 a8[WM], b8[WN];
+#pragma unroll
+            for (int r = 0; r < WM; r++) a8[r] = *reinterpret_cast<const v8 *>(&As[wr + r * 32 + i][s * 16 + h * 8]);
+#pragma unroll
+            for (int c = 0; c < WN; c++) b8[c] = *reinterpret_cast<const v8 *>(&Bs[wc + c * 32 + i][s * 16 + h * 8]);
+#pragma unroll
+            for (int r = 0; r < WM; r++)
+#pragma unroll
+                for (int c = 0; c < WN; c++) acc[r][c] = Op16<T>::mfma(a8[r], b8[c], acc[r][c]);
         }
+        lds_barrier();
+    }
+    conv_gemm_epilogue<WM, WN>(k, ph, acc, img0, rows, hwg, r0, c0, wr, wc, i, h);
 }
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -203,6 +383,7 @@ bool check_desc(const ConvGemm &k, int64_t M)
         return false;
     }
     if (k.act < 0 || k.act > ACT_RELU) { set_error("conv_gemm: act must be 0 (none), 1 (GELU) or 2 (ReLU) (got %d)", k.act); return false; }
+    if (k.wtype < 0 || k.wtype > WT_F16) { set_error("conv_gemm: wtype must be 0 (f32), 1 (bf16) or 2 (f16) (got %d)", k.wtype); return false; }
     if (k.stride < 1 || k.os < 1 || k.Cout < 1 || k.Hin < 1 || k.Win < 1) {
         set_error("conv_gemm: stride, os, Cout, Hin and Win must be at least 1 (stride=%d, os=%d, Cout=%d, Hin=%d, Win=%d)", k.stride, k.os,
                   k.Cout, k.Hin, k.Win);
@@ -212,6 +393,11 @@ bool check_desc(const ConvGemm &k, int64_t M)
     if (!aligned16(k.x) || k.ldx % 4 || k.wbat % 4) {
         set_error("conv_gemm: x must be 16-byte aligned, ldx and wbat multiples of 4: the loads are float4 (x=%p, ldx=%lld, wbat=%lld)",
                   (const void *)k.x, (long long)k.ldx, (long long)k.wbat);
+        return false;
+    }
+    if (k.wtype && k.wbat % 8) {
+        set_error("conv_gemm: with 16-bit weights wbat must be a multiple of 8: the loads are 8 elements (wbat=%lld, wtype=%d)",
+                  (long long)k.wbat, k.wtype);
         return false;
     }
     for (int p = 0; p < k.nph; p++) {
@@ -225,6 +411,11 @@ bool check_desc(const ConvGemm &k, int64_t M)
         if (!aligned16(t.w) || t.ldw % 4) {
             set_error("conv_gemm: tap table %d: w must be 16-byte aligned and ldw a multiple of 4: the loads are float4 (w=%p, ldw=%lld)", p,
                       (const void *)t.w, (long long)t.ldw);
+            return false;
+        }
+        if (k.wtype && t.ldw % 8) {
+            set_error("conv_gemm: tap table %d: with 16-bit weights ldw must be a multiple of 8: the loads are 8 elements (ldw=%lld, "
+                      "wtype=%d)", p, (long long)t.ldw, k.wtype);
             return false;
         }
         if (!k.reflect) continue;
@@ -265,9 +456,26 @@ int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream)
     k.tiles_n = (k.Cout + bt - 1) / bt;
     k.tiles_img = (int)((hwg + bt - 1) / bt);
     const int64_t tiles = (k.per_image ? (int64_t)k.N * k.tiles_img : (M + bt - 1) / bt) * k.tiles_n;
-    if (big_tiles) hipLaunchKernelGGL((conv_gemm_kernel<2, 2>), dim3((unsigned)tiles, (unsigned)k.nph), dim3(256), 0, stream, k);
-    else hipLaunchKernelGGL((conv_gemm_kernel<1, 1>), dim3((unsigned)tiles, (unsigned)k.nph), dim3(256), 0, stream, k);
+    const dim3 grid((unsigned)tiles, (unsigned)k.nph);
+    if (k.wtype == WT_BF16) {
+        if (big_tiles) hipLaunchKernelGGL((conv_gemm16_kernel<__bf16, 2, 2>), grid, dim3(256), 0, stream, k);
+        else hipLaunchKernelGGL((conv_gemm16_kernel<__bf16, 1, 1>), grid, dim3(256), 0, stream, k);
+    } else if (k.wtype == WT_F16) {
+        if (big_tiles) hipLaunchKernelGGL((conv_gemm16_kernel<_Float16, 2, 2>), grid, dim3(256), 0, stream, k);
+        else hipLaunchKernelGGL((conv_gemm16_kernel<_Float16, 1, 1>), grid, dim3(256), 0, stream, k);
+    } else if (big_tiles) hipLaunchKernelGGL((conv_gemm_kernel<2, 2>), grid, dim3(256), 0, stream, k);
+    else hipLaunchKernelGGL((conv_gemm_kernel<1, 1>), grid, dim3(256), 0, stream, k);
     SOAR_LAUNCH_OK("conv_gemm", stream, 0);
+    return 0;
+}
+
+int launch_conv_pack16(const float *w, void *fwd, int Cout, int Cin, int Cinp, int kk, int wtype, hipStream_t stream)
+{
+    if (wtype != WT_BF16 && wtype != WT_F16) { set_error("conv_pack16: wtype must be 1 (bf16) or 2 (f16) (got %d)", wtype); return 1; }
+    const dim3 grid(blocks((int64_t)Cout * kk * Cinp));
+    if (wtype == WT_BF16) hipLaunchKernelGGL(conv_pack16_kernel<__bf16>, grid, dim3(256), 0, stream, w, static_cast<__bf16 *>(fwd), Cout, Cin, Cinp, kk);
+    else hipLaunchKernelGGL(conv_pack16_kernel<_Float16>, grid, dim3(256), 0, stream, w, static_cast<_Float16 *>(fwd), Cout, Cin, Cinp, kk);
+    SOAR_LAUNCH_OK("conv_pack16", stream, 0);
     return 0;
 }
 
@@ -281,10 +489,11 @@ int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, 
 }  // namespace soar
 
 // ---- the launcher and the packer by themselves (tests/test_conv_gemm_*.py) ----
-extern "C" int soar_selftest_conv_gemm(const SoarConvGemmArgs *a, int32_t *tile_out, void *stream_)
+static int selftest_conv_gemm(const char *me, const SoarConvGemmArgs *a, int wtype, int act, int32_t *tile_out, void *stream_)
 {
-    if (!a || !tile_out) { soar::set_error("soar_selftest_conv_gemm: NULL %s", a ? "tile_out" : "args"); return 1; }
+    if (!a || !tile_out) { soar::set_error("%s: NULL %s", me, a ? "tile_out" : "args"); return 1; }
     soar::ConvGemm k{};
+    k.wtype = wtype; k.act = act;
     k.x = a->x; k.ldx = a->ldx; k.xim = a->xim; k.wbat = a->wbat;
     k.bias = a->bias; k.res = a->res; k.y = a->y; k.ldy = a->ldy; k.yim = a->yim; k.alpha = a->alpha;
     k.N = a->N; k.Hg = a->Hg; k.Wg = a->Wg; k.Hin = a->Hin; k.Win = a->Win; k.Cin = a->Cin; k.Cout = a->Cout;
@@ -298,6 +507,35 @@ extern "C" int soar_selftest_conv_gemm(const SoarConvGemmArgs *a, int32_t *tile_
     }
     *tile_out = soar::conv_gemm_tile(k);
     return soar::launch_conv_gemm(k, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int soar_selftest_conv_gemm(const SoarConvGemmArgs *a, int32_t *tile_out, void *stream_)
+{
+    return selftest_conv_gemm("soar_selftest_conv_gemm", a, soar::WT_F32, soar::ACT_NONE, tile_out, stream_);
+}
+
+// the taps' w read as 16-bit values of wtype (1 bf16, 2 f16; anything else is the launcher's refusal)
+extern "C" int soar_selftest_conv_gemm16(const SoarConvGemmArgs *a, int32_t wtype, int32_t *tile_out, void *stream_)
+{
+    if (wtype == soar::WT_F32) { soar::set_error("soar_selftest_conv_gemm16: wtype must be 1 (bf16) or 2 (f16) (got %d)", wtype); return 1; }
+    return selftest_conv_gemm("soar_selftest_conv_gemm16", a, wtype, soar::ACT_NONE, tile_out, stream_);
+}
+
+// SoarConvGemmArgs carries no activation: the descriptor at either operand type (wtype 0 .. 2) with act (0 none, 1 GELU, 2 ReLU)
+extern "C" int soar_selftest_conv_gemm_act(const SoarConvGemmArgs *a, int32_t wtype, int32_t act, int32_t *tile_out, void *stream_)
+{
+    return selftest_conv_gemm("soar_selftest_conv_gemm_act", a, wtype, act, tile_out, stream_);
+}
+
+extern "C" int soar_selftest_conv_pack16(const float *w, void *fwd, int32_t Cout, int32_t Cin, int32_t Cinp, int32_t kk, int32_t wtype,
+                                         void *stream_)
+{
+    if (!w || !fwd || Cout < 1 || Cin < 1 || kk < 1 || Cinp < Cin) {
+        soar::set_error("soar_selftest_conv_pack16: need w, fwd, positive sizes and Cinp >= Cin (Cout=%d, Cin=%d, Cinp=%d, kk=%d)", Cout, Cin,
+                        Cinp, kk);
+        return 1;
+    }
+    return soar::launch_conv_pack16(w, fwd, Cout, Cin, Cinp, kk, wtype, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb,

@@ -8,6 +8,9 @@
 //   the rest               input staging (any strides, channels padded to 8), the sinusoidal embedding, SiLU, GEGLU's product, the
 //                          concatenation with a skip, nearest 2 x up-sampling: plain VALU kernels
 // Every matrix product (convolutions, linear layers) is launch_conv_gemm (conv_gemm.h).  Activations are channels-last [N][H W][C].
+// SoarUnetConfig::precision 1 (bf16) or 2 (f16): the products' weights are packed as 16-bit values and every product runs on the
+// 16-bit matrix core, its A operand rounded on load (conv_gemm16_kernel); everything else, the activations in memory
+// included, stays float32.
 // No atomics; no sum's order depends on the batch: a group's result does not depend on the other groups.
 #include "attention.h"
 #include "layer_norm.h"
@@ -33,6 +36,7 @@ struct Blk {
 struct Repack { int idx, Cout, Cin, Cinp; };
 struct Plan {
     std::vector<size_t> off, n;        // floats: where a tensor starts in the packed buffer (a multiple of 4), how many the source holds
+    std::vector<char> mat;             // the B operand of a gemm() or conv3x3(): laid as 16-bit values where the precision asks for them
     std::vector<Repack> convs;         // the 3 x 3 convolutions
     std::vector<Blk> in, out;
     Blk mid;
@@ -45,35 +49,41 @@ Plan make_plan(const SoarUnetConfig &c)
 {
     Plan P;
     const size_t E = (size_t)4 * c.model_channels, ctx = c.context_dim;
-    auto add = [&](size_t n, size_t packed = 0) {
-        P.off.push_back(P.total); P.n.push_back(n); P.floats += n;
-        P.total += ((packed ? packed : n) + 3) / 4 * 4;
+    // mat: a product's B operand, which a non-zero precision lays as 16-bit values: half the floats, a start still 16-byte aligned
+    auto add = [&](size_t n, size_t packed = 0, bool mat = false) {
+        P.off.push_back(P.total); P.n.push_back(n); P.mat.push_back(mat); P.floats += n;
+        if (!packed) packed = n;
+        if (mat && c.precision) packed = (packed + 1) / 2;
+        P.total += (packed + 3) / 4 * 4;
         return (int)P.off.size() - 1;
     };
+    auto mat = [&](size_t n) { return add(n, 0, true); };
     auto conv3 = [&](int Cout, int Cin, int Cinp) {
-        const int i = add((size_t)Cout * Cin * 9, (size_t)Cout * Cinp * 9);
+        const int i = add((size_t)Cout * Cin * 9, (size_t)Cout * Cinp * 9, true);
         P.convs.push_back({i, Cout, Cin, Cinp});
         add(Cout);
         return i;
     };
     auto res = [&](int cin, int cout) {
-        const int i = add(cin); add(cin); conv3(cout, cin, cin); add((size_t)cout * E); add(cout); add(cout); add(cout); conv3(cout, cout, cout);
-        if (cin != cout) { add((size_t)cout * cin); add(cout); }
+        const int i = add(cin); add(cin); conv3(cout, cin, cin); mat((size_t)cout * E); add(cout); add(cout); add(cout); conv3(cout, cout, cout);
+        if (cin != cout) { mat((size_t)cout * cin); add(cout); }
         return i;
     };
     auto tr = [&](int C) {
         const size_t CC = (size_t)C * C;
-        const int i = add(C); add(C); add(CC); add(C);
-        add(C); add(C); add(CC); add(CC); add(CC); add(CC); add(C);
-        add(C); add(C); add(CC); add(C * ctx); add(C * ctx);
-        if (c.with_ip) { add(C * ctx); add(C * ctx); }
-        add(CC); add(C); add(C); add(C); add(8 * CC); add((size_t)8 * C); add(4 * CC); add(C); add(CC); add(C);
+        // (q | k | v of attn1, k | v of attn2 and of the image tokens are each read as one matrix: C C and C ctx are multiples of 8,
+        // so they lie one behind the other in 16 bits as in 32)
+        const int i = add(C); add(C); mat(CC); add(C);
+        add(C); add(C); mat(CC); mat(CC); mat(CC); mat(CC); add(C);
+        add(C); add(C); mat(CC); mat(C * ctx); mat(C * ctx);
+        if (c.with_ip) { mat(C * ctx); mat(C * ctx); }
+        mat(CC); add(C); add(C); add(C); mat(8 * CC); add((size_t)8 * C); mat(4 * CC); add(C); mat(CC); add(C);
         return i;
     };
     P.tr_tail = c.with_ip ? 18 : 16;
     const int mc = c.model_channels;
-    P.time0 = add(E * mc); add(E); add(E * E); add(E);
-    if (c.camera_dim) { P.cam0 = add(E * c.camera_dim); add(E); add(E * E); add(E); }
+    P.time0 = mat(E * mc); add(E); mat(E * E); add(E);
+    if (c.camera_dim) { P.cam0 = mat(E * c.camera_dim); add(E); mat(E * E); add(E); }
     std::vector<int> chans;
     Blk b0;
     b0.cin = c.in_channels; b0.cout = mc; b0.conv = conv3(mc, c.in_channels, CIN0);
@@ -122,7 +132,8 @@ bool check_cfg(const SoarUnetConfig *cp, const char *me)
     bool ok = c.in_channels >= 1 && c.in_channels <= CIN0 && c.out_channels >= 1 && c.out_channels <= 4096 && c.model_channels >= 32 &&
               c.model_channels <= 4096 && c.levels >= 1 && c.levels <= SOAR_UNET_MAX_LEVELS && c.num_res_blocks >= 1 && c.num_res_blocks <= 8 &&
               c.context_dim >= 8 && c.context_dim % 8 == 0 && c.camera_dim >= 0 && c.camera_dim % 8 == 0 && c.head_channels >= 4 &&
-              c.head_channels <= 64 && c.head_channels % 4 == 0 && c.n_view >= 1 && c.n_view <= 64;
+              c.head_channels <= 64 && c.head_channels % 4 == 0 && c.n_view >= 1 && c.n_view <= 64 && c.precision >= WT_F32 &&
+              c.precision <= WT_F16;
     for (int l = 0; ok && l < c.levels; l++) {
         const int64_t ch = (int64_t)c.model_channels * c.channel_mult[l];
         ok = c.channel_mult[l] >= 1 && ch <= 8192 && ch % GN_GROUPS == 0 && ch % c.head_channels == 0;
@@ -130,8 +141,8 @@ bool check_cfg(const SoarUnetConfig *cp, const char *me)
     if (!ok)
         set_error("%s: a configuration the kernels cannot run (in %d <= 8, out %d, model_channels=%d, %d levels, %d ResBlocks a level, "
                   "context_dim=%d, camera_dim=%d: multiples of 8, head_channels=%d: a multiple of 4 up to 64, n_view=%d; every level's "
-                  "width a multiple of 32 and of head_channels)", me, c.in_channels, c.out_channels, c.model_channels, c.levels,
-                  c.num_res_blocks, c.context_dim, c.camera_dim, c.head_channels, c.n_view);
+                  "width a multiple of 32 and of head_channels; precision=%d: 0 f32, 1 bf16 or 2 f16)", me, c.in_channels, c.out_channels,
+                  c.model_channels, c.levels, c.num_res_blocks, c.context_dim, c.camera_dim, c.head_channels, c.n_view, c.precision);
     return ok;
 }
 
@@ -153,10 +164,12 @@ bool check_sizes(const SoarUnetConfig &c, int N, int H, int W, int T, int n_ip, 
 }
 
 // ---- plain matrix product through the shared kernel: y [M][N] = x [M][K] w[N][K]^T + bias + res ------------------------------------
+// (wtype: what w holds, WT_*; w's 16-bit values lie behind the float pointer)
 int gemm(const float *x, int64_t ldx, const float *w, int K, int N, const float *bias, const float *res, float *y, int64_t ldy, int64_t M,
-         hipStream_t stream)
+         int wtype, hipStream_t stream)
 {
     ConvGemm k{};
+    k.wtype = wtype;
     k.x = x; k.ldx = ldx; k.bias = bias; k.res = res; k.y = y; k.ldy = ldy; k.alpha = 1.f;
     k.N = 1; k.Hg = 1; k.Wg = (int)M; k.Hin = 1; k.Win = (int)M; k.Cin = K; k.Cout = N; k.stride = 1; k.dil = 1; k.Wout = (int)M; k.os = 1;
     k.nph = 1;
@@ -171,11 +184,13 @@ int gemm(const float *x, int64_t ldx, const float *w, int K, int N, const float 
 constexpr int SPLIT_PIXELS = 64;
 int conv_sum3(const float *part, const float *bias, const float *res, float *y, int N, int Ho, int Wo, int Cout, hipStream_t stream);
 int conv3x3(const float *x, int Cin, const float *w, const float *bias, const float *res, float *y, int Cout, int N, int H, int W, int stride,
-            float *part, hipStream_t stream)
+            float *part, int wtype, hipStream_t stream)
 {
     const int Ho = H / stride, Wo = W / stride;
     const bool split = Ho * Wo <= SPLIT_PIXELS && Cout % 4 == 0;
+    const int wsz = wtype ? 2 : 4;                               // bytes of an element of w
     ConvGemm k{};
+    k.wtype = wtype;
     k.x = x; k.ldx = Cin; k.xim = (int64_t)H * W; k.alpha = 1.f;
     k.N = N; k.Hg = Ho; k.Wg = Wo; k.Hin = H; k.Win = W; k.Cin = Cin; k.Cout = Cout; k.stride = stride; k.dil = 1;
     if (!split) {
@@ -186,7 +201,8 @@ int conv3x3(const float *x, int Cin, const float *w, const float *bias, const fl
     k.y = part; k.ldy = Cout; k.yim = (int64_t)4 * Ho * Wo; k.Wout = 2 * Wo; k.os = 2; k.nph = 3;
     for (int r = 0; r < 3; r++) {                                // kernel row r: taps 3 r .. 3 r + 2, to parity (r >> 1, r & 1)
         ConvTaps &t = k.ph[r];
-        t.w = w + (size_t)3 * r * Cin; t.ldw = (int64_t)9 * Cin; t.ntaps = 3; t.py = r >> 1; t.px = r & 1;
+        t.w = reinterpret_cast<const float *>(reinterpret_cast<const char *>(w) + (size_t)3 * r * Cin * wsz);
+        t.ldw = (int64_t)9 * Cin; t.ntaps = 3; t.py = r >> 1; t.px = r & 1;
         for (int j = 0; j < 3; j++) { t.dy[j] = (signed char)(r - 1); t.dx[j] = (signed char)(j - 1); }
     }
     if (launch_conv_gemm(k, stream)) return 1;
@@ -419,6 +435,17 @@ int soar_unet_pack_weights(const SoarUnetConfig *cfg, const float *const *tensor
     for (size_t j = 0; j < P.convs.size(); j++) conv_of[P.convs[j].idx] = (int)j;
     for (int i = 0; i < count; i++) {
         float *dst = base + P.off[i];
+        if (cfg->precision && P.mat[i]) {                        // a product's B operand: 16-bit, a linear layer's matrix as one long row
+            int rc;
+            if (conv_of[i] >= 0) {
+                const Repack &r = P.convs[conv_of[i]];
+                rc = launch_conv_pack16(tensors[i], dst, r.Cout, r.Cin, r.Cinp, 9, cfg->precision, stream);
+            } else {
+                rc = launch_conv_pack16(tensors[i], dst, 1, (int)P.n[i], (int)P.n[i], 1, cfg->precision, stream);
+            }
+            if (rc) return 1;
+            continue;
+        }
         if (conv_of[i] >= 0) {
             const Repack &r = P.convs[conv_of[i]];
             hipLaunchKernelGGL(unet_pack_pad_kernel, dim3(blocks((int64_t)r.Cout * 9 * r.Cinp)), dim3(256), 0, stream, tensors[i], dst, r.Cout, r.Cin, r.Cinp, 9);
@@ -466,7 +493,7 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
     auto Wt = [&](int i) { return base + P.off[i]; };
     Ws w;
     carve(c, P, a.N, a.H, a.W, a.T, a.n_ip, workspace, &w);
-    const int N = a.N, mc = c.model_channels, E = 4 * mc, ctx = c.context_dim;
+    const int N = a.N, mc = c.model_channels, E = 4 * mc, ctx = c.context_dim, wt = c.precision;
 
     auto probe = [&](int code, const float *src, size_t floats) -> int {
         for (int i = 0; i < a.n_probes; i++)
@@ -490,13 +517,13 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
     // ---- the embedding
     hipLaunchKernelGGL(unet_time_kernel, dim3(blocks((int64_t)N * mc)), dim3(256), 0, stream, a.t, w.temb, N, mc / 2);
     SOAR_LAUNCH_OK("unet_time", stream, 0);
-    if (gemm(w.temb, mc, Wt(P.time0), mc, E, Wt(P.time0 + 1), nullptr, w.e1, E, N, stream)) return 1;
+    if (gemm(w.temb, mc, Wt(P.time0), mc, E, Wt(P.time0 + 1), nullptr, w.e1, E, N, wt, stream)) return 1;
     if (silu_of(w.e1, w.e1, (int64_t)N * E)) return 1;
-    if (gemm(w.e1, E, Wt(P.time0 + 2), E, E, Wt(P.time0 + 3), nullptr, w.emb, E, N, stream)) return 1;
+    if (gemm(w.e1, E, Wt(P.time0 + 2), E, E, Wt(P.time0 + 3), nullptr, w.emb, E, N, wt, stream)) return 1;
     if (a.camera) {
-        if (gemm(a.camera, c.camera_dim, Wt(P.cam0), c.camera_dim, E, Wt(P.cam0 + 1), nullptr, w.e1, E, N, stream)) return 1;
+        if (gemm(a.camera, c.camera_dim, Wt(P.cam0), c.camera_dim, E, Wt(P.cam0 + 1), nullptr, w.e1, E, N, wt, stream)) return 1;
         if (silu_of(w.e1, w.e1, (int64_t)N * E)) return 1;
-        if (gemm(w.e1, E, Wt(P.cam0 + 2), E, E, Wt(P.cam0 + 3), w.emb, w.emb, E, N, stream)) return 1;
+        if (gemm(w.e1, E, Wt(P.cam0 + 2), E, E, Wt(P.cam0 + 3), w.emb, w.emb, E, N, wt, stream)) return 1;
     }
     if (probe(SOAR_UNET_PROBE_EMB, w.emb, (size_t)N * E)) return 1;
     if (silu_of(w.emb, w.semb, (int64_t)N * E)) return 1;
@@ -505,15 +532,15 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
     auto res_block = [&](int t0, const float *x, int cin, int cout, int H, int W, float *y) -> int {
         const int64_t hw = (int64_t)H * W;
         if (group_norm(x, nullptr, hw, cin, Wt(t0), Wt(t0 + 1), 1e-5f, 1, w.tmp)) return 1;
-        if (conv3x3(w.tmp, cin, Wt(t0 + 2), Wt(t0 + 3), nullptr, w.h1, cout, N, H, W, 1, w.part, stream)) return 1;
-        if (gemm(w.semb, E, Wt(t0 + 4), E, cout, Wt(t0 + 5), nullptr, w.eo, cout, N, stream)) return 1;
+        if (conv3x3(w.tmp, cin, Wt(t0 + 2), Wt(t0 + 3), nullptr, w.h1, cout, N, H, W, 1, w.part, wt, stream)) return 1;
+        if (gemm(w.semb, E, Wt(t0 + 4), E, cout, Wt(t0 + 5), nullptr, w.eo, cout, N, wt, stream)) return 1;
         if (group_norm(w.h1, w.eo, hw, cout, Wt(t0 + 6), Wt(t0 + 7), 1e-5f, 1, w.tmp)) return 1;
         const float *skip = x;
         if (cin != cout) {
-            if (gemm(x, cin, Wt(t0 + 10), cin, cout, Wt(t0 + 11), nullptr, y, cout, (int64_t)N * hw, stream)) return 1;
+            if (gemm(x, cin, Wt(t0 + 10), cin, cout, Wt(t0 + 11), nullptr, y, cout, (int64_t)N * hw, wt, stream)) return 1;
             skip = y;
         }
-        return conv3x3(w.tmp, cout, Wt(t0 + 8), Wt(t0 + 9), skip, y, cout, N, H, W, 1, w.part, stream);
+        return conv3x3(w.tmp, cout, Wt(t0 + 8), Wt(t0 + 9), skip, y, cout, N, H, W, 1, w.part, wt, stream);
     };
     // in place on x [N][H W][C]
     auto transformer = [&](int t0, float *x, int C, int H, int W, int code) -> int {
@@ -521,40 +548,40 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
         const int heads = C / c.head_channels, hd = c.head_channels, o = t0 + P.tr_tail;
         const float scale = 1.f / sqrtf((float)hd);
         if (group_norm(x, nullptr, hw, C, Wt(t0), Wt(t0 + 1), 1e-6f, 0, w.tmp)) return 1;
-        if (gemm(w.tmp, C, Wt(t0 + 2), C, C, Wt(t0 + 3), nullptr, w.tx, C, M, stream)) return 1;
+        if (gemm(w.tmp, C, Wt(t0 + 2), C, C, Wt(t0 + 3), nullptr, w.tx, C, M, wt, stream)) return 1;
         // attn1 over the tokens of all the views of a group: q | k | v from the three weights, which lie one behind the other
         if (layer_norm(w.tx, Wt(t0 + 4), Wt(t0 + 5), w.tn, M, C, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.tn, C, Wt(t0 + 6), C, 3 * C, nullptr, nullptr, w.qkv, 3 * C, M, stream)) return 1;
+        if (gemm(w.tn, C, Wt(t0 + 6), C, 3 * C, nullptr, nullptr, w.qkv, 3 * C, M, wt, stream)) return 1;
         SoarUnetAttnArgs s{};
         s.q = w.qkv; s.k = w.qkv + C; s.v = w.qkv + 2 * C; s.out = w.ao;
         s.ldq = s.ldk = s.ldv = 3 * C; s.ldo = C;
         s.B = N / c.n_view; s.Lq = s.Lk = (int)(c.n_view * hw); s.heads = heads; s.hd = hd; s.scale = scale;
         if (launch_kv_attention(s, stream)) return 1;
-        if (gemm(w.ao, C, Wt(t0 + 9), C, C, Wt(t0 + 10), w.tx, w.tx, C, M, stream)) return 1;
+        if (gemm(w.ao, C, Wt(t0 + 9), C, C, Wt(t0 + 10), w.tx, w.tx, C, M, wt, stream)) return 1;
         if (probe(code + 1, w.tx, (size_t)M * C)) return 1;
         // attn2 per view: the text tokens, and the image tokens as a second key set
         if (layer_norm(w.tx, Wt(t0 + 11), Wt(t0 + 12), w.tn, M, C, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.tn, C, Wt(t0 + 13), C, C, nullptr, nullptr, w.qkv, C, M, stream)) return 1;
-        if (gemm(a.context, ctx, Wt(t0 + 14), ctx, 2 * C, nullptr, nullptr, w.kv, 2 * C, (int64_t)N * a.T, stream)) return 1;
+        if (gemm(w.tn, C, Wt(t0 + 13), C, C, nullptr, nullptr, w.qkv, C, M, wt, stream)) return 1;
+        if (gemm(a.context, ctx, Wt(t0 + 14), ctx, 2 * C, nullptr, nullptr, w.kv, 2 * C, (int64_t)N * a.T, wt, stream)) return 1;
         SoarUnetAttnArgs x2{};
         x2.q = w.qkv; x2.k = w.kv; x2.v = w.kv + C; x2.out = w.ao;
         x2.ldq = C; x2.ldk = x2.ldv = 2 * C; x2.ldo = C;
         x2.B = N; x2.Lq = (int)hw; x2.Lk = a.T; x2.heads = heads; x2.hd = hd; x2.scale = scale;
         if (a.ip_tokens) {
-            if (gemm(a.ip_tokens, ctx, Wt(t0 + 16), ctx, 2 * C, nullptr, nullptr, w.kvip, 2 * C, (int64_t)N * a.n_ip, stream)) return 1;
+            if (gemm(a.ip_tokens, ctx, Wt(t0 + 16), ctx, 2 * C, nullptr, nullptr, w.kvip, 2 * C, (int64_t)N * a.n_ip, wt, stream)) return 1;
             x2.k2 = w.kvip; x2.v2 = w.kvip + C; x2.ldk2 = x2.ldv2 = 2 * C; x2.Lk2 = a.n_ip; x2.w2 = a.ip_weight;
         }
         if (launch_kv_attention(x2, stream)) return 1;
-        if (gemm(w.ao, C, Wt(o), C, C, Wt(o + 1), w.tx, w.tx, C, M, stream)) return 1;
+        if (gemm(w.ao, C, Wt(o), C, C, Wt(o + 1), w.tx, w.tx, C, M, wt, stream)) return 1;
         if (probe(code + 2, w.tx, (size_t)M * C)) return 1;
         // GEGLU feed-forward
         if (layer_norm(w.tx, Wt(o + 2), Wt(o + 3), w.tn, M, C, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.tn, C, Wt(o + 4), C, 8 * C, Wt(o + 5), nullptr, w.ff, 8 * C, M, stream)) return 1;
+        if (gemm(w.tn, C, Wt(o + 4), C, 8 * C, Wt(o + 5), nullptr, w.ff, 8 * C, M, wt, stream)) return 1;
         hipLaunchKernelGGL(unet_geglu_kernel, dim3(blocks(M * 4 * C)), dim3(256), 0, stream, w.ff, w.gg, M * 4 * C, 4 * C);
         SOAR_LAUNCH_OK("unet_geglu", stream, 0);
-        if (gemm(w.gg, 4 * C, Wt(o + 6), 4 * C, C, Wt(o + 7), w.tx, w.tx, C, M, stream)) return 1;
+        if (gemm(w.gg, 4 * C, Wt(o + 6), 4 * C, C, Wt(o + 7), w.tx, w.tx, C, M, wt, stream)) return 1;
         if (probe(code + 3, w.tx, (size_t)M * C)) return 1;
-        if (gemm(w.tx, C, Wt(o + 8), C, C, Wt(o + 9), x, x, C, M, stream)) return 1;
+        if (gemm(w.tx, C, Wt(o + 8), C, C, Wt(o + 9), x, x, C, M, wt, stream)) return 1;
         return probe(code + 4, x, (size_t)M * C);
     };
 
@@ -573,9 +600,9 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
         float *y = w.skips[bi];
         size_t floats = (size_t)N * H * W * b.cout;
         if (bi == 0) {
-            if (conv3x3(w.x0, CIN0, Wt(b.conv), Wt(b.conv + 1), nullptr, y, b.cout, N, H, W, 1, w.part, stream)) return 1;
+            if (conv3x3(w.x0, CIN0, Wt(b.conv), Wt(b.conv + 1), nullptr, y, b.cout, N, H, W, 1, w.part, wt, stream)) return 1;
         } else if (b.down) {
-            if (conv3x3(cur, b.cin, Wt(b.conv), Wt(b.conv + 1), nullptr, y, b.cout, N, H, W, 2, w.part, stream)) return 1;
+            if (conv3x3(cur, b.cin, Wt(b.conv), Wt(b.conv + 1), nullptr, y, b.cout, N, H, W, 2, w.part, wt, stream)) return 1;
             floats /= 4;
         } else {
             if (res_block(b.res, cur, b.cin, b.cout, H, W, y)) return 1;
@@ -619,7 +646,7 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
             hipLaunchKernelGGL(unet_up_kernel, dim3(blocks(total4)), dim3(256), 0, stream, cur, w.up, total4, H, W, b.cout);
             SOAR_LAUNCH_OK("unet_up", stream, 0);
             y = w.act[flip];
-            if (conv3x3(w.up, b.cout, Wt(b.conv), Wt(b.conv + 1), nullptr, y, b.cout, N, 2 * H, 2 * W, 1, w.part, stream)) return 1;
+            if (conv3x3(w.up, b.cout, Wt(b.conv), Wt(b.conv + 1), nullptr, y, b.cout, N, 2 * H, 2 * W, 1, w.part, wt, stream)) return 1;
             if (probe(code + 5, y, (size_t)rows * 4 * b.cout)) return 1;
             cur = y;
             flip ^= 1;
@@ -627,7 +654,7 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
     }
     // ---- out
     if (group_norm(cur, nullptr, (int64_t)a.H * a.W, mc * c.channel_mult[0], Wt(P.out0), Wt(P.out0 + 1), 1e-5f, 1, w.tmp)) return 1;
-    return conv3x3(w.tmp, mc * c.channel_mult[0], Wt(P.out0 + 2), Wt(P.out0 + 3), nullptr, a.eps, c.out_channels, N, a.H, a.W, 1, w.part, stream);
+    return conv3x3(w.tmp, mc * c.channel_mult[0], Wt(P.out0 + 2), Wt(P.out0 + 3), nullptr, a.eps, c.out_channels, N, a.H, a.W, 1, w.part, wt, stream);
 }
 
 int soar_unet_attention(const SoarUnetAttnArgs *args, void *stream_)

@@ -330,7 +330,7 @@ class SoarUnetConfig(C.Structure):
     """Mirror of ``struct SoarUnetConfig`` (include/soar_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("in_channels", "out_channels", "model_channels", "levels", "num_res_blocks")] + \
                [("channel_mult", C.c_int32 * UNET_MAX_LEVELS), ("attention", C.c_int32 * UNET_MAX_LEVELS)] + \
-               [(n, C.c_int32) for n in ("context_dim", "camera_dim", "with_ip", "head_channels", "n_view")]
+               [(n, C.c_int32) for n in ("context_dim", "camera_dim", "with_ip", "head_channels", "n_view", "precision")]
 
 
 class SoarUnetArgs(C.Structure):
@@ -472,6 +472,9 @@ SIGNATURES = {
     "soar_selftest_affine_scan": (C.c_int, [_vp, _vp, _vp, _vp]),
     "soar_selftest_conv_gemm": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.POINTER(C.c_int32), _vp]),
     "soar_selftest_conv_pack": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp]),
+    "soar_selftest_conv_gemm16": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.POINTER(C.c_int32), _vp]),
+    "soar_selftest_conv_pack16": (C.c_int, [_vp, _vp] + [C.c_int32] * 5 + [_vp]),
+    "soar_selftest_conv_gemm_act": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.c_int32, C.POINTER(C.c_int32), _vp]),
     "soar_prof_enable": (C.c_int, [C.c_int]),
     "soar_prof_reset": (C.c_int, []),
     "soar_prof_stage_count": (C.c_int, []),

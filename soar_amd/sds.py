@@ -342,7 +342,10 @@ class MultiviewGuidance(nn.Module):
     ``text_embeddings [2, T, ctx]``: the prompt's and the unconditional prompt's CLIP text tokens (the caller's encoder); a row is
     repeated for every view of its half.  ``image_tokens(ref_rgb) -> (cond [ip_dim, ctx], uncond [ip_dim, ctx])``: the caller's CLIP
     image encoder and ``Resampler``; None: no image tokens are used, whatever ``ref_rgb`` is.  The cameras ``c2w [B, 4, 4]`` are
-    normalised (``soar_amd.unet.normalize_camera``) and repeated for both halves.  Further arguments are ``MultiviewSDS``'s."""
+    normalised (``soar_amd.unet.normalize_camera``) and repeated for both halves.  Further arguments are ``MultiviewSDS``'s.
+
+    ``unet`` may be a ``MultiviewUNet(..., precision="bf16")`` or ``"f16"`` (the reference's ``half_precision_weights``): its inputs
+    and ``eps`` are float32 either way, so nothing here changes (tests/test_unet_half_gpu.py runs it with a bf16 UNet)."""
 
     def __init__(self, encoder: LatentEncoder, unet, text_embeddings: torch.Tensor, image_tokens: Optional[Callable] = None, **sds_args):
         super().__init__()

@@ -1,5 +1,6 @@
 """The multi-view diffusion UNet of the SDS guidance on HIP kernels (csrc/unet.hip, csrc/attention.h): ImageDream's
-``sd-v2.1-base-4view-ipmv`` denoiser, forward only, in float32.
+``sd-v2.1-base-4view-ipmv`` denoiser, forward only, in float32 or -- ``precision="bf16"`` / ``"f16"`` -- with every matrix product
+on the 16-bit matrix core.
 
 ``MultiviewUNet(state_dict)`` takes ldm's ``openaimodel.UNetModel`` keys with MVDream's / ImageDream's additions (``camera_embed.*``,
 ``attn2.to_k_ip`` / ``to_v_ip``), with or without the prefix ``model.diffusion_model.``; other keys (the VAE, CLIP, ``image_embed.*``)
@@ -26,6 +27,8 @@ from .hip_lib import _bytes, _stream, _workspace, check
 PREFIX = "model.diffusion_model."
 # stages of a block a probe can name (include/soar_hip.h SoarUnetArgs)
 STAGES = {"res": 0, "attn1": 1, "attn2": 2, "ff": 3, "transformer": 4, "up": 5, "cat": 6, "res2": 7}
+# the operands of the matrix products (SoarUnetConfig.precision)
+PRECISIONS = {"f32": 0, "bf16": 1, "f16": 2}
 
 
 def _shape(sd, key: str, ndim: int) -> Tuple[int, ...]:
@@ -158,11 +161,19 @@ def normalize_camera(c2w: torch.Tensor) -> torch.Tensor:
 class MultiviewUNet(nn.Module):
     """The UNet in eval mode from its state dict.  The weights are one frozen flat float32 buffer (``weights``, the tensors of
     ``tensor_keys`` one behind the other; move the module with ``.to(device)``), packed for the kernels once per device on first use.
-    ``num_head_channels``, ``ip_dim`` (image tokens), ``ip_weight`` and ``n_view`` are what no shape shows."""
+    ``num_head_channels``, ``ip_dim`` (image tokens), ``ip_weight`` and ``n_view`` are what no shape shows.
+
+    ``precision``: ``"f32"`` (the default), ``"bf16"`` or ``"f16"``.  With a 16-bit precision the packed copy holds the convolutions'
+    and linear layers' weights rounded to that type and every product rounds its activations to it as they are loaded, accumulating
+    in float32; ``weights``, the activations in memory, the norms, the attention, inputs, outputs and probes stay float32, and what
+    the float32 path promises bit for bit (equal runs, groups independent of the batch, any strides of ``x``) holds as well."""
 
     def __init__(self, state_dict: Mapping[str, torch.Tensor], num_head_channels: int = 64, ip_dim: int = 16, ip_weight: float = 1.0,
-                 n_view: int = 4):
+                 n_view: int = 4, precision: str = "f32"):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError(f"MultiviewUNet: precision must be one of 'f32', 'bf16', 'f16' (got {precision!r})")
+        self.precision = precision
         sd = strip_prefix(state_dict)
         cfg = infer_config(sd)
         cfg.update(num_head_channels=int(num_head_channels), ip_dim=int(ip_dim), ip_weight=float(ip_weight), n_view=int(n_view))
@@ -184,7 +195,7 @@ class MultiviewUNet(nn.Module):
         for l, (m, a) in enumerate(zip(cfg["channel_mult"], cfg["attention"])):
             c.channel_mult[l], c.attention[l] = m, int(a)
         c.context_dim, c.camera_dim, c.with_ip = cfg["context_dim"], cfg["camera_dim"], int(cfg["with_ip"])
-        c.head_channels, c.n_view = cfg["num_head_channels"], cfg["n_view"]
+        c.head_channels, c.n_view, c.precision = cfg["num_head_channels"], cfg["n_view"], PRECISIONS[precision]
         nb, cnt, nf = C.c_size_t(0), C.c_int32(0), C.c_size_t(0)
         check(hip_lib.lib().soar_unet_weights_bytes(C.byref(c), C.byref(nb), C.byref(cnt), C.byref(nf)), "soar_unet_weights_bytes")
         self._sizes = [int(np.prod(shape)) for _, shape in keys]
