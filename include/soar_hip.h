@@ -1985,7 +1985,7 @@ int soar_sam_postprocess(int32_t B, int32_t K, int32_t L, int32_t image_size, in
 int soar_sam_attention(const float *qkv, const float *bias, const float *rel_h, const float *rel_w, float *out, int32_t B, int32_t gh,
                        int32_t gw, int32_t heads, int32_t hd, int32_t window, float scale, void *stream);
 
-/* ---- The multi-view diffusion UNet of the SDS guidance, forward only, float32 (unet.hip, attention.h, soar_amd/unet.py) ----
+/* ---- The multi-view diffusion UNet of the SDS guidance, forward only, float32 (unet.hip, attention.hip, soar_amd/unet.py) ----
  * ldm's openaimodel.UNetModel with MVDream's / ImageDream's additions (camera embedding, self-attention over the views of a group,
  * image-token cross-attention), transformer depth 1, linear proj_in / proj_out.  The sizes are what soar_amd/unet.py reads from a
  * state dict.  model_channels times every multiplier is a multiple of 32 (GroupNorm) and of head_channels; context_dim, camera_dim
@@ -2049,7 +2049,7 @@ typedef struct SoarUnetAttnArgs {
 } SoarUnetAttnArgs;
 int soar_unet_attention(const SoarUnetAttnArgs *args, void *stream);
 
-/* ---- The SDS guidance's conditioning, forward only, float32 (clip.hip, attention.h, soar_amd/clip.py) ----
+/* ---- The SDS guidance's conditioning, forward only, float32 (clip.hip, attention.hip, soar_amd/clip.py) ----
  * One pre-LN transformer tower serves CLIP's text encoder (causal mask; token + position embedding in front) and its ViT image
  * encoder (patch product, class token, position embedding and ln_pre in front): x += out_proj(attn(ln_1 x)); x += c_proj(gelu_erf(
  * c_fc(ln_2 x))), LayerNorm eps 1e-5, scale head_dim^-0.5.  width and mlp are multiples of 8, head_dim = width / heads a multiple of

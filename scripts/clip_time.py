@@ -1,4 +1,4 @@
-"""Time the SDS guidance's conditioning (soar_amd/clip.py, csrc/clip.hip, csrc/attention.h) at the shipped shapes with seeded random
+"""Time the SDS guidance's conditioning (soar_amd/clip.py, csrc/clip.hip, csrc/attention.hip) at the shipped shapes with seeded random
 weights (no checkpoint needed) against the same networks composed from torch-float32 operations (tests/clip_ref.py, its attention
 replaced by ``F.scaled_dot_product_attention``) on the same GPU -> profiles/clip_time.json.
 

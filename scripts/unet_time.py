@@ -1,4 +1,4 @@
-"""Time the multi-view diffusion UNet (soar_amd/unet.py, csrc/unet.hip, csrc/attention.h) at the shipped model's shapes with seeded
+"""Time the multi-view diffusion UNet (soar_amd/unet.py, csrc/unet.hip, csrc/attention.hip) at the shipped model's shapes with seeded
 random weights (no checkpoint needed): N = 8 latents of 32 x 32 (text and unconditional halves of 4 views), 77 text and 16 image
 tokens, against the same network composed from torch-float32 operations (tests/unet_ref.py) on the same GPU -> profiles/unet_time.json.
 

@@ -78,7 +78,7 @@ EXTRA_FLAGS = {
 SOURCES = ["api.hip", "rast_preprocess.hip", "rast_binning.hip", "rast_tilebin.hip", "rast_blockmask.hip", "rast_render_fwd.hip", "rast_render_bwd.hip",
            "rast_geom_bwd.hip", "lbs.hip", "lbs_knn.hip", "frame_loss.hip", "postops.hip", "ssim.hip", "image_losses.hip", "smplx_joints.hip", "densify.hip", "optim.hip", "view.hip",
            "mesh.hip", "mesh_simplify.hip", "mesh_attr.hip", "mesh_holes.hip", "mesh_texture.hip", "field.hip", "envmap.hip", "conv_gemm.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip", "playback.hip",
-           "normalnet.hip", "normal_io.hip", "smplify.hip", "prior.hip", "masks.hip", "step_terms.hip", "fitviz.hip", "video.hip", "png.hip", "png_decode.hip", "jpeg_decode.hip", "image_resize.hip", "sam.hip", "unet.hip", "clip.hip"]
+           "normalnet.hip", "normal_io.hip", "smplify.hip", "prior.hip", "masks.hip", "step_terms.hip", "fitviz.hip", "video.hip", "png.hip", "png_decode.hip", "jpeg_decode.hip", "image_resize.hip", "attention.hip", "sam.hip", "unet.hip", "clip.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(_HERE, "..", "include", "soar_hip.h")]
 
 

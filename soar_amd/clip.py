@@ -1,4 +1,4 @@
-"""The SDS guidance's conditioning on HIP kernels (csrc/clip.hip, csrc/attention.h): CLIP's text encoder, its ViT image
+"""The SDS guidance's conditioning on HIP kernels (csrc/clip.hip, csrc/attention.hip): CLIP's text encoder, its ViT image
 encoder and IP-Adapter's image-token ``Resampler`` as ImageDream ships them, forward only, in float32.
 
 ``ClipTextEncoder(state_dict)`` and ``ClipImageEncoder(state_dict)`` take transformers' or open_clip's keys (detected from the keys, under
@@ -449,7 +449,7 @@ class ImageTokens(nn.Module):
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None, causal: bool = False) -> torch.Tensor:
-    """The towers' attention kernel by itself (csrc/attention.h): q ``[B, Lq, heads hd]``, k, v ``[B, Lk, heads hd]`` (rows may be views
+    """The towers' attention kernel by itself (csrc/attention.hip): q ``[B, Lq, heads hd]``, k, v ``[B, Lk, heads hd]`` (rows may be views
     into wider rows: the last axis contiguous, pitches multiples of 4), hd a multiple of 4 up to 96 -> ``softmax(scale q k^T) v`` per
     head; ``causal``: key j counts for query i when j <= i."""
     for t in (q, k, v):

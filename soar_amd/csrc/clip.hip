@@ -1,20 +1,19 @@
 // clip.hip -- the SDS guidance's conditioning, forward only, float32 (soar_amd/clip.py): the CLIP text and image
 // encoders (one pre-LN transformer tower, causal for text) and IP-Adapter's image-token Resampler.
 //
-//   kv_attn_kernel         (attention.h) the towers' self-attention -- causal for text, head dimension up to 96 -- and the Resampler's
+//   kv_attn_kernel         (attention.hip) the towers' self-attention -- causal for text, head dimension up to 96 -- and the Resampler's
 //                          attention of a few queries over n + n_q keys
 //   ln_rows_kernel         (layer_norm.h)
 //   clip_embed_kernel      token embedding gather + position embedding
 //   clip_patches_kernel    bytes -> (x / 255 - mean) / std, unfolded into the patch product's rows (K = 3 p^2 padded to a multiple of 8)
 //   clip_class_pos_kernel  the class row and the position embedding, in place on the tokens
 //   clip_repeat_kernel     the Resampler's latents, once per batch entry
-// Every linear layer is launch_conv_gemm (conv_gemm.h): bias, the erf GELU and the residual are its epilogue.  Tokens are
+// Every linear layer is launch_conv_gemm (conv_gemm.h: gemm()): bias, the erf GELU and the residual are its epilogue.  Tokens are
 // [B][L][width].  No atomics; nothing depends on the batch: a sequence's result is the same bits alone and in any batch.
 #include "attention.h"
 #include "layer_norm.h"
+#include "net_weights.h"
 #include "workspace.h"
-
-#include <vector>
 
 namespace soar {
 namespace {
@@ -24,17 +23,9 @@ constexpr int BLOCK_TENSORS = 12;      // ln_1 w b, in_proj w b, out_proj w b, l
 constexpr int LAYER_TENSORS = 11;      // norm1 w b, norm2 w b, to_q, to_kv, to_out, ff norm w b, ff in, ff out
 
 // ---- where the tensors lie in the packed buffer --------------------------------------------------------------------------------------
-struct Plan {
-    std::vector<size_t> off, n;        // floats: where a tensor starts (a multiple of 4), how many the source holds
-    size_t total = 0, floats = 0;
+struct Plan : WeightPlan {
     int pad_idx = -1, pad_rows = 0, pad_k = 0, pad_kp = 0;     // the patch convolution: rows of pad_k floats laid pad_kp apart
     int tok = 0, pos = 0, cls = -1, pre = -1, blocks = 0, fin = 0;
-    int add(size_t count, size_t packed = 0)
-    {
-        off.push_back(total); n.push_back(count); floats += count;
-        total += ((packed ? packed : count) + 3) / 4 * 4;
-        return (int)off.size() - 1;
-    }
 };
 
 int patch_k(const SoarClipConfig &c) { return 3 * c.patch * c.patch; }
@@ -127,20 +118,10 @@ bool check_resampler(const SoarResamplerConfig *cp, const char *me)
     return true;
 }
 
-// ---- y [N][rows][Cout] = act(alpha x [N][rows][K] w[Cout][K]^T + bias) + res: image n's rows at x + n xim ldx and y + n yim ldy -----
-int gemm(const float *x, int64_t ldx, const float *w, int K, int Cout, const float *bias, const float *res, float *y, int64_t ldy, int N, int rows,
-         int64_t xim, int64_t yim, int act, float alpha, hipStream_t stream)
-{
-    ConvGemm k{};
-    k.x = x; k.ldx = ldx; k.xim = xim; k.bias = bias; k.res = res; k.y = y; k.ldy = ldy; k.yim = yim; k.alpha = alpha;
-    k.N = N; k.Hg = 1; k.Wg = rows; k.Hin = 1; k.Win = rows; k.Cin = K; k.Cout = Cout; k.stride = 1; k.dil = 1; k.Wout = rows; k.os = 1;
-    k.nph = 1; k.act = act;
-    square_taps(k.ph[0], w, K, 1, 0);
-    return launch_conv_gemm(k, stream);
-}
+// a linear layer on contiguous rows: y [M][Cout] = act(x [M][K] w[Cout][K]^T + bias) + res
 int linear(const float *x, const float *w, int K, int Cout, const float *bias, const float *res, float *y, int64_t M, int act, hipStream_t stream)
 {
-    return gemm(x, K, w, K, Cout, bias, res, y, Cout, 1, (int)M, 0, 0, act, 1.f, stream);
+    return gemm(x, K, w, K, Cout, bias, res, y, Cout, M, stream, act);
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------------------
@@ -196,34 +177,21 @@ int attention(const float *q, const float *k, const float *v, float *out, int64_
     SoarUnetAttnArgs s{};
     s.q = q; s.k = k; s.v = v; s.out = out; s.ldq = ldq; s.ldk = ldk; s.ldv = ldv; s.ldo = ldo;
     s.B = B; s.Lq = Lq; s.Lk = Lk; s.heads = heads; s.hd = hd; s.scale = scale;
-    return launch_kv_attention<true>(s, stream, causal, me);
+    return launch_kv_attention(s, 96, causal, me, stream);
 }
 
 // ---- packing and probes, the same for the three networks ---------------------------------------------------------------------------
 int pack(const Plan &P, const float *const *tensors, const int64_t *sizes, int count, void *packed, size_t packed_bytes, void *stream_, const char *me)
 {
-    if (!tensors || !sizes || !packed || count != (int)P.off.size() || packed_bytes < P.total * sizeof(float) || ((uintptr_t)packed & 255)) {
-        set_error("%s: need %zu tensors with their sizes (got %d) and %zu bytes, 256-byte aligned (got %zu)", me, P.off.size(), count,
-                  P.total * sizeof(float), packed_bytes);
-        return 1;
-    }
-    for (int i = 0; i < count; i++) {
-        if (!tensors[i]) { set_error("%s: tensor %d is NULL", me, i); return 1; }
-        if (sizes[i] != (int64_t)P.n[i]) { set_error("%s: tensor %d has %lld floats, the layout %zu", me, i, (long long)sizes[i], P.n[i]); return 1; }
-    }
+    if (!sizes) { set_error("%s: NULL sizes", me); return 1; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float *base = static_cast<float *>(packed);
-    for (int i = 0; i < count; i++) {
-        float *dst = base + P.off[i];
-        if (i == P.pad_idx && P.pad_kp != P.pad_k) {             // rows of K floats, laid Kp apart behind zeros
-            SOAR_HIP_OK(hipMemsetAsync(dst, 0, (size_t)P.pad_rows * P.pad_kp * sizeof(float), stream));
-            SOAR_HIP_OK(hipMemcpy2DAsync(dst, P.pad_kp * sizeof(float), tensors[i], P.pad_k * sizeof(float), P.pad_k * sizeof(float), P.pad_rows,
-                                         hipMemcpyDeviceToDevice, stream));
-            continue;
-        }
-        SOAR_HIP_OK(hipMemcpyAsync(dst, tensors[i], P.n[i] * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    }
-    return 0;
+    return pack_weights(P, tensors, sizes, count, packed, packed_bytes, stream, me, [&](int i, const float *src, float *dst) -> int {
+        if (i != P.pad_idx || P.pad_kp == P.pad_k) return PACK_COPY;
+        SOAR_HIP_OK(hipMemsetAsync(dst, 0, (size_t)P.pad_rows * P.pad_kp * sizeof(float), stream));    // rows of K floats, laid Kp apart behind zeros
+        SOAR_HIP_OK(hipMemcpy2DAsync(dst, P.pad_kp * sizeof(float), src, P.pad_k * sizeof(float), P.pad_k * sizeof(float), P.pad_rows,
+                                     hipMemcpyDeviceToDevice, stream));
+        return 0;
+    });
 }
 bool check_probes(int n, const float *const *dst, const char *me)
 {
@@ -270,7 +238,7 @@ int soar_clip_weights_bytes(const SoarClipConfig *cfg, size_t *bytes, int32_t *c
     if (!bytes) { set_error("soar_clip_weights_bytes: NULL bytes"); return 1; }
     const Plan P = clip_plan(*cfg);
     *bytes = align_up(P.total * sizeof(float));
-    if (count) *count = (int32_t)P.off.size();
+    if (count) *count = P.count();
     if (floats) *floats = P.floats;
     return 0;
 }
@@ -340,7 +308,7 @@ int soar_clip_forward(const SoarClipConfig *cfg, const void *packed, const SoarC
         if (probe(SOAR_CLIP_PROBE_EMBED, w.x)) return 1;
     } else {
         // the patch product writes rows 1 .. of every image's tokens; the class row has no product row
-        if (gemm(a.patches, P.pad_kp, Wt(P.tok), P.pad_kp, W, nullptr, nullptr, w.x + W, W, B, L - 1, L - 1, L, ACT_NONE, 1.f, stream)) return 1;
+        if (gemm(a.patches, P.pad_kp, Wt(P.tok), P.pad_kp, W, nullptr, nullptr, w.x + W, W, L - 1, stream, ACT_NONE, WT_F32, B, L - 1, L)) return 1;
         hipLaunchKernelGGL(clip_class_pos_kernel, dim3(blocks(M * W / 4)), dim3(256), 0, stream, w.x, Wt(P.cls), Wt(P.pos), M * W / 4, L, W);
         SOAR_LAUNCH_OK("clip_class_pos", stream, 0);
         if (probe(SOAR_CLIP_PROBE_EMBED, w.x)) return 1;
@@ -378,7 +346,7 @@ int soar_resampler_weights_bytes(const SoarResamplerConfig *cfg, size_t *bytes, 
     if (!bytes) { set_error("soar_resampler_weights_bytes: NULL bytes"); return 1; }
     const Plan P = resampler_plan(*cfg);
     *bytes = align_up(P.total * sizeof(float));
-    if (count) *count = (int32_t)P.off.size();
+    if (count) *count = P.count();
     if (floats) *floats = P.floats;
     return 0;
 }
@@ -437,8 +405,8 @@ int soar_resampler_forward(const SoarResamplerConfig *cfg, const void *packed, c
         if (layer_norm(w.lat, Wt(t0 + 2), Wt(t0 + 3), w.ln, Ml, D, LN_EPS, ACT_NONE, stream)) return 1;
         if (linear(w.ln, Wt(t0 + 4), D, I, nullptr, nullptr, w.q, Ml, ACT_NONE, stream)) return 1;
         // k | v of the image tokens and of the latents into one buffer [B][n + nq][2 I]: one joint softmax, no concatenation
-        if (gemm(w.xn, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv, 2 * I, B, n, n, keys, ACT_NONE, 1.f, stream)) return 1;
-        if (gemm(w.ln, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv + (size_t)n * 2 * I, 2 * I, B, nq, nq, keys, ACT_NONE, 1.f, stream)) return 1;
+        if (gemm(w.xn, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv, 2 * I, n, stream, ACT_NONE, WT_F32, B, n, keys)) return 1;
+        if (gemm(w.ln, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv + (size_t)n * 2 * I, 2 * I, nq, stream, ACT_NONE, WT_F32, B, nq, keys)) return 1;
         if (attention(w.q, w.kv, w.kv + I, w.ao, I, 2 * I, 2 * I, I, B, nq, keys, c.heads, c.dim_head, s * s, false, "resampler attention", stream)) return 1;
         if (linear(w.ao, Wt(t0 + 6), I, D, nullptr, w.lat, w.lat, Ml, ACT_NONE, stream)) return 1;
         if (probe(2 * l, w.lat)) return 1;

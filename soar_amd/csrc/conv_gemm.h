@@ -1,6 +1,7 @@
 // conv_gemm.h -- the implicit-GEMM convolution and the weight packer that the convolutional networks share (lpips.hip, vae.hip,
-// normalnet.hip), its form with 16-bit operands (bf16 / f16), and the small pieces every kernel on
-// v_mfma_f32_32x32x2_f32 needs.
+// normalnet.hip), the plain matrix product through it that is every linear layer of the transformers (sam.hip, unet.hip,
+// clip.hip), its form with 16-bit operands (bf16 / f16), and the small pieces every kernel on v_mfma_f32_32x32x2_f32
+// needs (attention.hip among them).
 #pragma once
 
 #include "soar_common.h"
@@ -60,6 +61,20 @@ struct ConvGemm {
 int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream);
 // the side of the tile launch_conv_gemm picks for desc: 128 or 64
 int conv_gemm_tile(const ConvGemm &desc);
+
+// A plain matrix product, a table of one tap: y [N][rows][Cout] = act(alpha x [N][rows][K] w[Cout][K]^T + bias) + res, image n's rows
+// at x + n xim ldx and y + n yim ldy (one image: every row ldx, ldy apart).  wtype: what w holds, 16-bit values behind the float pointer.
+inline int gemm(const float *x, int64_t ldx, const float *w, int K, int Cout, const float *bias, const float *res, float *y, int64_t ldy,
+                int64_t rows, hipStream_t stream, int act = ACT_NONE, int wtype = WT_F32, int N = 1, int64_t xim = 0, int64_t yim = 0,
+                float alpha = 1.f)
+{
+    ConvGemm k{};
+    k.x = x; k.ldx = ldx; k.xim = xim; k.bias = bias; k.res = res; k.y = y; k.ldy = ldy; k.yim = yim; k.alpha = alpha;
+    k.N = N; k.Hg = 1; k.Wg = (int)rows; k.Hin = 1; k.Win = (int)rows; k.Cin = K; k.Cout = Cout; k.stride = 1; k.dil = 1; k.Wout = (int)rows; k.os = 1;
+    k.nph = 1; k.act = act; k.wtype = wtype;
+    square_taps(k.ph[0], w, K, 1, 0);
+    return launch_conv_gemm(k, stream);
+}
 
 // torch [Cout][Cin][kk] -> fwd [Cout][kk][Cin] and, unless bwd is NULL, the data gradient's form, spatially flipped and transposed:
 // bwd[(ci kk + kk - 1 - t) ldb + co]

@@ -1,4 +1,4 @@
-// layer_norm.h -- LayerNorm over rows, shared by the transformers (sam.hip, unet.hip).
+// layer_norm.h -- LayerNorm over rows, shared by the transformers (sam.hip, unet.hip, clip.hip).
 #pragma once
 
 #include "conv_gemm.h"

@@ -1,40 +1,33 @@
 // sam.hip -- SAM (Segment Anything) for point prompts, forward only, float32 (soar_amd/sam.py).
 //
-//   sam_attn_kernel        multi-head attention with the decomposed relative-position bias, windows and whole grids alike: an
-//                          online softmax over tiles of 32 keys, q k^T and p v on v_mfma_f32_32x32x2_f32, nothing of the score
-//                          matrix in memory.  Window partition, its zero padding and the un-partition are index arithmetic
+//   sam_attn_kernel        (attention.hip) multi-head attention with the decomposed relative-position bias, windows and whole grids alike
 //   ln_rows_kernel         (layer_norm.h) LayerNorm over the last axis (tokens, and the channels of an NHWC map), optionally GELU behind it
 //   the rest               pre- and post-processing, Fourier features, the decoder's small attentions, the transposed convolutions
 //                          and the hyper-network product: plain VALU kernels
-// Every matrix product (linear layers, patch embedding, the neck's convolutions) is launch_conv_gemm (conv_gemm.h).
+// Every matrix product (linear layers, patch embedding, the neck's convolutions) is launch_conv_gemm (conv_gemm.h: gemm()).
 // No atomics; no sum's order depends on the batch: a frame's result does not depend on its neighbours or its place among them.
-#include "conv_gemm.h"
+#include "attention.h"
 #include "layer_norm.h"
+#include "net_weights.h"
 #include "workspace.h"
-
-#include <vector>
 
 namespace soar {
 namespace {
 
-constexpr int AQ = 64;                 // queries per workgroup: two waves of 32
-constexpr int AK = 32;                 // keys per tile
-constexpr int AS = 64;                 // longest side of a sequence (a window or the grid)
 constexpr int TOK_MAX = 64;            // decoder tokens per frame
 
 // ---- the packed weights -----------------------------------------------------------------------------------------------------------
 // tensors in the order of soar_amd.sam.tensor_keys
-struct Layout {
-    std::vector<size_t> off, n;        // floats: where a tensor starts (a multiple of 4) and how many it holds
-    size_t image_pe = 0, total = 0;
-    int enc_block0 = 3, neck0 = 0, prompt0 = 0, dec0 = 0, dec_layer0 = 0, final0 = 0, up0 = 0, hyper0 = 0, iou0 = 0, count = 0;
+struct Layout : WeightPlan {
+    size_t image_pe = 0;               // behind the tensors: the dense positional encoding, computed by the packer
+    int enc_block0 = 3, neck0 = 0, prompt0 = 0, dec0 = 0, dec_layer0 = 0, final0 = 0, up0 = 0, hyper0 = 0, iou0 = 0;
 };
 constexpr int ENC_BLOCK_TENSORS = 14, DEC_LAYER_TENSORS = 36;
 
 Layout make_layout(const SoarSamConfig &c)
 {
     Layout L;
-    auto add = [&](size_t n) { L.off.push_back(L.total); L.n.push_back(n); L.total += (n + 3) / 4 * 4; };
+    auto add = [&](size_t n) { L.add(n); };
     const size_t g2 = (size_t)c.grid * c.grid, C = c.embed, P = c.out_chans, pp3 = (size_t)3 * c.patch * c.patch;
     add(g2 * C); add(C * pp3); add(C);
     for (int b = 0; b < c.depth; b++) {
@@ -69,7 +62,6 @@ Layout make_layout(const SoarSamConfig &c)
         const size_t i = l == 0 ? P : (size_t)c.iou_hidden, o = l == c.iou_depth - 1 ? (size_t)c.mask_tokens : (size_t)c.iou_hidden;
         add(o * i); add(o);
     }
-    L.count = (int)L.off.size();
     L.image_pe = L.total;
     L.total += g2 * P;
     return L;
@@ -79,7 +71,7 @@ bool check_cfg(const SoarSamConfig *cp, const char *me)
 {
     if (!cp) { set_error("%s: NULL cfg", me); return false; }
     const SoarSamConfig &c = *cp;
-    bool ok = c.image_size >= 1 && c.patch >= 1 && c.grid >= 1 && c.grid <= AS && (int64_t)c.grid * c.patch == c.image_size && c.embed >= 8 &&
+    bool ok = c.image_size >= 1 && c.patch >= 1 && c.grid >= 1 && c.grid <= ATTN_SIDE && (int64_t)c.grid * c.patch == c.image_size && c.embed >= 8 &&
               c.embed % 8 == 0 && c.depth >= 1 && c.depth <= SOAR_SAM_MAX_DEPTH && c.heads >= 1 && c.head_dim >= 4 && c.head_dim <= 96 &&
               c.head_dim % 4 == 0 && (int64_t)c.heads * c.head_dim == c.embed && c.mlp >= 8 && c.mlp % 8 == 0 && c.out_chans >= 8 &&
               c.out_chans % 8 == 0 && (3 * c.patch * c.patch) % 8 == 0 && c.dec_layers >= 1 && c.dec_layers <= 8 && c.dec_heads >= 1 &&
@@ -87,204 +79,13 @@ bool check_cfg(const SoarSamConfig *cp, const char *me)
               (c.out_chans / c.dec_down) % c.dec_heads == 0 && c.out_chans % c.dec_heads == 0 && c.out_chans / c.dec_heads <= 64 &&
               c.dec_mlp >= 8 && c.dec_mlp % 8 == 0 && c.mask_tokens >= 2 && c.mask_tokens <= 8 && c.hyper_depth >= 2 && c.hyper_depth <= 8 &&
               c.iou_depth >= 2 && c.iou_depth <= 8 && c.iou_hidden >= 8 && c.iou_hidden % 8 == 0;
-    for (int b = 0; ok && b < c.depth; b++) ok = c.window[b] >= 0 && c.window[b] <= AS;
+    for (int b = 0; ok && b < c.depth; b++) ok = c.window[b] >= 0 && c.window[b] <= ATTN_SIDE;
     if (!ok)
         set_error("%s: a configuration the kernels cannot run (image_size=%d, patch=%d, grid=%d <= 64, embed=%d = heads %d x head_dim %d "
                   "<= 96, mlp=%d, out_chans=%d, decoder %d layers %d heads down %d mlp %d, mask_tokens=%d, hyper_depth=%d, iou %d x %d; "
                   "widths multiples of 8, head_dim of 4, windows 0 .. 64)", me, c.image_size, c.patch, c.grid, c.embed, c.heads, c.head_dim,
                   c.mlp, c.out_chans, c.dec_layers, c.dec_heads, c.dec_down, c.dec_mlp, c.mask_tokens, c.hyper_depth, c.iou_depth, c.iou_hidden);
     return ok;
-}
-
-// ---- plain matrix product through the shared kernel: y [M][N] = act(x [M][K] w[N][K]^T + bias) + res -------------------------------
-int gemm(const float *x, int64_t ldx, const float *w, int K, int N, const float *bias, const float *res, float *y, int64_t ldy, int64_t M,
-         int act, hipStream_t stream)
-{
-    ConvGemm k{};
-    k.x = x; k.ldx = ldx; k.bias = bias; k.res = res; k.y = y; k.ldy = ldy; k.alpha = 1.f;
-    k.N = 1; k.Hg = 1; k.Wg = (int)M; k.Hin = 1; k.Win = (int)M; k.Cin = K; k.Cout = N; k.stride = 1; k.dil = 1; k.Wout = (int)M; k.os = 1;
-    k.nph = 1; k.act = act;
-    square_taps(k.ph[0], w, K, 1, 0);
-    return launch_conv_gemm(k, stream);
-}
-
-// ---- attention ----------------------------------------------------------------------------------------------------------------------
-struct AttnArgs {
-    const float *qkv, *bias, *rel_h, *rel_w;
-    float *out;
-    int gh, gw, heads, hd, win;        // win = 0: one sequence, the grid
-    int Sh, Sw, nwx;                   // the sequence's sides; windows per row of windows
-    float scale;
-};
-
-// Workgroup: 64 queries of one sequence (a window, or the grid) and one head; wave w owns queries 32 w .. + 32.
-// Transposed products, so that a lane owns ONE query (column i = lane & 31) and softmax statistics stay in the lane:
-//   S^T = K Q^T: A = K tile (row = key), B = Q^T; the lane's 16 registers are keys mfma_row(e, h) of the tile, h = lane >> 5
-//   O^T += V^T P^T: A = V^T (row = channel), B = P^T with the MFMA's k index walking the keys in the order the lane holds them
-//   (k = step s, half h <-> key mfma_row(s, h)): p never leaves its registers.
-// The head dimension is padded to HDP (a multiple of 32) with zeros in LDS only.  rel_h / rel_w: Sh + Sw dot products per query, once,
-// into LDS; a key (ky, kx) adds rel_h[ky] + rel_w[kx].
-template <int HDP>
-__global__ void __launch_bounds__(128) sam_attn_kernel(AttnArgs a)
-{
-    constexpr int PITCH = HDP + 4, NC = HDP / 32;
-    __shared__ float kv[2 * AK * PITCH];                         // K tile | V tile; first the 64 queries (AQ = 2 AK rows)
-    __shared__ float relh[AQ][AS + 1], relw[AQ][AS + 1];
-    float(*Ks)[PITCH] = reinterpret_cast<float(*)[PITCH]>(kv);
-    float(*Vs)[PITCH] = reinterpret_cast<float(*)[PITCH]>(kv + AK * PITCH);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, h = lane >> 5;
-    const int head = blockIdx.z % a.heads, b = blockIdx.z / a.heads;
-    const int wy = blockIdx.y / a.nwx, wx = blockIdx.y - wy * a.nwx;
-    const int oy = wy * a.win, ox = wx * a.win;                  // the sequence's corner on the grid (0, 0 when global)
-    const int nk = a.Sh * a.Sw, C = a.heads * a.hd;
-    const size_t tok0 = (size_t)b * a.gh * a.gw;
-    // token of position j of the sequence, or -1 where the window hangs over the grid's edge (or j is past the sequence)
-    auto token = [&](int j) -> int {
-        if (j >= nk) return -1;
-        const int y = oy + j / a.Sw, x = ox + j % a.Sw;
-        return y < a.gh && x < a.gw ? y * a.gw + x : -1;
-    };
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-
-    // the queries, zero rows where there is none
-    for (int f = tid; f < AQ * (HDP / 4); f += 128) {
-        const int r = f / (HDP / 4), d = (f - r * (HDP / 4)) * 4;
-        const int t = token(blockIdx.x * AQ + r);
-        float4 v = zero4;
-        if (t >= 0 && d < a.hd) v = *reinterpret_cast<const float4 *>(a.qkv + (tok0 + t) * 3 * C + head * a.hd + d);
-        *reinterpret_cast<float4 *>(&Ks[r][d]) = v;              // (rows 32 .. 63 run on into the V tile)
-    }
-    __syncthreads();
-    if (a.rel_h) {
-        for (int e = tid; e < AQ * (a.Sh + a.Sw); e += 128) {
-            const int q = e % AQ, r = e / AQ;
-            const int j = blockIdx.x * AQ + q;
-            float s = 0.f;
-            if (j < nk) {
-                const int qy = j / a.Sw, qx = j - qy * a.Sw;
-                const float *tab = r < a.Sh ? a.rel_h + (size_t)(qy - r + a.Sh - 1) * a.hd : a.rel_w + (size_t)(qx - (r - a.Sh) + a.Sw - 1) * a.hd;
-                for (int d = 0; d < a.hd; d += 4) {
-                    const float4 qv = *reinterpret_cast<const float4 *>(&Ks[q][d]);
-                    const float4 tv = *reinterpret_cast<const float4 *>(tab + d);
-                    s += qv.x * tv.x + qv.y * tv.y + qv.z * tv.z + qv.w * tv.w;
-                }
-            }
-            if (r < a.Sh) relh[q][r] = s; else relw[q][r - a.Sh] = s;
-        }
-    }
-    // this lane's query, scaled, in the k order of the S^T product: chunk c, group g holds channels 32 c + 16 h + 4 g .. + 4
-    float4 qreg[NC][4];
-#pragma unroll
-    for (int c = 0; c < NC; c++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            float4 v = *reinterpret_cast<const float4 *>(&Ks[wave * 32 + i][c * 32 + h * 16 + 4 * g]);
-            v.x *= a.scale; v.y *= a.scale; v.z *= a.scale; v.w *= a.scale;
-            qreg[c][g] = v;
-        }
-    __syncthreads();
-
-    const int ql = wave * 32 + i;                                // this lane's query in the tile
-    float m = -INFINITY, l = 0.f;
-    f32x16 o[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) o[c][e] = 0.f;
-
-    const int ntiles = (nk + AK - 1) / AK;
-    for (int kt = 0; kt < ntiles; kt++) {
-        // K and V of 32 keys: four threads a key; a key off the grid is the bias (the projection of a zero token)
-        {
-            const int r = tid >> 2, j = kt * AK + r;
-            const int t = token(j);
-            const float *kp = nullptr;
-            if (t >= 0) kp = a.qkv + (tok0 + t) * 3 * C + C + head * a.hd;
-            else if (j < nk) kp = a.bias + C + head * a.hd;
-            for (int f = tid & 3; f < HDP / 4; f += 4) {
-                const int d = f * 4;
-                float4 kk = zero4, vv = zero4;
-                if (kp && d < a.hd) { kk = *reinterpret_cast<const float4 *>(kp + d); vv = *reinterpret_cast<const float4 *>(kp + C + d); }
-                *reinterpret_cast<float4 *>(&Ks[r][d]) = kk;
-                *reinterpret_cast<float4 *>(&Vs[r][d]) = vv;
-            }
-        }
-        __syncthreads();
-        f32x16 s;
-#pragma unroll
-        for (int e = 0; e < 16; e++) s[e] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; c++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const float4 k4 = *reinterpret_cast<const float4 *>(&Ks[i][c * 32 + h * 16 + 4 * g]);
-#pragma unroll
-                for (int u = 0; u < 4; u++) s = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(k4, u), comp(qreg[c][g], u), s, 0, 0, 0);
-            }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int j = kt * AK + mfma_row(e, h);
-            float v = -INFINITY;
-            if (j < nk) {
-                v = s[e];
-                if (a.rel_h) { const int ky = j / a.Sw; v += relh[ql][ky] + relw[ql][j - ky * a.Sw]; }
-            }
-            s[e] = v;
-            mx = fmaxf(mx, v);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mn = fmaxf(m, mx);                           // finite: key 0 of the first tile exists
-        const float corr = expf(m - mn);                         // (0 at the first tile)
-        float sum = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; e++) { s[e] = expf(s[e] - mn); sum += s[e]; }
-        sum += __shfl_xor(sum, 32);
-        l = l * corr + sum;
-        m = mn;
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-#pragma unroll
-            for (int e = 0; e < 16; e++) o[c][e] *= corr;
-#pragma unroll
-            for (int u = 0; u < 16; u++) o[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[mfma_row(u, h)][c * 32 + i], s[u], o[c], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    const int t = token(blockIdx.x * AQ + ql);
-    if (t < 0) return;                                           // no such query, or a padded one: dropped
-    const float inv = 1.f / l;
-    float *dst = a.out + (tok0 + t) * C + head * a.hd;
-#pragma unroll
-    for (int c = 0; c < NC; c++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int d = c * 32 + 8 * g + 4 * h;                // registers 4 g .. 4 g + 3: channels d .. d + 3
-            if (d < a.hd) *reinterpret_cast<float4 *>(dst + d) = make_float4(o[c][4 * g] * inv, o[c][4 * g + 1] * inv, o[c][4 * g + 2] * inv, o[c][4 * g + 3] * inv);
-        }
-}
-
-int launch_attention(const float *qkv, const float *bias, const float *rel_h, const float *rel_w, float *out, int B, int gh, int gw,
-                     int heads, int hd, int win, float scale, hipStream_t stream)
-{
-    const char *me = "sam attention";
-    if (B < 0 || gh < 1 || gw < 1 || heads < 1 || hd < 4 || hd > 96 || hd % 4 || win < 0 || (int64_t)B * heads > 65535 ||
-        (int64_t)B * gh * gw * heads * hd * 3 > (int64_t(1) << 40)) {
-        set_error("%s: bad sizes (B=%d, grid %d x %d, heads=%d, hd=%d: a multiple of 4 up to 96, window=%d, B heads <= 65535)", me, B, gh, gw, heads, hd, win);
-        return 1;
-    }
-    AttnArgs a{qkv, bias, rel_h, rel_w, out, gh, gw, heads, hd, win, win ? win : gh, win ? win : gw, win ? (gw + win - 1) / win : 1, scale};
-    const int nwy = win ? (gh + win - 1) / win : 1;
-    if (a.Sh > AS || a.Sw > AS) { set_error("%s: a sequence of %d x %d tokens: at most %d a side", me, a.Sh, a.Sw, AS); return 1; }
-    if (B == 0) return 0;
-    if (!qkv || !out || (win && !bias) || (!rel_h != !rel_w)) { set_error("%s: NULL qkv, out or (with windows) bias, or one rel table without the other", me); return 1; }
-    if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)rel_h | (uintptr_t)rel_w) & 15) { set_error("%s: pointers must be 16-byte aligned", me); return 1; }
-    const dim3 grid((unsigned)((a.Sh * a.Sw + AQ - 1) / AQ), (unsigned)(nwy * a.nwx), (unsigned)(B * heads));
-    if (hd <= 32) hipLaunchKernelGGL(sam_attn_kernel<32>, grid, dim3(128), 0, stream, a);
-    else if (hd <= 64) hipLaunchKernelGGL(sam_attn_kernel<64>, grid, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL(sam_attn_kernel<96>, grid, dim3(128), 0, stream, a);
-    SOAR_LAUNCH_OK("sam_attn", stream, 0);
-    return 0;
 }
 
 // ---- small pieces ------------------------------------------------------------------------------------------------------------------
@@ -525,7 +326,7 @@ int soar_sam_weights_bytes(const SoarSamConfig *cfg, size_t *bytes, int32_t *cou
     if (!bytes) { set_error("soar_sam_weights_bytes: NULL bytes"); return 1; }
     const Layout L = make_layout(*cfg);
     *bytes = align_up(L.total * sizeof(float));
-    if (count) *count = L.count;
+    if (count) *count = L.count();
     return 0;
 }
 
@@ -535,30 +336,19 @@ int soar_sam_pack_weights(const SoarSamConfig *cfg, const float *const *tensors,
     if (!check_cfg(cfg, me)) return 1;
     const SoarSamConfig &c = *cfg;
     const Layout L = make_layout(c);
-    if (!tensors || !packed || count != L.count || packed_bytes < L.total * sizeof(float) || ((uintptr_t)packed & 255)) {
-        set_error("%s: need %d tensors (got %d) and %zu bytes, 256-byte aligned (got %zu)", me, L.count, count, L.total * sizeof(float), packed_bytes);
-        return 1;
-    }
-    for (int i = 0; i < count; i++)
-        if (!tensors[i]) { set_error("%s: tensor %d is NULL", me, i); return 1; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float *base = static_cast<float *>(packed);
     const int P = c.out_chans;
     const int neck_conv = L.neck0 + 3, upa = L.up0, upb = L.up0 + 4;
-    for (int i = 0; i < count; i++) {
-        float *dst = base + L.off[i];
-        if (i == neck_conv) {
-            if (launch_conv_pack(tensors[i], dst, nullptr, P, P, 9, 0, stream)) return 1;
-            continue;
-        }
-        if (i == upa || i == upb) {
-            const int Cin = i == upa ? P : P / 4, Cout = i == upa ? P / 4 : P / 8;
-            hipLaunchKernelGGL(convt_pack_kernel, dim3(blocks((int64_t)Cin * Cout * 4)), dim3(256), 0, stream, tensors[i], dst, Cin, Cout);
-            SOAR_LAUNCH_OK("sam_convt_pack", stream, 0);
-            continue;
-        }
-        SOAR_HIP_OK(hipMemcpyAsync(dst, tensors[i], L.n[i] * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    }
+    auto special = [&](int i, const float *src, float *dst) -> int {
+        if (i == neck_conv) return launch_conv_pack(src, dst, nullptr, P, P, 9, 0, stream);
+        if (i != upa && i != upb) return PACK_COPY;
+        const int Cin = i == upa ? P : P / 4, Cout = i == upa ? P / 4 : P / 8;
+        hipLaunchKernelGGL(convt_pack_kernel, dim3(blocks((int64_t)Cin * Cout * 4)), dim3(256), 0, stream, src, dst, Cin, Cout);
+        SOAR_LAUNCH_OK("sam_convt_pack", stream, 0);
+        return 0;
+    };
+    if (pack_weights(L, tensors, nullptr, count, packed, packed_bytes, stream, me, special)) return 1;
+    float *base = static_cast<float *>(packed);
     hipLaunchKernelGGL(image_pe_kernel, dim3(blocks((int64_t)c.grid * c.grid * P)), dim3(256), 0, stream, base + L.off[L.prompt0], base + L.image_pe, c.grid, P);
     SOAR_LAUNCH_OK("sam_image_pe", stream, 0);
     return 0;
@@ -623,7 +413,7 @@ int soar_sam_encode(const SoarSamConfig *cfg, const void *packed, const SoarSamE
     if (a.patches) {
         const int K = 3 * c.patch * c.patch;
         for (int b = 0; b < a.B; b++)                            // pos_embed rides as the residual: one product per frame
-            if (gemm(a.patches + (size_t)b * g2 * K, K, W(1), K, C, W(2), W(0), w.x + (size_t)b * g2 * C, C, g2, ACT_NONE, stream)) return 1;
+            if (gemm(a.patches + (size_t)b * g2 * K, K, W(1), K, C, W(2), W(0), w.x + (size_t)b * g2 * C, C, g2, stream)) return 1;
     } else {
         SOAR_HIP_OK(hipMemcpyAsync(w.x, a.tokens_in, M * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
@@ -631,17 +421,17 @@ int soar_sam_encode(const SoarSamConfig *cfg, const void *packed, const SoarSamE
     for (int blk = a.block_begin; blk < a.block_end; blk++) {
         const int t0 = L.enc_block0 + ENC_BLOCK_TENSORS * blk;
         if (layer_norm(w.x, W(t0), W(t0 + 1), w.t, M, C, 1e-6f, ACT_NONE, stream)) return 1;
-        if (gemm(w.t, C, W(t0 + 2), C, 3 * C, W(t0 + 3), nullptr, w.qkv, 3 * C, M, ACT_NONE, stream)) return 1;
-        if (launch_attention(w.qkv, W(t0 + 3), W(t0 + 4), W(t0 + 5), w.t, a.B, c.grid, c.grid, c.heads, c.head_dim, c.window[blk], scale, stream)) return 1;
-        if (gemm(w.t, C, W(t0 + 6), C, C, W(t0 + 7), w.x, w.x, C, M, ACT_NONE, stream)) return 1;
+        if (gemm(w.t, C, W(t0 + 2), C, 3 * C, W(t0 + 3), nullptr, w.qkv, 3 * C, M, stream)) return 1;
+        if (launch_sam_attention(w.qkv, W(t0 + 3), W(t0 + 4), W(t0 + 5), w.t, a.B, c.grid, c.grid, c.heads, c.head_dim, c.window[blk], scale, stream)) return 1;
+        if (gemm(w.t, C, W(t0 + 6), C, C, W(t0 + 7), w.x, w.x, C, M, stream)) return 1;
         if (layer_norm(w.x, W(t0 + 8), W(t0 + 9), w.t, M, C, 1e-6f, ACT_NONE, stream)) return 1;
-        if (gemm(w.t, C, W(t0 + 10), C, c.mlp, W(t0 + 11), nullptr, w.h, c.mlp, M, ACT_GELU, stream)) return 1;
-        if (gemm(w.h, c.mlp, W(t0 + 12), c.mlp, C, W(t0 + 13), w.x, w.x, C, M, ACT_NONE, stream)) return 1;
+        if (gemm(w.t, C, W(t0 + 10), C, c.mlp, W(t0 + 11), nullptr, w.h, c.mlp, M, stream, ACT_GELU)) return 1;
+        if (gemm(w.h, c.mlp, W(t0 + 12), c.mlp, C, W(t0 + 13), w.x, w.x, C, M, stream)) return 1;
     }
     if (a.tokens_out) SOAR_HIP_OK(hipMemcpyAsync(a.tokens_out, w.x, M * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (a.embeddings) {
         const int P = c.out_chans, n0 = L.neck0;
-        if (gemm(w.x, C, W(n0), C, P, nullptr, nullptr, w.n1, P, M, ACT_NONE, stream)) return 1;
+        if (gemm(w.x, C, W(n0), C, P, nullptr, nullptr, w.n1, P, M, stream)) return 1;
         if (layer_norm(w.n1, W(n0 + 1), W(n0 + 2), w.n1, M, P, 1e-6f, ACT_NONE, stream)) return 1;
         ConvGemm k{};
         k.x = w.n1; k.ldx = P; k.xim = g2; k.y = w.n2; k.ldy = P; k.yim = g2; k.alpha = 1.f;
@@ -692,13 +482,13 @@ int soar_sam_decode(const SoarSamConfig *cfg, const void *packed, const SoarSamD
     auto attention = [&](int t0, int I, const float *qin, int64_t nq, const float *kin, const float *vin, int64_t nkv, bool qtok, bool ktok,
                          const float *res, float *out) -> int {
         const int Nq = qtok ? T : HW, Nk = ktok ? T : HW, hd = I / c.dec_heads;
-        if (gemm(qin, P, W(t0), P, I, W(t0 + 1), nullptr, w.qp, I, nq, ACT_NONE, stream)) return 1;
-        if (gemm(kin, P, W(t0 + 2), P, I, W(t0 + 3), nullptr, w.kp, I, nkv, ACT_NONE, stream)) return 1;
-        if (gemm(vin, P, W(t0 + 4), P, I, W(t0 + 5), nullptr, w.vp, I, nkv, ACT_NONE, stream)) return 1;
+        if (gemm(qin, P, W(t0), P, I, W(t0 + 1), nullptr, w.qp, I, nq, stream)) return 1;
+        if (gemm(kin, P, W(t0 + 2), P, I, W(t0 + 3), nullptr, w.kp, I, nkv, stream)) return 1;
+        if (gemm(vin, P, W(t0 + 4), P, I, W(t0 + 5), nullptr, w.vp, I, nkv, stream)) return 1;
         hipLaunchKernelGGL(small_attn_kernel, dim3((unsigned)Nq, (unsigned)c.dec_heads, (unsigned)B), dim3(64), 0, stream, w.qp, w.kp, w.vp, w.ao, Nq, Nk,
                            I, hd, a.counts, extra, Mp, qtok ? 1 : 0, ktok ? 1 : 0, 1.f / sqrtf((float)hd));
         SOAR_LAUNCH_OK("sam_small_attn", stream, 0);
-        return gemm(w.ao, I, W(t0 + 6), I, P, W(t0 + 7), res, out, P, nq, ACT_NONE, stream);
+        return gemm(w.ao, I, W(t0 + 6), I, P, W(t0 + 7), res, out, P, nq, stream);
     };
     // (rows of w.ao that no query wrote -- unused token slots -- hold whatever was there; they feed only their own rows)
     SOAR_HIP_OK(hipMemsetAsync(w.ao, 0, (size_t)B * (HW > T ? HW : T) * P * sizeof(float), stream));
@@ -715,8 +505,8 @@ int soar_sam_decode(const SoarSamConfig *cfg, const void *packed, const SoarSamD
         if (add(w.keys, image_pe, w.kpe, BHW * P, (int64_t)HW * P, stream)) return 1;
         if (attention(t0 + 10, I2, w.qpe, BT, w.kpe, w.keys, BHW, true, false, w.q, w.q)) return 1;
         if (layer_norm(w.q, W(t0 + 18), W(t0 + 19), w.q, BT, P, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.q, P, W(t0 + 20), P, c.dec_mlp, W(t0 + 21), nullptr, w.hid, c.dec_mlp, BT, ACT_RELU, stream)) return 1;
-        if (gemm(w.hid, c.dec_mlp, W(t0 + 22), c.dec_mlp, P, W(t0 + 23), w.q, w.q, P, BT, ACT_NONE, stream)) return 1;
+        if (gemm(w.q, P, W(t0 + 20), P, c.dec_mlp, W(t0 + 21), nullptr, w.hid, c.dec_mlp, BT, stream, ACT_RELU)) return 1;
+        if (gemm(w.hid, c.dec_mlp, W(t0 + 22), c.dec_mlp, P, W(t0 + 23), w.q, w.q, P, BT, stream)) return 1;
         if (layer_norm(w.q, W(t0 + 24), W(t0 + 25), w.q, BT, P, 1e-5f, ACT_NONE, stream)) return 1;
         if (add(w.q, w.q0, w.qpe, BT * P, BT * P, stream)) return 1;
         if (attention(t0 + 28, I2, w.kpe, BHW, w.qpe, w.q, BT, false, true, w.keys, w.keys)) return 1;
@@ -745,7 +535,7 @@ int soar_sam_decode(const SoarSamConfig *cfg, const void *packed, const SoarSamD
             const bool last = l == c.hyper_depth - 1;
             float *y = last ? w.hin + (size_t)mk * C8 : bufs[l & 1];
             const int64_t ldy = last ? (int64_t)nm * C8 : (int64_t)nm * P;
-            if (gemm(x, ldx, W(t0), P, last ? C8 : P, W(t0 + 1), nullptr, y, ldy, B, last ? ACT_NONE : ACT_RELU, stream)) return 1;
+            if (gemm(x, ldx, W(t0), P, last ? C8 : P, W(t0 + 1), nullptr, y, ldy, B, stream, last ? ACT_NONE : ACT_RELU)) return 1;
             x = y; ldx = ldy;
         }
     }
@@ -762,7 +552,7 @@ int soar_sam_decode(const SoarSamConfig *cfg, const void *packed, const SoarSamD
         for (int l = 0; l < c.iou_depth; l++) {
             const bool last = l == c.iou_depth - 1;
             const int N = last ? nm : c.iou_hidden;
-            if (gemm(x, ldx, W(L.iou0 + 2 * l), K, N, W(L.iou0 + 2 * l + 1), nullptr, bufs[l & 1], iw, B, last ? ACT_NONE : ACT_RELU, stream)) return 1;
+            if (gemm(x, ldx, W(L.iou0 + 2 * l), K, N, W(L.iou0 + 2 * l + 1), nullptr, bufs[l & 1], iw, B, stream, last ? ACT_NONE : ACT_RELU)) return 1;
             x = bufs[l & 1]; ldx = iw; K = N;
         }
         hipLaunchKernelGGL(gather_kernel, dim3(blocks((int64_t)B * (nm - 1))), dim3(256), 0, stream, x, a.iou, B, nm - 1, iw, 1);
@@ -792,7 +582,7 @@ int soar_sam_postprocess(int32_t B, int32_t K, int32_t L, int32_t image_size, in
 int soar_sam_attention(const float *qkv, const float *bias, const float *rel_h, const float *rel_w, float *out, int32_t B, int32_t gh, int32_t gw,
                        int32_t heads, int32_t hd, int32_t window, float scale, void *stream_)
 {
-    return launch_attention(qkv, bias, rel_h, rel_w, out, B, gh, gw, heads, hd, window, scale, static_cast<hipStream_t>(stream_));
+    return launch_sam_attention(qkv, bias, rel_h, rel_w, out, B, gh, gw, heads, hd, window, scale, static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

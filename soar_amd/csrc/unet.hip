@@ -1,22 +1,21 @@
 // unet.hip -- the multi-view diffusion UNet of the SDS guidance, forward only, float32 (soar_amd/unet.py).
 //
-//   kv_attn_kernel         (attention.h) self-attention over the views of a group and cross-attention with the text and image tokens
+//   kv_attn_kernel         (attention.hip) self-attention over the views of a group and cross-attention with the text and image tokens
 //   unet_gn_stats_kernel   GroupNorm (32 groups, any channels per group) mean and rstd of one (image, group) in double, fixed order;
 //   unet_gn_apply_kernel   y = silu?((x (+ e[n][c]) - mean) rstd gamma + beta): the ResBlock's embedding term rides in on the read
 //   ln_rows_kernel         (layer_norm.h)
 //   unet_sum3_kernel       the three partial results of a small 3 x 3 convolution split by kernel rows (conv3x3 below), bias, residual
 //   the rest               input staging (any strides, channels padded to 8), the sinusoidal embedding, SiLU, GEGLU's product, the
 //                          concatenation with a skip, nearest 2 x up-sampling: plain VALU kernels
-// Every matrix product (convolutions, linear layers) is launch_conv_gemm (conv_gemm.h).  Activations are channels-last [N][H W][C].
+// Every matrix product (convolutions, linear layers: gemm()) is launch_conv_gemm (conv_gemm.h).  Activations are channels-last [N][H W][C].
 // SoarUnetConfig::precision 1 (bf16) or 2 (f16): the products' weights are packed as 16-bit values and every product runs on the
 // 16-bit matrix core, its A operand rounded on load (conv_gemm16_kernel); everything else, the activations in memory
 // included, stays float32.
 // No atomics; no sum's order depends on the batch: a group's result does not depend on the other groups.
 #include "attention.h"
 #include "layer_norm.h"
+#include "net_weights.h"
 #include "workspace.h"
-
-#include <vector>
 
 namespace soar {
 namespace {
@@ -34,14 +33,11 @@ struct Blk {
     bool down = false, up = false;
 };
 struct Repack { int idx, Cout, Cin, Cinp; };
-struct Plan {
-    std::vector<size_t> off, n;        // floats: where a tensor starts in the packed buffer (a multiple of 4), how many the source holds
-    std::vector<char> mat;             // the B operand of a gemm() or conv3x3(): laid as 16-bit values where the precision asks for them
+struct Plan : WeightPlan {             // (mat: the B operand of a gemm() or conv3x3())
     std::vector<Repack> convs;         // the 3 x 3 convolutions
     std::vector<Blk> in, out;
     Blk mid;
-    size_t total = 0, floats = 0;
-    int time0 = 0, cam0 = -1, out0 = 0, count = 0;
+    int time0 = 0, cam0 = -1, out0 = 0;
     int tr_tail = 16;                  // the transformer's tensors behind attn2's keys and values start here
 };
 
@@ -49,14 +45,8 @@ Plan make_plan(const SoarUnetConfig &c)
 {
     Plan P;
     const size_t E = (size_t)4 * c.model_channels, ctx = c.context_dim;
-    // mat: a product's B operand, which a non-zero precision lays as 16-bit values: half the floats, a start still 16-byte aligned
-    auto add = [&](size_t n, size_t packed = 0, bool mat = false) {
-        P.off.push_back(P.total); P.n.push_back(n); P.mat.push_back(mat); P.floats += n;
-        if (!packed) packed = n;
-        if (mat && c.precision) packed = (packed + 1) / 2;
-        P.total += (packed + 3) / 4 * 4;
-        return (int)P.off.size() - 1;
-    };
+    P.half = c.precision != WT_F32;    // a product's B operand as 16-bit values
+    auto add = [&](size_t n, size_t packed = 0, bool mat = false) { return P.add(n, packed, mat); };
     auto mat = [&](size_t n) { return add(n, 0, true); };
     auto conv3 = [&](int Cout, int Cin, int Cinp) {
         const int i = add((size_t)Cout * Cin * 9, (size_t)Cout * Cinp * 9, true);
@@ -121,7 +111,6 @@ Plan make_plan(const SoarUnetConfig &c)
             P.out.push_back(b);
         }
     P.out0 = add(ch); add(ch); conv3(c.out_channels, ch, ch);
-    P.count = (int)P.off.size();
     return P;
 }
 
@@ -163,19 +152,7 @@ bool check_sizes(const SoarUnetConfig &c, int N, int H, int W, int T, int n_ip, 
     return true;
 }
 
-// ---- plain matrix product through the shared kernel: y [M][N] = x [M][K] w[N][K]^T + bias + res ------------------------------------
-// (wtype: what w holds, WT_*; w's 16-bit values lie behind the float pointer)
-int gemm(const float *x, int64_t ldx, const float *w, int K, int N, const float *bias, const float *res, float *y, int64_t ldy, int64_t M,
-         int wtype, hipStream_t stream)
-{
-    ConvGemm k{};
-    k.wtype = wtype;
-    k.x = x; k.ldx = ldx; k.bias = bias; k.res = res; k.y = y; k.ldy = ldy; k.alpha = 1.f;
-    k.N = 1; k.Hg = 1; k.Wg = (int)M; k.Hin = 1; k.Win = (int)M; k.Cin = K; k.Cout = N; k.stride = 1; k.dil = 1; k.Wout = (int)M; k.os = 1;
-    k.nph = 1;
-    square_taps(k.ph[0], w, K, 1, 0);
-    return launch_conv_gemm(k, stream);
-}
+// ---- the 3 x 3 convolutions -------------------------------------------------------------------------------------------------------
 // 3 x 3, pad 1, stride 1 or 2: x [N][H][W][Cin] -> y [N][H / stride][W / stride][Cout] (+ bias + res).
 // An output of at most SPLIT_PIXELS pixels an image (the two deepest levels of the shipped model: 128 and 512 rows against K up to
 // 23,040) is too few rows to fill the chip as one product.  It runs as three, the kernel's rows of three taps each, in ONE launch --
@@ -409,7 +386,7 @@ int soar_unet_weights_bytes(const SoarUnetConfig *cfg, size_t *bytes, int32_t *c
     if (!bytes) { set_error("soar_unet_weights_bytes: NULL bytes"); return 1; }
     const Plan P = make_plan(*cfg);
     *bytes = align_up(P.total * sizeof(float));
-    if (count) *count = P.count;
+    if (count) *count = P.count();
     if (floats) *floats = P.floats;
     return 0;
 }
@@ -420,41 +397,20 @@ int soar_unet_pack_weights(const SoarUnetConfig *cfg, const float *const *tensor
     const char *me = "soar_unet_pack_weights";
     if (!check_cfg(cfg, me)) return 1;
     const Plan P = make_plan(*cfg);
-    if (!tensors || !sizes || !packed || count != P.count || packed_bytes < P.total * sizeof(float) || ((uintptr_t)packed & 255)) {
-        set_error("%s: need %d tensors with their sizes (got %d) and %zu bytes, 256-byte aligned (got %zu)", me, P.count, count,
-                  P.total * sizeof(float), packed_bytes);
-        return 1;
-    }
-    for (int i = 0; i < count; i++) {
-        if (!tensors[i]) { set_error("%s: tensor %d is NULL", me, i); return 1; }
-        if (sizes[i] != (int64_t)P.n[i]) { set_error("%s: tensor %d has %lld floats, the layout %zu", me, i, (long long)sizes[i], P.n[i]); return 1; }
-    }
+    if (!sizes) { set_error("%s: NULL sizes", me); return 1; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float *base = static_cast<float *>(packed);
-    std::vector<int> conv_of(count, -1);
+    std::vector<int> conv_of(P.count(), -1);
     for (size_t j = 0; j < P.convs.size(); j++) conv_of[P.convs[j].idx] = (int)j;
-    for (int i = 0; i < count; i++) {
-        float *dst = base + P.off[i];
-        if (cfg->precision && P.mat[i]) {                        // a product's B operand: 16-bit, a linear layer's matrix as one long row
-            int rc;
-            if (conv_of[i] >= 0) {
-                const Repack &r = P.convs[conv_of[i]];
-                rc = launch_conv_pack16(tensors[i], dst, r.Cout, r.Cin, r.Cinp, 9, cfg->precision, stream);
-            } else {
-                rc = launch_conv_pack16(tensors[i], dst, 1, (int)P.n[i], (int)P.n[i], 1, cfg->precision, stream);
-            }
-            if (rc) return 1;
-            continue;
-        }
-        if (conv_of[i] >= 0) {
-            const Repack &r = P.convs[conv_of[i]];
-            hipLaunchKernelGGL(unet_pack_pad_kernel, dim3(blocks((int64_t)r.Cout * 9 * r.Cinp)), dim3(256), 0, stream, tensors[i], dst, r.Cout, r.Cin, r.Cinp, 9);
-            SOAR_LAUNCH_OK("unet_pack_pad", stream, 0);
-            continue;
-        }
-        SOAR_HIP_OK(hipMemcpyAsync(dst, tensors[i], P.n[i] * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    }
-    return 0;
+    return pack_weights(P, tensors, sizes, count, packed, packed_bytes, stream, me, [&](int i, const float *src, float *dst) -> int {
+        const Repack *r = conv_of[i] >= 0 ? &P.convs[conv_of[i]] : nullptr;
+        if (P.half && P.mat[i])                                  // a product's B operand: 16-bit, a linear layer's matrix as one long row
+            return r ? launch_conv_pack16(src, dst, r->Cout, r->Cin, r->Cinp, 9, cfg->precision, stream)
+                     : launch_conv_pack16(src, dst, 1, (int)P.n[i], (int)P.n[i], 1, cfg->precision, stream);
+        if (!r) return PACK_COPY;
+        hipLaunchKernelGGL(unet_pack_pad_kernel, dim3(blocks((int64_t)r->Cout * 9 * r->Cinp)), dim3(256), 0, stream, src, dst, r->Cout, r->Cin, r->Cinp, 9);
+        SOAR_LAUNCH_OK("unet_pack_pad", stream, 0);
+        return 0;
+    });
 }
 
 int soar_unet_workspace_bytes(const SoarUnetConfig *cfg, int32_t N, int32_t H, int32_t W, int32_t T, int32_t ip_tokens, size_t *bytes)
@@ -517,13 +473,13 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
     // ---- the embedding
     hipLaunchKernelGGL(unet_time_kernel, dim3(blocks((int64_t)N * mc)), dim3(256), 0, stream, a.t, w.temb, N, mc / 2);
     SOAR_LAUNCH_OK("unet_time", stream, 0);
-    if (gemm(w.temb, mc, Wt(P.time0), mc, E, Wt(P.time0 + 1), nullptr, w.e1, E, N, wt, stream)) return 1;
+    if (gemm(w.temb, mc, Wt(P.time0), mc, E, Wt(P.time0 + 1), nullptr, w.e1, E, N, stream, ACT_NONE, wt)) return 1;
     if (silu_of(w.e1, w.e1, (int64_t)N * E)) return 1;
-    if (gemm(w.e1, E, Wt(P.time0 + 2), E, E, Wt(P.time0 + 3), nullptr, w.emb, E, N, wt, stream)) return 1;
+    if (gemm(w.e1, E, Wt(P.time0 + 2), E, E, Wt(P.time0 + 3), nullptr, w.emb, E, N, stream, ACT_NONE, wt)) return 1;
     if (a.camera) {
-        if (gemm(a.camera, c.camera_dim, Wt(P.cam0), c.camera_dim, E, Wt(P.cam0 + 1), nullptr, w.e1, E, N, wt, stream)) return 1;
+        if (gemm(a.camera, c.camera_dim, Wt(P.cam0), c.camera_dim, E, Wt(P.cam0 + 1), nullptr, w.e1, E, N, stream, ACT_NONE, wt)) return 1;
         if (silu_of(w.e1, w.e1, (int64_t)N * E)) return 1;
-        if (gemm(w.e1, E, Wt(P.cam0 + 2), E, E, Wt(P.cam0 + 3), w.emb, w.emb, E, N, wt, stream)) return 1;
+        if (gemm(w.e1, E, Wt(P.cam0 + 2), E, E, Wt(P.cam0 + 3), w.emb, w.emb, E, N, stream, ACT_NONE, wt)) return 1;
     }
     if (probe(SOAR_UNET_PROBE_EMB, w.emb, (size_t)N * E)) return 1;
     if (silu_of(w.emb, w.semb, (int64_t)N * E)) return 1;
@@ -533,11 +489,11 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
         const int64_t hw = (int64_t)H * W;
         if (group_norm(x, nullptr, hw, cin, Wt(t0), Wt(t0 + 1), 1e-5f, 1, w.tmp)) return 1;
         if (conv3x3(w.tmp, cin, Wt(t0 + 2), Wt(t0 + 3), nullptr, w.h1, cout, N, H, W, 1, w.part, wt, stream)) return 1;
-        if (gemm(w.semb, E, Wt(t0 + 4), E, cout, Wt(t0 + 5), nullptr, w.eo, cout, N, wt, stream)) return 1;
+        if (gemm(w.semb, E, Wt(t0 + 4), E, cout, Wt(t0 + 5), nullptr, w.eo, cout, N, stream, ACT_NONE, wt)) return 1;
         if (group_norm(w.h1, w.eo, hw, cout, Wt(t0 + 6), Wt(t0 + 7), 1e-5f, 1, w.tmp)) return 1;
         const float *skip = x;
         if (cin != cout) {
-            if (gemm(x, cin, Wt(t0 + 10), cin, cout, Wt(t0 + 11), nullptr, y, cout, (int64_t)N * hw, wt, stream)) return 1;
+            if (gemm(x, cin, Wt(t0 + 10), cin, cout, Wt(t0 + 11), nullptr, y, cout, (int64_t)N * hw, stream, ACT_NONE, wt)) return 1;
             skip = y;
         }
         return conv3x3(w.tmp, cout, Wt(t0 + 8), Wt(t0 + 9), skip, y, cout, N, H, W, 1, w.part, wt, stream);
@@ -548,40 +504,40 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
         const int heads = C / c.head_channels, hd = c.head_channels, o = t0 + P.tr_tail;
         const float scale = 1.f / sqrtf((float)hd);
         if (group_norm(x, nullptr, hw, C, Wt(t0), Wt(t0 + 1), 1e-6f, 0, w.tmp)) return 1;
-        if (gemm(w.tmp, C, Wt(t0 + 2), C, C, Wt(t0 + 3), nullptr, w.tx, C, M, wt, stream)) return 1;
+        if (gemm(w.tmp, C, Wt(t0 + 2), C, C, Wt(t0 + 3), nullptr, w.tx, C, M, stream, ACT_NONE, wt)) return 1;
         // attn1 over the tokens of all the views of a group: q | k | v from the three weights, which lie one behind the other
         if (layer_norm(w.tx, Wt(t0 + 4), Wt(t0 + 5), w.tn, M, C, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.tn, C, Wt(t0 + 6), C, 3 * C, nullptr, nullptr, w.qkv, 3 * C, M, wt, stream)) return 1;
+        if (gemm(w.tn, C, Wt(t0 + 6), C, 3 * C, nullptr, nullptr, w.qkv, 3 * C, M, stream, ACT_NONE, wt)) return 1;
         SoarUnetAttnArgs s{};
         s.q = w.qkv; s.k = w.qkv + C; s.v = w.qkv + 2 * C; s.out = w.ao;
         s.ldq = s.ldk = s.ldv = 3 * C; s.ldo = C;
         s.B = N / c.n_view; s.Lq = s.Lk = (int)(c.n_view * hw); s.heads = heads; s.hd = hd; s.scale = scale;
-        if (launch_kv_attention(s, stream)) return 1;
-        if (gemm(w.ao, C, Wt(t0 + 9), C, C, Wt(t0 + 10), w.tx, w.tx, C, M, wt, stream)) return 1;
+        if (launch_kv_attention(s, 64, false, "unet attention", stream)) return 1;
+        if (gemm(w.ao, C, Wt(t0 + 9), C, C, Wt(t0 + 10), w.tx, w.tx, C, M, stream, ACT_NONE, wt)) return 1;
         if (probe(code + 1, w.tx, (size_t)M * C)) return 1;
         // attn2 per view: the text tokens, and the image tokens as a second key set
         if (layer_norm(w.tx, Wt(t0 + 11), Wt(t0 + 12), w.tn, M, C, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.tn, C, Wt(t0 + 13), C, C, nullptr, nullptr, w.qkv, C, M, wt, stream)) return 1;
-        if (gemm(a.context, ctx, Wt(t0 + 14), ctx, 2 * C, nullptr, nullptr, w.kv, 2 * C, (int64_t)N * a.T, wt, stream)) return 1;
+        if (gemm(w.tn, C, Wt(t0 + 13), C, C, nullptr, nullptr, w.qkv, C, M, stream, ACT_NONE, wt)) return 1;
+        if (gemm(a.context, ctx, Wt(t0 + 14), ctx, 2 * C, nullptr, nullptr, w.kv, 2 * C, (int64_t)N * a.T, stream, ACT_NONE, wt)) return 1;
         SoarUnetAttnArgs x2{};
         x2.q = w.qkv; x2.k = w.kv; x2.v = w.kv + C; x2.out = w.ao;
         x2.ldq = C; x2.ldk = x2.ldv = 2 * C; x2.ldo = C;
         x2.B = N; x2.Lq = (int)hw; x2.Lk = a.T; x2.heads = heads; x2.hd = hd; x2.scale = scale;
         if (a.ip_tokens) {
-            if (gemm(a.ip_tokens, ctx, Wt(t0 + 16), ctx, 2 * C, nullptr, nullptr, w.kvip, 2 * C, (int64_t)N * a.n_ip, wt, stream)) return 1;
+            if (gemm(a.ip_tokens, ctx, Wt(t0 + 16), ctx, 2 * C, nullptr, nullptr, w.kvip, 2 * C, (int64_t)N * a.n_ip, stream, ACT_NONE, wt)) return 1;
             x2.k2 = w.kvip; x2.v2 = w.kvip + C; x2.ldk2 = x2.ldv2 = 2 * C; x2.Lk2 = a.n_ip; x2.w2 = a.ip_weight;
         }
-        if (launch_kv_attention(x2, stream)) return 1;
-        if (gemm(w.ao, C, Wt(o), C, C, Wt(o + 1), w.tx, w.tx, C, M, wt, stream)) return 1;
+        if (launch_kv_attention(x2, 64, false, "unet attention", stream)) return 1;
+        if (gemm(w.ao, C, Wt(o), C, C, Wt(o + 1), w.tx, w.tx, C, M, stream, ACT_NONE, wt)) return 1;
         if (probe(code + 2, w.tx, (size_t)M * C)) return 1;
         // GEGLU feed-forward
         if (layer_norm(w.tx, Wt(o + 2), Wt(o + 3), w.tn, M, C, 1e-5f, ACT_NONE, stream)) return 1;
-        if (gemm(w.tn, C, Wt(o + 4), C, 8 * C, Wt(o + 5), nullptr, w.ff, 8 * C, M, wt, stream)) return 1;
+        if (gemm(w.tn, C, Wt(o + 4), C, 8 * C, Wt(o + 5), nullptr, w.ff, 8 * C, M, stream, ACT_NONE, wt)) return 1;
         hipLaunchKernelGGL(unet_geglu_kernel, dim3(blocks(M * 4 * C)), dim3(256), 0, stream, w.ff, w.gg, M * 4 * C, 4 * C);
         SOAR_LAUNCH_OK("unet_geglu", stream, 0);
-        if (gemm(w.gg, 4 * C, Wt(o + 6), 4 * C, C, Wt(o + 7), w.tx, w.tx, C, M, wt, stream)) return 1;
+        if (gemm(w.gg, 4 * C, Wt(o + 6), 4 * C, C, Wt(o + 7), w.tx, w.tx, C, M, stream, ACT_NONE, wt)) return 1;
         if (probe(code + 3, w.tx, (size_t)M * C)) return 1;
-        if (gemm(w.tx, C, Wt(o + 8), C, C, Wt(o + 9), x, x, C, M, wt, stream)) return 1;
+        if (gemm(w.tx, C, Wt(o + 8), C, C, Wt(o + 9), x, x, C, M, stream, ACT_NONE, wt)) return 1;
         return probe(code + 4, x, (size_t)M * C);
     };
 
@@ -660,7 +616,7 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
 int soar_unet_attention(const SoarUnetAttnArgs *args, void *stream_)
 {
     if (!args) { set_error("soar_unet_attention: NULL args"); return 1; }
-    return launch_kv_attention(*args, static_cast<hipStream_t>(stream_));
+    return launch_kv_attention(*args, 64, false, "unet attention", static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""The multi-view diffusion UNet of the SDS guidance on HIP kernels (csrc/unet.hip, csrc/attention.h): ImageDream's
+"""The multi-view diffusion UNet of the SDS guidance on HIP kernels (csrc/unet.hip, csrc/attention.hip): ImageDream's
 ``sd-v2.1-base-4view-ipmv`` denoiser, forward only, in float32 or -- ``precision="bf16"`` / ``"f16"`` -- with every matrix product
 on the 16-bit matrix core.
 
@@ -355,7 +355,7 @@ class MultiviewUNet(nn.Module):
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None, k2: Optional[torch.Tensor] = None,
               v2: Optional[torch.Tensor] = None, w2: float = 1.0) -> torch.Tensor:
-    """The attention kernel by itself (csrc/attention.h): q ``[B,Lq,heads hd]``, k, v ``[B,Lk,heads hd]`` (rows may be views into wider
+    """The attention kernel by itself (csrc/attention.hip): q ``[B,Lq,heads hd]``, k, v ``[B,Lk,heads hd]`` (rows may be views into wider
     rows: the last axis contiguous, pitches multiples of 4) -> ``softmax(scale q k^T) v`` per head ``[B,Lq,heads hd]``, plus ``w2``
     times the same with ``k2, v2 [B,Lk2,heads hd]``."""
     ts = [q, k, v] + ([k2, v2] if k2 is not None else [])

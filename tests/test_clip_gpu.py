@@ -1,4 +1,4 @@
-"""The SDS guidance's conditioning on the device (soar_amd/clip.py, csrc/clip.hip, csrc/attention.h) against the
+"""The SDS guidance's conditioning on the device (soar_amd/clip.py, csrc/clip.hip, csrc/attention.hip) against the
 plain-torch restatement of tests/clip_ref.py in float64.
 
 Tolerance, measured not fixed (the bar of tests/test_sam_gpu.py and tests/test_unet_gpu.py): for every compared tensor ``e32`` is the

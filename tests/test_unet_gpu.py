@@ -1,4 +1,4 @@
-"""The multi-view diffusion UNet on the device (soar_amd/unet.py, csrc/unet.hip, csrc/attention.h) against the
+"""The multi-view diffusion UNet on the device (soar_amd/unet.py, csrc/unet.hip, csrc/attention.hip) against the
 plain-torch restatement of tests/unet_ref.py in float64.
 
 Tolerance, measured not fixed (the bar of tests/test_sam_gpu.py): for every compared tensor ``e32`` is the distance of the restatement
