@@ -66,7 +66,9 @@ extern "C" {
  * (+ SoarUnetConfig, SoarUnetArgs, SoarUnetAttnArgs): the SDS guidance's multi-view diffusion UNet.  soar_clip_weights_bytes /
  * _pack_weights / _workspace_bytes / _preprocess / _forward / _attention and soar_resampler_weights_bytes / _pack_weights /
  * _workspace_bytes / _forward (+ SoarClipConfig, SoarClipArgs, SoarClipAttnArgs, SoarResamplerConfig, SoarResamplerArgs): the
- * guidance's conditioning, CLIP's two encoders and the image-token Resampler. */
+ * guidance's conditioning, CLIP's two encoders and the image-token Resampler.  soar_attention16: soar_unet_attention's /
+ * soar_clip_attention's attention on the 16-bit matrix core (SoarUnetConfig.attn_precision, SoarClipConfig.attn_precision and
+ * SoarResamplerConfig.attn_precision use it). */
 #define SOAR_HIP_ABI_VERSION 8
 
 /* Mirrors GaussianRasterizationSettings (DGR/diff_gaussian_rasterization/__init__.py:267-284) and the
@@ -1998,6 +2000,8 @@ typedef struct SoarUnetConfig {
     int32_t channel_mult[SOAR_UNET_MAX_LEVELS], attention[SOAR_UNET_MAX_LEVELS];
     int32_t context_dim, camera_dim, with_ip, head_channels, n_view;
     int32_t precision;             /* of the products' operands: 0 float32 (what a zero-initialised struct asks for), 1 bf16, 2 f16 */
+    int32_t attn_precision;        /* of the attentions' operands, independent of `precision`: 0 float32 (what a zero-initialised
+                                      struct asks for), 1 bf16, 2 f16: soar_attention16's kernel and contract */
 } SoarUnetConfig;
 /* The packed weights: `count` contiguous float32 device tensors of sizes[i] floats in the order of soar_amd.unet.tensor_keys (ldm's
  * layouts; a size that is not the layout's is refused, naming the index), copied, the 3 x 3 convolutions re-laid as [Cout][tap][Cin]
@@ -2006,7 +2010,10 @@ typedef struct SoarUnetConfig {
  * rounded to nearest even, its start still 16-byte aligned; biases, norm gains and the rest stay float32.  The sources are the same
  * float32 tensors; `bytes` shrinks, `count` and `floats` do not change.  soar_unet_forward then runs every product on the 16-bit
  * matrix core with float32 accumulation, its activations rounded as they are loaded; activations in memory, GroupNorm, LayerNorm,
- * attention, inputs, outputs and probes stay float32, and the bit-exact promises below hold for each precision. */
+ * attention, inputs, outputs and probes stay float32, and the bit-exact promises below hold for each precision.
+ * attn_precision != 0: both attentions of every transformer run as soar_attention16 (q scale, k, v and p rounded to the type inside
+ * the kernel, every sum float32); it changes neither the packed weights nor the workspace, and the bit-exact promises hold for each
+ * value.  A value outside 0 .. 2 is refused, naming the number. */
 int soar_unet_weights_bytes(const SoarUnetConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
 int soar_unet_pack_weights(const SoarUnetConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
                            size_t packed_bytes, void *stream);
@@ -2048,6 +2055,15 @@ typedef struct SoarUnetAttnArgs {
     float scale, w2;
 } SoarUnetAttnArgs;
 int soar_unet_attention(const SoarUnetAttnArgs *args, void *stream);
+/* The same attention on the 16-bit matrix core.  type: 1 bf16, 2 f16; hd a multiple of 4 up to 96; causal != 0: key j counts for query
+ * i when j <= i (needs one key set and Lq = Lk).  Everything in memory stays float32.  Inside the kernel q * scale (computed in
+ * float32), k and v are rounded to the type, nearest even; the scores are v_mfma_f32_32x32x16_{bf16,f16} sums in float32; the masks,
+ * the running maximum, p = expf(s - m) and the running sum l (of the unrounded p) are float32 as in soar_unet_attention; p is rounded
+ * to the type only as the operand of p v, which accumulates in float32; 1 / l, the w2 combination and the store are float32.
+ * Operands that overflow or are denormal in the type are outside the contract.  No atomics; a (batch, head, 128-query tile)'s result
+ * does not depend on the rest of the launch; two runs give the same bits.  Every refusal (a type outside 1 .. 2 and all of
+ * soar_unet_attention's) comes before any launch. */
+int soar_attention16(const SoarUnetAttnArgs *args, int32_t type, int32_t causal, void *stream);
 
 /* ---- The SDS guidance's conditioning, forward only, float32 (clip.hip, attention.hip, soar_amd/clip.py) ----
  * One pre-LN transformer tower serves CLIP's text encoder (causal mask; token + position embedding in front) and its ViT image
@@ -2063,10 +2079,19 @@ typedef struct SoarClipConfig {
     int32_t width, heads, layers, mlp, tokens;
     int32_t vocab;                     /* text */
     int32_t patch, grid;               /* vision: the image is grid patch pixels a side */
+    int32_t precision;                 /* of the products' operands: 0 float32 (what a zero-initialised struct asks for), 1 bf16, 2 f16 */
+    int32_t attn_precision;            /* of the attention's operands, independent of `precision`: 0 float32, 1 bf16, 2 f16
+                                          (soar_attention16's kernel and contract) */
 } SoarClipConfig;
 /* The packed weights: `count` contiguous float32 device tensors of sizes[i] floats in the order of soar_amd.clip.tower_keys (open_clip's
  * layouts: q | k | v as one in_proj), copied; the patch convolution's rows are padded from 3 patch^2 to a multiple of 8 with zeros.
- * floats (or NULL): the sum of the sizes.  packed: 256-byte aligned. */
+ * floats (or NULL): the sum of the sizes.  packed: 256-byte aligned.
+ * precision != 0: every tensor that is a product's B operand (the patch convolution, in_proj, out_proj, c_fc and c_proj weights) is
+ * laid as bf16 / f16, rounded to nearest even, its start still 16-byte aligned; the token table, the class and position rows, biases
+ * and norm gains stay float32.  The sources are the same float32 tensors; `bytes` shrinks, `count` and `floats` do not change, nor
+ * does the workspace.  soar_clip_forward then runs every product on the 16-bit matrix core with float32 accumulation, its
+ * activations rounded as they are loaded; everything in memory stays float32.  attn_precision != 0: the attention runs as
+ * soar_attention16.  The bit-exact promises below hold for every pair of values; one outside 0 .. 2 is refused, naming the number. */
 int soar_clip_weights_bytes(const SoarClipConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
 int soar_clip_pack_weights(const SoarClipConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
                            size_t packed_bytes, void *stream);
@@ -2109,6 +2134,8 @@ int soar_clip_attention(const SoarClipAttnArgs *args, void *stream);
  * multiples of 8, dim_head a multiple of 4 up to 96.  Tensors in the order of soar_amd.clip.resampler_keys. */
 typedef struct SoarResamplerConfig {
     int32_t dim, depth, heads, dim_head, queries, emb, out, ff;
+    int32_t precision, attn_precision; /* as SoarClipConfig's: the B operands are proj_in, proj_out, to_q, to_kv, to_out and the two
+                                          feed-forward matrices; the latents, biases and norm gains stay float32 */
 } SoarResamplerConfig;
 int soar_resampler_weights_bytes(const SoarResamplerConfig *cfg, size_t *bytes, int32_t *count, size_t *floats);
 int soar_resampler_pack_weights(const SoarResamplerConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,

@@ -1,5 +1,7 @@
 """The SDS guidance's conditioning on HIP kernels (csrc/clip.hip, csrc/attention.hip): CLIP's text encoder, its ViT image
-encoder and IP-Adapter's image-token ``Resampler`` as ImageDream ships them, forward only, in float32.
+encoder and IP-Adapter's image-token ``Resampler`` as ImageDream ships them, forward only, in float32 or -- ``precision="bf16"`` /
+``"f16"`` -- with every matrix product on the 16-bit matrix core and, independently -- ``attention_precision`` -- the
+attention there too.
 
 ``ClipTextEncoder(state_dict)`` and ``ClipImageEncoder(state_dict)`` take transformers' or open_clip's keys (detected from the keys, under
 their usual prefixes); ``Resampler(state_dict)`` takes IP-Adapter's, with or without ``image_embed.``.  Other keys are ignored, a missing
@@ -26,6 +28,7 @@ from torch import nn
 
 from . import hip_lib
 from .hip_lib import _bytes, _stream, _workspace, check
+from .unet import precision_code
 
 # the twelve tensors of a block in the packed order (csrc/clip.hip clip_plan): canonical name -> transformers' name
 _BLOCK = [("ln_1.weight", "layer_norm1.weight"), ("ln_1.bias", "layer_norm1.bias"), ("attn.in_proj_weight", None), ("attn.in_proj_bias", None),
@@ -114,9 +117,19 @@ def _count_blocks(sd, pre: str, hf: bool) -> int:
 
 class _Packed(nn.Module):
     """A network whose weights are one frozen flat float32 buffer (``weights``: the tensors of the packed order one behind the other;
-    move the module with ``.to(device)``), packed for the kernels once per device on first use."""
+    move the module with ``.to(device)``), packed for the kernels once per device on first use.
+
+    ``precision``: ``"f32"`` (the default), ``"bf16"`` or ``"f16"``.  With a 16-bit precision the module's packed copy holds the
+    linear layers' (and the patch convolution's) weights rounded to that type and every product rounds its activations to it as they
+    are loaded, accumulating in float32.  ``attention_precision``, independently: the attention rounds ``q scale``, ``k``, ``v`` and
+    the softmax's ``p`` (as the operand of ``p v`` only) to the type inside the kernel.  ``weights``, embeddings, biases, norms, the
+    softmax, everything in memory and the probes stay float32, and what the float32 path promises bit for bit holds as well."""
     who = ""
     _pack_fn = _bytes_fn = ""
+
+    def _precisions(self, precision: str, attention_precision: str) -> None:
+        self._codes = (precision_code(self.who, "precision", precision), precision_code(self.who, "attention_precision", attention_precision))
+        self.precision, self.attention_precision = precision, attention_precision
 
     def _set_weights(self, tensors: List[torch.Tensor], names: List[str]) -> None:
         L = hip_lib.lib()
@@ -172,6 +185,7 @@ class _Tower(_Packed):
             raise ValueError(f"{self.who}: {layers} layers: at most {hip_lib.CLIP_MAX_LAYERS}")
         c = hip_lib.SoarClipConfig()
         c.kind, c.width, c.heads, c.layers, c.mlp, c.tokens, c.vocab, c.patch, c.grid = kind, W, heads, layers, mlp, tokens, vocab, patch, grid
+        c.precision, c.attn_precision = self._codes
         self._c = c
         self.cfg = dict(width=W, heads=heads, head_dim=W // heads, layers=layers, mlp=mlp, tokens=tokens)
 
@@ -214,12 +228,13 @@ class ClipTextEncoder(_Tower):
 
     ``skip_last``: final blocks not run -- default 0 for transformers' layout (SD-2.1's converted encoder has 23 layers), 1 for
     open_clip's (``layer="penultimate"`` of 24).  ``heads``: default width / 64.  ``hidden_act``: what the checkpoint's configuration
-    says; anything but ``"gelu"`` is refused."""
+    says; anything but ``"gelu"`` is refused.  ``precision``, ``attention_precision``: ``"f32"`` (default), ``"bf16"``, ``"f16"``."""
     who = "ClipTextEncoder"
 
     def __init__(self, state_dict: Mapping[str, torch.Tensor], skip_last: Optional[int] = None, heads: Optional[int] = None,
-                 hidden_act: str = "gelu"):
+                 hidden_act: str = "gelu", precision: str = "f32", attention_precision: str = "f32"):
         super().__init__()
+        self._precisions(precision, attention_precision)
         sd = state_dict
         pre = _prefix(sd, "embeddings.token_embedding.weight")
         hf = pre is not None
@@ -279,12 +294,14 @@ def encode_prompts(encoder: ClipTextEncoder, prompt_ids: torch.Tensor, negative_
 class ClipImageEncoder(_Tower):
     """CLIP's ViT: ``forward(images) -> [B, 1 + grid^2, width]``, the hidden states of all tokens (class token first) -- without
     ``visual.proj``: the Resampler takes hidden states.  ``skip_last`` final blocks are not run; ``post_norm``: ``ln_post`` on all
-    tokens.  ``heads``: default width / 80 when width is 1280 (ViT-H), else width / 64."""
+    tokens.  ``heads``: default width / 80 when width is 1280 (ViT-H), else width / 64.  ``precision``, ``attention_precision``:
+    ``"f32"`` (default), ``"bf16"``, ``"f16"``."""
     who = "ClipImageEncoder"
 
     def __init__(self, state_dict: Mapping[str, torch.Tensor], skip_last: int = 0, post_norm: bool = False, heads: Optional[int] = None,
-                 hidden_act: str = "gelu"):
+                 hidden_act: str = "gelu", precision: str = "f32", attention_precision: str = "f32"):
         super().__init__()
+        self._precisions(precision, attention_precision)
         sd = state_dict
         pre = _prefix(sd, "embeddings.patch_embedding.weight")       # under vision_model., or bare as CLIPVisionModel saves it
         hf = pre is not None
@@ -360,12 +377,14 @@ def _resampler_prefix(sd) -> str:
 
 class Resampler(_Packed):
     """IP-Adapter's ``Resampler`` as ImageDream ships it (``image_embed.*``): ``forward(x [B, n, emb]) -> [B, queries, out]``.
-    ``dim_head`` is what no shape shows; everything else is read from the shapes."""
+    ``dim_head`` is what no shape shows; everything else is read from the shapes.  ``precision``, ``attention_precision``: ``"f32"``
+    (default), ``"bf16"``, ``"f16"``."""
     who = "Resampler"
     _pack_fn, _bytes_fn = "soar_resampler_pack_weights", "soar_resampler_weights_bytes"
 
-    def __init__(self, state_dict: Mapping[str, torch.Tensor], dim_head: int = 64):
+    def __init__(self, state_dict: Mapping[str, torch.Tensor], dim_head: int = 64, precision: str = "f32", attention_precision: str = "f32"):
         super().__init__()
+        self._precisions(precision, attention_precision)
         sd = state_dict
         pre = _resampler_prefix(sd)
         K = _Keys(self.who, sd)
@@ -383,6 +402,7 @@ class Resampler(_Packed):
             raise ValueError(f"{self.who}: {depth} layers: at most {hip_lib.CLIP_MAX_LAYERS}")
         c = hip_lib.SoarResamplerConfig()
         c.dim, c.depth, c.heads, c.dim_head, c.queries, c.emb, c.out, c.ff = dim, depth, inner // int(dim_head), int(dim_head), nq, emb, out, ff
+        c.precision, c.attn_precision = self._codes
         self._c = c
         self.cfg = dict(dim=dim, depth=depth, heads=c.heads, dim_head=int(dim_head), queries=nq, emb=emb, out=out, ff=ff)
         for name, shape in resampler_keys(self.cfg):
@@ -448,10 +468,13 @@ class ImageTokens(nn.Module):
         return cond, torch.zeros_like(cond)
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None, causal: bool = False) -> torch.Tensor:
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None, causal: bool = False,
+              precision: str = "f32") -> torch.Tensor:
     """The towers' attention kernel by itself (csrc/attention.hip): q ``[B, Lq, heads hd]``, k, v ``[B, Lk, heads hd]`` (rows may be views
     into wider rows: the last axis contiguous, pitches multiples of 4), hd a multiple of 4 up to 96 -> ``softmax(scale q k^T) v`` per
-    head; ``causal``: key j counts for query i when j <= i."""
+    head; ``causal``: key j counts for query i when j <= i.  ``precision="bf16"`` / ``"f16"``: the 16-bit kernel (``soar_attention16``;
+    ``soar_amd.unet.attention`` states its rounding rule); tensors stay float32."""
+    code = precision_code("attention", "precision", precision)
     for t in (q, k, v):
         _need_hip("attention", "q, k, v", t, q.device)
         if t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != q.shape[0] or t.shape[2] != q.shape[2] or t.stride(2) != 1 or \
@@ -466,5 +489,11 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
     a.B, a.Lq, a.Lk, a.heads, a.hd, a.causal = B, Lq, k.shape[1], heads, hd, int(causal)
     a.scale = float(hd) ** -0.5 if scale is None else float(scale)
     with torch.cuda.device(q.device):
-        check(hip_lib.lib().soar_clip_attention(C.byref(a), _stream(q.device)), "soar_clip_attention")
+        if code:
+            u = hip_lib.SoarUnetAttnArgs()
+            u.q, u.k, u.v, u.out, u.ldq, u.ldk, u.ldv, u.ldo = a.q, a.k, a.v, a.out, a.ldq, a.ldk, a.ldv, a.ldo
+            u.B, u.Lq, u.Lk, u.heads, u.hd, u.scale = a.B, a.Lq, a.Lk, a.heads, a.hd, a.scale
+            check(hip_lib.lib().soar_attention16(C.byref(u), code, int(causal), _stream(q.device)), "soar_attention16")
+        else:
+            check(hip_lib.lib().soar_clip_attention(C.byref(a), _stream(q.device)), "soar_clip_attention")
     return out

@@ -17,6 +17,11 @@
 // The head dimension is padded to HDP (32, 64 or 96) with zeros in LDS only.  What a kernel keeps to itself: where K and V rows come
 // from (its tile loader and LDS layout), its workgroup and grid, and what it adds to or masks from a score.
 // No atomics; a (batch, head, query tile)'s sums do not depend on the rest of the launch.
+//
+//   kv_attn16_kernel       kv_attn_kernel on v_mfma_f32_32x32x16_{bf16,f16} (the contract is attention.h's): the same
+//                          sources, masks, second key set and orientation; q scale, k and v rounded to the type (nearest even) on their
+//                          way into registers and LDS, p rounded only as the operand of p v, every sum and the softmax in float32.
+//                          Its tile step is attn_tile16; attn_store and mfma_row are shared, the C / D layout being the same
 #include "attention.h"
 #include "conv_gemm.h"
 
@@ -271,6 +276,178 @@ __global__ void __launch_bounds__(256) kv_attn_kernel(SoarUnetAttnArgs a)
     attn_store<HDP>(a.out + ((size_t)b * a.Lq + qi) * a.ldo + head * a.hd, total, 1.f, a.hd, h);
 }
 
+// ---- 16-bit operands ----------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// float -> T is the compiler's conversion, which rounds to nearest even (v_cvt_pk_bf16_f32, v_cvt_f16_f32)
+template <typename T> struct Op16;
+template <> struct Op16<__bf16> {
+    typedef bf16x8 v8;
+    typedef __bf16 v4 __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct Op16<_Float16> {
+    typedef f16x8 v8;
+    typedef _Float16 v4 __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
+// LDS row pitches in 16-bit elements.  K is [key][channel], pitch HDP + 8: 80, 144 or 208 bytes, an ODD number (5, 9, 13) of 16-byte
+// slots.  V is transposed, [channel][key position], pitch 32 + 8: 80 bytes, five slots.  Every fragment is one ds_read_b128 of lane
+// (i, h) at slot odd (row0 + i) + 2 step + h.  That instruction is served in groups of 16 lanes of one h whose i cover every residue
+// modulo 16 ({0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}); a bank row is 16 slots wide and i -> odd i mod 16 is one-to-one, so a
+// group's 16 lanes hit 16 different slots: conflict-free.  The staging writes are ds_write_b64 (groups of 16 consecutive lanes, 32
+// banks): K's group is two keys' 64 contiguous bytes, pitch 20 / 4 / 20 banks apart (2-way on 4 / 12 / 4 of the 16 banks); V's group
+// is 8 key positions' 64 bytes of two channel quads 320 bytes = 16 banks apart: conflict-free.
+constexpr int KPAD16 = 8;
+constexpr int VPITCH16 = AK + 8;
+// where key kk of a tile lies in a V^T row: the k order in which the score registers, converted pairwise, are the P^T operand --
+// element j of lane half h of step s is key 16 s + 8 (j >> 2) + 4 h + (j & 3), and sits at position 16 s + 8 h + j
+__device__ __forceinline__ int vt_pos(int kk) { return (kk & 16) + 8 * ((kk >> 2) & 1) + 4 * ((kk >> 3) & 1) + (kk & 3); }
+
+// the lane's query, scaled in float32 and then rounded to T, as the B operand of the S^T product: step c holds channels
+// 16 c + 8 h .. + 8 of `row`; zeros where there is no query or the channel is past hd
+template <typename T, int HDP>
+__device__ __forceinline__ void attn_query16(typename Op16<T>::v8 (&qreg)[HDP / 16], const float *row, bool valid, int hd, float scale, int h)
+{
+#pragma unroll
+    for (int c = 0; c < HDP / 16; c++)
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            const int d = c * 16 + h * 8 + 4 * g;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (valid && d < hd) v = *reinterpret_cast<const float4 *>(row + d);
+            qreg[c][4 * g] = (T)(v.x * scale); qreg[c][4 * g + 1] = (T)(v.y * scale);
+            qreg[c][4 * g + 2] = (T)(v.z * scale); qreg[c][4 * g + 3] = (T)(v.w * scale);
+        }
+}
+
+// attn_tile with 16-bit operands: K [key][channel] and V^T [channel][vt_pos(key)] of T in LDS.  The scores, the mask, m, corr, p and l
+// are float32 exactly as in attn_tile (l sums the unrounded p); p is rounded to T only as the operand of o += p v: registers
+// 8 s .. 8 s + 7 are the B fragment of step s as they stand.
+template <typename T, int HDP, class Score>
+__device__ __forceinline__ void attn_tile16(const T (*Ks)[HDP + KPAD16], const T (*Vt)[VPITCH16], const typename Op16<T>::v8 (&qreg)[HDP / 16],
+                                            int key0, int i, int h, Score score, float &m, float &l, f32x16 (&o)[HDP / 32])
+{
+    typedef typename Op16<T>::v8 v8;
+    constexpr int NC = HDP / 32;
+    f32x16 s;
+#pragma unroll
+    for (int e = 0; e < 16; e++) s[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < HDP / 16; c++) s = Op16<T>::mfma(*reinterpret_cast<const v8 *>(&Ks[i][c * 16 + h * 8]), qreg[c], s);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        s[e] = score(key0 + mfma_row(e, h), s[e]);
+        mx = fmaxf(mx, s[e]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mn = fmaxf(m, mx);
+    const float corr = expf(m - mn);                             // (0 at the first tile)
+    float sum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; e++) { s[e] = expf(s[e] - mn); sum += s[e]; }
+    sum += __shfl_xor(sum, 32);
+    l = l * corr + sum;
+    m = mn;
+    v8 p[2];
+#pragma unroll
+    for (int e = 0; e < 16; e++) p[e >> 3][e & 7] = (T)s[e];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+#pragma unroll
+        for (int e = 0; e < 16; e++) o[c][e] *= corr;
+#pragma unroll
+        for (int u = 0; u < 2; u++) o[c] = Op16<T>::mfma(*reinterpret_cast<const v8 *>(&Vt[c * 32 + i][u * 16 + h * 8]), p[u], o[c]);
+    }
+}
+
+// kv_attn_kernel's workgroup, grid, sources and masks.  Staging is through registers, one tile ahead: the next tile's global loads are
+// issued (and rounded) before this tile's products and written to LDS behind them.  K: eight threads a key, four channels each a pass
+// (as kv_attn_kernel).  V: thread (kg = tid & 7, cq = tid >> 3) takes keys 4 kg .. + 3 at channels 4 cq .. + 3, transposes the
+// 4 x 4 in registers and writes each channel's four keys (consecutive positions of vt_pos) as 8 bytes.
+template <typename T, int HDP, bool CAUSAL>
+__global__ void __launch_bounds__(256) kv_attn16_kernel(SoarUnetAttnArgs a)
+{
+    typedef typename Op16<T>::v8 v8;
+    typedef typename Op16<T>::v4 v4;
+    constexpr int NC = HDP / 32, KF = HDP / 32;                  // (K: HDP / 4 float4 a key over eight threads)
+    __shared__ __attribute__((aligned(16))) T Ks[AK][HDP + KPAD16], Vt[HDP][VPITCH16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, h = lane >> 5;
+    const int head = blockIdx.y, b = blockIdx.z;
+    const int qi = blockIdx.x * KVA_Q + wave * 32 + i;           // this lane's query
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+
+    v8 qreg[HDP / 16];
+    attn_query16<T, HDP>(qreg, a.q + ((size_t)b * a.Lq + qi) * a.ldq + head * a.hd, qi < a.Lq, a.hd, a.scale, h);
+    f32x16 total[NC];
+    attn_zero(total);
+
+    const int kr = tid >> 3, kf = tid & 7;                       // K staging: key of the tile, first float4
+    const int kg = tid & 7, cq = tid >> 3;                       // V staging: group of four keys, channel quad
+    const int vpos = vt_pos(4 * kg);
+
+    // one key / value set: its normalised result times wgt is added to total
+    auto run = [&](const float *kp, const float *vp, int64_t ldk, int64_t ldv, int nk, float wgt) {
+        float m = -INFINITY, l = 0.f;
+        f32x16 o[NC];
+        attn_zero(o);
+        int ntiles = (nk + AK - 1) / AK;
+        if (CAUSAL) {                                            // the workgroup's last query sees keys 0 .. itself
+            const int last = min(a.Lq, ((int)blockIdx.x + 1) * KVA_Q) - 1;
+            ntiles = min(ntiles, last / AK + 1);
+        }
+        v4 kreg[KF], vreg[4];
+        // tile kt, rounded, into registers; rows past the last key and channels past hd are zeros
+        auto fetch = [&](int kt) {
+#pragma unroll
+            for (int u = 0; u < KF; u++) {
+                const int j = kt * AK + kr, d = (kf + 8 * u) * 4;
+                float4 kk = zero4;
+                if (j < nk && d < a.hd) kk = *reinterpret_cast<const float4 *>(kp + ((size_t)b * nk + j) * ldk + head * a.hd + d);
+                kreg[u][0] = (T)kk.x; kreg[u][1] = (T)kk.y; kreg[u][2] = (T)kk.z; kreg[u][3] = (T)kk.w;
+            }
+            if (cq < HDP / 4) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int j = kt * AK + 4 * kg + u, d = cq * 4;
+                    float4 vv = zero4;
+                    if (j < nk && d < a.hd) vv = *reinterpret_cast<const float4 *>(vp + ((size_t)b * nk + j) * ldv + head * a.hd + d);
+                    vreg[0][u] = (T)vv.x; vreg[1][u] = (T)vv.y; vreg[2][u] = (T)vv.z; vreg[3][u] = (T)vv.w;
+                }
+            }
+        };
+        auto stash = [&]() {
+#pragma unroll
+            for (int u = 0; u < KF; u++) *reinterpret_cast<v4 *>(&Ks[kr][(kf + 8 * u) * 4]) = kreg[u];
+            if (cq < HDP / 4) {
+#pragma unroll
+                for (int ch = 0; ch < 4; ch++) *reinterpret_cast<v4 *>(&Vt[cq * 4 + ch][vpos]) = vreg[ch];
+            }
+        };
+        fetch(0);
+        for (int kt = 0; kt < ntiles; kt++) {
+            stash();
+            __syncthreads();
+            if (kt + 1 < ntiles) fetch(kt + 1);
+            // the tail of the last tile; the keys behind the query
+            attn_tile16<T, HDP>(Ks, Vt, qreg, kt * AK, i, h, [&](int j, float s) { return j < nk && (!CAUSAL || j <= qi) ? s : -INFINITY; }, m, l, o);
+            __syncthreads();
+        }
+        const float inv = 1.f / l;
+#pragma unroll
+        for (int c = 0; c < NC; c++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) total[c][e] += wgt * (o[c][e] * inv);
+    };
+    run(a.k, a.v, a.ldk, a.ldv, a.Lk, 1.f);
+    if (a.k2) run(a.k2, a.v2, a.ldk2, a.ldv2, a.Lk2, a.w2);
+
+    if (qi >= a.Lq) return;                                      // the tail of the last query tile
+    attn_store<HDP>(a.out + ((size_t)b * a.Lq + qi) * a.ldo + head * a.hd, total, 1.f, a.hd, h);
+}
+
 }  // namespace
 
 int launch_sam_attention(const float *qkv, const float *bias, const float *rel_h, const float *rel_w, float *out, int B, int gh, int gw,
@@ -295,7 +472,8 @@ int launch_sam_attention(const float *qkv, const float *bias, const float *rel_h
     return 0;
 }
 
-int launch_kv_attention(const SoarUnetAttnArgs &a, int hd_max, bool causal, const char *me, hipStream_t stream)
+// what both key / value launchers refuse; 0: launch, 1: refused (the error set), -1: B = 0, nothing to do
+static int check_kv_attention(const SoarUnetAttnArgs &a, int hd_max, bool causal, const char *me)
 {
     const int64_t C = (int64_t)a.heads * a.hd;
     if (a.B < 0 || a.B > 65535 || a.Lq < 1 || a.Lk < 1 || a.heads < 1 || a.heads > 65535 || a.hd < 4 || a.hd > hd_max || a.hd % 4 ||
@@ -303,7 +481,7 @@ int launch_kv_attention(const SoarUnetAttnArgs &a, int hd_max, bool causal, cons
         set_error("%s: bad sizes (B=%d <= 65535, Lq=%d, Lk=%d from 1, heads=%d, hd=%d: a multiple of 4 up to %d)", me, a.B, a.Lq, a.Lk, a.heads, a.hd, hd_max);
         return 1;
     }
-    if (a.B == 0) return 0;
+    if (a.B == 0) return -1;
     if (!a.q || !a.k || !a.v || !a.out || (!a.k2 != !a.v2) || (a.k2 && (a.Lk2 < 1 || (int64_t)a.B * a.Lk2 > (int64_t(1) << 30)))) {
         set_error("%s: NULL q, k, v or out, or a second key set without its values or with Lk2 = %d below 1", me, a.Lk2);
         return 1;
@@ -316,6 +494,12 @@ int launch_kv_attention(const SoarUnetAttnArgs &a, int hd_max, bool causal, cons
         return 1;
     }
     if (causal && (a.k2 || a.Lq != a.Lk)) { set_error("%s: a causal mask needs one key set and Lq = Lk (Lq=%d, Lk=%d)", me, a.Lq, a.Lk); return 1; }
+    return 0;
+}
+
+int launch_kv_attention(const SoarUnetAttnArgs &a, int hd_max, bool causal, const char *me, hipStream_t stream)
+{
+    if (const int rc = check_kv_attention(a, hd_max, causal, me)) return rc > 0;
     const dim3 grid((unsigned)((a.Lq + KVA_Q - 1) / KVA_Q), (unsigned)a.heads, (unsigned)a.B);
     void (*const kern[3][2])(SoarUnetAttnArgs) = {{kv_attn_kernel<32, false>, kv_attn_kernel<32, true>},
                                                   {kv_attn_kernel<64, false>, kv_attn_kernel<64, true>},
@@ -325,4 +509,31 @@ int launch_kv_attention(const SoarUnetAttnArgs &a, int hd_max, bool causal, cons
     return 0;
 }
 
+int launch_kv_attention16(const SoarUnetAttnArgs &a, int type, int hd_max, bool causal, const char *me, hipStream_t stream)
+{
+    if (type != WT_BF16 && type != WT_F16) { set_error("%s: the 16-bit attention's type must be 1 (bf16) or 2 (f16) (got %d)", me, type); return 1; }
+    if (const int rc = check_kv_attention(a, hd_max, causal, me)) return rc > 0;
+    const dim3 grid((unsigned)((a.Lq + KVA_Q - 1) / KVA_Q), (unsigned)a.heads, (unsigned)a.B);
+    void (*const kern[2][3][2])(SoarUnetAttnArgs) = {{{kv_attn16_kernel<__bf16, 32, false>, kv_attn16_kernel<__bf16, 32, true>},
+                                                      {kv_attn16_kernel<__bf16, 64, false>, kv_attn16_kernel<__bf16, 64, true>},
+                                                      {kv_attn16_kernel<__bf16, 96, false>, kv_attn16_kernel<__bf16, 96, true>}},
+                                                     {{kv_attn16_kernel<_Float16, 32, false>, kv_attn16_kernel<_Float16, 32, true>},
+                                                      {kv_attn16_kernel<_Float16, 64, false>, kv_attn16_kernel<_Float16, 64, true>},
+                                                      {kv_attn16_kernel<_Float16, 96, false>, kv_attn16_kernel<_Float16, 96, true>}}};
+    hipLaunchKernelGGL(kern[type - 1][(a.hd - 1) / 32][causal], grid, dim3(256), 0, stream, a);
+    SOAR_LAUNCH_OK("kv_attn16", stream, 0);
+    return 0;
+}
+
+int launch_attention(const SoarUnetAttnArgs &a, int type, int hd_max, bool causal, const char *me, hipStream_t stream)
+{
+    return type ? launch_kv_attention16(a, type, hd_max, causal, me, stream) : launch_kv_attention(a, hd_max, causal, me, stream);
+}
+
 }  // namespace soar
+
+extern "C" int soar_attention16(const SoarUnetAttnArgs *args, int32_t type, int32_t causal, void *stream)
+{
+    if (!args) { soar::set_error("soar_attention16: NULL args"); return 1; }
+    return soar::launch_kv_attention16(*args, type, 96, causal != 0, "soar_attention16", static_cast<hipStream_t>(stream));
+}

@@ -9,7 +9,10 @@
 //   clip_class_pos_kernel  the class row and the position embedding, in place on the tokens
 //   clip_repeat_kernel     the Resampler's latents, once per batch entry
 // Every linear layer is launch_conv_gemm (conv_gemm.h: gemm()): bias, the erf GELU and the residual are its epilogue.  Tokens are
-// [B][L][width].  No atomics; nothing depends on the batch: a sequence's result is the same bits alone and in any batch.
+// [B][L][width].  precision 1 (bf16) or 2 (f16) in either configuration: the products' weights are packed as 16-bit values and every
+// product runs on the 16-bit matrix core, its A operand rounded on load (conv_gemm16_kernel); attn_precision 1 or 2,
+// independently: the attention runs as kv_attn16_kernel (attention.h's contract).  Everything in memory stays float32.
+// No atomics; nothing depends on the batch: a sequence's result is the same bits alone and in any batch.
 #include "attention.h"
 #include "layer_norm.h"
 #include "net_weights.h"
@@ -35,11 +38,13 @@ Plan clip_plan(const SoarClipConfig &c)
 {
     Plan P;
     const size_t W = c.width, M = c.mlp;
+    P.half = c.precision != WT_F32;    // a product's B operand as 16-bit values
+    auto mat = [&](size_t n) { return P.add(n, 0, true); };
     if (c.kind == SOAR_CLIP_TEXT) {
         P.tok = P.add((size_t)c.vocab * W);
         P.pos = P.add((size_t)c.tokens * W);
     } else {
-        P.tok = P.pad_idx = P.add(W * patch_k(c), W * patch_kp(c));
+        P.tok = P.pad_idx = P.add(W * patch_k(c), W * patch_kp(c), true);
         P.pad_rows = c.width; P.pad_k = patch_k(c); P.pad_kp = patch_kp(c);
         P.cls = P.add(W);
         P.pos = P.add((size_t)c.tokens * W);
@@ -47,8 +52,8 @@ Plan clip_plan(const SoarClipConfig &c)
     }
     P.blocks = (int)P.off.size();
     for (int l = 0; l < c.layers; l++) {
-        P.add(W); P.add(W); P.add(3 * W * W); P.add(3 * W); P.add(W * W); P.add(W);
-        P.add(W); P.add(W); P.add(M * W); P.add(M); P.add(W * M); P.add(W);
+        P.add(W); P.add(W); mat(3 * W * W); P.add(3 * W); mat(W * W); P.add(W);
+        P.add(W); P.add(W); mat(M * W); P.add(M); mat(W * M); P.add(W);
     }
     P.fin = P.add(W); P.add(W);
     return P;
@@ -58,18 +63,26 @@ Plan resampler_plan(const SoarResamplerConfig &c)
 {
     Plan P;
     const size_t D = c.dim, I = (size_t)c.heads * c.dim_head, F = c.ff;
+    P.half = c.precision != WT_F32;
+    auto mat = [&](size_t n) { return P.add(n, 0, true); };
     P.add((size_t)c.queries * D);                                // latents
-    P.add(D * c.emb); P.add(D);                                  // proj_in
-    P.add((size_t)c.out * D); P.add(c.out);                      // proj_out
+    mat(D * c.emb); P.add(D);                                    // proj_in
+    mat((size_t)c.out * D); P.add(c.out);                        // proj_out
     P.add(c.out); P.add(c.out);                                  // norm_out
     P.blocks = (int)P.off.size();
     for (int l = 0; l < c.depth; l++) {
-        P.add(D); P.add(D); P.add(D); P.add(D); P.add(I * D); P.add(2 * I * D); P.add(D * I);
-        P.add(D); P.add(D); P.add(F * D); P.add(D * F);
+        P.add(D); P.add(D); P.add(D); P.add(D); mat(I * D); mat(2 * I * D); mat(D * I);
+        P.add(D); P.add(D); mat(F * D); mat(D * F);
     }
     return P;
 }
 
+bool check_precisions(int precision, int attn_precision, const char *me)
+{
+    if (precision < WT_F32 || precision > WT_F16) { set_error("%s: precision = %d: 0 f32, 1 bf16 or 2 f16", me, precision); return false; }
+    if (attn_precision < WT_F32 || attn_precision > WT_F16) { set_error("%s: attn_precision = %d: 0 f32, 1 bf16 or 2 f16", me, attn_precision); return false; }
+    return true;
+}
 bool check_clip(const SoarClipConfig *cp, const char *me)
 {
     if (!cp) { set_error("%s: NULL cfg", me); return false; }
@@ -91,7 +104,7 @@ bool check_clip(const SoarClipConfig *cp, const char *me)
         set_error("%s: need patch in 1 .. 64, grid in 1 .. 255 and tokens = 1 + grid^2 (patch=%d, grid=%d, tokens=%d)", me, c.patch, c.grid, c.tokens);
         return false;
     }
-    return true;
+    return check_precisions(c.precision, c.attn_precision, me);
 }
 bool check_clip_sizes(const SoarClipConfig &c, int B, int L, const char *me)
 {
@@ -115,13 +128,13 @@ bool check_resampler(const SoarResamplerConfig *cp, const char *me)
         set_error("%s: need 0 .. %d layers, 1 .. 65535 queries and out from 1 (depth=%d, queries=%d, out=%d)", me, SOAR_CLIP_MAX_LAYERS, c.depth, c.queries, c.out);
         return false;
     }
-    return true;
+    return check_precisions(c.precision, c.attn_precision, me);
 }
 
 // a linear layer on contiguous rows: y [M][Cout] = act(x [M][K] w[Cout][K]^T + bias) + res
-int linear(const float *x, const float *w, int K, int Cout, const float *bias, const float *res, float *y, int64_t M, int act, hipStream_t stream)
+int linear(const float *x, const float *w, int K, int Cout, const float *bias, const float *res, float *y, int64_t M, int act, int wtype, hipStream_t stream)
 {
-    return gemm(x, K, w, K, Cout, bias, res, y, Cout, M, stream, act);
+    return gemm(x, K, w, K, Cout, bias, res, y, Cout, M, stream, act, wtype);
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------------------
@@ -172,20 +185,24 @@ __global__ void __launch_bounds__(256) clip_repeat_kernel(const float *__restric
 }
 
 int attention(const float *q, const float *k, const float *v, float *out, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int B, int Lq, int Lk,
-              int heads, int hd, float scale, bool causal, const char *me, hipStream_t stream)
+              int heads, int hd, float scale, bool causal, int type, const char *me, hipStream_t stream)
 {
     SoarUnetAttnArgs s{};
     s.q = q; s.k = k; s.v = v; s.out = out; s.ldq = ldq; s.ldk = ldk; s.ldv = ldv; s.ldo = ldo;
     s.B = B; s.Lq = Lq; s.Lk = Lk; s.heads = heads; s.hd = hd; s.scale = scale;
-    return launch_kv_attention(s, 96, causal, me, stream);
+    return launch_attention(s, type, 96, causal, me, stream);
 }
 
 // ---- packing and probes, the same for the three networks ---------------------------------------------------------------------------
-int pack(const Plan &P, const float *const *tensors, const int64_t *sizes, int count, void *packed, size_t packed_bytes, void *stream_, const char *me)
+int pack(const Plan &P, int wtype, const float *const *tensors, const int64_t *sizes, int count, void *packed, size_t packed_bytes, void *stream_,
+         const char *me)
 {
     if (!sizes) { set_error("%s: NULL sizes", me); return 1; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     return pack_weights(P, tensors, sizes, count, packed, packed_bytes, stream, me, [&](int i, const float *src, float *dst) -> int {
+        if (P.half && P.mat[i])                                  // a product's B operand: 16-bit, a matrix as one long row; the patch rows padded
+            return i == P.pad_idx ? launch_conv_pack16(src, dst, P.pad_rows, P.pad_k, P.pad_kp, 1, wtype, stream)
+                                  : launch_conv_pack16(src, dst, 1, (int)P.n[i], (int)P.n[i], 1, wtype, stream);
         if (i != P.pad_idx || P.pad_kp == P.pad_k) return PACK_COPY;
         SOAR_HIP_OK(hipMemsetAsync(dst, 0, (size_t)P.pad_rows * P.pad_kp * sizeof(float), stream));    // rows of K floats, laid Kp apart behind zeros
         SOAR_HIP_OK(hipMemcpy2DAsync(dst, P.pad_kp * sizeof(float), src, P.pad_k * sizeof(float), P.pad_k * sizeof(float), P.pad_rows,
@@ -247,7 +264,7 @@ int soar_clip_pack_weights(const SoarClipConfig *cfg, const float *const *tensor
                            size_t packed_bytes, void *stream)
 {
     if (!check_clip(cfg, "soar_clip_pack_weights")) return 1;
-    return pack(clip_plan(*cfg), tensors, sizes, count, packed, packed_bytes, stream, "soar_clip_pack_weights");
+    return pack(clip_plan(*cfg), cfg->precision, tensors, sizes, count, packed, packed_bytes, stream, "soar_clip_pack_weights");
 }
 
 int soar_clip_workspace_bytes(const SoarClipConfig *cfg, int32_t B, int32_t L, size_t *bytes)
@@ -294,7 +311,7 @@ int soar_clip_forward(const SoarClipConfig *cfg, const void *packed, const SoarC
     auto Wt = [&](int i) { return base + P.off[i]; };
     ClipWs w;
     clip_carve(c, a.B, a.L, workspace, &w);
-    const int B = a.B, L = a.L, W = c.width, hd = W / c.heads;
+    const int B = a.B, L = a.L, W = c.width, hd = W / c.heads, wt = c.precision;
     const int64_t M = (int64_t)B * L;
     auto probe = [&](int code, const float *src) -> int {
         for (int i = 0; i < a.n_probes; i++)
@@ -308,7 +325,7 @@ int soar_clip_forward(const SoarClipConfig *cfg, const void *packed, const SoarC
         if (probe(SOAR_CLIP_PROBE_EMBED, w.x)) return 1;
     } else {
         // the patch product writes rows 1 .. of every image's tokens; the class row has no product row
-        if (gemm(a.patches, P.pad_kp, Wt(P.tok), P.pad_kp, W, nullptr, nullptr, w.x + W, W, L - 1, stream, ACT_NONE, WT_F32, B, L - 1, L)) return 1;
+        if (gemm(a.patches, P.pad_kp, Wt(P.tok), P.pad_kp, W, nullptr, nullptr, w.x + W, W, L - 1, stream, ACT_NONE, wt, B, L - 1, L)) return 1;
         hipLaunchKernelGGL(clip_class_pos_kernel, dim3(blocks(M * W / 4)), dim3(256), 0, stream, w.x, Wt(P.cls), Wt(P.pos), M * W / 4, L, W);
         SOAR_LAUNCH_OK("clip_class_pos", stream, 0);
         if (probe(SOAR_CLIP_PROBE_EMBED, w.x)) return 1;
@@ -319,13 +336,13 @@ int soar_clip_forward(const SoarClipConfig *cfg, const void *packed, const SoarC
     for (int l = 0; l < a.run_layers; l++) {
         const int t0 = P.blocks + l * BLOCK_TENSORS;
         if (layer_norm(w.x, Wt(t0), Wt(t0 + 1), w.tn, M, W, LN_EPS, ACT_NONE, stream)) return 1;
-        if (linear(w.tn, Wt(t0 + 2), W, 3 * W, Wt(t0 + 3), nullptr, w.qkv, M, ACT_NONE, stream)) return 1;
-        if (attention(w.qkv, w.qkv + W, w.qkv + 2 * W, w.ao, 3 * W, 3 * W, 3 * W, W, B, L, L, c.heads, hd, scale, text, "clip attention", stream)) return 1;
-        if (linear(w.ao, Wt(t0 + 4), W, W, Wt(t0 + 5), w.x, w.x, M, ACT_NONE, stream)) return 1;
+        if (linear(w.tn, Wt(t0 + 2), W, 3 * W, Wt(t0 + 3), nullptr, w.qkv, M, ACT_NONE, wt, stream)) return 1;
+        if (attention(w.qkv, w.qkv + W, w.qkv + 2 * W, w.ao, 3 * W, 3 * W, 3 * W, W, B, L, L, c.heads, hd, scale, text, c.attn_precision, "clip attention", stream)) return 1;
+        if (linear(w.ao, Wt(t0 + 4), W, W, Wt(t0 + 5), w.x, w.x, M, ACT_NONE, wt, stream)) return 1;
         if (probe(2 * l, w.x)) return 1;
         if (layer_norm(w.x, Wt(t0 + 6), Wt(t0 + 7), w.tn, M, W, LN_EPS, ACT_NONE, stream)) return 1;
-        if (linear(w.tn, Wt(t0 + 8), W, c.mlp, Wt(t0 + 9), nullptr, w.ff, M, ACT_GELU, stream)) return 1;
-        if (linear(w.ff, Wt(t0 + 10), c.mlp, W, Wt(t0 + 11), w.x, w.x, M, ACT_NONE, stream)) return 1;
+        if (linear(w.tn, Wt(t0 + 8), W, c.mlp, Wt(t0 + 9), nullptr, w.ff, M, ACT_GELU, wt, stream)) return 1;
+        if (linear(w.ff, Wt(t0 + 10), c.mlp, W, Wt(t0 + 11), w.x, w.x, M, ACT_NONE, wt, stream)) return 1;
         if (probe(2 * l + 1, w.x)) return 1;
     }
     if (a.final_norm) return layer_norm(w.x, Wt(P.fin), Wt(P.fin + 1), a.out, M, W, LN_EPS, ACT_NONE, stream);
@@ -337,7 +354,7 @@ int soar_clip_attention(const SoarClipAttnArgs *a, void *stream)
 {
     if (!a) { set_error("soar_clip_attention: NULL args"); return 1; }
     return attention(a->q, a->k, a->v, a->out, a->ldq, a->ldk, a->ldv, a->ldo, a->B, a->Lq, a->Lk, a->heads, a->hd, a->scale, a->causal != 0,
-                     "soar_clip_attention", static_cast<hipStream_t>(stream));
+                     WT_F32, "soar_clip_attention", static_cast<hipStream_t>(stream));
 }
 
 int soar_resampler_weights_bytes(const SoarResamplerConfig *cfg, size_t *bytes, int32_t *count, size_t *floats)
@@ -355,7 +372,7 @@ int soar_resampler_pack_weights(const SoarResamplerConfig *cfg, const float *con
                                 size_t packed_bytes, void *stream)
 {
     if (!check_resampler(cfg, "soar_resampler_pack_weights")) return 1;
-    return pack(resampler_plan(*cfg), tensors, sizes, count, packed, packed_bytes, stream, "soar_resampler_pack_weights");
+    return pack(resampler_plan(*cfg), cfg->precision, tensors, sizes, count, packed, packed_bytes, stream, "soar_resampler_pack_weights");
 }
 
 int soar_resampler_workspace_bytes(const SoarResamplerConfig *cfg, int32_t B, int32_t n, size_t *bytes)
@@ -387,7 +404,7 @@ int soar_resampler_forward(const SoarResamplerConfig *cfg, const void *packed, c
     auto Wt = [&](int i) { return base + P.off[i]; };
     ResWs w;
     resampler_carve(c, a.B, a.n, workspace, &w);
-    const int B = a.B, n = a.n, nq = c.queries, D = c.dim, I = c.heads * c.dim_head, keys = n + nq;
+    const int B = a.B, n = a.n, nq = c.queries, D = c.dim, I = c.heads * c.dim_head, keys = n + nq, wt = c.precision;
     const int64_t Mx = (int64_t)B * n, Ml = (int64_t)B * nq;
     auto probe = [&](int code, const float *src) -> int {
         for (int i = 0; i < a.n_probes; i++)
@@ -396,26 +413,26 @@ int soar_resampler_forward(const SoarResamplerConfig *cfg, const void *packed, c
     };
     hipLaunchKernelGGL(clip_repeat_kernel, dim3(blocks(Ml * D / 4)), dim3(256), 0, stream, Wt(0), w.lat, Ml * D / 4, (int64_t)nq * D / 4);
     SOAR_LAUNCH_OK("clip_repeat", stream, 0);
-    if (linear(a.x, Wt(1), c.emb, D, Wt(2), nullptr, w.xp, Mx, ACT_NONE, stream)) return 1;
+    if (linear(a.x, Wt(1), c.emb, D, Wt(2), nullptr, w.xp, Mx, ACT_NONE, wt, stream)) return 1;
     // q and k are each scaled by dim_head^-0.25 in the definition; here the query carries both factors
     const float s = 1.f / sqrtf(sqrtf((float)c.dim_head));
     for (int l = 0; l < c.depth; l++) {
         const int t0 = P.blocks + l * LAYER_TENSORS;
         if (layer_norm(w.xp, Wt(t0), Wt(t0 + 1), w.xn, Mx, D, LN_EPS, ACT_NONE, stream)) return 1;
         if (layer_norm(w.lat, Wt(t0 + 2), Wt(t0 + 3), w.ln, Ml, D, LN_EPS, ACT_NONE, stream)) return 1;
-        if (linear(w.ln, Wt(t0 + 4), D, I, nullptr, nullptr, w.q, Ml, ACT_NONE, stream)) return 1;
+        if (linear(w.ln, Wt(t0 + 4), D, I, nullptr, nullptr, w.q, Ml, ACT_NONE, wt, stream)) return 1;
         // k | v of the image tokens and of the latents into one buffer [B][n + nq][2 I]: one joint softmax, no concatenation
-        if (gemm(w.xn, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv, 2 * I, n, stream, ACT_NONE, WT_F32, B, n, keys)) return 1;
-        if (gemm(w.ln, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv + (size_t)n * 2 * I, 2 * I, nq, stream, ACT_NONE, WT_F32, B, nq, keys)) return 1;
-        if (attention(w.q, w.kv, w.kv + I, w.ao, I, 2 * I, 2 * I, I, B, nq, keys, c.heads, c.dim_head, s * s, false, "resampler attention", stream)) return 1;
-        if (linear(w.ao, Wt(t0 + 6), I, D, nullptr, w.lat, w.lat, Ml, ACT_NONE, stream)) return 1;
+        if (gemm(w.xn, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv, 2 * I, n, stream, ACT_NONE, wt, B, n, keys)) return 1;
+        if (gemm(w.ln, D, Wt(t0 + 5), D, 2 * I, nullptr, nullptr, w.kv + (size_t)n * 2 * I, 2 * I, nq, stream, ACT_NONE, wt, B, nq, keys)) return 1;
+        if (attention(w.q, w.kv, w.kv + I, w.ao, I, 2 * I, 2 * I, I, B, nq, keys, c.heads, c.dim_head, s * s, false, c.attn_precision, "resampler attention", stream)) return 1;
+        if (linear(w.ao, Wt(t0 + 6), I, D, nullptr, w.lat, w.lat, Ml, ACT_NONE, wt, stream)) return 1;
         if (probe(2 * l, w.lat)) return 1;
         if (layer_norm(w.lat, Wt(t0 + 7), Wt(t0 + 8), w.ln, Ml, D, LN_EPS, ACT_NONE, stream)) return 1;
-        if (linear(w.ln, Wt(t0 + 9), D, c.ff, nullptr, nullptr, w.ff, Ml, ACT_GELU, stream)) return 1;
-        if (linear(w.ff, Wt(t0 + 10), c.ff, D, nullptr, w.lat, w.lat, Ml, ACT_NONE, stream)) return 1;
+        if (linear(w.ln, Wt(t0 + 9), D, c.ff, nullptr, nullptr, w.ff, Ml, ACT_GELU, wt, stream)) return 1;
+        if (linear(w.ff, Wt(t0 + 10), c.ff, D, nullptr, w.lat, w.lat, Ml, ACT_NONE, wt, stream)) return 1;
         if (probe(2 * l + 1, w.lat)) return 1;
     }
-    if (linear(w.lat, Wt(3), D, c.out, Wt(4), nullptr, w.po, Ml, ACT_NONE, stream)) return 1;
+    if (linear(w.lat, Wt(3), D, c.out, Wt(4), nullptr, w.po, Ml, ACT_NONE, wt, stream)) return 1;
     return layer_norm(w.po, Wt(5), Wt(6), a.out, Ml, c.out, LN_EPS, ACT_NONE, stream);
 }
 

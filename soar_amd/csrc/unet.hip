@@ -10,7 +10,8 @@
 // Every matrix product (convolutions, linear layers: gemm()) is launch_conv_gemm (conv_gemm.h).  Activations are channels-last [N][H W][C].
 // SoarUnetConfig::precision 1 (bf16) or 2 (f16): the products' weights are packed as 16-bit values and every product runs on the
 // 16-bit matrix core, its A operand rounded on load (conv_gemm16_kernel); everything else, the activations in memory
-// included, stays float32.
+// included, stays float32.  SoarUnetConfig::attn_precision 1 or 2, independently: both attentions run as kv_attn16_kernel
+// (attention.h's contract).
 // No atomics; no sum's order depends on the batch: a group's result does not depend on the other groups.
 #include "attention.h"
 #include "layer_norm.h"
@@ -122,7 +123,7 @@ bool check_cfg(const SoarUnetConfig *cp, const char *me)
               c.model_channels <= 4096 && c.levels >= 1 && c.levels <= SOAR_UNET_MAX_LEVELS && c.num_res_blocks >= 1 && c.num_res_blocks <= 8 &&
               c.context_dim >= 8 && c.context_dim % 8 == 0 && c.camera_dim >= 0 && c.camera_dim % 8 == 0 && c.head_channels >= 4 &&
               c.head_channels <= 64 && c.head_channels % 4 == 0 && c.n_view >= 1 && c.n_view <= 64 && c.precision >= WT_F32 &&
-              c.precision <= WT_F16;
+              c.precision <= WT_F16 && c.attn_precision >= WT_F32 && c.attn_precision <= WT_F16;
     for (int l = 0; ok && l < c.levels; l++) {
         const int64_t ch = (int64_t)c.model_channels * c.channel_mult[l];
         ok = c.channel_mult[l] >= 1 && ch <= 8192 && ch % GN_GROUPS == 0 && ch % c.head_channels == 0;
@@ -130,8 +131,9 @@ bool check_cfg(const SoarUnetConfig *cp, const char *me)
     if (!ok)
         set_error("%s: a configuration the kernels cannot run (in %d <= 8, out %d, model_channels=%d, %d levels, %d ResBlocks a level, "
                   "context_dim=%d, camera_dim=%d: multiples of 8, head_channels=%d: a multiple of 4 up to 64, n_view=%d; every level's "
-                  "width a multiple of 32 and of head_channels; precision=%d: 0 f32, 1 bf16 or 2 f16)", me, c.in_channels, c.out_channels,
-                  c.model_channels, c.levels, c.num_res_blocks, c.context_dim, c.camera_dim, c.head_channels, c.n_view, c.precision);
+                  "width a multiple of 32 and of head_channels; precision=%d and attn_precision=%d: 0 f32, 1 bf16 or 2 f16)", me, c.in_channels,
+                  c.out_channels, c.model_channels, c.levels, c.num_res_blocks, c.context_dim, c.camera_dim, c.head_channels, c.n_view, c.precision,
+                  c.attn_precision);
     return ok;
 }
 
@@ -512,7 +514,7 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
         s.q = w.qkv; s.k = w.qkv + C; s.v = w.qkv + 2 * C; s.out = w.ao;
         s.ldq = s.ldk = s.ldv = 3 * C; s.ldo = C;
         s.B = N / c.n_view; s.Lq = s.Lk = (int)(c.n_view * hw); s.heads = heads; s.hd = hd; s.scale = scale;
-        if (launch_kv_attention(s, 64, false, "unet attention", stream)) return 1;
+        if (launch_attention(s, c.attn_precision, 64, false, "unet attention", stream)) return 1;
         if (gemm(w.ao, C, Wt(t0 + 9), C, C, Wt(t0 + 10), w.tx, w.tx, C, M, stream, ACT_NONE, wt)) return 1;
         if (probe(code + 1, w.tx, (size_t)M * C)) return 1;
         // attn2 per view: the text tokens, and the image tokens as a second key set
@@ -527,7 +529,7 @@ int soar_unet_forward(const SoarUnetConfig *cfg, const void *packed, const SoarU
             if (gemm(a.ip_tokens, ctx, Wt(t0 + 16), ctx, 2 * C, nullptr, nullptr, w.kvip, 2 * C, (int64_t)N * a.n_ip, stream, ACT_NONE, wt)) return 1;
             x2.k2 = w.kvip; x2.v2 = w.kvip + C; x2.ldk2 = x2.ldv2 = 2 * C; x2.Lk2 = a.n_ip; x2.w2 = a.ip_weight;
         }
-        if (launch_kv_attention(x2, 64, false, "unet attention", stream)) return 1;
+        if (launch_attention(x2, c.attn_precision, 64, false, "unet attention", stream)) return 1;
         if (gemm(w.ao, C, Wt(o), C, C, Wt(o + 1), w.tx, w.tx, C, M, stream, ACT_NONE, wt)) return 1;
         if (probe(code + 2, w.tx, (size_t)M * C)) return 1;
         // GEGLU feed-forward

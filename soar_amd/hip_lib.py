@@ -330,7 +330,8 @@ class SoarUnetConfig(C.Structure):
     """Mirror of ``struct SoarUnetConfig`` (include/soar_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("in_channels", "out_channels", "model_channels", "levels", "num_res_blocks")] + \
                [("channel_mult", C.c_int32 * UNET_MAX_LEVELS), ("attention", C.c_int32 * UNET_MAX_LEVELS)] + \
-               [(n, C.c_int32) for n in ("context_dim", "camera_dim", "with_ip", "head_channels", "n_view", "precision")]
+               [(n, C.c_int32) for n in ("context_dim", "camera_dim", "with_ip", "head_channels", "n_view", "precision",
+                                            "attn_precision")]
 
 
 class SoarUnetArgs(C.Structure):
@@ -354,7 +355,8 @@ CLIP_PROBE_EMBED, CLIP_PROBE_PRE = 1000000, 1000001
 
 class SoarClipConfig(C.Structure):
     """Mirror of ``struct SoarClipConfig`` (include/soar_hip.h)."""
-    _fields_ = [(n, C.c_int32) for n in ("kind", "width", "heads", "layers", "mlp", "tokens", "vocab", "patch", "grid")]
+    _fields_ = [(n, C.c_int32) for n in ("kind", "width", "heads", "layers", "mlp", "tokens", "vocab", "patch", "grid", "precision",
+                                           "attn_precision")]
 
 
 class SoarClipArgs(C.Structure):
@@ -371,7 +373,7 @@ class SoarClipAttnArgs(C.Structure):
 
 class SoarResamplerConfig(C.Structure):
     """Mirror of ``struct SoarResamplerConfig`` (include/soar_hip.h)."""
-    _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "heads", "dim_head", "queries", "emb", "out", "ff")]
+    _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "heads", "dim_head", "queries", "emb", "out", "ff", "precision", "attn_precision")]
 
 
 class SoarResamplerArgs(C.Structure):
@@ -621,6 +623,7 @@ SIGNATURES = {
     "soar_unet_workspace_bytes": (C.c_int, [C.POINTER(SoarUnetConfig)] + [C.c_int32] * 5 + [C.POINTER(C.c_size_t)]),
     "soar_unet_forward": (C.c_int, [C.POINTER(SoarUnetConfig), _vp, C.POINTER(SoarUnetArgs), _vp, C.c_size_t, _vp]),
     "soar_unet_attention": (C.c_int, [C.POINTER(SoarUnetAttnArgs), _vp]),
+    "soar_attention16": (C.c_int, [C.POINTER(SoarUnetAttnArgs), C.c_int32, C.c_int32, _vp]),
     "soar_clip_weights_bytes": (C.c_int, [C.POINTER(SoarClipConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
     "soar_clip_pack_weights": (C.c_int, [C.POINTER(SoarClipConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
     "soar_clip_workspace_bytes": (C.c_int, [C.POINTER(SoarClipConfig), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),

@@ -1,6 +1,7 @@
 """The multi-view diffusion UNet of the SDS guidance on HIP kernels (csrc/unet.hip, csrc/attention.hip): ImageDream's
 ``sd-v2.1-base-4view-ipmv`` denoiser, forward only, in float32 or -- ``precision="bf16"`` / ``"f16"`` -- with every matrix product
-on the 16-bit matrix core.
+on the 16-bit matrix core and, independently -- ``attention_precision="bf16"`` / ``"f16"`` -- both attentions of
+every transformer there too.
 
 ``MultiviewUNet(state_dict)`` takes ldm's ``openaimodel.UNetModel`` keys with MVDream's / ImageDream's additions (``camera_embed.*``,
 ``attn2.to_k_ip`` / ``to_v_ip``), with or without the prefix ``model.diffusion_model.``; other keys (the VAE, CLIP, ``image_embed.*``)
@@ -27,8 +28,15 @@ from .hip_lib import _bytes, _stream, _workspace, check
 PREFIX = "model.diffusion_model."
 # stages of a block a probe can name (include/soar_hip.h SoarUnetArgs)
 STAGES = {"res": 0, "attn1": 1, "attn2": 2, "ff": 3, "transformer": 4, "up": 5, "cat": 6, "res2": 7}
-# the operands of the matrix products (SoarUnetConfig.precision)
+# the operands of the matrix products (SoarUnetConfig.precision) and of the attentions (attn_precision; soar_attention16's type)
 PRECISIONS = {"f32": 0, "bf16": 1, "f16": 2}
+
+
+def precision_code(who: str, name: str, value) -> int:
+    """``PRECISIONS[value]``, or a ValueError naming the three choices."""
+    if not isinstance(value, str) or value not in PRECISIONS:
+        raise ValueError(f"{who}: {name} must be one of 'f32', 'bf16', 'f16' (got {value!r})")
+    return PRECISIONS[value]
 
 
 def _shape(sd, key: str, ndim: int) -> Tuple[int, ...]:
@@ -165,15 +173,21 @@ class MultiviewUNet(nn.Module):
 
     ``precision``: ``"f32"`` (the default), ``"bf16"`` or ``"f16"``.  With a 16-bit precision the packed copy holds the convolutions'
     and linear layers' weights rounded to that type and every product rounds its activations to it as they are loaded, accumulating
-    in float32; ``weights``, the activations in memory, the norms, the attention, inputs, outputs and probes stay float32, and what
-    the float32 path promises bit for bit (equal runs, groups independent of the batch, any strides of ``x``) holds as well."""
+    in float32; ``weights``, the activations in memory, the norms, inputs, outputs and probes stay float32, and what the float32
+    path promises bit for bit (equal runs, groups independent of the batch, any strides of ``x``) holds as well.
+
+    ``attention_precision``: ``"f32"`` (the default), ``"bf16"`` or ``"f16"``, independent of ``precision``.  With a 16-bit type
+    both attentions round ``q scale``, ``k``, ``v`` and the softmax's ``p`` (as the operand of ``p v`` only) to it inside the kernel
+    and run their two products on the 16-bit matrix core; the softmax, every sum and everything in memory stay float32
+    (``attention`` below states the rule), and the same bit-for-bit promises hold."""
 
     def __init__(self, state_dict: Mapping[str, torch.Tensor], num_head_channels: int = 64, ip_dim: int = 16, ip_weight: float = 1.0,
-                 n_view: int = 4, precision: str = "f32"):
+                 n_view: int = 4, precision: str = "f32", attention_precision: str = "f32"):
         super().__init__()
         if precision not in PRECISIONS:
             raise ValueError(f"MultiviewUNet: precision must be one of 'f32', 'bf16', 'f16' (got {precision!r})")
-        self.precision = precision
+        attn_code = precision_code("MultiviewUNet", "attention_precision", attention_precision)
+        self.precision, self.attention_precision = precision, attention_precision
         sd = strip_prefix(state_dict)
         cfg = infer_config(sd)
         cfg.update(num_head_channels=int(num_head_channels), ip_dim=int(ip_dim), ip_weight=float(ip_weight), n_view=int(n_view))
@@ -196,6 +210,7 @@ class MultiviewUNet(nn.Module):
             c.channel_mult[l], c.attention[l] = m, int(a)
         c.context_dim, c.camera_dim, c.with_ip = cfg["context_dim"], cfg["camera_dim"], int(cfg["with_ip"])
         c.head_channels, c.n_view, c.precision = cfg["num_head_channels"], cfg["n_view"], PRECISIONS[precision]
+        c.attn_precision = attn_code
         nb, cnt, nf = C.c_size_t(0), C.c_int32(0), C.c_size_t(0)
         check(hip_lib.lib().soar_unet_weights_bytes(C.byref(c), C.byref(nb), C.byref(cnt), C.byref(nf)), "soar_unet_weights_bytes")
         self._sizes = [int(np.prod(shape)) for _, shape in keys]
@@ -354,10 +369,15 @@ class MultiviewUNet(nn.Module):
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None, k2: Optional[torch.Tensor] = None,
-              v2: Optional[torch.Tensor] = None, w2: float = 1.0) -> torch.Tensor:
+              v2: Optional[torch.Tensor] = None, w2: float = 1.0, precision: str = "f32") -> torch.Tensor:
     """The attention kernel by itself (csrc/attention.hip): q ``[B,Lq,heads hd]``, k, v ``[B,Lk,heads hd]`` (rows may be views into wider
     rows: the last axis contiguous, pitches multiples of 4) -> ``softmax(scale q k^T) v`` per head ``[B,Lq,heads hd]``, plus ``w2``
-    times the same with ``k2, v2 [B,Lk2,heads hd]``."""
+    times the same with ``k2, v2 [B,Lk2,heads hd]``.
+
+    ``precision="bf16"`` / ``"f16"``: the 16-bit kernel (``soar_attention16``).  Tensors stay float32; inside, ``q scale`` (computed
+    in float32), ``k`` and ``v`` are rounded to the type, nearest even, the scores and the softmax are float32 (its sum runs over the
+    unrounded ``p``), and ``p`` is rounded only as the operand of ``p v``, which accumulates in float32."""
+    code = precision_code("attention", "precision", precision)
     ts = [q, k, v] + ([k2, v2] if k2 is not None else [])
     for t in ts:
         MultiviewUNet._need_hip("q, k, v", t, q.device)
@@ -375,5 +395,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
     if k2 is not None:
         a.k2, a.v2, a.ldk2, a.ldv2, a.Lk2 = k2.data_ptr(), v2.data_ptr(), k2.stride(1), v2.stride(1), k2.shape[1]
     with torch.cuda.device(q.device):
-        check(hip_lib.lib().soar_unet_attention(C.byref(a), _stream(q.device)), "soar_unet_attention")
+        if code:
+            check(hip_lib.lib().soar_attention16(C.byref(a), code, 0, _stream(q.device)), "soar_attention16")
+        else:
+            check(hip_lib.lib().soar_unet_attention(C.byref(a), _stream(q.device)), "soar_unet_attention")
     return out
