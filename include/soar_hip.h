@@ -928,6 +928,10 @@ int soar_selftest_conv_pack16(const float *w, void *fwd, int32_t Cout, int32_t C
 /* SoarConvGemmArgs carries no activation: the descriptor at either operand type (wtype 0 .. 2) with the epilogue's act (0 none, 1 exact
  * GELU, 2 ReLU): y = act(alpha (A B^T) + bias) + res */
 int soar_selftest_conv_gemm_act(const SoarConvGemmArgs *args, int32_t wtype, int32_t act, int32_t *tile_out, void *stream);
+/* ... and with the epilogue's PReLU: slope [Cout], one per output channel, or NULL (off).  Legal with act == 0 only (the
+ * launcher refuses the pair); then y = (v > 0 ? v : slope[co] v) + res with v = alpha (A B^T) + bias, at every wtype. */
+int soar_selftest_conv_gemm_slope(const SoarConvGemmArgs *args, int32_t wtype, int32_t act, const float *slope, int32_t *tile_out,
+                                  void *stream);
 
 /* ---- mesh export (mesh.hip, soar_amd/mesh.py; DESIGN.md "Mesh export").  Not part of the training step.
  * soar_tsdf_integrate: fuses n_views (1..64) rendered depth / opacity planes [n_views][H][W] into the TSDF of a dense grid
@@ -2153,6 +2157,78 @@ typedef struct SoarResamplerArgs {
 } SoarResamplerArgs;
 int soar_resampler_forward(const SoarResamplerConfig *cfg, const void *packed, const SoarResamplerArgs *args, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* ---- body keypoint detection (pose.hip, soar_amd/pose.py).  Preprocessing; forward only, float32.
+ * The BODY_25 network: a VGG front (conv1_1 .. conv4_2, three 2 x 2 max pools), conv4_3_CPM and conv4_4_CPM to `feat` features at 1/8
+ * resolution, then n_paf stages of the part-affinity branch (L2, 52 channels) and n_heat stages of the heat-map branch (L1, 26
+ * channels).  A stage is five blocks of three 3 x 3 convolutions (each with a PReLU; a block's output is the three outputs side by
+ * side), a 1 x 1 convolution with a PReLU and a 1 x 1 convolution to the maps.  Widths: c1 .. c4 the VGG's, cpm conv4_3_CPM's, w0 / m0
+ * the blocks' and the 1 x 1's in stage 0 of a branch, w1 / m1 in the later stages.  Every width is a multiple of 8.
+ * Tensors in the order of soar_amd.pose.layer_keys: per convolution weight [Cout][Cin][k][k], bias [Cout] and, where a PReLU follows,
+ * its slopes [Cout].  Stage inputs (the weights' Cin order): L2 stage 0 (features); L2 stage k (features, previous PAF); L1 stage 0
+ * (features, last PAF); L1 stage k (features, previous heat maps, last PAF). */
+#define SOAR_POSE_PAF 52
+#define SOAR_POSE_HEAT 26
+#define SOAR_POSE_PARTS 25
+#define SOAR_POSE_PAIRS 26
+#define SOAR_POSE_MAX_STAGES 8
+#define SOAR_POSE_MAX_PEAKS 32
+#define SOAR_POSE_MAX_PEOPLE 32
+typedef struct SoarPoseConfig {
+    int32_t c1, c2, c3, c4, cpm, feat, w0, w1, m0, m1, n_paf, n_heat;
+} SoarPoseConfig;
+/* The two sizing calls (bytes; *count: the tensors soar_pose_pack_weights takes). */
+int soar_pose_weights_size(const SoarPoseConfig *cfg, size_t *bytes, int32_t *count);
+int soar_pose_workspace_size(const SoarPoseConfig *cfg, int32_t B, int32_t H, int32_t W, size_t *bytes);
+int soar_pose_pack_weights(const SoarPoseConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
+                           size_t packed_bytes, void *stream);
+/* uint8 RGB [B][H][W][3] -> float32 BGR [B][H][W][3]: v / 256 - 0.5 */
+int soar_pose_preprocess(int32_t B, int32_t H, int32_t W, const uint8_t *rgb, float *bgr, void *stream);
+/* x: the image, [B][3][H][W] at x_stride (elements); H and W multiples of 16, at least 16.  stage_out[k]: stage k's maps, dense
+ * [B][H/8][W/8][52] for k < n_paf, then [..][26]; NULL skips one, but the last stage of either branch is the result and must be given.
+ * features: [B][H/8][W/8][feat] or NULL.  A frame's result does not depend on the batch it is in. */
+typedef struct SoarPoseNetArgs {
+    int32_t B, H, W, pad_;
+    const float *x;
+    int64_t x_stride[4];
+    float *features;
+    float *stage_out[2 * SOAR_POSE_MAX_STAGES];
+} SoarPoseNetArgs;
+int soar_pose_forward(const SoarPoseConfig *cfg, const void *packed, const SoarPoseNetArgs *args, void *workspace, size_t workspace_bytes,
+                      void *stream);
+/* heat [B][h][w][P] (P = 26: the last map is the background and is not read) -> peaks [B][P][max_peaks][3] (x, y, score) and
+ * counts [B][P] (the true number; the background's is 0).  The map upsampled by 8 with the bicubic rule (a = -0.75,
+ * source coordinate (X + 0.5) / 8 - 0.5, edge samples clamped; weights ((a (t+1) - 5a)(t+1) + 8a)(t+1) - 4a, ((a+2) t - (a+3)) t t + 1,
+ * the same of 1 - t, and 1 - w0 - w1 - w2; each row's four products summed left to right, then the four rows top to bottom), evaluated
+ * in LDS strip by strip with a halo of 4 and never stored.  A pixel is a peak if it exceeds `threshold` and is strictly greater than
+ * its 8 neighbours (a plateau has none); pixels of the outermost ring are none.  Position: sum(X s) / sum(s) + 0.5 (and Y) over the
+ * 7 x 7 window clipped to the map, samples s > 0 only, summed row-major.  Score: the peak's value.  Peaks in raster order; only the
+ * first max_peaks (1 .. 32) are written, rows behind min(count, max_peaks) are left alone.  8 w <= 1800. */
+int soar_pose_peaks(int32_t B, int32_t h, int32_t w, const float *heat, float threshold, int32_t max_peaks, float *peaks, int32_t *counts,
+                    void *stream);
+/* peaks, counts as above; paf [B][h][w][52], read at the cell (floor(x / 8), floor(y / 8)) of a sample, clamped: not upsampled.
+ * -> people [B][max_people][25][3] (x, y, score in net-input pixels; a missing part and an unused row are zeros) and n_people [B] (the true
+ * number).  One workgroup per frame.  Per pair of the BODY_25 table, every candidate (a, b): d = b - a, n = |d| (skipped below 1e-6),
+ * m = min(max(5, floor(sqrt(5 n) + 0.5)), 25) samples a + d (i / max(m - 1, 1)); s_i = paf . (d / n); k = samples with s_i >
+ * inter_threshold; valid if k / m > min_above; score = (sum of those s_i, in order) / k.  Connections in descending score, ties by
+ * (a, b) ascending, no endpoint twice.  Assembly, pair by pair in table order, connection by connection: with persons holding a and b: the
+ * two merge if they are different and share no part; with a person holding only one end: it gets the other unless it has that part;
+ * with none: a new person.  A person's score is the sum of its peaks' and connections' scores; persons with fewer than min_parts
+ * parts or score / parts below min_score are dropped; the others in order of creation, the first max_people (1 .. 32) written. */
+typedef struct SoarPoseAssembleArgs {
+    int32_t B, h, w, max_peaks, max_people, min_parts;
+    float inter_threshold, min_above, min_score;
+    int8_t pair_a[SOAR_POSE_PAIRS], pair_b[SOAR_POSE_PAIRS]; /* the limbs in the order they are assembled: parts (a, b) ... */
+    int8_t paf_x[SOAR_POSE_PAIRS], paf_y[SOAR_POSE_PAIRS];   /* ... and the PAF channels of the limb's x and y components */
+    const float *peaks;
+    const int32_t *counts;
+    const float *paf;
+    float *people;
+    int32_t *n_people;
+} SoarPoseAssembleArgs;
+int soar_pose_assemble(const SoarPoseAssembleArgs *args, void *stream);
+/* people [n][3] in place: (x W / net_w, y H / net_h, score) */
+int soar_pose_scale(int64_t n, float *people, float W, float net_w, float H, float net_h, void *stream);
 
 const char *soar_last_error(void);
 int soar_abi_version(void);

@@ -52,12 +52,14 @@ struct ConvGemm {
     int tiles_n, tiles_img;        // (the launcher's)
     int act;                       // ACT_NONE (0: what a zero-initialised descriptor asks for), ACT_GELU (exact, erf) or ACT_RELU
     int wtype;                     // WT_F32 (0: what a zero-initialised descriptor asks for), WT_BF16 or WT_F16: conv_gemm16_kernel
+    const float *slope;            // [Cout] or NULL (off: what a zero-initialised descriptor asks for).  PReLU, with act == ACT_NONE only:
+                                   //   y = (v > 0 ? v : slope[co] v) + res with v = alpha acc + bias, at every wtype
 };
 // Refuses (set_error, 1, nothing launched) a descriptor the kernel cannot run: more than 2^30 rows; Cin no multiple of 8; nph outside
 // 1 .. 4; act outside 0 .. 2; wbat without per_image; dil not 1 or 2, or 2 with reflect; stride, os, Cout, Hin or Win below 1; x, y or a table's w NULL; x
 // or w off 16 bytes, or ldx, ldw, wbat no multiple of 4 (the loads are float4); a table with ntaps outside 1 .. 9 or py, px outside
 // [0, os); with reflect, a coordinate gy stride + dy outside [-(Hin - 1), 2 (Hin - 1)] (mirror() reflects once), likewise along x;
-// a wtype outside 0 .. 2; with wtype != 0, ldw or wbat no multiple of 8 (B's loads are 8 elements of 16 bits).
+// a wtype outside 0 .. 2; with wtype != 0, ldw or wbat no multiple of 8 (B's loads are 8 elements of 16 bits); a slope with act != 0.
 int launch_conv_gemm(const ConvGemm &desc, hipStream_t stream);
 // the side of the tile launch_conv_gemm picks for desc: 128 or 64
 int conv_gemm_tile(const ConvGemm &desc);

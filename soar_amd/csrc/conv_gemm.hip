@@ -6,7 +6,8 @@
 //   conv_gemm_kernel       an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32 products): M = grid positions, N = output
 //                          channels, K = (tap, cin), tiles staged through LDS.  The A loader does strides, padding (zero or mirrored)
 //                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = act(alpha acc + bias) + res,
-//                          scattered to the tap table's output parity (act: none, exact GELU or ReLU)
+//                          scattered to the tap table's output parity (act: none, exact GELU or ReLU; or, with act none, a PReLU of
+//                          one slope per output channel: ConvGemm::slope)
 //   conv_pack16_kernel     torch [Cout][Cin][kk] float32 -> [Cout][tap][Cinp] bf16 / f16, rounded to nearest even (forward only)
 //   conv_gemm16_kernel     the same implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16}: B read as 16-bit values, A rounded to the type
 //                          on its way into LDS, float32 accumulators and the same epilogue (ConvGemm::wtype)
@@ -48,19 +49,20 @@ __global__ void __launch_bounds__(256) conv_pack16_kernel(const float *__restric
     out[e] = ci < Cin ? (T)w[((size_t)co * Cin + ci) * kk + t] : (T)0.f;
 }
 
-// The epilogue of both kernels: y = act(alpha acc + bias) + res of a wave's WM x WN accumulator blocks (C / D layout: mfma_row),
+// The epilogue of both kernels: y = act(alpha acc + bias) + res (act none and a slope: y = prelu(alpha acc + bias) + res) of a wave's WM x WN accumulator blocks (C / D layout: mfma_row),
 // scattered to the tap table's output parity.  Lane (i, h); the wave's blocks start at row r0 + wr, column c0 + wc of the product.
 template <int WM, int WN>
 __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemm &k, const ConvTaps &ph, const f32x16 (&acc)[WM][WN], int img0, int rows,
                                                    int hwg, int r0, int c0, int wr, int wc, int i, int h)
 {
     bool cv[WN];
-    float bias[WN];
+    float bias[WN], slope[WN];
 #pragma unroll
     for (int c = 0; c < WN; c++) {
         const int co = c0 + wc + c * 32 + i;
         cv[c] = co < k.Cout;
         bias[c] = k.bias && cv[c] ? k.bias[co] : 0.f;
+        slope[c] = k.slope && cv[c] ? k.slope[co] : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < WM; r++)
@@ -77,6 +79,7 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemm &k, const Conv
                 const size_t idx = base + (c0 + wc + c * 32 + i);
                 float v = acc[r][c][e] * k.alpha + bias[c];
                 if (k.act) v = k.act == ACT_GELU ? gelu_erf(v) : fmaxf(v, 0.f);     // (act = 0: the arithmetic of every call before it)
+                else if (k.slope) v = v > 0.f ? v : slope[c] * v;                   // (slope = NULL: likewise)
                 if (k.res) v += k.res[idx];
                 k.y[idx] = v;
             }
@@ -383,6 +386,7 @@ bool check_desc(const ConvGemm &k, int64_t M)
         return false;
     }
     if (k.act < 0 || k.act > ACT_RELU) { set_error("conv_gemm: act must be 0 (none), 1 (GELU) or 2 (ReLU) (got %d)", k.act); return false; }
+    if (k.slope && k.act != ACT_NONE) { set_error("conv_gemm: slope (PReLU) goes with act == 0 only (got act=%d)", k.act); return false; }
     if (k.wtype < 0 || k.wtype > WT_F16) { set_error("conv_gemm: wtype must be 0 (f32), 1 (bf16) or 2 (f16) (got %d)", k.wtype); return false; }
     if (k.stride < 1 || k.os < 1 || k.Cout < 1 || k.Hin < 1 || k.Win < 1) {
         set_error("conv_gemm: stride, os, Cout, Hin and Win must be at least 1 (stride=%d, os=%d, Cout=%d, Hin=%d, Win=%d)", k.stride, k.os,
@@ -489,11 +493,12 @@ int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, 
 }  // namespace soar
 
 // ---- the launcher and the packer by themselves (tests/test_conv_gemm_*.py) ----
-static int selftest_conv_gemm(const char *me, const SoarConvGemmArgs *a, int wtype, int act, int32_t *tile_out, void *stream_)
+static int selftest_conv_gemm(const char *me, const SoarConvGemmArgs *a, int wtype, int act, int32_t *tile_out, void *stream_,
+                              const float *slope = nullptr)
 {
     if (!a || !tile_out) { soar::set_error("%s: NULL %s", me, a ? "tile_out" : "args"); return 1; }
     soar::ConvGemm k{};
-    k.wtype = wtype; k.act = act;
+    k.wtype = wtype; k.act = act; k.slope = slope;
     k.x = a->x; k.ldx = a->ldx; k.xim = a->xim; k.wbat = a->wbat;
     k.bias = a->bias; k.res = a->res; k.y = a->y; k.ldy = a->ldy; k.yim = a->yim; k.alpha = a->alpha;
     k.N = a->N; k.Hg = a->Hg; k.Wg = a->Wg; k.Hin = a->Hin; k.Win = a->Win; k.Cin = a->Cin; k.Cout = a->Cout;
@@ -525,6 +530,13 @@ extern "C" int soar_selftest_conv_gemm16(const SoarConvGemmArgs *a, int32_t wtyp
 extern "C" int soar_selftest_conv_gemm_act(const SoarConvGemmArgs *a, int32_t wtype, int32_t act, int32_t *tile_out, void *stream_)
 {
     return selftest_conv_gemm("soar_selftest_conv_gemm_act", a, wtype, act, tile_out, stream_);
+}
+
+// ... and with the epilogue's PReLU: slope [Cout] (NULL: off); the launcher refuses a slope together with act != 0
+extern "C" int soar_selftest_conv_gemm_slope(const SoarConvGemmArgs *a, int32_t wtype, int32_t act, const float *slope, int32_t *tile_out,
+                                             void *stream_)
+{
+    return selftest_conv_gemm("soar_selftest_conv_gemm_slope", a, wtype, act, tile_out, stream_, slope);
 }
 
 extern "C" int soar_selftest_conv_pack16(const float *w, void *fwd, int32_t Cout, int32_t Cin, int32_t Cinp, int32_t kk, int32_t wtype,

@@ -382,6 +382,29 @@ class SoarResamplerArgs(C.Structure):
                 ("probe_code", C.c_int32 * CLIP_MAX_PROBES), ("probe_dst", _vp * CLIP_MAX_PROBES)]
 
 
+POSE_PAF, POSE_HEAT, POSE_PARTS, POSE_PAIRS = 52, 26, 25, 26      # SOAR_POSE_PAF, SOAR_POSE_HEAT, SOAR_POSE_PARTS, SOAR_POSE_PAIRS
+POSE_MAX_STAGES, POSE_MAX_PEAKS, POSE_MAX_PEOPLE = 8, 32, 32     # SOAR_POSE_MAX_STAGES, SOAR_POSE_MAX_PEAKS, SOAR_POSE_MAX_PEOPLE
+
+
+class SoarPoseConfig(C.Structure):
+    """Mirror of ``struct SoarPoseConfig`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("c1", "c2", "c3", "c4", "cpm", "feat", "w0", "w1", "m0", "m1", "n_paf", "n_heat")]
+
+
+class SoarPoseNetArgs(C.Structure):
+    """Mirror of ``struct SoarPoseNetArgs`` (include/soar_hip.h)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pad_", C.c_int32), ("x", _vp), ("x_stride", C.c_int64 * 4),
+                ("features", _vp), ("stage_out", _vp * (2 * POSE_MAX_STAGES))]
+
+
+class SoarPoseAssembleArgs(C.Structure):
+    """Mirror of ``struct SoarPoseAssembleArgs`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "h", "w", "max_peaks", "max_people", "min_parts")] + \
+               [(n, C.c_float) for n in ("inter_threshold", "min_above", "min_score")] + \
+               [(n, C.c_int8 * POSE_PAIRS) for n in ("pair_a", "pair_b", "paf_x", "paf_y")] + \
+               [(n, _vp) for n in ("peaks", "counts", "paf", "people", "n_people")]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -477,6 +500,7 @@ SIGNATURES = {
     "soar_selftest_conv_gemm16": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.POINTER(C.c_int32), _vp]),
     "soar_selftest_conv_pack16": (C.c_int, [_vp, _vp] + [C.c_int32] * 5 + [_vp]),
     "soar_selftest_conv_gemm_act": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.c_int32, C.POINTER(C.c_int32), _vp]),
+    "soar_selftest_conv_gemm_slope": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.c_int32, _vp, C.POINTER(C.c_int32), _vp]),
     "soar_prof_enable": (C.c_int, [C.c_int]),
     "soar_prof_reset": (C.c_int, []),
     "soar_prof_stage_count": (C.c_int, []),
@@ -634,6 +658,14 @@ SIGNATURES = {
     "soar_resampler_pack_weights": (C.c_int, [C.POINTER(SoarResamplerConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
     "soar_resampler_workspace_bytes": (C.c_int, [C.POINTER(SoarResamplerConfig), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_resampler_forward": (C.c_int, [C.POINTER(SoarResamplerConfig), _vp, C.POINTER(SoarResamplerArgs), _vp, C.c_size_t, _vp]),
+    "soar_pose_weights_size": (C.c_int, [C.POINTER(SoarPoseConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "soar_pose_workspace_size": (C.c_int, [C.POINTER(SoarPoseConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_pose_pack_weights": (C.c_int, [C.POINTER(SoarPoseConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_pose_preprocess": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, _vp]),
+    "soar_pose_forward": (C.c_int, [C.POINTER(SoarPoseConfig), _vp, C.POINTER(SoarPoseNetArgs), _vp, C.c_size_t, _vp]),
+    "soar_pose_peaks": (C.c_int, [C.c_int32] * 3 + [_vp, C.c_float, C.c_int32, _vp, _vp, _vp]),
+    "soar_pose_assemble": (C.c_int, [C.POINTER(SoarPoseAssembleArgs), _vp]),
+    "soar_pose_scale": (C.c_int, [C.c_int64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
