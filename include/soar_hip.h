@@ -2230,6 +2230,82 @@ int soar_pose_assemble(const SoarPoseAssembleArgs *args, void *stream);
 /* people [n][3] in place: (x W / net_w, y H / net_h, score) */
 int soar_pose_scale(int64_t n, float *people, float W, float net_w, float H, float net_h, void *stream);
 
+/* ---- hand and face keypoint detection (pose_parts.hip, soar_amd/pose_parts.py).  Preprocessing; forward only, float32.
+ * One convolutional pose machine (CPM) serves the hand network and the face network.  Its layers, in the order of
+ * soar_amd.pose_parts.layer_keys: the front conv1_1 .. conv5_3_CPM (SOAR_CPM_FRONT = 15 convolutions; a 2 x 2 max pool behind front
+ * layer i where bit i of pool_mask is set: three bits, so that the maps are at 1/8 resolution), whose last gives the features; stage 1:
+ * conv6_1_CPM, conv6_2_CPM (the maps); every later stage: Mconv1 .. Mconv7, reading the previous stage's maps and the features side
+ * by side (maps_first != 0: the weights' input channels are (maps, features), else (features, maps)).  n_layers = 17 + 7 (n_stages - 1).
+ * ReLU behind every convolution except a stage's last.  width[i]: layer i's output channels, a multiple of 8 except the maps'
+ * (n_maps >= 2, the same for every stage); side[i]: its kernel side, 1, 3 or 7, zero padding side / 2.
+ * A 7 x 7 convolution runs through the shared implicit GEMM as seven launches, one per kernel row (seven taps each): the first carries
+ * the bias, each later one adds to the output in place, a last pass applies the ReLU.  So its sum runs over the kernel's rows top to
+ * bottom, inside a row over (tap left to right, input channel) in the GEMM's order.
+ * Tensors: per convolution weight [Cout][Cin][side][side] and bias [Cout]. */
+#define SOAR_CPM_FRONT 15
+#define SOAR_CPM_MAX_STAGES 8
+#define SOAR_CPM_MAX_LAYERS (17 + 7 * (SOAR_CPM_MAX_STAGES - 1))
+typedef struct SoarCpmConfig {
+    int32_t n_stages, n_maps, n_layers, pool_mask, maps_first, pad_;
+    int32_t width[SOAR_CPM_MAX_LAYERS];
+    int32_t side[SOAR_CPM_MAX_LAYERS];
+} SoarCpmConfig;
+/* The two sizing calls (bytes; *count: the tensors soar_cpm_pack_weights takes).  They refuse what the kernels cannot run: a width that
+ * is no multiple of 8 in 8 .. 4096, a side other than 1, 3, 7, n_maps outside 2 .. 4096, n_stages outside 1 .. 8, a pool_mask without
+ * exactly three bits below SOAR_CPM_FRONT - 1, an S that is no multiple of 8, M S S > 2^30. */
+int soar_cpm_weights_size(const SoarCpmConfig *cfg, size_t *bytes, int32_t *count);
+int soar_cpm_workspace_size(const SoarCpmConfig *cfg, int32_t M, int32_t S, size_t *bytes);
+int soar_cpm_pack_weights(const SoarCpmConfig *cfg, const float *const *tensors, const int64_t *sizes, int32_t count, void *packed,
+                          size_t packed_bytes, void *stream);
+/* x: the crops, [M][3][S][S] at x_stride (elements).  stage_out[k]: stage k + 1's maps, dense [M][S/8][S/8][n_maps]; NULL skips one, but
+ * the last stage's is the result and must be given.  features: [M][S/8][S/8][feat] or NULL.  A crop's result does not depend on its batch. */
+typedef struct SoarCpmArgs {
+    int32_t M, S;
+    const float *x;
+    int64_t x_stride[4];
+    float *features;
+    float *stage_out[SOAR_CPM_MAX_STAGES];
+} SoarCpmArgs;
+int soar_cpm_forward(const SoarCpmConfig *cfg, const void *packed, const SoarCpmArgs *args, void *workspace, size_t workspace_bytes,
+                     void *stream);
+/* The rectangles of the left hand, the right hand and the face of the first part_people persons of every frame, from their BODY_25
+ * keypoints: people [B][max_people][25][3] (x, y, confidence in image pixels), n_people [B] -> boxes [B][part_people][3][4] =
+ * (x0, y0, side, valid: 1 or 0), an invalid one all zeros.  A person index at or beyond min(n_people, max_people) is invalid.  One
+ * thread per rectangle; float32, every expression as written here, |v| = sqrt(v.x v.x + v.y v.y).
+ * Hand (left: shoulder 5, elbow 6, wrist 7; right: 2, 3, 4): c = wrist + 0.33 (wrist - elbow), side = 1.5 max(|wrist - elbow|,
+ * 0.9 |elbow - shoulder|), x0 = c.x - side / 2, y0 = c.y - side / 2; valid if the three confidences exceed hand_min_conf, side > 1 and
+ * side side > min_hand_area.
+ * Face (neck 1, nose 0, right eye 15, left eye 16, right ear 17, left ear 18; present: confidence > face_min_conf): centre, size and
+ * count start at 0.  With neck and nose: in profile (lEye == lEar, rEye == rEar, lEye != rEye as presence flags) centre +=
+ * ((eye + ear) + nose) / 3 of the visible side and size += 0.85 ((|nose - eye| + |nose - ear|) + |neck - nose|), otherwise centre +=
+ * (neck + nose) / 2 and size += 2 |neck - nose|; count + 1.  With both eyes: centre += (lEye + rEye) / 2, size += 3 |lEye - rEye|,
+ * count + 1.  With both ears: centre += (lEar + rEar) / 2, size += 2 |lEar - rEar|, count + 1.  With count > 0 centre and size are
+ * divided by it; x0 = centre.x - size / 2, y0 = centre.y - size / 2, side = size; valid if count > 0 and side side > min_face_area. */
+typedef struct SoarPartBoxArgs {
+    int32_t B, max_people, part_people, pad_;
+    float hand_min_conf, min_hand_area, face_min_conf, min_face_area;
+    const float *people;
+    const int32_t *n_people;
+    float *boxes;
+} SoarPartBoxArgs;
+int soar_part_boxes(const SoarPartBoxArgs *args, void *stream);
+/* The two networks' inputs in one launch: images uint8 RGB [B][H][W][3], boxes [B][P][3][4] -> hands [B P 2][3][S][S] (left before
+ * right) and faces [B P][3][S][S], either NULL to skip it.  With s = side / S, crop pixel (u, v) samples the image at x = x0 + u' s,
+ * y = y0 + v s, u' = S - 1 - u for a left hand (mirrored) and u otherwise; integer coordinates are pixel centres.  Bilinear over the
+ * four neighbours, a neighbour outside the image counting 0: ax = x - floor(x), ay likewise,
+ * val = (p00 (1 - ax) + p01 ax) (1 - ay) + (p10 (1 - ax) + p11 ax) ay; a sample that is not inside (-1, W) x (-1, H) is 0.  Channels
+ * reversed to BGR, val / 256 - 0.5.  An invalid box's crop is all -0.5.  No anti-aliasing when side > S. */
+int soar_part_crop(int32_t B, int32_t H, int32_t W, int32_t P, int32_t S, const uint8_t *images, const float *boxes, float *hands,
+                   float *faces, void *stream);
+/* heat [M][h][w][n_maps] (the last map, the background, is not read), boxes as above -> out [M][n_maps - 1][3] in image pixels.
+ * which 0: hand crops, crop m belongs to rectangle m % 2 (0 left, mirrored; 1 right) of person m / 2; which 1: face crops, rectangle
+ * 2 of person m.  One workgroup per (crop, map): the map upsampled by 8 with soar_pose_peaks' bicubic rule (never stored: the source
+ * map lies in LDS, h w <= 12288), its maximum over all 8 h x 8 w positions, ties to the smallest raster index.  The winner (X, Y)
+ * with value m > 0 in a valid rectangle gives (x0 + X' s, y0 + Y s, m) with s = side / (8 w) and X' = 8 w - 1 - X for a left hand;
+ * anything else (0, 0, 0).  No sub-pixel refinement. */
+int soar_part_keypoints(int32_t M, int32_t h, int32_t w, int32_t n_maps, const float *heat, const float *boxes, int32_t which, float *out,
+                        void *stream);
+
 const char *soar_last_error(void);
 int soar_abi_version(void);
 

@@ -1,6 +1,8 @@
 // pose.hip -- body keypoint detection of the preprocessing stage (soar_amd/pose.py): the BODY_25 network and the part-affinity
 // post-processing, as include/soar_hip.h and DESIGN.md 9za state them.  Forward only, float32.
 //
+//   (pose_common.h, shared with pose_parts.hip: pose_pack_kernel, pose_pad_kernel, pose_ingest_kernel, pose_pool_kernel,
+//                          pose_slice_kernel and the bicubic rule of the peaks, up_cell / up_phase / up_weights / up_sum4)
 //   pose_pack_kernel       torch [Cout][Cin][kk] -> [Coutp][tap][Cinp]: up to three runs of input channels moved to where the padded
 //                          activation row holds them, every other column and the rows behind Cout zeros
 //   pose_preprocess_kernel uint8 RGB -> float32 BGR, v / 256 - 0.5
@@ -18,8 +20,8 @@
 //
 // Compiled with -ffp-contract=off: the post-processing's float32 expressions evaluate as written (tests/pose_ref.py restates them in
 // NumPy, bit for bit).  No float atomics, no host synchronisation, no allocation; a frame's result does not depend on its batch.
-#include "conv_gemm.h"
 #include "net_weights.h"
+#include "pose_common.h"
 #include "workspace.h"
 
 namespace soar {
@@ -28,7 +30,6 @@ namespace {
 
 constexpr int PAF = SOAR_POSE_PAF, HEAT = SOAR_POSE_HEAT, NPARTS = SOAR_POSE_PARTS, NPAIRS = SOAR_POSE_PAIRS;
 constexpr int PAFP = 56, HEATP = 32;            // the maps' segments of a stage-input row, padded to multiples of 8
-constexpr int IMGP = 8;                         // the image's three channels likewise
 constexpr int MAXP = SOAR_POSE_MAX_PEAKS, MAX_PEOPLE = SOAR_POSE_MAX_PEOPLE;
 constexpr int MAX_WIDTH = 4096;
 constexpr int64_t MAX_PIX = int64_t(1) << 30;
@@ -59,7 +60,6 @@ bool check_size(const char *me, int32_t B, int32_t H, int32_t W)
 }
 
 // ---- the layers, in the order of soar_amd.pose.layer_keys ----
-struct Seg { int dst, src, len; };              // input channels src .. src + len of the tensor lie at dst .. of the packed row
 struct Layer {
     int cin, cout, kk, cinp, coutp, nseg;
     bool prelu;
@@ -135,34 +135,6 @@ WsLayout ws_layout(const SoarPoseConfig &c, int B, int H, int W)
     return L;
 }
 
-// ---- weight packing ----
-struct PackK {
-    const float *w;
-    float *out;
-    int cin, cout, kk, cinp, nseg;
-    Seg seg[3];
-    int64_t n;
-};
-__global__ void __launch_bounds__(256) pose_pack_kernel(PackK k)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= k.n) return;
-    // e walks the packed layout [co][t][cip]
-    const int cip = (int)(e % k.cinp);
-    const int64_t r = e / k.cinp;
-    const int t = (int)(r % k.kk), co = (int)(r / k.kk);
-    int ci = -1;
-    for (int s = 0; s < k.nseg; s++)
-        if (cip >= k.seg[s].dst && cip < k.seg[s].dst + k.seg[s].len) ci = k.seg[s].src + (cip - k.seg[s].dst);
-    k.out[e] = co < k.cout && ci >= 0 ? k.w[((size_t)co * k.cin + ci) * k.kk + t] : 0.f;
-}
-// [cout] -> [coutp], zeros behind
-__global__ void __launch_bounds__(256) pose_pad_kernel(const float *src, float *dst, int cout, int coutp)
-{
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < coutp) dst[e] = e < cout ? src[e] : 0.f;
-}
-
 // ---- small image kernels ----
 __global__ void __launch_bounds__(256) pose_preprocess_kernel(const uint8_t *rgb, float *bgr, int64_t npix)
 {
@@ -171,53 +143,6 @@ __global__ void __launch_bounds__(256) pose_preprocess_kernel(const uint8_t *rgb
 #pragma unroll
     for (int c = 0; c < 3; c++) bgr[p * 3 + c] = (float)rgb[p * 3 + (2 - c)] / 256.f - 0.5f;
 }
-struct IngestK {
-    const float *x;
-    int64_t xs[4];
-    float *y;
-    int64_t npix;
-    int H, W;
-};
-__global__ void __launch_bounds__(256) pose_ingest_kernel(IngestK k)
-{
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= k.npix) return;
-    const int64_t hw = (int64_t)k.H * k.W, n = p / hw;
-    const int q = (int)(p - n * hw), y = q / k.W, x = q - y * k.W;
-    const float *s = k.x + n * k.xs[0] + y * k.xs[2] + x * k.xs[3];
-    float4 *dst = reinterpret_cast<float4 *>(k.y + (size_t)p * IMGP);
-    dst[0] = make_float4(s[0], s[k.xs[1]], s[2 * k.xs[1]], 0.f);
-    dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-// x [N][H][W][C] -> y [N][H/2][W/2][C]; thread = (output pixel, channel quad)
-__global__ void __launch_bounds__(256) pose_pool_kernel(const float *x, float *y, int64_t n4, int H, int W, int C)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n4) return;
-    const int c4 = C / 4, cq = (int)(e % c4);
-    const int64_t p = e / c4;
-    const int Wo = W / 2, Ho = H / 2;
-    const int ox = (int)(p % Wo);
-    const int64_t r = p / Wo;
-    const int oy = (int)(r % Ho);
-    const int64_t n = r / Ho;
-    const float4 *s = reinterpret_cast<const float4 *>(x + ((size_t)(n * H + 2 * oy) * W + 2 * ox) * C) + cq;
-    const float4 a = s[0], b = s[c4], c = s[(size_t)W * c4], d = s[(size_t)W * c4 + c4];
-    float4 o;
-    o.x = fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x));
-    o.y = fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y));
-    o.z = fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z));
-    o.w = fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w));
-    reinterpret_cast<float4 *>(y)[e] = o;
-}
-// channels off .. off + C of rows ld apart -> dense [rows][C]
-__global__ void __launch_bounds__(256) pose_slice_kernel(const float *x, int64_t ld, int off, int C, float *y, int64_t n)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    y[e] = x[(e / C) * ld + off + (int)(e % C)];
-}
-
 ConvGemm conv_k(const float *x, int64_t ldx, float *y, int64_t ldy, int N, int H, int W, int Cin, int Cout, int kk, const float *w,
                 const float *bias, const float *slope, int act)
 {
@@ -233,11 +158,6 @@ ConvGemm conv_k(const float *x, int64_t ldx, float *y, int64_t ldy, int N, int H
 }
 
 // ---- the peaks ----
-// source sample of upsampled coordinate Y: (Y + 0.5) / 8 - 0.5 = i + t with i = floor((2 Y - 7) / 16) and t = (2 ph + 1) / 16,
-// ph = ((2 Y - 7) mod 16) / 2: eight phases
-__device__ __forceinline__ int up_cell(int Y) { return (2 * Y - 7) >> 4; }
-__device__ __forceinline__ int up_phase(int Y) { return ((2 * Y - 7) & 15) >> 1; }
-
 struct PeaksK {
     const float *heat;
     float *peaks;
@@ -267,13 +187,7 @@ __global__ void __launch_bounds__(PEAK_THREADS) pose_peaks_kernel(PeaksK k)
     float *wt = reinterpret_cast<float *>(mask + (size_t)R * nw);                          // [8][4]
     float *U = wt + 32;                                                                    // [R + 8][Wp]
     float *src = U + (size_t)(R + 8) * Wp;                                                 // [NS][w]
-    if (tid < 8) {
-        const float a = -0.75f, t = (float)(2 * tid + 1) / 16.f, t1 = t + 1.f, u = 1.f - t;
-        const float w0 = ((a * t1 - 5.f * a) * t1 + 8.f * a) * t1 - 4.f * a;
-        const float w1 = ((a + 2.f) * t - (a + 3.f)) * t * t + 1.f;
-        const float w2 = ((a + 2.f) * u - (a + 3.f)) * u * u + 1.f;
-        wt[4 * tid] = w0; wt[4 * tid + 1] = w1; wt[4 * tid + 2] = w2; wt[4 * tid + 3] = 1.f - w0 - w1 - w2;
-    }
+    if (tid < 8) up_weights(tid, wt + 4 * tid);
     if (tid == 0) count = 0;
     const float *heat = k.heat + (size_t)b * k.h * k.w * k.P + part;
     float *out = k.peaks + ((size_t)b * k.P + part) * k.max_peaks * 3;
@@ -300,9 +214,9 @@ __global__ void __launch_bounds__(PEAK_THREADS) pose_peaks_kernel(PeaksK k)
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float *s = src + (size_t)(iy - 1 + j - iy_lo) * k.w;
-                    row[j] = ((wx[0] * s[x0] + wx[1] * s[x1]) + wx[2] * s[x2]) + wx[3] * s[x3];
+                    row[j] = up_sum4(wx, s[x0], s[x1], s[x2], s[x3]);
                 }
-                v = ((wy[0] * row[0] + wy[1] * row[1]) + wy[2] * row[2]) + wy[3] * row[3];
+                v = up_sum4(wy, row[0], row[1], row[2], row[3]);
             }
             U[e] = v;
         }

@@ -405,6 +405,29 @@ class SoarPoseAssembleArgs(C.Structure):
                [(n, _vp) for n in ("peaks", "counts", "paf", "people", "n_people")]
 
 
+CPM_FRONT, CPM_MAX_STAGES = 15, 8                                # SOAR_CPM_FRONT, SOAR_CPM_MAX_STAGES
+CPM_MAX_LAYERS = 17 + 7 * (CPM_MAX_STAGES - 1)                   # SOAR_CPM_MAX_LAYERS
+
+
+class SoarCpmConfig(C.Structure):
+    """Mirror of ``struct SoarCpmConfig`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_stages", "n_maps", "n_layers", "pool_mask", "maps_first", "pad_")] + \
+               [("width", C.c_int32 * CPM_MAX_LAYERS), ("side", C.c_int32 * CPM_MAX_LAYERS)]
+
+
+class SoarCpmArgs(C.Structure):
+    """Mirror of ``struct SoarCpmArgs`` (include/soar_hip.h)."""
+    _fields_ = [("M", C.c_int32), ("S", C.c_int32), ("x", _vp), ("x_stride", C.c_int64 * 4), ("features", _vp),
+                ("stage_out", _vp * CPM_MAX_STAGES)]
+
+
+class SoarPartBoxArgs(C.Structure):
+    """Mirror of ``struct SoarPartBoxArgs`` (include/soar_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "max_people", "part_people", "pad_")] + \
+               [(n, C.c_float) for n in ("hand_min_conf", "min_hand_area", "face_min_conf", "min_face_area")] + \
+               [(n, _vp) for n in ("people", "n_people", "boxes")]
+
+
 # name -> (restype, argtypes); every symbol include/soar_hip.h declares
 SIGNATURES = {
     "soar_last_error": (C.c_char_p, []),
@@ -666,6 +689,13 @@ SIGNATURES = {
     "soar_pose_peaks": (C.c_int, [C.c_int32] * 3 + [_vp, C.c_float, C.c_int32, _vp, _vp, _vp]),
     "soar_pose_assemble": (C.c_int, [C.POINTER(SoarPoseAssembleArgs), _vp]),
     "soar_pose_scale": (C.c_int, [C.c_int64, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "soar_cpm_weights_size": (C.c_int, [C.POINTER(SoarCpmConfig), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "soar_cpm_workspace_size": (C.c_int, [C.POINTER(SoarCpmConfig), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_cpm_pack_weights": (C.c_int, [C.POINTER(SoarCpmConfig), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_cpm_forward": (C.c_int, [C.POINTER(SoarCpmConfig), _vp, C.POINTER(SoarCpmArgs), _vp, C.c_size_t, _vp]),
+    "soar_part_boxes": (C.c_int, [C.POINTER(SoarPartBoxArgs), _vp]),
+    "soar_part_crop": (C.c_int, [C.c_int32] * 5 + [_vp] * 5),
+    "soar_part_keypoints": (C.c_int, [C.c_int32] * 4 + [_vp, _vp, C.c_int32, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

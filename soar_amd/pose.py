@@ -10,8 +10,9 @@
   ``smplify.load_keypoints`` reads back from what ``save_keypoints`` writes (OpenPose's ``<stem>_keypoints.json``).
 
 **The network's structure, the concatenation orders and the BODY_25 tables below are stated from the published model; they have not
-been compared with OpenPose or its weights** (neither is available to the tests).  Hands and faces (two more networks) are not
-detected: their 112 rows carry confidence 0.  HIP only: CPU tensors are refused, there is no CPU fallback.
+been compared with OpenPose or its weights** (neither is available to the tests).  Hands and faces are two more networks
+(``soar_amd.pose_parts``): ``detect_sequence`` and ``save_keypoints`` take them as options, and without them the 112 rows carry
+confidence 0.  HIP only: CPU tensors are refused, there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -321,10 +322,12 @@ def _read_chunk(paths: Sequence[str], dev) -> torch.Tensor:
 
 
 @torch.no_grad()
-def detect_sequence(net: PoseNet, images_or_paths, chunk: int = 8, device=None, net_height: int = 368, **thresholds) -> np.ndarray:
-    """A sequence's keypoints, ``[N,137,3]`` float32 in image pixels: the first person's 25 body keypoints and 112 rows of zeros (no
-    hands, no face).  ``images_or_paths``: uint8 ``[N,H,W,3]`` RGB (moved to ``device``) or a list of picture files, decoded on the
-    device; ``chunk`` frames go through the network per call.  A frame with nobody in it is all zeros."""
+def detect_sequence(net: PoseNet, images_or_paths, chunk: int = 8, device=None, net_height: int = 368, hand_net=None, face_net=None,
+                    part_net_side: int = 368, **thresholds) -> np.ndarray:
+    """A sequence's keypoints, ``[N,137,3]`` float32 in image pixels: the first person's 25 body keypoints, then 112 rows of zeros
+    unless ``hand_net`` / ``face_net`` (``pose_parts.CpmNet``) are given, which fill rows 25:46 (left hand), 46:67 (right hand) and
+    67:137 (face) from crops of ``part_net_side``.  ``images_or_paths``: uint8 ``[N,H,W,3]`` RGB (moved to ``device``) or a list of
+    picture files, decoded on the device; ``chunk`` frames go through the networks per call.  A frame with nobody in it is all zeros."""
     if chunk < 1:
         raise ValueError(f"detect_sequence: chunk must be >= 1 (got {chunk})")
     is_tensor = isinstance(images_or_paths, torch.Tensor)
@@ -340,28 +343,48 @@ def detect_sequence(net: PoseNet, images_or_paths, chunk: int = 8, device=None, 
         frames = part.to(dev) if is_tensor else _read_chunk(list(part), dev)
         people, n_people = detect(net, frames, net_height, **thresholds)
         out[i:i + chunk, :N_PARTS] = people[:, 0] * (n_people > 0).to(torch.float32)[:, None, None]
+        if hand_net is not None or face_net is not None:
+            from .pose_parts import detect_parts
+            hands, face = detect_parts(hand_net, face_net, frames, people, n_people, 1, part_net_side)
+            out[i:i + chunk, N_PARTS:N_PARTS + 2 * N_HAND] = hands[:, 0].reshape(-1, 2 * N_HAND, 3)
+            out[i:i + chunk, N_PARTS + 2 * N_HAND:] = face[:, 0]
     return out.cpu().numpy()
 
 
-def save_keypoints(kp_dir: str, people, n_people, stems: Sequence[str]) -> None:
-    """Writes OpenPose's ``<stem>_keypoints.json`` per frame: ``version`` and ``people[]`` with ``pose_keypoints_2d`` (75 numbers) and
-    zeros for ``face_keypoints_2d`` (210), ``hand_left_keypoints_2d`` and ``hand_right_keypoints_2d`` (63 each).  ``people``
-    ``[N,max_people,25,3]`` and ``n_people [N]`` as ``detect`` returns them (tensors or arrays).  A frame with nobody found gets one
-    all-zero person, so that ``smplify.load_keypoints`` still reads it, and a warning names the frame."""
+def save_keypoints(kp_dir: str, people, n_people, stems: Sequence[str], hands=None, face=None) -> None:
+    """Writes OpenPose's ``<stem>_keypoints.json`` per frame: ``version`` and ``people[]`` with ``pose_keypoints_2d`` (75 numbers),
+    ``face_keypoints_2d`` (210), ``hand_left_keypoints_2d`` and ``hand_right_keypoints_2d`` (63 each).  ``people``
+    ``[N,max_people,25,3]`` and ``n_people [N]`` as ``detect`` returns them (tensors or arrays); ``hands [N,P,2,21,3]`` and ``face
+    [N,P,70,3]`` as ``pose_parts.detect_parts`` returns them, for a frame's first P persons: the others', and everybody's without the
+    argument, are zeros.  A frame with nobody found gets one all-zero person, so that ``smplify.load_keypoints`` still reads it, and a
+    warning names the frame."""
     people = people.detach().cpu().numpy() if isinstance(people, torch.Tensor) else np.asarray(people)
     n_people = n_people.detach().cpu().numpy() if isinstance(n_people, torch.Tensor) else np.asarray(n_people)
     people = people.astype(np.float32, copy=False)
     if people.ndim != 4 or people.shape[2:] != (N_PARTS, 3) or n_people.shape != people.shape[:1] or len(stems) != people.shape[0]:
         raise ValueError(f"save_keypoints: need people [N,max_people,25,3], n_people [N] and N stems (got {people.shape}, {n_people.shape}, {len(stems)})")
+    def parts(t, name, tail):
+        if t is None:
+            return None
+        t = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float32, copy=False)
+        if t.ndim != 2 + len(tail) or t.shape[0] != people.shape[0] or t.shape[2:] != tail:
+            raise ValueError(f"save_keypoints: need {name} [N,P,{','.join(map(str, tail))}] (got {t.shape})")
+        return t
+
+    hands, face = parts(hands, "hands", (2, N_HAND, 3)), parts(face, "face", (N_FACE, 3))
     os.makedirs(kp_dir, exist_ok=True)
     zeros = lambda n: [0.0] * (3 * n)
+    # person q's rows of a part array, zeros where it has none
+    rows_of = lambda t, i, q, n: zeros(n) if t is None or q >= t.shape[1] else [float(v) for v in t[i, q].reshape(-1)]
     for i, stem in enumerate(stems):
         n = min(int(n_people[i]), people.shape[1])
         if n == 0:
             warnings.warn(f"save_keypoints: nobody found in frame '{stem}': writing one all-zero person")
         rows = people[i, :n] if n else np.zeros((1, N_PARTS, 3), np.float32)
         doc = {"version": 1.3, "people": [{"person_id": [-1], "pose_keypoints_2d": [float(v) for v in row.reshape(-1)],
-                                           "face_keypoints_2d": zeros(N_FACE), "hand_left_keypoints_2d": zeros(N_HAND),
-                                           "hand_right_keypoints_2d": zeros(N_HAND)} for row in rows]}
+                                           "face_keypoints_2d": rows_of(face, i, q, N_FACE),
+                                           "hand_left_keypoints_2d": rows_of(None if hands is None else hands[:, :, 0], i, q, N_HAND),
+                                           "hand_right_keypoints_2d": rows_of(None if hands is None else hands[:, :, 1], i, q, N_HAND)}
+                                          for q, row in enumerate(rows)]}
         with open(os.path.join(kp_dir, f"{stem}_keypoints.json"), "w") as fh:
             json.dump(doc, fh)
