@@ -1584,6 +1584,57 @@ typedef struct SoarSmplifyBody {
 } SoarSmplifyBody;
 int soar_smplify_objective_body(const SoarSmplifyRig *rig, const SoarSmplifyBody *body, const SoarSmplifyArgs *args, void *stream);
 int soar_smplify_target_scales(int32_t N, const float *target_kps, float img_w, float img_h, float *scales, void *stream);
+/* The rig's static model points alone, forward only, one launch (a workgroup per frame): points [N][PA][3] float32, the 55 posed
+ *   joints (point p < 55 is joint p), then the selected vertices and the static landmarks as sum_k mp_w[p][k] x gathered row
+ *   mp_idx[p][k] (mp_idx in [0, VS), the caller's to check; rows p < 55 of both tables are not read), plus transl: what the objective
+ *   computes before the OpenPose conversion and the camera, for all PA >= 55 points and not only the P mapped ones.  Of args the ten
+ *   parameter pointers and N are read.  body = NULL: the static rig.  Otherwise VU gives the posedirs row length and
+ *   mean_mask / pose_mean the pose mean; the contour table is not read: a rig with one returns its static points only.
+ *   Refuses N <= 0.  No atomics; two calls give the same bits; the objective's kernels are untouched by it. */
+int soar_smplify_model_points(const SoarSmplifyRig *rig, const SoarSmplifyBody *body, const SoarSmplifyArgs *args, int32_t PA,
+                              const int32_t *mp_idx, const float *mp_w, float *points, void *stream);
+
+/* ---- SMPL-X initialisation from keypoints alone (pose_init.hip, soar_amd/pose_init.py) ----
+ * Stands in for the reference's SMPLer-X call and is a different algorithm: a bank of pose hypotheses, a closed-form camera
+ * translation per hypothesis, the fit's keypoint term as the score, a shortest path through the frames.  The bank, the intrinsics
+ * rule and the defaults are this project's definitions, not tuned on real video, and were compared neither with SMPLer-X nor with
+ * the licensed SMPL-X model.
+ * soar_pose_init_search, one launch (a workgroup per frame, a wavefront per state): state s = b H + h is base pose b turned by
+ *   rotations[h] about pivot[b]: X = R_h (points0[b] - pivot[b]) + pivot[b]; then convert_kps by src_inds / dst_inds (an entry with
+ *   src_inds >= PA is a contour landmark: its keypoint stays 0 and gets weight 0), Yc = R_w2c Y.  Weights c_k = confidence_k
+ *   kp_mask[k], 0 for rows 25 .. 66 (the hands), for confidence_k < conf_min and for contour keypoints.  With (a_k, b_k, 1) =
+ *   K^-1 (u_k, v_k, 1) (K upper triangular, skew honoured) the camera-space t' minimises sum_k c_k [(Yc_x + t'_x - a_k (Yc_z + t'_z))^2
+ *   + (Yc_y + t'_y - b_k (Yc_z + t'_z))^2]: seven weighted sums and a closed-form 3 x 3 solve in double.  transl = R_w2c^T (t' - t_w2c).
+ *   A state is invalid (cost +inf, transl 0) when fewer than min_points weights are positive, the determinant is not positive, or the
+ *   smallest depth Yc_z + t'_z over the weighted keypoints is below z_min.  cost = sum_k c_k (gmof(e_kx) + gmof(e_ky)), e = (projection
+ *   - target pixel) / scales[n] * 200, divisor max(z, 1e-5): the fit's keypoint term of the frame without the mean and the weight.
+ *   valid[n] = 1 when any state of frame n is finite.  No atomics; a frame's outputs are the same bits alone, in any batch, in any
+ *   order; nothing is read back.  Refuses N <= 0 and S = B H > 1024.
+ * soar_pose_init_viterbi, one launch of one workgroup, S <= 1024: D[0] = U[0], D[n][s] = (min_s' (D[n-1][s'] + T[s'][s])) + U[n][s] in
+ *   float32 in that order of additions; ties to the lowest s', the final minimum to the lowest s; a unary row that is all +inf
+ *   counts as zeros.  backptr [N][S] int32 is the caller's scratch.  path [N] int64, total [1].  With transl [N][S][3], valid [N] and
+ *   transl_path [N][3] (all three or none): the path's translations, linearly interpolated between the nearest valid frames on
+ *   either side of a frame that is not valid, held at the ends, 0 when no frame is valid. */
+typedef struct SoarPoseSearch {
+    int32_t N, B, H, PA, P, min_points;
+    const float *points0;         /* [B][PA][3] */
+    const float *pivot;           /* [B][3] */
+    const float *rotations;       /* [H][3][3] */
+    const int32_t *src_inds;      /* [P] model point; >= PA: a contour landmark */
+    const int32_t *dst_inds;      /* [P] distinct, in [0, 137) */
+    const float *kp_mask;         /* [137] */
+    const float *target_kps;      /* [N][137][3]: x / img_w, y / img_h, confidence */
+    const float *Ks;              /* [N][3][3] */
+    const float *w2c;             /* [4][4], rows 0 .. 2 are read */
+    const float *scales;          /* [N] */
+    float img_w, img_h, sigma, conf_min, z_min, pad_;
+    float *cost;                  /* [N][B H] */
+    float *transl;                /* [N][B H][3] */
+    uint8_t *valid;               /* [N] */
+} SoarPoseSearch;
+int soar_pose_init_search(const SoarPoseSearch *args, void *stream);
+int soar_pose_init_viterbi(int32_t N, int32_t S, const float *unary, const float *trans, int32_t *backptr, int64_t *path, float *total,
+                           const float *transl, const uint8_t *valid, float *transl_path, void *stream);
 
 /* ---- SMPL-X normal priors: an indexed triangle mesh drawn as a normal map (prior.hip, soar_amd/prior.py) ----
  * N frames of one topology: faces [F][3] (indices in [0, V): the caller's to check, soar_amd.prior.MeshTopology does, on the host)

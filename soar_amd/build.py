@@ -74,6 +74,8 @@ EXTRA_FLAGS = {
     "pose.hip": ["-ffp-contract=off"],
     # rectangles, crops and the maps' maxima equal a NumPy float32 restatement bit for bit (tests/pose_parts_ref.py)
     "pose_parts.hip": ["-ffp-contract=off"],
+    # the frame's sums and the sign of the determinant equal a NumPy float64 restatement bit for bit (tests/pose_init_ref.py)
+    "pose_init.hip": ["-ffp-contract=off"],
     # the SLP vectoriser pairs neighbouring float operations into v_pk_* and pays for it with register shuffles (v_mov, v_pk_mov);
     # a packed float instruction occupies the SIMD as long as the two plain ones it replaces (32 lanes per cycle either way)
     "rast_render_bwd.hip": ["-fno-slp-vectorize"],
@@ -82,7 +84,7 @@ EXTRA_FLAGS = {
 SOURCES = ["api.hip", "rast_preprocess.hip", "rast_binning.hip", "rast_tilebin.hip", "rast_blockmask.hip", "rast_render_fwd.hip", "rast_render_bwd.hip",
            "rast_geom_bwd.hip", "lbs.hip", "lbs_knn.hip", "frame_loss.hip", "postops.hip", "ssim.hip", "image_losses.hip", "smplx_joints.hip", "densify.hip", "optim.hip", "view.hip",
            "mesh.hip", "mesh_simplify.hip", "mesh_attr.hip", "mesh_holes.hip", "mesh_texture.hip", "field.hip", "envmap.hip", "conv_gemm.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip", "playback.hip",
-           "normalnet.hip", "normal_io.hip", "smplify.hip", "prior.hip", "masks.hip", "step_terms.hip", "fitviz.hip", "video.hip", "png.hip", "png_decode.hip", "jpeg_decode.hip", "image_resize.hip", "attention.hip", "sam.hip", "unet.hip", "clip.hip", "pose.hip", "pose_parts.hip"]
+           "normalnet.hip", "normal_io.hip", "smplify.hip", "prior.hip", "masks.hip", "step_terms.hip", "fitviz.hip", "video.hip", "png.hip", "png_decode.hip", "jpeg_decode.hip", "image_resize.hip", "attention.hip", "sam.hip", "unet.hip", "clip.hip", "pose.hip", "pose_parts.hip", "pose_init.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(_HERE, "..", "include", "soar_hip.h")]
 
 

@@ -29,6 +29,10 @@
 //   c = (tr R - 1) / 2, v = a atan2(s, c) / s; for s < 1e-3 with c > 0 the series 1 + s^2/6 + 3 s^4/40 of asin(s)/s (the next term
 //   is below 5e-20), so v = 0 with a finite gradient at R = I.  Specified for angles up to 3.0 rad: towards pi, s -> 0 divides.
 //   The adjoint runs Rodrigues' adjoint, then log's, then Gram-Schmidt's.  The preserve and smooth terms read the 6-D vectors.
+//
+// smplify_points_kernel (soar_smplify_model_points) is a kernel of its own: the forward up to the model points, for every static
+//   point and not only the mapped ones, through the same device functions.  It feeds the pose search of pose_init.hip
+//   and adds nothing to the kernels above: their instructions are the parent's, one for one.
 #include <type_traits>
 
 #include "soar_common.h"
@@ -779,6 +783,155 @@ __global__ void __launch_bounds__(256) target_scales_kernel(int N, const float *
     if (tid == 0) out[n] = hi[0][0] < lo[0][0] ? -1.f : fmaxf(hi[0][0] - lo[0][0], hi[1][0] - lo[1][0]);
 }
 
+// ---- the static model points alone (soar_smplify_model_points; pose_init.hip searches over them) ----
+// The forward half of smplify_frame_kernel up to the model points, statement for statement, for ALL PA = 55 + NX + L static points
+// (mp_idx / mp_w: point p < 55 is joint p, the others weighted sums of gathered rows) instead of the P mapped ones, and without the
+// contour table: the static rows are the first VS of the gathered arrays, PS3 their posedirs row length.  The pose mean is applied.
+struct PointsArgs {
+    SoarSmplifyRig rig;
+    SoarSmplifyArgs a;
+    const float *pose_mean;
+    uint64_t mean_mask;
+    const int32_t *mp_idx;      // [PA][3]
+    const float *mp_w;          // [PA][3]
+    float *out;                 // [N][PA][3]
+    int PA, PS3;
+};
+
+__global__ void __launch_bounds__(S_THREADS) smplify_points_kernel(PointsArgs fa)
+{
+    const SoarSmplifyRig &rig = fa.rig;
+    const SoarSmplifyArgs &a = fa.a;
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int NB = rig.NBS + rig.NE, VS = rig.VS, VS3 = rig.VS * 3, PS3 = fa.PS3;
+    __shared__ float coef[S_MAX_NB];
+    __shared__ float Rl[SJ][9], Rw[SJ][9], Jr[SJ][3], tw[SJ][3], At[SJ][3];
+    __shared__ float feat[SFEAT];
+    __shared__ float vposed[S_MAX_VS][3], vert[S_MAX_VS][3];
+    __shared__ int par[SJ];
+    __shared__ float tr[3];
+
+    if (tid < NB) coef[tid] = tid < rig.NBS ? a.betas[tid] : a.expression[(size_t)n * rig.NE + (tid - rig.NBS)];
+    if (tid < 3) tr[tid] = a.transl[(size_t)n * 3 + tid];
+    if (tid < SJ) {
+        par[tid] = rig.parents[tid];
+        const bool mean = (fa.mean_mask >> tid) & 1ull;
+        const int o = joint_to_opt(tid);
+        if (o >= 0) {
+            int j, key, jk;
+            opt_joint(o, j, key, jk);
+            float x[6];
+            const float *src = pose_ptr(a, key, false) + ((size_t)n * key_joints(key) + jk) * 6;
+            for (int c = 0; c < 6; c++) x[c] = src[c];
+            if (mean) {                                            // rodrigues(log(R) + mean)
+                float R6[9], v[3];
+                rot6d(x, R6);
+                so3_log(R6, v);
+                for (int c = 0; c < 3; c++) v[c] += fa.pose_mean[tid * 3 + c];
+                rodrigues<3>(v, Rl[tid]);
+            } else {
+                rot6d(x, Rl[tid]);
+            }
+        } else {
+            const float *src = (tid == 22 ? a.jaw_pose : (tid == 23 ? a.leye_pose : a.reye_pose)) + (size_t)n * 3;
+            if (mean) {
+                const float v[3] = {src[0] + fa.pose_mean[tid * 3], src[1] + fa.pose_mean[tid * 3 + 1], src[2] + fa.pose_mean[tid * 3 + 2]};
+                rodrigues<3>(v, Rl[tid]);
+            } else {
+                rodrigues<3>(src, Rl[tid]);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- rest joints and pose features ----
+    if (tid < SJ) {
+        for (int c = 0; c < 3; c++) {
+            float s = 0.f;
+            const float *jd = rig.J_dirs + ((size_t)tid * 3 + c) * NB;
+            for (int l = 0; l < NB; l++) s = fmaf(coef[l], jd[l], s);
+            Jr[tid][c] = rig.J_template[tid * 3 + c] + s;
+        }
+    }
+    for (int k = tid; k < SFEAT; k += S_THREADS) {
+        const int j = 1 + k / 9, e = k % 9;
+        feat[k] = Rl[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+    }
+    __syncthreads();
+    // ---- the chain ----
+    if (tid < SJ) {
+        int path[S_MAX_DEPTH];
+        int dp = 0;
+        for (int p = tid; p >= 0 && dp < S_MAX_DEPTH; p = par[p]) path[dp++] = p;
+        float W[12];
+        {
+            const int r0 = path[dp - 1];
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) W[r * 4 + c] = Rl[r0][r * 3 + c];
+                W[r * 4 + 3] = Jr[r0][r];
+            }
+        }
+        for (int d = dp - 2; d >= 0; d--) {
+            const int j = path[d], p = path[d + 1];
+            const float rel[3] = {Jr[j][0] - Jr[p][0], Jr[j][1] - Jr[p][1], Jr[j][2] - Jr[p][2]};
+            float Nw[12];
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++)
+                    Nw[r * 4 + c] = fmaf(W[r * 4 + 2], Rl[j][6 + c], fmaf(W[r * 4 + 1], Rl[j][3 + c], W[r * 4] * Rl[j][c]));
+                Nw[r * 4 + 3] = fmaf(W[r * 4 + 2], rel[2], fmaf(W[r * 4 + 1], rel[1], W[r * 4] * rel[0])) + W[r * 4 + 3];
+            }
+            for (int k = 0; k < 12; k++) W[k] = Nw[k];
+        }
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) Rw[tid][r * 3 + c] = W[r * 4 + c];
+            tw[tid][r] = W[r * 4 + 3];
+            At[tid][r] = W[r * 4 + 3] - fmaf(W[r * 4 + 2], Jr[tid][2], fmaf(W[r * 4 + 1], Jr[tid][1], W[r * 4] * Jr[tid][0]));
+        }
+    }
+    // ---- shape blend and pose correctives of the static rows ----
+    for (int col = tid; col < VS3; col += S_THREADS) {
+        float sh = 0.f;
+        const float *sd = rig.shapedirs + (size_t)col * NB;
+        for (int l = 0; l < NB; l++) sh = fmaf(coef[l], sd[l], sh);
+        const float *pd = rig.posedirs + col;
+        float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
+        for (int k = 0; k < SFEAT; k += 3) {
+            acc0 = fmaf(feat[k], pd[(size_t)k * PS3], acc0);
+            acc1 = fmaf(feat[k + 1], pd[(size_t)(k + 1) * PS3], acc1);
+            acc2 = fmaf(feat[k + 2], pd[(size_t)(k + 2) * PS3], acc2);
+        }
+        (&vposed[0][0])[col] = ((acc0 + acc1) + acc2) + (rig.v_template[col] + sh);
+    }
+    __syncthreads();
+    // ---- skinning ----
+    if (tid < VS) {
+        float T[12];
+        for (int c = 0; c < 12; c++) T[c] = 0.f;
+        const float *w = rig.lbs_weights + (size_t)tid * SJ;
+        for (int j = 0; j < SJ; j++) {
+            const float wj = w[j];
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) T[r * 4 + c] = fmaf(wj, Rw[j][r * 3 + c], T[r * 4 + c]);
+                T[r * 4 + 3] = fmaf(wj, At[j][r], T[r * 4 + 3]);
+            }
+        }
+        for (int r = 0; r < 3; r++)
+            vert[tid][r] = fmaf(T[r * 4 + 2], vposed[tid][2], fmaf(T[r * 4 + 1], vposed[tid][1], T[r * 4] * vposed[tid][0])) + T[r * 4 + 3];
+    }
+    __syncthreads();
+    // ---- the model points ----
+    for (int p = tid; p < fa.PA; p += S_THREADS) {
+        float pos[3];
+        if (p < SJ) {
+            for (int c = 0; c < 3; c++) pos[c] = tw[p][c];
+        } else {
+            const int i0 = fa.mp_idx[p * 3], i1 = fa.mp_idx[p * 3 + 1], i2 = fa.mp_idx[p * 3 + 2];
+            const float w0 = fa.mp_w[p * 3], w1 = fa.mp_w[p * 3 + 1], w2 = fa.mp_w[p * 3 + 2];
+            for (int c = 0; c < 3; c++) pos[c] = fmaf(w2, vert[i2][c], fmaf(w1, vert[i1][c], w0 * vert[i0][c]));
+        }
+        for (int c = 0; c < 3; c++) fa.out[((size_t)n * fa.PA + p) * 3 + c] = pos[c] + tr[c];
+    }
+}
+
 }  // namespace
 
 }  // namespace soar
@@ -889,6 +1042,58 @@ extern "C" int soar_smplify_objective_body(const SoarSmplifyRig *rig, const Soar
         hipLaunchKernelGGL(smplify_finish_kernel, dim3(1), dim3(F_THREADS), 0, stream, a, r.NBS);
         SOAR_LAUNCH_OK("smplify_finish", stream, 0);
     }
+    return 0;
+}
+
+extern "C" int soar_smplify_model_points(const SoarSmplifyRig *rig, const SoarSmplifyBody *body, const SoarSmplifyArgs *args, int32_t PA,
+                                         const int32_t *mp_idx, const float *mp_w, float *points, void *stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!rig || !args) { set_error("soar_smplify_model_points: NULL rig / args"); return 1; }
+    const SoarSmplifyRig &r = *rig;
+    const SoarSmplifyArgs &a = *args;
+    if (r.J != SJ || r.NBS < 1 || r.NE < 0 || r.NBS + r.NE > S_MAX_NB || r.VS < 1 || r.VS > S_MAX_VS) {
+        set_error("soar_smplify_model_points: need J = %d, 1 <= NBS, NBS + NE <= %d, 1 <= VS <= %d (J=%d NBS=%d NE=%d VS=%d)",
+                  SJ, S_MAX_NB, S_MAX_VS, r.J, r.NBS, r.NE, r.VS);
+        return 1;
+    }
+    if (a.N <= 0 || PA < SJ || (int64_t)a.N * PA > 0x7fffffff / 3) {
+        set_error("soar_smplify_model_points: need N >= 1 and PA >= %d with N PA 3 below 2^31 (N=%d PA=%d)", SJ, a.N, PA);
+        return 1;
+    }
+    int PS3 = r.VS * 3;
+    uint64_t mean_mask = 0;
+    if (body) {
+        if (body->VU < r.VS || (body->mean_mask >> SJ) != 0 || (body->mean_mask != 0 && !body->pose_mean)) {
+            set_error("soar_smplify_model_points: the union VU=%d is below the static rows VS=%d, or a mean_mask without pose_mean or past "
+                      "joint %d", body->VU, r.VS, SJ - 1);
+            return 1;
+        }
+        PS3 = body->VU * 3;
+        mean_mask = body->mean_mask;
+    }
+    if (!r.J_template || !r.J_dirs || !r.parents || !r.v_template || !r.shapedirs || !r.posedirs || !r.lbs_weights
+        || (PA > SJ && (!mp_idx || !mp_w))) {
+        set_error("soar_smplify_model_points: NULL rig table");
+        return 1;
+    }
+    if (!a.global_orient || !a.body_pose || !a.left_hand_pose || !a.right_hand_pose || !a.betas || !a.transl || !a.jaw_pose || !a.leye_pose
+        || !a.reye_pose || (r.NE > 0 && !a.expression) || !points) {
+        set_error("soar_smplify_model_points: NULL input or output");
+        return 1;
+    }
+    PointsArgs fa;
+    fa.rig = r;
+    fa.a = a;
+    fa.pose_mean = mean_mask ? body->pose_mean : nullptr;
+    fa.mean_mask = mean_mask;
+    fa.mp_idx = mp_idx;
+    fa.mp_w = mp_w;
+    fa.out = points;
+    fa.PA = PA;
+    fa.PS3 = PS3;
+    hipLaunchKernelGGL(smplify_points_kernel, dim3(a.N), dim3(S_THREADS), 0, stream, fa);
+    SOAR_LAUNCH_OK("smplify_points", stream, 0);
     return 0;
 }
 

@@ -248,6 +248,14 @@ class SoarSmplifyArgs(C.Structure):
                 + [("g_" + k, _vp) for k in _SMPLIFY_PARAMS[:6]] + [("loss", _vp), ("kps", _vp), ("frame_betas", _vp), ("frame_loss", _vp)])
 
 
+class SoarPoseSearch(C.Structure):
+    """Mirror of ``struct SoarPoseSearch`` (include/soar_hip.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("N", "B", "H", "PA", "P", "min_points")]
+                + [(k, _vp) for k in ("points0", "pivot", "rotations", "src_inds", "dst_inds", "kp_mask", "target_kps", "Ks", "w2c", "scales")]
+                + [(k, C.c_float) for k in ("img_w", "img_h", "sigma", "conf_min", "z_min", "pad_")]
+                + [("cost", _vp), ("transl", _vp), ("valid", _vp)])
+
+
 class SoarSmplifyBody(C.Structure):
     """Mirror of ``struct SoarSmplifyBody`` (include/soar_hip.h)."""
     _fields_ = [("L_dyn", C.c_int32), ("n_rows", C.c_int32), ("neck", C.c_int32), ("VU", C.c_int32), ("dyn_vrow", _vp), ("dyn_bary", _vp),
@@ -627,6 +635,10 @@ SIGNATURES = {
     "soar_smplify_objective": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyArgs), _vp]),
     "soar_smplify_objective_body": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyBody), C.POINTER(SoarSmplifyArgs), _vp]),
     "soar_smplify_target_scales": (C.c_int, [C.c_int32, _vp, C.c_float, C.c_float, _vp, _vp]),
+    "soar_smplify_model_points": (C.c_int, [C.POINTER(SoarSmplifyRig), C.POINTER(SoarSmplifyBody), C.POINTER(SoarSmplifyArgs), C.c_int32,
+                                            _vp, _vp, _vp, _vp]),
+    "soar_pose_init_search": (C.c_int, [C.POINTER(SoarPoseSearch), _vp]),
+    "soar_pose_init_viterbi": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 8 + [_vp]),
     "soar_prior_vertex_setup": (C.c_int, [C.c_int32] * 3 + [_vp, C.POINTER(C.c_int64), _vp, C.c_int32] + [_vp] * 7 + [_vp]),
     "soar_prior_face_boxes": (C.c_int, [C.c_int32] * 3 + [_vp] * 3 + [_vp]),
     "soar_prior_raster": (C.c_int, [C.c_int32] * 6 + [_vp] * 8 + [_vp]),

@@ -10,7 +10,8 @@ here it is two launches:
   ``lbs_weights``, and ``J_regressor @ v_template`` / ``J_regressor @ shapedirs``.  The joint-to-keypoint tables (``src_inds``,
   ``dst_inds``, ``kp_mask``) are the caller's: the product ships no default for them.
 * ``smplify_objective``: the three weighted losses and the gradient of their sum.
-* ``project_keypoints``, ``target_scales``: forward-only by-products.
+* ``project_keypoints``, ``target_scales``, ``model_points``: forward-only by-products (``model_points`` feeds the search of
+  ``soar_amd.pose_init``, which makes the fit's start from keypoints alone).
 * ``SMPLify(rig).fit``: the reference's two stages with ``torch.optim.LBFGS`` (plumbing); ``save_params`` writes ``params.pth``;
   ``load_keypoints`` / ``load_smplerx`` read the inputs.
 
@@ -203,6 +204,12 @@ class KeypointRig:
         self.pt_kind, self.pt_idx, self.pt_w, self.pt_dst = d(kind), d(idx), d(w), d(dst.to(torch.int32))
         self.kp_mask = d(mask)
         self.src_inds, self.dst_inds = src, dst
+        # every static model point, mapped or not (model_points): joints, then selected vertices, then static landmarks
+        self.PA = J + NX + L
+        mp_idx, mp_w = torch.zeros(self.PA, 3, dtype=torch.int32), torch.zeros(self.PA, 3)
+        mp_idx[J:J + NX], mp_w[J:J + NX, 0] = pos[ex].to(torch.int32)[:, None], 1.0
+        mp_idx[J + NX:], mp_w[J + NX:] = pos[tri].to(torch.int32), bary
+        self.mp_idx, self.mp_w = d(mp_idx), d(mp_w)
 
     @classmethod
     def from_body_model(cls, body, src_inds, dst_inds, kp_mask, device="cuda", dynamic_contour=False, use_pose_mean=False) -> "KeypointRig":
@@ -375,6 +382,29 @@ def project_keypoints(rig: KeypointRig, params, Ks, w2c) -> torch.Tensor:
         dummy = torch.ones(N, N_KEYPOINTS, 3, dtype=torch.float32, device=rig.device)
         _launch(rig, p, None, N, Ks, w2c, (1.0, 1.0), dummy, dummy[:, 0, 0].contiguous(), (0.0, 0.0, 0.0), 1.0, False, None, False, kps)
     return kps
+
+
+@torch.no_grad()
+def model_points(rig: KeypointRig, params) -> torch.Tensor:
+    """The rig's static model points [N, 55 + NX + L, 3] float32 for every frame: the posed joints, the selected vertices and the static
+    landmarks, plus ``transl`` -- what the objective computes before the OpenPose conversion and the camera, for every point and
+    not only those ``src_inds`` names.  ``params`` as for ``smplify_objective``.  Forward only, one launch of a kernel of its own.
+    A rig with a contour table returns its static points only; a pose mean is applied."""
+    p, N = _prepare(rig, params, "params")
+    if N == 0:
+        raise ValueError("no frames")
+    a = hip_lib.SoarSmplifyArgs()
+    a.N = N
+    for k in PARAM_KEYS:
+        setattr(a, k, p[k].data_ptr() if p[k].numel() else None)
+    out = torch.empty(N, rig.PA, 3, dtype=torch.float32, device=rig.device)
+    rs = rig._struct(p["betas"].shape[1], p["expression"].shape[1])
+    bs = rig._body_struct(None) if rig.body_path else None
+    with torch.cuda.device(rig.device):
+        check(hip_lib.lib().soar_smplify_model_points(C.byref(rs), C.byref(bs) if bs is not None else None, C.byref(a), rig.PA,
+                                                      rig.mp_idx.data_ptr(), rig.mp_w.data_ptr(), out.data_ptr(), _stream(rig.device)),
+              "soar_smplify_model_points")
+    return out
 
 
 def target_scales(target_kps: torch.Tensor, img_wh) -> torch.Tensor:
