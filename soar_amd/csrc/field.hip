@@ -10,8 +10,8 @@
 //   field_reduce_kernel    the partial rows summed in double in a fixed order (four slices, then the slices in order)
 //   field_dz_kernel        dL/dz = W1[:, 32:34]^T . (sum over points of dL/dh of the offsets head)
 //   field_scatter_kernel   one thread per point: dL/de of the heads summed in a fixed order, scattered into the table
-//                          gradients with float atomics (runs of equal rows in a wave summed first: wave_add), and dL/dxyz
-//                          through the offsets o
+//                          gradients with float atomics (runs of equal rows in a wave summed first: wave_add; tables of at
+//                          most 32 rows per level summed per block in LDS first), and dL/dxyz through the offsets o
 //
 // The table gradients are the only atomics: their last bits depend on arrival order.  Everything else is bit-identical
 // from run to run.  No host synchronisation, no allocation.
@@ -486,9 +486,22 @@ __device__ inline void wave_add(float *dt, float *dq, uint32_t key, bool act, fl
     }
 }
 
+// A table with fewer rows per level than a wave has lanes (T <= 32) makes every wave, and every block, hit the same few rows
+// over and over: N * 8 / T float atomics land on one element, one after the other, and their rounding grows with the root of
+// that count (3 000 points on 2 rows: 3e-6 of the largest element, past the bar of DESIGN.md 9g).  SMALL sums the block's
+// contributions in LDS first (both tables: 2 x 16 x T x 2 floats, 8 KB at most) and adds each element to HBM once per block.
+constexpr int SMALL_T = 32;
+constexpr int SMALL_FLOATS = 2 * LEVELS * SMALL_T * 2;
+
+template <bool SMALL>
 __global__ void __launch_bounds__(128) field_scatter_kernel(FieldK a)
 {
-    // no early exit: every lane of a wave takes part in wave_add's shuffles; lanes past N carry nothing
+    // no early exit: every lane of a wave takes part in wave_add's shuffles and in the block's barriers; lanes past N carry nothing
+    __shared__ float acc[SMALL ? SMALL_FLOATS : 1];
+    if constexpr (SMALL) {
+        for (int e = threadIdx.x; e < SMALL_FLOATS; e += blockDim.x) acc[e] = 0.f;
+        __syncthreads();
+    }
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = n < a.N;
     float g[ENC], qg[ENC];
@@ -534,7 +547,13 @@ __global__ void __launch_bounds__(128) field_scatter_kernel(FieldK a)
             const uint32_t r = base + corner_slot(cl, k, mask);
             const float wx = lerp_w(k & 1, cl.o[0]), wy = lerp_w(k & 2, cl.o[1]), wz = lerp_w(k & 4, cl.o[2]);
             const float w = wx * wy * wz;
-            if (dt || dq) wave_add(dt, dq, r, scatter, w * g0, w * g1, w * h0, w * h1);
+            if constexpr (SMALL) {
+                // r < 16 * T <= 512: the first table's rows at acc[2 r], the second's behind them
+                if (scatter && dt) { atomicAdd(&acc[2 * r], w * g0); atomicAdd(&acc[2 * r + 1], w * g1); }
+                if (scatter && dq) { atomicAdd(&acc[2 * (LEVELS * a.T + r)], w * h0); atomicAdd(&acc[2 * (LEVELS * a.T + r) + 1], w * h1); }
+            } else if (dt || dq) {
+                wave_add(dt, dq, r, scatter, w * g0, w * g1, w * h0, w * h1);
+            }
             if (want_xyz) {
                 float v = 0.f;
                 if (any_g) { const float2 t = t2[r]; v += g0 * t.x + g1 * t.y; }
@@ -549,6 +568,14 @@ __global__ void __launch_bounds__(128) field_scatter_kernel(FieldK a)
     }
     if (valid && a.d_xyz)
         for (int d = 0; d < 3; d++) a.d_xyz[3 * n + d] = want_xyz ? dx[d] * inv_ext[d] : 0.f;
+    if constexpr (SMALL) {
+        __syncthreads();
+        const int floats = 2 * LEVELS * a.T;                              // of one table: <= SMALL_FLOATS / 2
+        for (int e = threadIdx.x; e < floats; e += blockDim.x) {
+            if (dt && acc[e] != 0.f) atomicAdd(dt + e, acc[e]);
+            if (dq && acc[floats + e] != 0.f) atomicAdd(dq + e, acc[floats + e]);
+        }
+    }
 }
 
 constexpr int FWD_BLOCK = 128;
@@ -676,7 +703,9 @@ extern "C" int soar_field_backward(const SoarFieldArgs *args, void *workspace, s
         SOAR_LAUNCH_OK("field_dz", stream, 0);
     }
     if (args->d_table || args->d_qtable || args->d_xyz) {
-        hipLaunchKernelGGL(field_scatter_kernel, dim3((args->N + FWD_BLOCK - 1) / FWD_BLOCK), dim3(FWD_BLOCK), 0, stream, k);
+        const dim3 grid((args->N + FWD_BLOCK - 1) / FWD_BLOCK);
+        if (k.T <= SMALL_T) hipLaunchKernelGGL(field_scatter_kernel<true>, grid, dim3(FWD_BLOCK), 0, stream, k);
+        else hipLaunchKernelGGL(field_scatter_kernel<false>, grid, dim3(FWD_BLOCK), 0, stream, k);
         SOAR_LAUNCH_OK("field_scatter", stream, 0);
     }
     return 0;

@@ -57,9 +57,9 @@ def _corner_bits(device):
     return _CORNER_BITS[device]
 
 
-def encode(p, p32, table, res, T, value32=False):
-    """-> [N, 2L] level-major; table [L*T, 2] in p's dtype.  value32: q takes its VALUE from the float32 product (the kernels'
-    input) and its derivative from p, so that a float64 restatement measures the arithmetic after the input's rounding"""
+def corner_terms(p, p32, res, T, value32=False):
+    """the eight corners' (rows [N, L] into a [L*T, 2] table, weights [N, L, 1] in p's dtype), in corner order; then the float32
+    cells (ceil, floor) [N, L, 3] int32 that they were taken from"""
     L = res.shape[0]
     res = res.to(p.device)
     if p.dtype == torch.float32:
@@ -74,12 +74,21 @@ def encode(p, p32, table, res, T, value32=False):
     o = q - f.to(p.dtype)
     off = (torch.arange(L, device=p.device) * T)[None, :]
     bits = _corner_bits(p.device)
-    enc = 0
+    terms = []
     for k in range(8):
         corner = torch.where(bits[k], c, f)
         w = torch.where(bits[k], o, 1 - o).prod(dim=-1, keepdim=True)       # [N, L, 1]
-        enc = enc + w * table[hash_slots(corner, T) + off]
-    return enc.reshape(p.shape[0], 2 * L)
+        terms.append((hash_slots(corner, T) + off, w))
+    return terms, (c, f)
+
+
+def encode(p, p32, table, res, T, value32=False):
+    """-> [N, 2L] level-major; table [L*T, 2] in p's dtype.  value32: q takes its VALUE from the float32 product (the kernels'
+    input) and its derivative from p, so that a float64 restatement measures the arithmetic after the input's rounding"""
+    enc = 0
+    for rows, w in corner_terms(p, p32, res, T, value32)[0]:
+        enc = enc + w * table[rows]
+    return enc.reshape(p.shape[0], 2 * res.shape[0])
 
 
 def heads(e, qe, z, W):
@@ -107,6 +116,31 @@ def params_of(module, dtype, device=None, requires_grad=True):
         m = getattr(module, f"mlp_base_{h}")
         W[h] = tuple(leaf(t) for t in (m.layers[0].weight, m.layers[0].bias, m.layers[1].weight, m.layers[1].bias))
     return leaf(module.encoding.hash_table), leaf(module.quat_encoding.hash_table), W
+
+
+PARAM_NAMES = ("layers.0.weight", "layers.0.bias", "layers.1.weight", "layers.1.bias")
+
+
+def run(module, xyz, z, loss, xyz_grad, dtype, is_normalized=False, res=None, T=None, value32=True, device=None):
+    """The restatement on leaf copies of ``module``'s parameters, then ``loss(out).backward()``: -> (out, grads), the gradients
+    under the names of ``module.named_parameters()`` plus "xyz" and "z".  ``res`` / ``T`` default to the module's own levels and
+    table size."""
+    table, qtable, W = params_of(module, dtype, device)
+    x = xyz.detach().to(table.device, dtype).clone().requires_grad_(xyz_grad)
+    zz = None if z is None else z.detach().to(table.device, dtype).clone().requires_grad_(z.requires_grad)
+    if res is None:
+        res = module.encoding.scalings.clone()
+    if T is None:
+        T = 2 ** int(module.log2_hashmap_size)
+    aabb = None if module.aabb is None else module.aabb.to(table.device)
+    out = field(x, zz, table, qtable, W, aabb, res, T, is_normalized, dtype, value32=value32)
+    loss(out).backward()
+    grads = {"encoding.hash_table": table.grad, "quat_encoding.hash_table": qtable.grad, "xyz": x.grad,
+             "z": None if zz is None else zz.grad}
+    for h in HEADS:
+        for i, nm in enumerate(PARAM_NAMES):
+            grads[f"mlp_base_{h}.{nm}"] = W[h][i].grad
+    return out, grads
 
 
 class RefField(torch.nn.Module):

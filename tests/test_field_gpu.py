@@ -93,18 +93,7 @@ def _names(f):
 
 
 def _run_ref(f, xyz, z, loss, xyz_grad, dtype, is_normalized=False):
-    table, qtable, W = R.params_of(f, dtype)
-    x = xyz.detach().to(dtype).clone().requires_grad_(xyz_grad)
-    zz = None if z is None else z.detach().to(dtype).clone().requires_grad_(z.requires_grad)
-    res = R.resolutions()
-    out = R.field(x, zz, table, qtable, W, f.aabb, res, 2 ** 18, is_normalized, dtype, value32=True)
-    loss(out).backward()
-    grads = {"encoding.hash_table": table.grad, "quat_encoding.hash_table": qtable.grad, "xyz": x.grad,
-             "z": None if zz is None else zz.grad}
-    for h in R.HEADS:
-        for i, nm in enumerate(("layers.0.weight", "layers.0.bias", "layers.1.weight", "layers.1.bias")):
-            grads[f"mlp_base_{h}.{nm}"] = W[h][i].grad
-    return out, grads
+    return R.run(f, xyz, z, loss, xyz_grad, dtype, is_normalized, res=R.resolutions(), T=2 ** 18)
 
 
 def _check_outputs(out, r64, r32):
