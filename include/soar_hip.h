@@ -51,14 +51,15 @@ extern "C" {
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
  * the LPIPS-VGG loss).  soar_vae_weights_floats / _weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward,
- * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail).  soar_data_mask_bbox / _crops /
+ * soar_sds_q_sample / _loss (+ SoarVaeArgs, SoarSdsArgs: the SDS guidance's VAE encoder and loss tail); soar_vae_weights_bytes16 /
+ * _pack_weights16 / _forward16 / _backward16: the encoder with bf16 / f16 weight products, both directions.  soar_data_mask_bbox / _crops /
  * _step_batch (+ SoarDataStepArgs: the training data module).  soar_frame_loss_partials / _pooled_partials,
  * soar_frames_geometry_warp_backward_losses (+ SoarLossFinish), soar_adam_step_at_gather: two small launches of the step plan folded
  * into their neighbours.  soar_eval_scratch_bytes / _image_metrics (+ SoarEvalArgs: test-split evaluation).
  * soar_normalnet_weights_bytes / _pack_weights / _workspace_bytes / _forward (+ SoarNormalNetArgs), soar_normal_crop_boxes / _sample /
  * _bytes: normal-map preprocessing.  soar_selftest_conv_gemm / _conv_pack (+ SoarConvGemmArgs, SoarConvGemmTaps): the shared
  * implicit-GEMM convolution and its weight packer by themselves, for the tests; soar_selftest_conv_gemm16 / _conv_pack16 /
- * _conv_gemm_act: the same with bf16 / f16 operands (SoarUnetConfig.precision uses them).  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
+ * _conv_pack16_bwd / _conv_gemm_act: the same with bf16 / f16 operands (SoarUnetConfig.precision uses them).  soar_prior_vertex_setup / _face_boxes / soar_prior_raster: the SMPL-X
  * normal priors (a triangle-mesh rasterizer).  soar_rast_backward_plan_loss (+ SoarBackwardLoss),
  * soar_frames_geometry_warp_backward_wave_losses: the frame loss inside the backward blend's launch.  soar_sam_weights_bytes /
  * _pack_weights / _workspace_bytes / _preprocess / _encode / _decode / _postprocess / _attention (+ SoarSamConfig, SoarSamEncodeArgs,
@@ -922,9 +923,12 @@ int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout
  * (ldw and wbat still count elements), rounds A to the type (nearest even) as it is loaded and accumulates in float32; x, bias, res
  * and y stay float32.  It refuses, besides the above: a wtype outside 1 .. 2; an ldw or wbat that is no multiple of 8.
  * soar_selftest_conv_pack16: torch [Cout][Cin][kk] float32 -> fwd [Cout][kk][Cinp] of the type, rounded to nearest even, channels
- * Cin .. Cinp - 1 zeros (Cinp >= Cin); kk = 1 converts a linear layer's matrix.  Forward only. */
+ * Cin .. Cinp - 1 zeros (Cinp >= Cin); kk = 1 converts a linear layer's matrix.
+ * soar_selftest_conv_pack16_bwd: the same tensor -> the data gradient's form in the type, soar_selftest_conv_pack's bwd:
+ * bwd[(ci kk + kk - 1 - t) ldb + co], rounded to nearest even; ldb >= Cout and a multiple of 8, columns Cout .. ldb - 1 zeros. */
 int soar_selftest_conv_gemm16(const SoarConvGemmArgs *args, int32_t wtype, int32_t *tile_out, void *stream);
 int soar_selftest_conv_pack16(const float *w, void *fwd, int32_t Cout, int32_t Cin, int32_t Cinp, int32_t kk, int32_t wtype, void *stream);
+int soar_selftest_conv_pack16_bwd(const float *w, void *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb, int32_t wtype, void *stream);
 /* SoarConvGemmArgs carries no activation: the descriptor at either operand type (wtype 0 .. 2) with the epilogue's act (0 none, 1 exact
  * GELU, 2 ReLU): y = act(alpha (A B^T) + bias) + res */
 int soar_selftest_conv_gemm_act(const SoarConvGemmArgs *args, int32_t wtype, int32_t act, int32_t *tile_out, void *stream);
@@ -1252,6 +1256,21 @@ int soar_vae_pack_weights(const float *raw, size_t raw_floats, void *packed, siz
 int soar_vae_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t image_size, size_t *bytes);
 int soar_vae_forward(const SoarVaeArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 int soar_vae_backward(const SoarVaeArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+/* The same encoder with 16-bit matrix-core products.  precision: 0 f32 (the entries above, bit for bit), 1 bf16,
+ * 2 f16; anything else is refused and nothing is launched.  At 1 / 2 exactly the products whose B operand is a weight tensor
+ * (the residual blocks' conv1 / conv2 / nin_shortcut, the stride-2 downsamples, q | k | v, proj_out, and the data gradient of each)
+ * read 16-bit packed weights and round their A operand to the type (nearest even) as it is loaded; sums, activations in memory,
+ * conv_in, conv_out, quant_conv, the attention's activation products, softmax, GroupNorm, the resize and the sample stay float32.
+ * SoarVaeArgs, the workspace and its size are those above.  soar_vae_weights_bytes16: the packed size at the precision (the 16-bit
+ * tensors take half).  soar_vae_pack_weights16 refuses a packed_bytes other than exactly that.  weights must come from
+ * soar_vae_pack_weights16 at the same precision.
+ * soar_vae_backward16 at 1 / 2 applies *g_scale behind the last 16-bit product (at conv_in's data gradient), not to g_latents, so a
+ * small loss weight never enters a 16-bit operand; at f16 it also runs on g_latents 2^10 and multiplies by 2^-10 in that same step.
+ * Both are exact in float32.  The 2^10 is this library's choice, checked on random weights only: train with bf16. */
+int soar_vae_weights_bytes16(int32_t precision, size_t *bytes);
+int soar_vae_pack_weights16(const float *raw, size_t raw_floats, void *packed, size_t packed_bytes, int32_t precision, void *stream);
+int soar_vae_forward16(const SoarVaeArgs *args, int32_t precision, void *workspace, size_t workspace_bytes, void *stream);
+int soar_vae_backward16(const SoarVaeArgs *args, int32_t precision, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The loss tail around the caller's UNet (ImageDream's MultiviewDiffusionGuidance.forward), t read from device memory (clamped to
  * [0, n_timesteps)).  tables [5][n_timesteps]: sqrt(ac), sqrt(1 - ac), sqrt(1 / ac), sqrt(1 / ac - 1), ac (alphas_cumprod).

@@ -83,8 +83,12 @@ inline int gemm(const float *x, int64_t ldx, const float *w, int K, int Cout, co
 int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, int kk, int64_t ldb, hipStream_t stream);
 
 // torch [Cout][Cin][kk] float32 -> fwd [Cout][kk][Cinp] of wtype's 16-bit type, rounded to nearest even, channels Cin .. Cinp - 1
-// zeros; kk = 1 converts a linear layer's matrix.  Forward only: there is no data-gradient form.
+// zeros; kk = 1 converts a linear layer's matrix.
 int launch_conv_pack16(const float *w, void *fwd, int Cout, int Cin, int Cinp, int kk, int wtype, hipStream_t stream);
+// ... and the data gradient's form in the same type and rounding, launch_conv_pack's bwd: bwd[(ci kk + kk - 1 - t) ldb + co].  ldb is a
+// multiple of 8 (conv_gemm16_kernel's loads); columns 0 .. cols - 1 of every row are written, Cout .. cols - 1 as zeros (cols = ldb:
+// the whole row; cols = Cout: one column block of a wider matrix, the others left alone).
+int launch_conv_pack16_bwd(const float *w, void *bwd, int Cout, int Cin, int kk, int64_t ldb, int cols, int wtype, hipStream_t stream);
 
 inline unsigned blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
 

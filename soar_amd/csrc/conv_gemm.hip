@@ -8,12 +8,14 @@
 //                          and zero dilation as index arithmetic over a table of taps.  Epilogue: y = act(alpha acc + bias) + res,
 //                          scattered to the tap table's output parity (act: none, exact GELU or ReLU; or, with act none, a PReLU of
 //                          one slope per output channel: ConvGemm::slope)
-//   conv_pack16_kernel     torch [Cout][Cin][kk] float32 -> [Cout][tap][Cinp] bf16 / f16, rounded to nearest even (forward only)
+//   conv_pack16_kernel     torch [Cout][Cin][kk] float32 -> [Cout][tap][Cinp] bf16 / f16, rounded to nearest even (forward)
+//   conv_pack16_bwd_kernel the same values spatially flipped and transposed, [Cin][tap][ldb] bf16 / f16: conv_pack_kernel's data-gradient
+//                          form in the 16-bit type
 //   conv_gemm16_kernel     the same implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16}: B read as 16-bit values, A rounded to the type
 //                          on its way into LDS, float32 accumulators and the same epilogue (ConvGemm::wtype)
 //
 // The launcher refuses the descriptors the kernel cannot run (conv_gemm.h); soar_selftest_conv_gemm / _conv_gemm16 / _conv_pack /
-// _conv_pack16 at the end of the file reach the launcher and the packers by themselves (tests/test_conv_gemm_*.py).
+// _conv_pack16 / _conv_pack16_bwd at the end of the file reach the launcher and the packers by themselves (tests/test_conv_gemm_*.py).
 // No atomics: every output has one fixed order of summation, the same whatever the tile and the batch.
 #include "conv_gemm.h"
 
@@ -47,6 +49,21 @@ __global__ void __launch_bounds__(256) conv_pack16_kernel(const float *__restric
     const int64_t r = e / Cinp;
     const int t = (int)(r % kk), co = (int)(r / kk);
     out[e] = ci < Cin ? (T)w[((size_t)co * Cin + ci) * kk + t] : (T)0.f;
+}
+
+// torch [Cout][Cin][kk] float32 -> the data gradient's form [(ci kk + kk - 1 - t) ldb + co] of T, rounded to nearest even: columns
+// 0 .. cols - 1 of every row are written, those from Cout on as zeros
+template <typename T>
+__global__ void __launch_bounds__(256) conv_pack16_bwd_kernel(const float *__restrict__ w, T *__restrict__ out, int Cout, int Cin, int kk,
+                                                              int64_t ldb, int cols)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)Cin * kk * cols) return;
+    // e walks the written part of the packed layout [ci][kk - 1 - t][co]
+    const int co = (int)(e % cols);
+    const int64_t r = e / cols;
+    const int t = kk - 1 - (int)(r % kk), ci = (int)(r / kk);
+    out[(size_t)r * ldb + co] = co < Cout ? (T)w[((size_t)co * Cin + ci) * kk + t] : (T)0.f;
 }
 
 // The epilogue of both kernels: y = act(alpha acc + bias) + res (act none and a slope: y = prelu(alpha acc + bias) + res) of a wave's WM x WN accumulator blocks (C / D layout: mfma_row),
@@ -483,6 +500,22 @@ int launch_conv_pack16(const float *w, void *fwd, int Cout, int Cin, int Cinp, i
     return 0;
 }
 
+int launch_conv_pack16_bwd(const float *w, void *bwd, int Cout, int Cin, int kk, int64_t ldb, int cols, int wtype, hipStream_t stream)
+{
+    if (wtype != WT_BF16 && wtype != WT_F16) { set_error("conv_pack16_bwd: wtype must be 1 (bf16) or 2 (f16) (got %d)", wtype); return 1; }
+    if (cols < Cout || cols > ldb || ldb % 8) {
+        set_error("conv_pack16_bwd: need Cout <= cols <= ldb and ldb a multiple of 8 (Cout=%d, cols=%d, ldb=%lld)", Cout, cols, (long long)ldb);
+        return 1;
+    }
+    const dim3 grid(blocks((int64_t)Cin * kk * cols));
+    if (wtype == WT_BF16)
+        hipLaunchKernelGGL(conv_pack16_bwd_kernel<__bf16>, grid, dim3(256), 0, stream, w, static_cast<__bf16 *>(bwd), Cout, Cin, kk, ldb, cols);
+    else
+        hipLaunchKernelGGL(conv_pack16_bwd_kernel<_Float16>, grid, dim3(256), 0, stream, w, static_cast<_Float16 *>(bwd), Cout, Cin, kk, ldb, cols);
+    SOAR_LAUNCH_OK("conv_pack16_bwd", stream, 0);
+    return 0;
+}
+
 int launch_conv_pack(const float *w, float *fwd, float *bwd, int Cout, int Cin, int kk, int64_t ldb, hipStream_t stream)
 {
     hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks((int64_t)Cout * Cin * kk)), dim3(256), 0, stream, w, fwd, bwd, Cout, Cin, kk, ldb);
@@ -548,6 +581,18 @@ extern "C" int soar_selftest_conv_pack16(const float *w, void *fwd, int32_t Cout
         return 1;
     }
     return soar::launch_conv_pack16(w, fwd, Cout, Cin, Cinp, kk, wtype, static_cast<hipStream_t>(stream_));
+}
+
+// the data gradient's form, every column 0 .. ldb - 1 written (Cout .. ldb - 1 zeros)
+extern "C" int soar_selftest_conv_pack16_bwd(const float *w, void *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb, int32_t wtype,
+                                             void *stream_)
+{
+    if (!w || !bwd || Cout < 1 || Cin < 1 || kk < 1 || ldb < Cout || ldb % 8 || ldb > INT32_MAX) {
+        soar::set_error("soar_selftest_conv_pack16_bwd: need w, bwd, positive sizes and ldb >= Cout, a multiple of 8 (Cout=%d, Cin=%d, kk=%d, "
+                        "ldb=%lld)", Cout, Cin, kk, (long long)ldb);
+        return 1;
+    }
+    return soar::launch_conv_pack16_bwd(w, bwd, Cout, Cin, kk, ldb, (int)ldb, wtype, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int soar_selftest_conv_pack(const float *w, float *fwd, float *bwd, int32_t Cout, int32_t Cin, int32_t kk, int64_t ldb,

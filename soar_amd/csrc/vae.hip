@@ -28,6 +28,12 @@
 //   sds_loss_kernel        one workgroup: CFG, x0 reconstruction, the per-group std rescale, loss, grad_norm and d loss / d latents
 //                          (recon mode), or w(t) (eps - noise) clipped and nan_to_num'ed (SDS mode); sums in double, fixed order
 //
+// Precision (soar_vae_*16): 0 is all of the above in float32.  1 (bf16) / 2 (f16) run exactly the products whose B
+// operand is a weight tensor on conv_gemm16_kernel: the packed forward and data-gradient forms are 16-bit values, A is rounded as it
+// is loaded, the sums and every activation in memory stay float32.  conv_in, conv_out, quant_conv, the attention's products of two
+// activations, softmax, GroupNorm, the resize and the loss tail stay float32.  The backward then keeps *g_scale away from the 16-bit
+// products: it multiplies at conv_in's data gradient, and f16 runs on g_latents 2^10 and divides there as well.
+//
 // No atomics: every value and gradient has one fixed order of summation, independent of N (bitwise reproducible, N = 4 equals four
 // N = 1 calls).  No host synchronisation, no allocation.  Offsets are size_t.
 #include "conv_gemm.h"
@@ -64,7 +70,9 @@ struct Layout {
     size_t raw_total;                                                 // floats
     size_t total;                                                     // floats of the packed form (raw copy first)
 };
-Layout layout()
+// prec != 0: the forward / data-gradient forms are 16-bit values, two to a float; their offsets still count floats, every region
+// 256-byte aligned.  The raw copy, the biases and the norm affines are float32 at every precision.
+Layout layout(int prec = 0)
 {
     Layout L{};
     size_t off = 0;
@@ -97,19 +105,20 @@ Layout layout()
     // packed regions, every one 256-byte aligned
     Carver pk;
     pk.float_offset(L.raw_total);       // behind the raw copy
+    auto wmat = [&](size_t n) { return pk.float_offset(prec ? (n + 1) / 2 : n); };      // a B operand of n elements
     auto rb_pack = [&](RB &b) {
-        b.c1f = pk.float_offset((size_t)b.cout * b.cin * 9); b.c1r = pk.float_offset((size_t)b.cout * b.cin * 9);
-        b.c2f = pk.float_offset((size_t)b.cout * b.cout * 9); b.c2r = pk.float_offset((size_t)b.cout * b.cout * 9);
-        if (b.cin != b.cout) { b.ninf = pk.float_offset((size_t)b.cout * b.cin); b.ninr = pk.float_offset((size_t)b.cout * b.cin); }
+        b.c1f = wmat((size_t)b.cout * b.cin * 9); b.c1r = wmat((size_t)b.cout * b.cin * 9);
+        b.c2f = wmat((size_t)b.cout * b.cout * 9); b.c2r = wmat((size_t)b.cout * b.cout * 9);
+        if (b.cin != b.cout) { b.ninf = wmat((size_t)b.cout * b.cin); b.ninr = wmat((size_t)b.cout * b.cin); }
     };
     for (int l = 0; l < NLEV; l++) {
         for (int j = 0; j < 2; j++) rb_pack(L.rb[l][j]);
-        if (l < 3) { L.df[l] = pk.float_offset((size_t)LEVC[l] * LEVC[l] * 9); L.dr[l] = pk.float_offset((size_t)LEVC[l] * LEVC[l] * 9); }
+        if (l < 3) { L.df[l] = wmat((size_t)LEVC[l] * LEVC[l] * 9); L.dr[l] = wmat((size_t)LEVC[l] * LEVC[l] * 9); }
     }
     rb_pack(L.mid1);
     rb_pack(L.mid2);
-    L.qkv_f = pk.float_offset((size_t)3 * CMID * CMID); L.qkv_b = pk.float_offset(3 * CMID); L.qkv_r = pk.float_offset((size_t)3 * CMID * CMID);
-    L.p_f = pk.float_offset((size_t)CMID * CMID); L.p_r = pk.float_offset((size_t)CMID * CMID);
+    L.qkv_f = wmat((size_t)3 * CMID * CMID); L.qkv_b = pk.float_offset(3 * CMID); L.qkv_r = wmat((size_t)3 * CMID * CMID);
+    L.p_f = wmat((size_t)CMID * CMID); L.p_r = wmat((size_t)CMID * CMID);
     L.total = pk.bytes() / sizeof(float);
     return L;
 }
@@ -454,6 +463,8 @@ struct FirstK {
     float *y;              // [N][S][S][128]
     const float *gpre;     // backward: [N][S][S][128]
     float *gxr;            // backward: [N][S][S][4] (3 used) gradient of the resized image (of x, before the * 2)
+    const float *g_scale;  // backward, 16-bit precisions: the device scalar that multiplies here instead of at the head, or NULL
+    float post;            // backward, 16-bit precisions: times this (undoes the head's pre-scale); 0: float32, neither is applied
     int64_t npix;          // N S S
 };
 // thread = (pixel, 32 output channels)
@@ -531,7 +542,14 @@ __global__ void __launch_bounds__(256) vae_first_bwd_kernel(FirstK k)
             }
         }
     }
-    *reinterpret_cast<float4 *>(k.gxr + (size_t)p * 4) = make_float4(2.f * acc[0], 2.f * acc[1], 2.f * acc[2], 0.f);
+    float o[3] = {2.f * acc[0], 2.f * acc[1], 2.f * acc[2]};
+    if (k.post != 0.f) {
+        // behind the last 16-bit product: the loss weight and the power of two are one exact factor, so one rounding each
+        const float f = (k.g_scale ? k.g_scale[0] : 1.f) * k.post;
+#pragma unroll
+        for (int c = 0; c < 3; c++) o[c] *= f;
+    }
+    *reinterpret_cast<float4 *>(k.gxr + (size_t)p * 4) = make_float4(o[0], o[1], o[2], 0.f);
 }
 
 struct ResizeBwdK {
@@ -590,6 +608,7 @@ struct HeadK {
     const float *eps;      // [N][4][h][w]
     float *mean, *logvar, *lat, *dlv;   // [N][4][h][w]
     const float *g_lat, *g_scale;
+    float pre;             // backward, 16-bit precisions: multiplies g_lat in place of *g_scale (1, or 2^10 at f16); 0: float32
     float *gx;             // backward: [N][h][w][512]
     float sf;
     int s;                 // h = w
@@ -685,7 +704,7 @@ __global__ void __launch_bounds__(256) vae_head_bwd_kernel(HeadK k)
     if (p >= k.npix) return;
     const int64_t ss = (int64_t)k.s * k.s;
     const int64_t n = p / ss, q = p - n * ss;
-    const float gs = k.g_scale ? k.g_scale[0] : 1.f;
+    const float gs = k.pre != 0.f ? k.pre : k.g_scale ? k.g_scale[0] : 1.f;
     float dmo[8];
 #pragma unroll
     for (int c = 0; c < ZC; c++) {
@@ -832,6 +851,7 @@ struct Ctx {
     const float *P;
     char *ws;
     hipStream_t stream;
+    int wt;                // WT_*: what the packed B operands hold
     float *F(size_t off) const { return reinterpret_cast<float *>(ws + off); }
     const float *R(size_t off) const { return P + off; }
 };
@@ -849,6 +869,13 @@ ConvGemm conv_k(const Ctx &c, int lev, const float *x, int Cin, const float *w, 
     k.stride = 1; k.dil = 1; k.per_image = 1; k.nph = 1;
     square_taps(k.ph[0], w, (int64_t)side * side * Cin, side, off);
     return k;
+}
+
+// a product whose B operand is a packed weight tensor: at the context's operand type
+int launch_w(const Ctx &c, ConvGemm k)
+{
+    k.wtype = c.wt;
+    return launch_conv_gemm(k, c.stream);
 }
 
 int gn_forward(const Ctx &c, const float *x, int64_t hw, int C, const float *gamma, const float *beta, float *stats, float *y, int silu)
@@ -893,27 +920,27 @@ int rb_forward(const Ctx &c, int lev, const RB &b, const RBws &s, float *out)
     const float *x = c.F(s.x);
     float *tmp = c.F(c.L.tmp), *h1 = c.F(s.h1);
     if (gn_forward(c, x, hw, b.cin, c.R(b.n1g), c.R(b.n1b), c.F(s.st1), tmp, 1)) return 1;
-    if (launch_conv_gemm(conv_k(c, lev, tmp, b.cin, c.R(b.c1f), b.cout, 3, -1, c.R(b.c1b), nullptr, h1), c.stream)) return 1;
+    if (launch_w(c, conv_k(c, lev, tmp, b.cin, c.R(b.c1f), b.cout, 3, -1, c.R(b.c1b), nullptr, h1))) return 1;
     if (gn_forward(c, h1, hw, b.cout, c.R(b.n2g), c.R(b.n2b), c.F(s.st2), tmp, 1)) return 1;
     const float *res = x;
     if (b.cin != b.cout) {
         ConvGemm k = conv_k(c, lev, x, b.cin, c.R(b.ninf), b.cout, 1, 0, c.R(b.ninb), nullptr, out);
-        if (launch_conv_gemm(k, c.stream)) return 1;
+        if (launch_w(c, k)) return 1;
         res = out;
     }
-    return launch_conv_gemm(conv_k(c, lev, tmp, b.cout, c.R(b.c2f), b.cout, 3, -1, c.R(b.c2b), res, out), c.stream);
+    return launch_w(c, conv_k(c, lev, tmp, b.cout, c.R(b.c2f), b.cout, 3, -1, c.R(b.c2b), res, out));
 }
 // g: gradient of the block's output (kept); writes the gradient of its input into gx.  t1 / t2: scratch at the level's size
 int rb_backward(const Ctx &c, int lev, const RB &b, const RBws &s, const float *g, float *gx, float *t1, float *t2)
 {
     const int64_t hw = (int64_t)c.d.S[lev] * c.d.S[lev];
-    if (launch_conv_gemm(conv_k(c, lev, g, b.cout, c.R(b.c2r), b.cout, 3, -1, nullptr, nullptr, t1), c.stream)) return 1;
+    if (launch_w(c, conv_k(c, lev, g, b.cout, c.R(b.c2r), b.cout, 3, -1, nullptr, nullptr, t1))) return 1;
     if (gn_backward(c, c.F(s.h1), hw, b.cout, c.R(b.n2g), c.R(b.n2b), c.F(s.st2), t1, nullptr, t1, 1)) return 1;
-    if (launch_conv_gemm(conv_k(c, lev, t1, b.cout, c.R(b.c1r), b.cin, 3, -1, nullptr, nullptr, t2), c.stream)) return 1;
+    if (launch_w(c, conv_k(c, lev, t1, b.cout, c.R(b.c1r), b.cin, 3, -1, nullptr, nullptr, t2))) return 1;
     const float *res = g;
     if (b.cin != b.cout) {
         ConvGemm k = conv_k(c, lev, g, b.cout, c.R(b.ninr), b.cin, 1, 0, nullptr, nullptr, t1);
-        if (launch_conv_gemm(k, c.stream)) return 1;
+        if (launch_w(c, k)) return 1;
         res = t1;
     }
     return gn_backward(c, c.F(s.x), hw, b.cin, c.R(b.n1g), c.R(b.n1b), c.F(s.st1), t2, res, gx, 1);
@@ -951,7 +978,7 @@ int attn_forward(const Ctx &c)
     if (Tp != T) SOAR_HIP_OK(hipMemsetAsync(qkv, 0, (size_t)d.N * Tp * C3 * sizeof(float), c.stream));
     ConvGemm k = mm_k(c, tmp, CMID, T, T, CMID, c.R(c.W.qkv_f), CMID, 0, C3, qkv, C3, Tp);
     k.bias = c.R(c.W.qkv_b);
-    if (launch_conv_gemm(k, c.stream)) return 1;
+    if (launch_w(c, k)) return 1;
     // scores into the dP buffer, then P
     float *Sc = c.F(c.L.dP);
     k = mm_k(c, qkv, C3, Tp, Tp, CMID, qkv + CMID, C3, (int64_t)Tp * C3, Tp, Sc, Tp, Tp);
@@ -966,7 +993,7 @@ int attn_forward(const Ctx &c)
     k = mm_k(c, O, CMID, Tp, T, CMID, c.R(c.W.p_f), CMID, 0, CMID, c.F(c.L.attn_out), CMID, T);
     k.bias = c.R(c.W.p_b);
     k.res = x;
-    return launch_conv_gemm(k, c.stream);
+    return launch_w(c, k);
 }
 // g: gradient of the attention block's output; writes the gradient of its input into gx (t: scratch)
 int attn_backward(const Ctx &c, const float *g, float *gx, float *t)
@@ -976,7 +1003,7 @@ int attn_backward(const Ctx &c, const float *g, float *gx, float *t)
     const float *qkv = c.F(c.L.qkv), *P = c.F(c.L.P);
     float *dO = c.F(c.L.dO), *dOT = c.F(c.L.dOT), *dP = c.F(c.L.dP), *XT = c.F(c.L.XT), *dqkv = c.F(c.L.dqkv);
     if (Tp != T) SOAR_HIP_OK(hipMemsetAsync(dO, 0, (size_t)d.N * Tp * CMID * sizeof(float), c.stream));
-    if (launch_conv_gemm(mm_k(c, g, CMID, T, T, CMID, c.R(c.W.p_r), CMID, 0, CMID, dO, CMID, Tp), c.stream)) return 1;
+    if (launch_w(c, mm_k(c, g, CMID, T, T, CMID, c.R(c.W.p_r), CMID, 0, CMID, dO, CMID, Tp))) return 1;
     // dV = P^T dO
     if (transpose(c, P, Tp, Tp, Tp, 0, XT)) return 1;
     if (transpose(c, dO, CMID, Tp, CMID, 0, dOT)) return 1;
@@ -994,7 +1021,7 @@ int attn_backward(const Ctx &c, const float *g, float *gx, float *t)
     if (transpose(c, qkv, C3, Tp, CMID, 0, dOT)) return 1;
     if (launch_conv_gemm(mm_k(c, XT, Tp, Tp, Tp, Tp, dOT, Tp, (int64_t)CMID * Tp, CMID, dqkv + CMID, C3, Tp), c.stream)) return 1;
     // d(normed input) = [dQ dK dV] [Wq; Wk; Wv], then the GroupNorm (no SiLU) + the residual
-    if (launch_conv_gemm(mm_k(c, dqkv, C3, Tp, T, C3, c.R(c.W.qkv_r), C3, 0, CMID, t, CMID, T), c.stream)) return 1;
+    if (launch_w(c, mm_k(c, dqkv, C3, Tp, T, C3, c.R(c.W.qkv_r), C3, 0, CMID, t, CMID, T))) return 1;
     return gn_backward(c, c.F(c.L.mid1_out), T, CMID, c.R(c.W.an_g), c.R(c.W.an_b), c.F(c.L.an_st), t, g, gx, 0);
 }
 
@@ -1038,22 +1065,48 @@ extern "C" int soar_vae_weights_bytes(size_t *bytes)
     return 0;
 }
 
-extern "C" int soar_vae_pack_weights(const float *raw, size_t raw_floats, void *packed, size_t packed_bytes, void *stream_)
+static bool check_precision(const char *what, int32_t precision)
 {
-    const Layout L = layout();
+    if (precision >= WT_F32 && precision <= WT_F16) return true;
+    set_error("%s: precision must be 0 (f32), 1 (bf16) or 2 (f16) (got %d)", what, precision);
+    return false;
+}
+
+extern "C" int soar_vae_weights_bytes16(int32_t precision, size_t *bytes)
+{
+    if (!bytes) { set_error("soar_vae_weights_bytes16: NULL bytes"); return 1; }
+    if (!check_precision("soar_vae_weights_bytes16", precision)) return 1;
+    *bytes = layout(precision).total * sizeof(float);
+    return 0;
+}
+
+// exact: the packed buffer must be exactly the precision's size (soar_vae_pack_weights16), or at least it (soar_vae_pack_weights)
+static int vae_pack_weights(const char *me, const float *raw, size_t raw_floats, void *packed, size_t packed_bytes, int prec, bool exact,
+                            void *stream_)
+{
+    const Layout L = layout(prec);
     if (!raw || raw_floats != L.raw_total) {
-        set_error("soar_vae_pack_weights: raw must hold %zu floats (got %zu%s)", L.raw_total, raw_floats, raw ? "" : ", NULL");
+        set_error("%s: raw must hold %zu floats (got %zu%s)", me, L.raw_total, raw_floats, raw ? "" : ", NULL");
         return 1;
     }
-    if (!packed || packed_bytes < L.total * sizeof(float) || ((uintptr_t)packed & (ALIGN - 1))) {
-        set_error("soar_vae_pack_weights: packed must be %zu bytes, 256-byte aligned (got %zu)", L.total * sizeof(float), packed_bytes);
+    const size_t need = L.total * sizeof(float);
+    if (!packed || (exact ? packed_bytes != need : packed_bytes < need) || ((uintptr_t)packed & (ALIGN - 1))) {
+        if (exact) set_error("%s: packed must be %zu bytes at precision %d, 256-byte aligned (got %zu)", me, need, prec, packed_bytes);
+        else set_error("%s: packed must be %zu bytes, 256-byte aligned (got %zu)", me, need, packed_bytes);
         return 1;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     float *P = static_cast<float *>(packed);
     SOAR_HIP_OK(hipMemcpyAsync(P, raw, L.raw_total * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    // fwd, bwd: the regions' offsets in floats; fcol, bcol: where inside them this tensor starts, in elements
+    auto pack_at = [&](size_t src, size_t fwd, size_t fcol, size_t bwd, size_t bcol, int Cout, int Cin, int kk, int64_t ldb) -> int {
+        if (!prec) return launch_conv_pack(raw + src, P + fwd + fcol, P + bwd + bcol, Cout, Cin, kk, ldb, stream);
+        uint16_t *f16 = reinterpret_cast<uint16_t *>(P + fwd) + fcol, *b16 = reinterpret_cast<uint16_t *>(P + bwd) + bcol;
+        if (launch_conv_pack16(raw + src, f16, Cout, Cin, Cin, kk, prec, stream)) return 1;
+        return launch_conv_pack16_bwd(raw + src, b16, Cout, Cin, kk, ldb, Cout, prec, stream);
+    };
     auto pack = [&](size_t src, size_t fwd, size_t bwd, int Cout, int Cin, int kk, int64_t ldb) {
-        return launch_conv_pack(raw + src, P + fwd, P + bwd, Cout, Cin, kk, ldb, stream);
+        return pack_at(src, fwd, 0, bwd, 0, Cout, Cin, kk, ldb);
     };
     auto pack_rb = [&](const RB &b) -> int {
         if (pack(b.c1w, b.c1f, b.c1r, b.cout, b.cin, 9, b.cout)) return 1;
@@ -1070,10 +1123,22 @@ extern "C" int soar_vae_pack_weights(const float *raw, size_t raw_floats, void *
     const size_t qkvw[3] = {L.q_w, L.k_w, L.v_w}, qkvb[3] = {L.q_b, L.k_b, L.v_b};
     for (int j = 0; j < 3; j++) {
         // forward rows j C .. of [3C][C]; data gradient columns j C .. of [C][3C]
-        if (pack(qkvw[j], L.qkv_f + (size_t)j * CMID * CMID, L.qkv_r + (size_t)j * CMID, CMID, CMID, 1, 3 * CMID)) return 1;
+        if (pack_at(qkvw[j], L.qkv_f, (size_t)j * CMID * CMID, L.qkv_r, (size_t)j * CMID, CMID, CMID, 1, 3 * CMID)) return 1;
         SOAR_HIP_OK(hipMemcpyAsync(P + L.qkv_b + (size_t)j * CMID, raw + qkvb[j], CMID * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
     return pack(L.p_w, L.p_f, L.p_r, CMID, CMID, 1, CMID);
+}
+
+extern "C" int soar_vae_pack_weights(const float *raw, size_t raw_floats, void *packed, size_t packed_bytes, void *stream_)
+{
+    return vae_pack_weights("soar_vae_pack_weights", raw, raw_floats, packed, packed_bytes, WT_F32, false, stream_);
+}
+
+extern "C" int soar_vae_pack_weights16(const float *raw, size_t raw_floats, void *packed, size_t packed_bytes, int32_t precision,
+                                       void *stream_)
+{
+    if (!check_precision("soar_vae_pack_weights16", precision)) return 1;
+    return vae_pack_weights("soar_vae_pack_weights16", raw, raw_floats, packed, packed_bytes, precision, true, stream_);
 }
 
 extern "C" int soar_vae_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t image_size, size_t *bytes)
@@ -1084,17 +1149,18 @@ extern "C" int soar_vae_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t
     return 0;
 }
 
-extern "C" int soar_vae_forward(const SoarVaeArgs *a, void *workspace, size_t workspace_bytes, void *stream_)
+static int vae_forward(const char *me, const SoarVaeArgs *a, int prec, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    if (!check_args("soar_vae_forward", a, workspace, workspace_bytes)) return 1;
+    if (!check_args(me, a, workspace, workspace_bytes)) return 1;
     if (a->N == 0) return 0;
-    if (!a->x) { set_error("soar_vae_forward: NULL x"); return 1; }
-    if (a->latents && !a->eps) { set_error("soar_vae_forward: latents need eps (the posterior noise)"); return 1; }
-    if (!a->latents && !a->mean && !a->logvar) { set_error("soar_vae_forward: no output (latents, mean, logvar all NULL)"); return 1; }
+    if (!a->x) { set_error("%s: NULL x", me); return 1; }
+    if (a->latents && !a->eps) { set_error("%s: latents need eps (the posterior noise)", me); return 1; }
+    if (!a->latents && !a->mean && !a->logvar) { set_error("%s: no output (latents, mean, logvar all NULL)", me); return 1; }
     Ctx c{};
     c.d = dims_of(a->N, a->image_size);
     c.L = ws_layout(c.d);
-    c.W = layout();
+    c.W = layout(prec);
+    c.wt = prec;
     c.P = static_cast<const float *>(a->weights);
     c.ws = static_cast<char *>(workspace);
     c.stream = static_cast<hipStream_t>(stream_);
@@ -1114,7 +1180,7 @@ extern "C" int soar_vae_forward(const SoarVaeArgs *a, void *workspace, size_t wo
         ConvGemm k = conv_k(c, l, c.F(c.L.rb_out[l][1]), LEVC[l], c.R(c.W.df[l]), LEVC[l], 3, 0, c.R(c.W.db[l]), nullptr, c.F(c.L.down[l]));
         k.Hg = k.Wg = k.Wout = d.S[l + 1]; k.yim = (int64_t)d.S[l + 1] * d.S[l + 1];
         k.stride = 2;                                 // taps at 0 .. 2: pad right / bottom by one, the bounds check loads the zeros
-        if (launch_conv_gemm(k, c.stream)) return 1;
+        if (launch_w(c, k)) return 1;
     }
     if (rb_forward(c, 3, c.W.mid1, c.L.mid1, c.F(c.L.mid1_out))) return 1;
     if (attn_forward(c)) return 1;
@@ -1132,15 +1198,30 @@ extern "C" int soar_vae_forward(const SoarVaeArgs *a, void *workspace, size_t wo
     return 0;
 }
 
-extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t workspace_bytes, void *stream_)
+extern "C" int soar_vae_forward(const SoarVaeArgs *a, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    if (!check_args("soar_vae_backward", a, workspace, workspace_bytes)) return 1;
+    return vae_forward("soar_vae_forward", a, WT_F32, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int soar_vae_forward16(const SoarVaeArgs *a, int32_t precision, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!check_precision("soar_vae_forward16", precision)) return 1;
+    return vae_forward("soar_vae_forward16", a, precision, workspace, workspace_bytes, stream_);
+}
+
+static int vae_backward(const char *me, const SoarVaeArgs *a, int prec, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!check_args(me, a, workspace, workspace_bytes)) return 1;
     if (a->N == 0) return 0;
-    if (!a->g_latents || !a->g_x) { set_error("soar_vae_backward: NULL g_latents / g_x"); return 1; }
+    if (!a->g_latents || !a->g_x) { set_error("%s: NULL g_latents / g_x", me); return 1; }
     Ctx c{};
     c.d = dims_of(a->N, a->image_size);
     c.L = ws_layout(c.d);
-    c.W = layout();
+    c.W = layout(prec);
+    c.wt = prec;
+    // 16-bit operands: the incoming weight (1e-4 in the shipped configs) would push the gradient below the types' range, so it
+    // multiplies behind the last such product instead (the chain is linear); f16 also runs on g_latents 2^10.  Both powers are exact.
+    const float pre = prec == WT_F16 ? 1024.f : 1.f;
     c.P = static_cast<const float *>(a->weights);
     c.ws = static_cast<char *>(workspace);
     c.stream = static_cast<hipStream_t>(stream_);
@@ -1150,6 +1231,7 @@ extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t w
     HeadK hk{};
     hk.cw = c.R(c.W.co_w); hk.qw = c.R(c.W.qc_w); hk.m8 = c.F(c.L.g8); hk.dlv = c.F(c.L.dlv);
     hk.g_lat = a->g_latents; hk.g_scale = a->g_scale; hk.gx = G[0];
+    if (prec) hk.pre = pre;
     hk.sf = a->scale_factor; hk.s = d.S[3]; hk.npix = d.pix(3);
     hipLaunchKernelGGL(vae_head_bwd_kernel, dim3(blocks(hk.npix)), dim3(256), 0, c.stream, hk);
     SOAR_LAUNCH_OK("vae_head_bwd", c.stream, 0);
@@ -1173,7 +1255,7 @@ extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t w
             ConvGemm k = conv_k(c, l, G[0], LEVC[l], c.R(c.W.dr[l]), LEVC[l], 3, -2, nullptr, nullptr, G[1]);
             k.Hin = k.Win = d.S[l + 1]; k.xim = (int64_t)d.S[l + 1] * d.S[l + 1];
             k.dil = 2;
-            if (launch_conv_gemm(k, c.stream)) return 1;
+            if (launch_w(c, k)) return 1;
             rot();
         }
         for (int j = 1; j >= 0; j--) {
@@ -1184,6 +1266,7 @@ extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t w
     FirstK fk{};
     fk.H = a->H; fk.W = a->W; fk.S = d.S[0];
     fk.w = c.R(c.W.cin_w); fk.gpre = G[0]; fk.gxr = c.F(c.L.gxr); fk.npix = d.pix(0);
+    if (prec) { fk.g_scale = a->g_scale; fk.post = 1.f / pre; }
     hipLaunchKernelGGL(vae_first_bwd_kernel, dim3(blocks(fk.npix)), dim3(256), 0, c.stream, fk);
     SOAR_LAUNCH_OK("vae_first_bwd", c.stream, 0);
     ResizeBwdK rk{};
@@ -1195,6 +1278,17 @@ extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t w
     hipLaunchKernelGGL(vae_resize_bwd_kernel, dim3(blocks(rk.npix)), dim3(256), 0, c.stream, rk);
     SOAR_LAUNCH_OK("vae_resize_bwd", c.stream, 0);
     return 0;
+}
+
+extern "C" int soar_vae_backward(const SoarVaeArgs *a, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return vae_backward("soar_vae_backward", a, WT_F32, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int soar_vae_backward16(const SoarVaeArgs *a, int32_t precision, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!check_precision("soar_vae_backward16", precision)) return 1;
+    return vae_backward("soar_vae_backward16", a, precision, workspace, workspace_bytes, stream_);
 }
 
 static bool check_sds(const char *what, const SoarSdsArgs *a)

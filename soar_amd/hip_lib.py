@@ -530,6 +530,7 @@ SIGNATURES = {
     "soar_selftest_conv_pack": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp]),
     "soar_selftest_conv_gemm16": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.POINTER(C.c_int32), _vp]),
     "soar_selftest_conv_pack16": (C.c_int, [_vp, _vp] + [C.c_int32] * 5 + [_vp]),
+    "soar_selftest_conv_pack16_bwd": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _vp]),
     "soar_selftest_conv_gemm_act": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.c_int32, C.POINTER(C.c_int32), _vp]),
     "soar_selftest_conv_gemm_slope": (C.c_int, [C.POINTER(SoarConvGemmArgs), C.c_int32, C.c_int32, _vp, C.POINTER(C.c_int32), _vp]),
     "soar_prof_enable": (C.c_int, [C.c_int]),
@@ -606,6 +607,10 @@ SIGNATURES = {
     "soar_vae_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_vae_forward": (C.c_int, [C.POINTER(SoarVaeArgs), _vp, C.c_size_t, _vp]),
     "soar_vae_backward": (C.c_int, [C.POINTER(SoarVaeArgs), _vp, C.c_size_t, _vp]),
+    "soar_vae_weights_bytes16": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_vae_pack_weights16": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_int32, _vp]),
+    "soar_vae_forward16": (C.c_int, [C.POINTER(SoarVaeArgs), C.c_int32, _vp, C.c_size_t, _vp]),
+    "soar_vae_backward16": (C.c_int, [C.POINTER(SoarVaeArgs), C.c_int32, _vp, C.c_size_t, _vp]),
     "soar_sds_q_sample": (C.c_int, [C.POINTER(SoarSdsArgs), _vp]),
     "soar_sds_loss": (C.c_int, [C.POINTER(SoarSdsArgs), _vp]),
     "soar_surfel_activations_forward": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 10 + [_vp]),

@@ -3,11 +3,13 @@ TS/guidance/imagedream_guidance.py, ``guidance_type: imagedream-multiview-diffus
 (csrc/vae.hip): the Stable-Diffusion-2.1 VAE encoder with the resize folded into its first convolution, and the loss tail around
 the caller's UNet.
 
-* ``LatentEncoder(state_dict, scale_factor=0.18215)`` takes the ldm ``AutoencoderKL`` key layout (``encoder.*``, ``quant_conv.*``),
+* ``LatentEncoder(state_dict, scale_factor=0.18215, precision="f32")`` takes the ldm ``AutoencoderKL`` key layout (``encoder.*``, ``quant_conv.*``),
   with or without the ``first_stage_model.`` prefix; other keys (the decoder, the UNet) are ignored, a missing or misshapen key
   raises, naming it.  ``forward(rgb_NCHW, image_size=256, posterior_noise=None, grad_scale=None) -> latents`` is
   ``get_first_stage_encoding(encode_first_stage(interpolate(rgb) * 2 - 1))`` through one autograd node; the weights are frozen.
-  ``encode(...) -> (mean, logvar)`` (no gradient) serves the tests.
+  ``encode(...) -> (mean, logvar)`` (no gradient) serves the tests.  ``precision="bf16"`` / ``"f16"`` (the reference's
+  ``half_precision_weights``; the default ``"f32"`` is what the reference's encoder runs at) puts every product with a weight tensor,
+  forward and data gradient, on the 16-bit matrix core; the rest and every activation in memory stay float32.
 * ``MultiviewSDS(encoder, ...)`` is the guidance's ``forward`` with the UNet left to the caller: ``eps_fn(latent_model_input [2B, 4,
   h, w], t_expand [2B]) -> [2B, 4, h, w]`` in the order (text, uncond), a closure over ``model.apply_model`` and its context.
 
@@ -27,6 +29,7 @@ from torch import nn
 
 from . import hip_lib
 from .hip_lib import _bytes, _stream, _workspace, check
+from .unet import PRECISIONS
 
 CH, CH_MULT, Z = 128, (1, 2, 4, 4), 4
 SCALE_FACTOR = 0.18215
@@ -128,10 +131,20 @@ class _EncodeFn(torch.autograd.Function):
 
 class LatentEncoder(nn.Module):
     """The SD-2.1 VAE encoder + quant_conv + posterior sample (see the module's docstring).  The weights are one frozen flat buffer
-    (``weights``, in WEIGHT_ORDER); move the module with ``.to(device)``.  They are packed for the kernels once per device."""
+    (``weights``, in WEIGHT_ORDER); move the module with ``.to(device)``.  They are packed for the kernels once per device.
 
-    def __init__(self, state_dict: Mapping[str, torch.Tensor], scale_factor: float = SCALE_FACTOR):
+    ``precision``: ``"f32"`` (the default), ``"bf16"`` or ``"f16"``.  With a 16-bit precision the packed copy holds the weight matrices
+    of conv1 / conv2 / nin_shortcut, the downsamples, q | k | v and proj_out, in both directions, in that type; those products round
+    their activations to it as they are loaded and sum in float32.  ``weights`` stays the float32 buffer.  In the backward the
+    incoming gradient's scale is applied behind the last 16-bit product, so a small loss weight reaches no 16-bit operand; f16 also
+    runs the backward on the gradient times 2^10 and divides at the end.  That constant has been checked on random weights only:
+    bf16 is the precision to train with."""
+
+    def __init__(self, state_dict: Mapping[str, torch.Tensor], scale_factor: float = SCALE_FACTOR, precision: str = "f32"):
         super().__init__()
+        if not isinstance(precision, str) or precision not in PRECISIONS:
+            raise ValueError(f"LatentEncoder: precision must be one of 'f32', 'bf16', 'f16' (got {precision!r})")
+        self.precision, self._code = precision, PRECISIONS[precision]
         sd = dict(state_dict)
         prefix = PREFIX if any(k.startswith(PREFIX + "encoder.") for k in sd) else ""
         parts = []
@@ -156,9 +169,10 @@ class LatentEncoder(nn.Module):
             nf = _bytes(L.soar_vae_weights_floats, "soar_vae_weights_floats")
             if nf != w.numel():
                 raise RuntimeError(f"LatentEncoder: the library expects {nf} weight floats, the module holds {w.numel()}")
-            packed = _workspace(_bytes(L.soar_vae_weights_bytes, "soar_vae_weights_bytes"), dev)
+            packed = _workspace(_bytes(L.soar_vae_weights_bytes16, "soar_vae_weights_bytes16", self._code), dev)
             with torch.cuda.device(dev):
-                check(L.soar_vae_pack_weights(w.data_ptr(), w.numel(), packed.data_ptr(), packed.numel(), _stream(dev)), "soar_vae_pack_weights")
+                check(L.soar_vae_pack_weights16(w.data_ptr(), w.numel(), packed.data_ptr(), packed.numel(), self._code, _stream(dev)),
+                      "soar_vae_pack_weights16")
             return packed
 
         return self._pack.get([w], dev, f"LatentEncoder: weights are not on {dev}: move the module with .to('{dev}')", pack)
@@ -188,7 +202,7 @@ class LatentEncoder(nn.Module):
             outs["mean"], outs["logvar"] = torch.empty(N, Z, h, h, device=dev), torch.empty(N, Z, h, h, device=dev)
             a.mean, a.logvar = hip_lib.ptr(outs["mean"]), hip_lib.ptr(outs["logvar"])
         with torch.cuda.device(dev):
-            check(L.soar_vae_forward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(dev)), "soar_vae_forward")
+            check(L.soar_vae_forward16(C.byref(a), self._code, ws.data_ptr(), ws.numel(), _stream(dev)), "soar_vae_forward16")
         res = outs["latents"] if want_latents else (outs["mean"], outs["logvar"])
         return res, ws
 
@@ -203,7 +217,8 @@ class LatentEncoder(nn.Module):
             a.grad_scale = grad_scale.data_ptr()
             _strides(a.grad_scale_stride, grad_scale)
         with torch.cuda.device(x.device):
-            check(hip_lib.lib().soar_vae_backward(C.byref(a), ws.data_ptr(), ws.numel(), _stream(x.device)), "soar_vae_backward")
+            check(hip_lib.lib().soar_vae_backward16(C.byref(a), self._code, ws.data_ptr(), ws.numel(), _stream(x.device)),
+                  "soar_vae_backward16")
         return g
 
     def _prepare(self, rgb, image_size):
