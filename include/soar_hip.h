@@ -46,7 +46,7 @@ extern "C" {
  * soar_rast_backward_rows; the geometry buffer grew (one statistics row per 64 Gaussians: ask soar_rast_geometry_bytes) and so did
  * soar_views_grad_scratch_floats (a block per back view).  Still 8, additive: soar_tsdf_integrate, soar_mc_workspace_bytes / _count / _emit,
  * soar_mesh_filter_bytes / _components, soar_mesh_simplify_bytes / _count / soar_mesh_simplify, soar_mesh_attr_transfer[_bytes],
- * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes], soar_mesh_close_holes[_bytes], soar_mesh_atlas_bytes / _levels / _place,
+ * soar_mesh_adjacency[_bytes], soar_mesh_smooth[_bytes], soar_mesh_prune[_bytes], soar_mesh_close_holes[_bytes], soar_mesh_repair_workspace_size / _count / soar_mesh_repair, soar_mesh_atlas_bytes / _levels / _place,
  * soar_mesh_texels_bytes / soar_mesh_texel_offsets / soar_mesh_texels / soar_mesh_texture_write (mesh export).  soar_field_workspace_bytes / _forward / _backward (+ SoarFieldHead,
  * SoarFieldArgs: the attribute field).  soar_envmap_workspace_bytes / _forward / _backward (+ SoarEnvmapArgs: the environment-map
  * background).  soar_lpips_weights_bytes / _pack_weights / _workspace_bytes / _forward / _backward (+ SoarLpipsWeights, SoarLpipsArgs:
@@ -1043,6 +1043,31 @@ int soar_mesh_close_holes_bytes(int32_t V, int32_t F, size_t *bytes);
 int soar_mesh_close_holes(int32_t V, int32_t F, const float *verts, const int32_t *faces, int32_t max_hole_edges, void *workspace,
                           size_t workspace_bytes, float *verts_out, int32_t *faces_out, int32_t *loop_edges_out, int64_t *counts_host,
                           void *stream);
+/* Repair of non-manifold edges and vertices of the exported mesh (mesh_repair.hip; DESIGN.md 9b, "Repairing non-manifold edges and
+ * vertices" states the definition; MeshLab's two repair filters made order-free, NOT its edge-splitting method).  In order: a face
+ * with two equal corners goes; on every undirected edge with k > 2 remaining faces the k - 2 that come first in ascending (bits of
+ * the float32 squared doubled area as uint32, face index) go, in one pass; over the corners of the surviving faces, the two faces of
+ * every edge that has exactly two are joined at both ends of the edge, a fan is a connected set of corners and its id its least
+ * corner index 3 f + c; per vertex the fan of least id keeps the vertex and every other fan gets a copy of it.  Output: the input
+ * vertices some surviving face names, in input order, then the copies in ascending fan id; the surviving faces in input order and
+ * winding.
+ * soar_mesh_repair_count: the analysis alone.  counts_host[9] = {output vertices, output faces, edges that had more than two faces,
+ *   faces removed on such edges, faces with two equal corners dropped, copies added, input vertices no surviving face names, edges
+ *   of the result whose two faces run in the same direction (counted, not changed), border edges of the result}.
+ * soar_mesh_repair: runs the same analysis again (it does not depend on what the workspace holds) and writes verts_out
+ *   [counts_host[0]][3], faces_out [counts_host[1]][3] and source_out [counts_host[0]] = the input vertex every output vertex came
+ *   from; the sizes are those soar_mesh_repair_count reports for the same mesh (never more than 3 F vertices and F faces).  The
+ *   outputs must not be the inputs.
+ * 1 <= V <= 2^30, 0 <= F <= 2^28; the workspace is the caller's, 256-byte aligned, sized by soar_mesh_repair_workspace_size; sizes, pointers
+ * and workspaces that are refused are refused before any launch.  F = 0 launches nothing (no vertex is named: the result is empty).
+ * A face naming a vertex outside [0, V) is counted on the device and the call refused at its one stream synchronisation, which also
+ * reads the counts: soar_mesh_repair_count writes nothing but its workspace; what soar_mesh_repair wrote by then is not to be used.
+ * Integer atomics only (atomicMin hooking, same-value flag stores, counters): bit-reproducible. */
+int soar_mesh_repair_workspace_size(int32_t V, int32_t F, size_t *bytes);
+int soar_mesh_repair_count(int32_t V, int32_t F, const float *verts, const int32_t *faces, void *workspace, size_t workspace_bytes,
+                           int64_t *counts_host, void *stream);
+int soar_mesh_repair(int32_t V, int32_t F, const float *verts, const int32_t *faces, void *workspace, size_t workspace_bytes,
+                     float *verts_out, int32_t *faces_out, int32_t *source_out, int64_t *counts_host, void *stream);
 /* The texture atlas of the exported mesh (mesh_texture.hip, soar_amd/texture.py; DESIGN.md 9b, "Texture atlas" states the layout).
  * Every face gets half of a square cell of side s texels, s a power of two in [4, texture_size / 2]; the cells stand one behind the
  * other, largest first, on the Morton curve of the image's 4 x 4 texel units.  texture_size is a power of two in [16, 16384];

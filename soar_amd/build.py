@@ -46,6 +46,8 @@ EXTRA_FLAGS = {
     "mesh_attr.hip": ["-ffp-contract=off"],
     # the new vertices' float64 sums are restated operation by operation (tests/mesh_holes_ref.py)
     "mesh_holes.hip": ["-ffp-contract=off"],
+    # the bits of the faces' squared areas decide which faces an edge loses; restated operation by operation (tests/mesh_repair_ref.py)
+    "mesh_repair.hip": ["-ffp-contract=off"],
     # face areas decide the atlas' integer layout, and barycentrics and positions are restated operation by operation (tests/texture_ref.py)
     "mesh_texture.hip": ["-ffp-contract=off"],
     # the background's composite must equal torch's three separate operations bit for bit
@@ -83,7 +85,7 @@ EXTRA_FLAGS = {
 }
 SOURCES = ["api.hip", "rast_preprocess.hip", "rast_binning.hip", "rast_tilebin.hip", "rast_blockmask.hip", "rast_render_fwd.hip", "rast_render_bwd.hip",
            "rast_geom_bwd.hip", "lbs.hip", "lbs_knn.hip", "frame_loss.hip", "postops.hip", "ssim.hip", "image_losses.hip", "smplx_joints.hip", "densify.hip", "optim.hip", "view.hip",
-           "mesh.hip", "mesh_simplify.hip", "mesh_attr.hip", "mesh_holes.hip", "mesh_texture.hip", "field.hip", "envmap.hip", "conv_gemm.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip", "playback.hip",
+           "mesh.hip", "mesh_simplify.hip", "mesh_attr.hip", "mesh_holes.hip", "mesh_repair.hip", "mesh_texture.hip", "field.hip", "envmap.hip", "conv_gemm.hip", "lpips.hip", "vae.hip", "geometry.hip", "body.hip", "data.hip", "eval.hip", "playback.hip",
            "normalnet.hip", "normal_io.hip", "smplify.hip", "prior.hip", "masks.hip", "step_terms.hip", "fitviz.hip", "video.hip", "png.hip", "png_decode.hip", "jpeg_decode.hip", "image_resize.hip", "attention.hip", "sam.hip", "unet.hip", "clip.hip", "pose.hip", "pose_parts.hip", "pose_init.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(_HERE, "..", "include", "soar_hip.h")]
 

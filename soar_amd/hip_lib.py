@@ -582,6 +582,9 @@ SIGNATURES = {
     "soar_mesh_close_holes_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_mesh_close_holes": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp,
                                         C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_repair_workspace_size": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "soar_mesh_repair_count": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "soar_mesh_repair": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.POINTER(C.c_int64), _vp]),
     "soar_mesh_atlas_bytes": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     "soar_mesh_atlas_levels": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
     "soar_mesh_atlas_place": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),

@@ -22,6 +22,10 @@ sphere, the depth is fused into a truncated signed-distance volume and its zero 
 * ``close_holes`` / ``open_border_edges`` (csrc/mesh_holes.hip): caps every simple border loop of at most ``max_hole_edges`` edges
   with a fan around its centroid, the place of ``meshing_close_holes(maxholesize=300)`` in that refinement -- a deterministic loop
   search, not MeshLab's ear cutting ("Closing holes") --, and the number of border edges of a mesh.
+* ``repair_manifold`` / ``manifold_report`` (csrc/mesh_repair.hip): on every edge with more than two faces the smallest faces go
+  until two are left, and every vertex whose faces form several fans is split -- the two repair filters of the reference's
+  ``clean_mesh`` made order-free ("Repairing non-manifold edges and vertices"); ``repair=True`` of ``decimate``,
+  ``extract_mesh`` and ``export_avatar`` runs it behind the clustering and the pruning.
 * ``skin_weights`` / ``pose_mesh``: SMPL-X blend weights of the mesh vertices (the rule ``query_weights_smpl`` applies to surfels)
   and the mesh in any number of poses with the existing warp and normal kernels: one export, many frames.
 * ``export_avatar``: all of it in the reference's order, from canonical surfels to mesh, colours, quality, normals and weights;
@@ -210,7 +214,8 @@ def simplify(mesh: Mesh, cell: float) -> Mesh:
     grid over the bounding box become one vertex, placed where the summed quadrics of the faces around them are least; faces
     that lose a corner this way, and repeated faces, go.  Surviving faces keep their order and winding.  DESIGN.md 9b states
     the computation; it is deterministic bit for bit.  Where two sheets of the surface pass through one cell the result has
-    non-manifold edges, and nothing repairs them."""
+    non-manifold edges: ``repair_manifold`` removes them (``manifold_report`` counts them; ``decimate(..., repair=True)`` does both
+    steps)."""
     verts, faces = _mesh_tensors(mesh)
     cell = float(cell)
     if not (cell > 0.0 and math.isfinite(cell)):
@@ -241,23 +246,28 @@ def _decimate_cells(count, target_faces: int, max_cells: int) -> int:
     return lo
 
 
-def decimate(mesh: Mesh, target_faces: int = DECIMATE_TARGET, max_cells: int = 4096) -> Mesh:
+def decimate(mesh: Mesh, target_faces: int = DECIMATE_TARGET, max_cells: int = 4096, repair: bool = False) -> Mesh:
     """``mesh`` with at most ``target_faces`` faces: ``simplify`` at cell = L / R (float32), L the longest extent of the
     bounding box, R the integer ``_decimate_cells`` finds (about two dozen counting passes, two int64 read back from each).  A
     mesh within the budget comes back as it is, the same tensors.  The face count is not exactly monotone in R, so R is what
-    the search finds, not a proven maximum.  (One cell, R = 1, leaves no face: every budget >= 0 can be met.)"""
+    the search finds, not a proven maximum.  (One cell, R = 1, leaves no face: every budget >= 0 can be met.)
+
+    The clustering leaves non-manifold edges where two sheets of the surface share a cell (fingers, an arm at the torso).  ``repair``:
+    False (the default) returns the clustered mesh as it is; True returns ``repair_manifold`` of it, the mesh alone (the repair only
+    removes faces, so the budget still holds)."""
     target_faces, max_cells = int(target_faces), int(max_cells)
     if target_faces < 0 or max_cells < 1:
         raise ValueError(f"need target_faces >= 0 and max_cells >= 1 (got {target_faces}, {max_cells})")
     verts, faces = _mesh_tensors(mesh)
     if faces.shape[0] <= target_faces:
-        return mesh
+        return repair_manifold(mesh)[0] if repair else mesh
     L = float((verts.max(0).values - verts.min(0).values).max())
     if not (L > 0.0 and math.isfinite(L)):
         raise ValueError(f"the mesh's bounding box has the longest extent {L}")
     s = _Simplifier(verts, faces)
     R = _decimate_cells(lambda r: s.count(_f32(L / r))[1], target_faces, max_cells)
-    return s.run(_f32(L / R))
+    out = s.run(_f32(L / R))
+    return repair_manifold(out)[0] if repair else out
 
 
 # ---- the whole path --------------------------------------------------------------------------------------------------
@@ -329,7 +339,8 @@ def render_depth(means3D, rotations, scales, opacities, cams, fov, image_size: i
 
 @torch.no_grad()
 def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.Tensor, opacities: torch.Tensor, resolution: int = 256,
-                 n_views: int = 48, image_size: int = 1024, group: int = 8, decimate_target: Optional[int] = None) -> Mesh:
+                 n_views: int = 48, image_size: int = 1024, group: int = 8, decimate_target: Optional[int] = None,
+                 repair: bool = False) -> Mesh:
     """World-space mesh of the surfels (rasterizer conventions: scales [P,3] with z = -1e10, opacities [P,1]).
 
     Renders ``n_views`` depth maps of ``image_size``^2 in groups of ``group`` views (one group's planes alive at a time), fuses
@@ -338,7 +349,10 @@ def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.T
     avatar, export the canonical surfels once (``export_avatar``) and pose the mesh (``pose_mesh``).
 
     ``decimate_target``: None (the default) returns that mesh; a number runs ``decimate`` on it, the face budget of the
-    reference's ``extract_mesh(decimate_target=1e5)`` (by vertex clustering, not pymeshlab's edge collapse)."""
+    reference's ``extract_mesh(decimate_target=1e5)`` (by vertex clustering, not pymeshlab's edge collapse).
+
+    ``repair``: False (the default) changes nothing; True runs ``repair_manifold`` after the clustering (``decimate(..., repair=True)``;
+    without a ``decimate_target``, on the filtered mesh), the two repair filters of the reference's ``clean_mesh``."""
     _hip(means3D, "means3D")
     dev = means3D.device
     f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()
@@ -361,7 +375,9 @@ def extract_mesh(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.T
     del field, valid
     verts, faces = filter_components(verts, faces)
     if decimate_target is not None:
-        verts, faces = decimate(Mesh(verts, faces), int(decimate_target))
+        verts, faces = decimate(Mesh(verts, faces), int(decimate_target), repair=bool(repair))
+    elif repair:
+        verts, faces = repair_manifold(Mesh(verts, faces))[0]
     org = torch.tensor(origin, dtype=torch.float32, device=dev)
     return Mesh(verts * voxel + org, faces)
 
@@ -526,7 +542,8 @@ def close_holes(mesh: Mesh, max_hole_edges: int = MAX_HOLE_EDGES) -> Tuple[Mesh,
 
     A border edge belongs to exactly one face (``adjacency``'s rule).  A border loop is closed when it has 3 .. ``max_hole_edges``
     edges, every vertex on it has exactly one border edge arriving and one leaving (two holes that touch in a vertex stay open, as
-    MeshLab leaves non-manifold borders) and it is not the rim of a lone triangle.  A loop of three gets one face; a longer one a
+    MeshLab leaves non-manifold borders; ``repair_manifold`` first splits such a vertex, and both holes then close) and it is not the
+    rim of a lone triangle.  A loop of three gets one face; a longer one a
     new vertex at the mean of its ring (summed in float64 in ring order) and one face per edge, each with the border edge reversed,
     so the patch continues the surface's orientation.  The rim of a small open component is a loop like any other.  The input's
     vertices and faces come first, unchanged; new vertices and faces follow loop by loop.  Deterministic bit for bit."""
@@ -549,6 +566,90 @@ def open_border_edges(mesh: Mesh) -> int:
         return 0
     _, _, loops, (_, _, nl, still_open) = _close_holes(verts, faces, HOLE_EDGES_RANGE[0])
     return still_open + 3 * nl
+
+
+# ---- repair of non-manifold edges and vertices (csrc/mesh_repair.hip) ----------------------------------------------------------
+
+REPAIR_COUNTS = ("vertices", "faces", "non_manifold_edges", "faces_removed", "null_faces", "vertex_copies", "unreferenced_vertices",
+                 "same_direction_edges", "border_edges")
+
+
+class _Repairer:
+    """The workspace and the two calls of one mesh with V >= 1 and F >= 1."""
+
+    def __init__(self, verts: torch.Tensor, faces: torch.Tensor):
+        self.verts, self.faces = verts, faces
+        self.V, self.F = int(verts.shape[0]), int(faces.shape[0])
+        self.lib = hip_lib.lib()
+        self.nb = _bytes(self.lib.soar_mesh_repair_workspace_size, "soar_mesh_repair_workspace_size", self.V, self.F)
+        self.ws = _workspace(self.nb, verts.device)
+
+    def count(self) -> dict:
+        counts = (C.c_int64 * len(REPAIR_COUNTS))()
+        dev = self.verts.device
+        with torch.cuda.device(dev):
+            check(self.lib.soar_mesh_repair_count(self.V, self.F, self.verts.data_ptr(), self.faces.data_ptr(), self.ws.data_ptr(), self.nb,
+                                                  counts, _stream(dev)), "soar_mesh_repair_count")
+        return dict(zip(REPAIR_COUNTS, (int(c) for c in counts)))
+
+    def run(self, info: dict) -> Tuple[Mesh, torch.Tensor, dict]:
+        dev = self.verts.device
+        vo = torch.empty(max(info["vertices"], 1), 3, device=dev)
+        fo = torch.empty(max(info["faces"], 1), 3, dtype=torch.int32, device=dev)
+        src = torch.empty(max(info["vertices"], 1), dtype=torch.int32, device=dev)
+        counts = (C.c_int64 * len(REPAIR_COUNTS))()
+        with torch.cuda.device(dev):
+            check(self.lib.soar_mesh_repair(self.V, self.F, self.verts.data_ptr(), self.faces.data_ptr(), self.ws.data_ptr(), self.nb,
+                                            vo.data_ptr(), fo.data_ptr(), src.data_ptr(), counts, _stream(dev)), "soar_mesh_repair")
+        got = dict(zip(REPAIR_COUNTS, (int(c) for c in counts)))
+        if got != info:
+            raise RuntimeError(f"soar_mesh_repair reports {got} after soar_mesh_repair_count reported {info} for the same mesh")
+        return Mesh(vo[:info["vertices"]], fo[:info["faces"]]), src[:info["vertices"]], got
+
+
+def _repair_empty(V: int) -> dict:
+    info = dict.fromkeys(REPAIR_COUNTS, 0)
+    info["unreferenced_vertices"] = V
+    return info
+
+
+@torch.no_grad()
+def manifold_report(mesh: Mesh) -> dict:
+    """What ``repair_manifold`` would do to ``mesh``, from the analysis alone: a dict of the nine counts ``REPAIR_COUNTS``; no output
+    mesh is allocated or written.  The three to read: ``non_manifold_edges`` (edges of more than two faces), ``vertex_copies``
+    (fans beyond the first at a vertex: bow-tie vertices) and ``border_edges`` (edges of one face in the repaired mesh).  A mesh with
+    0 / 0 there, no ``null_faces`` and no ``unreferenced_vertices`` is one that ``repair_manifold`` returns as it is."""
+    verts, faces = _mesh_tensors(mesh)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if V == 0 or F == 0:
+        return _repair_empty(V)
+    return _Repairer(verts, faces).count()
+
+
+@torch.no_grad()
+def repair_manifold(mesh: Mesh) -> Tuple[Mesh, torch.Tensor, dict]:
+    """Remove the non-manifold edges and split the non-manifold vertices of ``mesh`` -> ``(Mesh, source, info)``: ``source`` [V']
+    int32 the input vertex every output vertex came from (use it as ``prune_by_quality``'s keep map is used: ``color[source]``),
+    ``info`` the nine counts ``REPAIR_COUNTS``.  The place of the reference's ``meshing_repair_non_manifold_edges(method=0)`` and
+    ``meshing_repair_non_manifold_vertices(vertdispratio=0)`` (geometry/mesh_utils.py, ``clean_mesh``); the definition is this
+    project's, MeshLab's rules made independent of any order ("Repairing non-manifold edges and vertices").
+
+    A face that names a vertex twice goes.  On every edge with k > 2 faces the k - 2 smallest go (by the bits of the float32 squared
+    area, ties by face index), in one pass: afterwards no edge has more than two faces.  Then, around every vertex, the faces that
+    hang together through edges of exactly two faces form a fan; the fan with the least corner index keeps the vertex and every other
+    fan gets a copy of it at the same place.  Kept vertices come first in their order (a vertex no surviving face names is dropped),
+    then the copies; surviving faces keep their order and winding.  Inconsistent winding is counted (``same_direction_edges``) and
+    not changed; nothing is re-oriented, merged or remeshed.  Running it on its own output changes nothing; a mesh that needs nothing
+    comes back with equal bits and ``source == arange(V)``.  An empty mesh, or one without faces, gives empty results.  A face that
+    names a vertex outside [0, V) is refused.  Deterministic bit for bit."""
+    verts, faces = _mesh_tensors(mesh)
+    dev = verts.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if V == 0 or F == 0:
+        return (Mesh(verts.new_zeros(0, 3), torch.zeros(0, 3, dtype=torch.int32, device=dev)),
+                torch.zeros(0, dtype=torch.int32, device=dev), _repair_empty(V))
+    r = _Repairer(verts, faces)
+    return r.run(r.count())                                   # the counts size the outputs; a refused mesh is refused before any is made
 
 
 # ---- the rig -------------------------------------------------------------------------------------------------------------------
@@ -642,7 +743,7 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
                   decimate_target: Optional[int] = DECIMATE_TARGET, quality_thresh: Optional[float] = None,
                   smooth_steps: int = SMOOTH_STEPS, k: int = ATTR_K, K: int = 30, n_views: int = 48, image_size: int = 1024,
                   group: int = 8, use_explicit: bool = False, max_hole_edges: Optional[int] = None,
-                  texture_size: Optional[int] = None) -> dict:
+                  texture_size: Optional[int] = None, repair: bool = False) -> dict:
     """A coloured, animatable mesh from CANONICAL-space surfels in one call -> ``dict(mesh, color, quality, normals, weights)``.
 
     ``model_or_tensors``: the tuple ``(means3D [P,3], rotations [P,4], scales [P,3] with z = -1e10, opacities [P,1], colors [P,3]
@@ -659,6 +760,11 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
     ``max_hole_edges``: None (the default) closes nothing and returns exactly what this function returned before it had the
     argument.  A number closes the holes of at most that many edges that the pruning (or the extraction) left, before the smoothing,
     and the dict gains ``closed`` (``close_holes``' second result); 300 is recommended, the reference's ``maxholesize``.
+
+    ``repair``: False (the default) changes nothing.  True runs ``repair_manifold`` twice: on ``extract_mesh``'s result, clustered
+    or not, and again after ``prune_by_quality`` (which leaves bow-tie vertices), before ``close_holes``, so that holes that touch
+    in a vertex can be closed; the dict gains ``repair``, the two ``info`` dicts in that order (the second is None without a
+    ``quality_thresh``).  Colours, qualities and weights are computed after the repair, as they are after the pruning.
 
     ``texture_size``: None (the default) returns exactly that dict.  A power of two adds ``atlas`` (``build_atlas`` of the final,
     smoothed mesh) and ``texture`` (``bake_texture`` from the same surfel colours and ``k`` as the vertex colours), for
@@ -679,9 +785,15 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
     means3D, colors = f32(means3D), f32(colors)
     m = extract_mesh(means3D, rotations, scales, opacities, resolution=resolution, n_views=n_views, image_size=image_size, group=group,
                      decimate_target=decimate_target)
+    repaired = None
+    if repair:
+        m, _, first = repair_manifold(m)                      # on the world-space mesh, for its counts
+        repaired = [first, None]
     if quality_thresh is not None:
         _, quality, _ = vertex_attributes(m.vertices, means3D, colors, k)
         m, _ = prune_by_quality(m, quality, quality_thresh)
+        if repair:
+            m, _, repaired[1] = repair_manifold(m)
     closed = None
     if max_hole_edges is not None:
         m, closed = close_holes(m, max_hole_edges)
@@ -692,6 +804,8 @@ def export_avatar(model_or_tensors, smpl_vertices: torch.Tensor, lbs_weights: to
     out = dict(mesh=m, color=color, quality=quality, normals=normals, weights=weights)
     if closed is not None:
         out["closed"] = closed
+    if repaired is not None:
+        out["repair"] = repaired
     if texture_size is not None:
         try:
             out["atlas"] = build_atlas(m, texture_size)
